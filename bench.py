@@ -1,6 +1,6 @@
 """bench.py -- headline benchmark of the MI355X-native HyperBO GP hot path.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
 
 N > 1: one rank per GPU.  Launched by torch.distributed.run (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* in the env) the
 ranks find each other through hyperbo_amd.parallel.SocketGroup on a port derived from MASTER_PORT; launched plainly
@@ -479,6 +479,16 @@ def bench_hgp():
   return out
 
 
+def dump_outputs(out_dir, result):
+  """(value, grads) of objectives.nll_value_and_grad -> out_dir/nll.npy and out_dir/grad_<leaf>.npy, float64, as returned
+  (D + 4 numbers: the headline's SE-ARD + constant-mean gradient is a flat dict)."""
+  os.makedirs(out_dir, exist_ok=True)
+  value, grads = result
+  np.save(os.path.join(out_dir, 'nll.npy'), np.asarray(value, dtype=np.float64))
+  for k, g in grads.items():
+    np.save(os.path.join(out_dir, f'grad_{k}.npy'), np.asarray(g, dtype=np.float64))
+
+
 def cpu_provenance():
   """Where the CPU baseline's flops come from: thread settings and the BLAS / LAPACK the port calls."""
   info = {'omp_num_threads': os.environ.get('OMP_NUM_THREADS'), 'openblas_num_threads': os.environ.get('OPENBLAS_NUM_THREADS')}
@@ -516,7 +526,11 @@ def main():
   ap.add_argument('--cpu-evals', type=int, default=8)
   ap.add_argument('--jax', action='store_true', help='also time a JAX expression of the same NLL+grad on the host (only if jax imports)')
   ap.add_argument('--secondary-timeout', type=float, default=420.0, help='seconds for the multitask + CPU legs')
+  ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                  help='write what the last timed step returned (NLL and gradient leaves, float64) as DIR/<name>.npy (rank 0)')
   args = ap.parse_args()
+  if args.steps < 1 or args.warmup < 0:
+    ap.error('--steps must be >= 1 and --warmup >= 0')
 
   if 'WORLD_SIZE' not in os.environ and args.gpus > 1:
     return spawn_ranks(args.gpus)
@@ -592,6 +606,8 @@ def main():
       a = prof.setdefault(k, [0.0, 0]); a[0] += ms; a[1] += cnt
   sync()
   elapsed = max_over_ranks(time.perf_counter() - t0)
+  if args.dump_outputs and rank == 0:
+    dump_outputs(args.dump_outputs, last)
   stage_prof, stage_evals = {}, 3
   ctx.profile_enable(1)
   for i in range(stage_evals):

@@ -117,6 +117,26 @@ def rel_err(a, b):
   return float(np.max(np.abs(a - b)) / (np.max(np.abs(b)) + 1e-300)) if a.size else 0.0
 
 
+_TORCH_PROCESS = None
+
+
+def in_torch_process(fn, *args):
+  """fn(*args) in a spawned child process (one, reused), its exception raised here; skips when torch is not installed.  The
+  tests that use torch go through this: torch-ROCm loads its own HIP runtime and librccl.so, and in one process with libhbo
+  either libhbo's dlopen("librccl.so") returns torch's RCCL (ncclCommInitRank fails) or, with libhbo's RCCL loaded first,
+  the process aborts at exit (double free between the two runtimes)."""
+  import concurrent.futures
+  import importlib.util
+  import multiprocessing
+  import pytest
+  global _TORCH_PROCESS
+  if importlib.util.find_spec('torch') is None:
+    pytest.skip('torch is not installed')
+  if _TORCH_PROCESS is None:
+    _TORCH_PROCESS = concurrent.futures.ProcessPoolExecutor(max_workers=1, mp_context=multiprocessing.get_context('spawn'))
+  return _TORCH_PROCESS.submit(fn, *args).result()
+
+
 def synthetic_task(rng, n, d, m=1, dtype=np.float64):
   x = rng.uniform(size=(n, d))
   w = rng.normal(size=(d, m))

@@ -44,8 +44,15 @@ def _worker(rank, world, port, out_dir):
 
 
 def test_sharded_objective_matches_single_process(tmp_path):
-  torch = pytest.importorskip('torch')
+  sys.path.insert(0, os.path.join(ROOT, 'tests'))
+  import helpers
+  helpers.in_torch_process(_sharded_objective_case, str(tmp_path))
+
+
+def _sharded_objective_case(tmp_path):
+  import pathlib
   import torch.multiprocessing as mp
+  tmp_path = pathlib.Path(tmp_path)
   sys.path.insert(0, os.path.join(ROOT, 'tests'))
   import helpers
   from oracle import hyperbo_oracle as o

@@ -183,7 +183,11 @@ def _torch_nll(kname, mlp, mname, model_t, xs, ys, torch):
 @pytest.mark.parametrize('kname', helpers.KERNELS)
 @pytest.mark.parametrize('mlp,mname', [(False, 'constant'), (True, 'linear_mlp'), (False, 'linear'), (True, 'zero')])
 def test_torch_autograd_matches_oracle_gradient(kname, mlp, mname):
-  torch = pytest.importorskip('torch')
+  helpers.in_torch_process(_torch_autograd_case, kname, mlp, mname)
+
+
+def _torch_autograd_case(kname, mlp, mname):
+  import torch
   rng = np.random.default_rng(31)
   d = 3
   model = helpers.make_model(rng, mname, mlp, d)
@@ -250,7 +254,11 @@ def test_divergence_gradient_finite_difference_and_value(kind, kname, mlp, mname
 @pytest.mark.parametrize('kname,mlp,mname', [('squared_exponential', False, 'constant'), ('matern32', True, 'linear_mlp'),
                                              ('dot_product', True, 'linear'), ('matern52', False, 'zero')])
 def test_divergence_torch_autograd(kind, kname, mlp, mname):
-  torch = pytest.importorskip('torch')
+  helpers.in_torch_process(_divergence_torch_case, kind, kname, mlp, mname)
+
+
+def _divergence_torch_case(kind, kname, mlp, mname):
+  import torch
   rng = np.random.default_rng(5)
   d = 2
   model = helpers.make_model(rng, mname, mlp, d)

@@ -184,6 +184,10 @@ def _rosen(p):
 def test_oracle_adam_matches_torch_optim_adam():
   """The optax-style Adam of the oracle against an independent third-party Adam (torch.optim.Adam, CPU): the two libraries'
   update rules are algebraically the same (bias correction by the incremented count, eps outside the square root)."""
+  helpers.in_torch_process(_adam_vs_torch_case)
+
+
+def _adam_vs_torch_case():
   import torch
   rng = np.random.default_rng(0)
   p0 = {'x': {'a': rng.normal(size=3)}, 'z': rng.normal(size=2)}
