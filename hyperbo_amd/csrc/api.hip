@@ -117,14 +117,9 @@ extern "C" int hbo_tune(hbo_ctx* c, const char* name, int64_t value) {
       {"sweep", &hbo_ctx::opt_sweep, 0, 2}, {"sweep_qs", &hbo_ctx::opt_sweep_qs, 0, 16}, {"sweep_side", &hbo_ctx::opt_sweep_side, 0, 1}, {"sweep_free", &hbo_ctx::opt_sweep_free, 1, 200}, {"sweep_big", &hbo_ctx::opt_sweep_big, 0, 1 << 30}, {"batch_bg", &hbo_ctx::opt_batch_bg, -1, 2},
       {"post_bf16x3", &hbo_ctx::opt_post_bf16x3, 0, 1}, {"post_f16x2", &hbo_ctx::opt_post_f16x2, 0, 1}, {"chol_f16x2", &hbo_ctx::opt_chol_f16x2, 0, 1}, {"group_inner", &hbo_ctx::opt_group_inner, -1, 16}, {"syrk_bf16x3", &hbo_ctx::opt_syrk_bf16x3, 0, 1},
       {"trtri_bf16x3", &hbo_ctx::opt_trtri_bf16x3, 0, 1}, {"lauum_bf16x3", &hbo_ctx::opt_lauum_bf16x3, 0, 1}, {"trtri3_min_s", &hbo_ctx::opt_trtri3_min_s, 1, 1024},
-      {"fault_shard", &hbo_ctx::opt_fault_shard, 0, 2}, {"small_fused", &hbo_ctx::opt_small_fused, 0, 1}, {"post_serial", &hbo_ctx::opt_post_serial, 0, 1},
+      {"fault_shard", &hbo_ctx::opt_fault_shard, 0, 2}, {"small_fused", &hbo_ctx::opt_small_fused, 0, 1}, {"gram_mfma", &hbo_ctx::opt_gram_mfma, 0, 4096}, {"post_serial", &hbo_ctx::opt_post_serial, 0, 1},
       {"syrk3_col", &hbo_ctx::opt_syrk3_col, 0, 1}, {"syrk3_sep", &hbo_ctx::opt_syrk3_sep, 0, 1}, {"syrk3_free", &hbo_ctx::opt_syrk3_free, 0, 200},
   };
-  if (!strcmp(name, "gram_mfma")) {   // process-wide: fp32 Gram matrices with at least `value` features on the matrix cores (gram.hip: gram_mfma_kernel); 0: never
-    if (value < 0 || value > 4096) return fail(c, HBO_ERR_ARG, "gram_mfma in 0..4096");
-    gram_set_mfma_min_features((int)value);
-    return HBO_OK;
-  }
   for (const Knob& k : knobs)
     if (!strcmp(name, k.name)) {
       if (value < k.lo || value > k.hi) return fail(c, HBO_ERR_ARG, std::string(name) + " out of range");
@@ -473,7 +468,7 @@ extern "C" int hbo_gram(hbo_ctx* c, const hbo_model* m, const void* x1, int64_t 
     HIPCHK_G(hipMemcpyAsync(out, dout, (size_t)n1 * es, hipMemcpyDeviceToHost, st));
   } else {
     HIPCHK_G(hbo_malloc(c, &dout, (size_t)n1 * n2 * es));
-    GramArgs g = {}; g.kernel_id = c->h_model->kernel_id; g.x1 = F1; g.x2 = F2; g.out = dout; g.n1 = n1; g.n2 = n2; g.ldo = n2; g.fdim = fdim;
+    GramArgs g = {}; g.kernel_id = c->h_model->kernel_id; g.mfma_min_f = c->opt_gram_mfma; g.x1 = F1; g.x2 = F2; g.out = dout; g.n1 = n1; g.n2 = n2; g.ldo = n2; g.fdim = fdim;
     launch_gram(dtype, g, c->d_model, dim3((unsigned)((n2 + 127) / 128), (unsigned)((n1 + 127) / 128), 1), st);
     HIPCHK_G(hipMemcpyAsync(out, dout, (size_t)n1 * n2 * es, hipMemcpyDeviceToHost, st));
   }

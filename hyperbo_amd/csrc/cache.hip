@@ -45,7 +45,7 @@ extern "C" int hbo_factor(hbo_ctx* c, const hbo_model* m, const void* x, int64_t
     launch_aug_rows(dtype, k->d_desc, 1, t->npad, c->d_model, st); }
   HIPCHK_K(hipMemcpy2DAsync(k->resid, (size_t)t->npad * es, (char*)t->A + (size_t)t->npad * t->ld * es, (size_t)t->ld * es, (size_t)t->npad * es, mcols, hipMemcpyDeviceToDevice, st));
   { ProfScope ps(c, "gram", 1);
-    GramArgs g = {}; g.kernel_id = c->h_model->kernel_id; g.tasks = k->d_desc; g.fdim = feature_dim(m); g.symmetric = 1; g.padded = 1;
+    GramArgs g = {}; g.kernel_id = c->h_model->kernel_id; g.mfma_min_f = c->opt_gram_mfma; g.tasks = k->d_desc; g.fdim = feature_dim(m); g.symmetric = 1; g.padded = 1;
     launch_gram(dtype, g, c->d_model, dim3(t->nblk, t->nblk, 1), st); }
   // the inverse W = L^-1 (kept for the posterior products) starts beside the panel chain, as in the objective path
   TrtriProgress trtri_pg;
@@ -160,7 +160,7 @@ extern "C" int hbo_cache_append(hbo_ctx* c, const hbo_model* m, hbo_cache* k, co
     launch_kdiag(dtype, Fq, 1, fdim, c->d_model, d_kd, st);
     // k(X, x*)  (n x 1), zero-padded to npad
     HIPCHK_A(hipMemsetAsync(d_kx, 0, (size_t)t->npad * es, st));
-    { GramArgs g = {}; g.kernel_id = c->h_model->kernel_id; g.x1 = k->h_desc.F; g.x2 = Fq; g.out = d_kx; g.n1 = n; g.n2 = 1; g.ldo = 1; g.fdim = fdim;
+    { GramArgs g = {}; g.kernel_id = c->h_model->kernel_id; g.mfma_min_f = c->opt_gram_mfma; g.x1 = k->h_desc.F; g.x2 = Fq; g.out = d_kx; g.n1 = n; g.n2 = 1; g.ldo = 1; g.fdim = fdim;
       launch_gram(dtype, g, c->d_model, dim3(1, (unsigned)((n + 127) / 128), 1), st); }
     // l = W kx ; wl = W^T l ; then the new rows and the updated z, alpha in one workgroup (no host round trip)
     launch_tri_matvec(dtype, t->W, t->ld, t->npad, d_kx, t->npad, 1, 0, d_l, t->npad, st);
@@ -349,7 +349,7 @@ static int posterior(hbo_ctx* c, const hbo_model* m, hbo_cache* k, const void* x
     if (!k) {  // prior branch (gp.py:275-282)
       HIPCHK_P(hipMemcpyAsync(mu_d, mu0_d, (size_t)mc * es, hipMemcpyDeviceToDevice, sb));
       if (full_cov) {
-        GramArgs g = {}; g.kernel_id = m->kernel_id; g.x1 = Fq; g.x2 = Fq; g.out = d_cov; g.n1 = mc; g.n2 = mc; g.ldo = mc; g.fdim = fdim;
+        GramArgs g = {}; g.kernel_id = m->kernel_id; g.mfma_min_f = c->opt_gram_mfma; g.x1 = Fq; g.x2 = Fq; g.out = d_cov; g.n1 = mc; g.n2 = mc; g.ldo = mc; g.fdim = fdim;
         launch_gram(dtype, g, md, dim3((unsigned)((mc + 127) / 128), (unsigned)((mc + 127) / 128), 1), sb);
       } else {
         HIPCHK_P(hipMemcpyAsync(var_d, kd_d, (size_t)mc * es, hipMemcpyDeviceToDevice, sb));
@@ -364,10 +364,10 @@ static int posterior(hbo_ctx* c, const hbo_model* m, hbo_cache* k, const void* x
     }
     char* K_d = d_K + b * K_b; char* colsq_d = d_colsq + b * colsq_b;
     { ProfScope ps(c, "cross_gram", 1, sb);
-      GramArgs g = {}; g.kernel_id = m->kernel_id; g.x1 = k->h_desc.F; g.x2 = Fq; g.out = K_d; g.n1 = t->n; g.n2 = mc; g.ldo = ldq;
+      GramArgs g = {}; g.kernel_id = m->kernel_id; g.mfma_min_f = c->opt_gram_mfma; g.x1 = k->h_desc.F; g.x2 = Fq; g.out = K_d; g.n1 = t->n; g.n2 = mc; g.ldo = ldq;
       g.n1pad = t->npad; g.n2pad = mpad; g.fdim = fdim; g.symmetric = 0; g.padded = 1;
       // the producer of a streamed posterior runs BESIDE the product of the previous chunk, in the slots its resident grid leaves: there the
-      // matrix-core form (62 KB of LDS per workgroup, the product's own MFMA pipes) is the slower one -- cfg 3: EI 58.5 ms with the direct
+      // matrix-core form (38 KB of LDS per workgroup, the product's own MFMA pipes) is the slower one -- cfg 3: EI 58.5 ms with the direct
       // form, 59.0 with it, although alone it takes 0.33 ms per chunk against 0.58 (round 6)
       g.direct_form = nbuf == 2;
       launch_gram(dtype, g, md, dim3(mpad / HBO_TILE, t->nblk, 1), sb); }
@@ -425,7 +425,7 @@ static int posterior(hbo_ctx* c, const hbo_model* m, hbo_cache* k, const void* x
     if (nbuf == 2) { ev_free[b] = pool_event(c, evi++); hipEventRecord(ev_free[b], sa); }
     if (full_cov) {
       ProfScope ps(c, "full_cov", 1, sa);
-      GramArgs g = {}; g.kernel_id = m->kernel_id; g.x1 = Fq; g.x2 = Fq; g.out = d_Kqq; g.n1 = mc; g.n2 = mc; g.ldo = ldq; g.fdim = fdim;
+      GramArgs g = {}; g.kernel_id = m->kernel_id; g.mfma_min_f = c->opt_gram_mfma; g.x1 = Fq; g.x2 = Fq; g.out = d_Kqq; g.n1 = mc; g.n2 = mc; g.ldo = ldq; g.fdim = fdim;
       launch_gram(dtype, g, md, dim3((unsigned)((mc + 127) / 128), (unsigned)((mc + 127) / 128), 1), sa);
       // (columns of V beyond the candidates are zero: Kxq is zero-padded; the padded part of the Kqq buffer is never copied out)
       GemmArgs a = {}; a.tasks = k->d_desc; a.mode = GEMM_VTV; a.B = d_V; a.ldb = ldq; a.V = d_Kqq;
@@ -572,7 +572,7 @@ extern "C" int hbo_acq_samples(hbo_ctx* c, const hbo_model* models, int32_t S, c
     if (mlp) for (int s = 0; s < S; ++s) run_mlp(c, m0, ks[s]->t->X, n, ks[s]->t->feat.acts.data(), &w_dev[(size_t)s * HBO_MAX_MLP_LAYERS], &b_dev[(size_t)s * HBO_MAX_MLP_LAYERS]);
     launch_aug_rows(dtype, d_batch, S, npad, d_models, st, 1); }
   { ProfScope ps(c, "gram", 1);
-    GramArgs g = {}; g.kernel_id = m0->kernel_id; g.tasks = d_batch; g.fdim = feature_dim(m0); g.symmetric = 1; g.padded = 1; g.model_stride = 1;
+    GramArgs g = {}; g.kernel_id = m0->kernel_id; g.mfma_min_f = c->opt_gram_mfma; g.tasks = d_batch; g.fdim = feature_dim(m0); g.symmetric = 1; g.padded = 1; g.model_stride = 1;
     launch_gram(dtype, g, d_models, dim3(nblk, nblk, S), st); }
   TrtriProgress trtri_pg;
   const bool early_trtri = use_lookahead(c, S, nblk) && c->opt_overlap_trtri && nblk >= 4;
@@ -671,7 +671,7 @@ extern "C" int hbo_acq_grad(hbo_ctx* c, const hbo_model* m, hbo_cache* k, const 
     launch_kdiag(dtype, Fq, mc, fdim, c->d_model, d_kd, st);
     if (t) {
       HIPCHK_D(hipMemsetAsync(d_K, 0, (size_t)mc * t->npad * es, st));
-      GramArgs g = {}; g.kernel_id = c->h_model->kernel_id; g.x1 = Fq; g.x2 = k->h_desc.F; g.out = d_K; g.n1 = mc; g.n2 = t->n; g.ldo = t->npad; g.fdim = fdim;
+      GramArgs g = {}; g.kernel_id = c->h_model->kernel_id; g.mfma_min_f = c->opt_gram_mfma; g.x1 = Fq; g.x2 = k->h_desc.F; g.out = d_K; g.n1 = mc; g.n2 = t->n; g.ldo = t->npad; g.fdim = fdim;
       launch_gram(dtype, g, c->d_model, dim3((unsigned)((t->n + 127) / 128), (unsigned)((mc + 127) / 128), 1), st);
       launch_tri_matvec(dtype, t->W, t->ld, t->npad, d_K, t->npad, (int)mc, 0, d_L, t->npad, st);
       launch_tri_matvec(dtype, t->W, t->ld, t->npad, d_L, t->npad, (int)mc, 1, d_B, t->npad, st);

@@ -109,7 +109,7 @@ def test_fp32_gram_on_the_matrix_cores_vs_oracle(gpu_ctx, kname, d):
   u = |a|^2 + |b|^2 - 2 a.b with the dot product from the exact three-way bf16 split on the matrix cores.  Symmetric and cross
   Gram, sizes off the 128-tile grid, a feature count that is not a multiple of the 32-feature chunk, duplicated rows (u ~ 0, where
   the expansion loses what the direct form keeps): against the fp64 oracle at the fp32 Gram's 2e-5, and against the direct-form
-  kernel (hbo_tune gram_mfma = 0) -- whose own error is recorded beside it."""
+  kernel (hbo_tune gram_mfma = 0, on a context of its own) -- whose own error is recorded beside it."""
   defs, _, _, _, kernel, _, _, utils = _native()
   rng = np.random.default_rng(100 + d)
   model = {'lengthscale': helpers.inv_softplus(rng.uniform(1.5, 3.0, size=d)).astype(np.float32), 'signal_variance': np.float32(helpers.inv_softplus(0.8)),
@@ -125,21 +125,32 @@ def test_fp32_gram_on_the_matrix_cores_vs_oracle(gpu_ctx, kname, d):
   ref_s = ko(po, x1.astype(np.float64), warp_func=WFO)
   ref_c = ko(po, x1.astype(np.float64), x2.astype(np.float64), warp_func=WFO)
   errs = {}
+  from hyperbo_amd import _model, _native as nat
+  direct_ctx = nat.Context(gpu_ctx.device)   # the direct form on a context of its own (gram_mfma is a per-context setting)
+  direct_ctx.set_option('gram_mfma', 0)
+
+  def gram(ctx, xa, xb=None):
+    if ctx is gpu_ctx:
+      return kn(pn, xa, xb, warp_func=utils.DEFAULT_WARP_FUNC)
+    out = np.empty((xa.shape[0], (xa if xb is None else xb).shape[0]), np.float32)
+    bm = _model.BuiltModel(_native()[5].zero, kn, pn, utils.DEFAULT_WARP_FUNC, np.float32, d)
+    ctx.check(nat.lib().hbo_gram(ctx.handle, bm.ref(), nat.ptr(xa), xa.shape[0], nat.ptr(xb), out.shape[1], 0, nat.ptr(out)),
+              allow_not_pd=False)
+    return out
   try:
-    for name, minf in (('mfma', 32), ('direct', 0)):
-      gpu_ctx.set_option('gram_mfma', minf)
-      gs = kn(pn, x1, warp_func=utils.DEFAULT_WARP_FUNC)
-      gc = kn(pn, x1, x2, warp_func=utils.DEFAULT_WARP_FUNC)
+    for name, ctx in (('mfma', gpu_ctx), ('direct', direct_ctx)):
+      gs = gram(ctx, x1)
+      gc = gram(ctx, x1, x2)
       assert gs.dtype == np.float32 and gs.shape == (300, 300) and gc.shape == (300, 150)
       errs[name] = (helpers.rel_err(gs, ref_s), helpers.rel_err(gc, ref_c))
       assert errs[name][0] < 2e-5 and errs[name][1] < 2e-5, errs
       np.testing.assert_allclose(gs, gs.T, atol=2e-5)
       if name == 'mfma':
         sv = float(np.log1p(np.exp(float(model['signal_variance']))) + 1e-10)
-        assert np.max(np.abs(np.diag(gs) - sv)) <= 2e-5 * sv               # a point and itself (hbo_gram's direct mode has no exact-zero rule: that is the symmetric factor path)
+        assert np.max(np.abs(np.diag(gs) - sv)) <= 2e-5 * sv               # a point and itself
         assert np.max(np.abs(gc[:20, :20].diagonal() - sv)) <= 2e-5 * sv     # exact duplicates across the sets: u ~ 1e-7 |a|^2
   finally:
-    gpu_ctx.set_option('gram_mfma', 32)
+    direct_ctx.close()
   if os.environ.get('HBO_GRAD_LOG'):
     with open(os.environ['HBO_GRAD_LOG'], 'a') as f_:
       f_.write('0 tol=gram32 %s d=%d (symmetric, cross) rel. error vs fp64: mfma %.3e %.3e direct %.3e %.3e\n' % ((kname, d) + errs['mfma'] + errs['direct']))
