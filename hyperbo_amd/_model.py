@@ -40,6 +40,7 @@ class BuiltModel:
     self.dtype = np.dtype(dtype)
     self.code = nat.dtype_code(self.dtype)
     self.uses_mlp_kernel = bool(getattr(cov_func, 'uses_mlp', False))
+    self.uses_kumar = bool(getattr(cov_func, 'uses_kumar', False))
     self.kernel_id, self.mean_id = kernel_id, mean_id
     self.warp_func = warp_func
     self.params = params
@@ -108,13 +109,38 @@ class BuiltModel:
         raise ValueError(f'linear_mean kernel has {w.size} entries, expected {fin}')
       m.linear_kernel = nat.ptr(w).value
       m.linear_bias = float(np.squeeze(lm['bias']))
+    self.kumar_raw = None
+    if self.uses_kumar:
+      # hyperbo/gp_utils/kernel.py:190-217: KumarWarp applies squareplus to kumar_params itself (warp_func never touches them)
+      if 'kumar_params' not in params.model:
+        raise ValueError(f'{getattr(cov_func, "__name__", cov_func)} is a Kumaraswamy kernel but params.model has no '
+                         "'kumar_params'; create them with kernel.init_kumar_warp_with_shape(key, params, input_shape)")
+      kp = params.model['kumar_params']
+      a_raw = np.reshape(np.asarray(kp['a'], dtype=np.float64), (-1,))
+      b_raw = np.reshape(np.asarray(kp['b'], dtype=np.float64), (-1,))
+      if a_raw.size != int(input_dim) or b_raw.size != int(input_dim):
+        raise ValueError(f"kumar_params 'a' / 'b' have {a_raw.size} / {b_raw.size} entries, expected {int(input_dim)}")
+      self.kumar_raw = (a_raw, b_raw)
+      ka, kb = arr(gp_utils_utils.squareplus_warp(a_raw)), arr(gp_utils_utils.squareplus_warp(b_raw))
+      m.input_warp = nat.WARP_KUMAR
+      self.kstruct = nat.ModelKumar()
+      self.kstruct.base = m
+      self.kstruct.kumar_a = nat.ptr(ka).value
+      self.kstruct.kumar_b = nat.ptr(kb).value
+      m = self.kstruct.base   # (a view into kstruct: one struct, the one the library reads)
     self.struct = m
     self.layout = nat.GradLayout()
-    rc = nat.lib().hbo_grad_layout_of(C.byref(m), C.byref(self.layout))
+    rc = nat.lib().hbo_grad_layout_of(self.ref(), C.byref(self.layout))
     if rc != nat.HBO_OK:
-      raise nat.HboError(rc, 'hbo_grad_layout_of failed')
+      raise nat.HboError(rc, 'hbo_grad_layout_of: ' + (nat.lib().hbo_last_error(None) or b'').decode())
+    if self.uses_kumar:
+      ao, bo = C.c_int32(-1), C.c_int32(-1)
+      nat.lib().hbo_grad_layout_kumar_of(self.ref(), C.byref(ao), C.byref(bo))
+      self.kumar_offsets = (ao.value, bo.value)
 
   def ref(self):
+    if self.uses_kumar:
+      return C.cast(C.pointer(self.kstruct), C.POINTER(nat.Model))
     return C.byref(self.struct)
 
   # -- gradient pytree -----------------------------------------------------------------
@@ -162,6 +188,16 @@ class BuiltModel:
             'bias': np.reshape(flat[bo:bo + int(np.prod(bshape))], bshape),
         }
       grads['mlp_params'] = g
+    if self.uses_kumar and 'kumar_params' in model:
+      # d/d squareplus(raw) -> d/d raw (squareplus'(t) = (1 + t / sqrt(t^2 + 4)) / 2), shaped like the raw leaves
+      kp = model['kumar_params']
+      ao, bo = self.kumar_offsets
+      d = self.kumar_raw[0].size
+      sp = lambda t: gp_utils_utils.warp_derivative(gp_utils_utils.squareplus_warp, t)
+      grads['kumar_params'] = {
+          'a': np.reshape(np.asarray(flat[ao:ao + d], dtype=np.float64) * sp(self.kumar_raw[0]), np.shape(kp['a'])),
+          'b': np.reshape(np.asarray(flat[bo:bo + d], dtype=np.float64) * sp(self.kumar_raw[1]), np.shape(kp['b'])),
+      }
     return grads
 
 

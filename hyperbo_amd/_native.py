@@ -16,6 +16,7 @@ HBO_NOT_PD = 1
 KERNEL_SE, KERNEL_MATERN32, KERNEL_MATERN52, KERNEL_DOT = 0, 1, 2, 3
 MEAN_ZERO, MEAN_CONSTANT, MEAN_LINEAR, MEAN_LINEAR_MLP = 0, 1, 2, 3
 F32, F64 = 0, 1
+WARP_NONE, WARP_KUMAR = 0, 1
 ACQ_EI, ACQ_PI, ACQ_UCB = 0, 1, 2
 MAX_MLP_LAYERS = 8
 MAX_FEATURE_DIM = 256
@@ -36,7 +37,7 @@ class Model(C.Structure):
   _fields_ = [
       ('kernel_id', C.c_int32), ('mean_id', C.c_int32), ('dtype', C.c_int32), ('input_dim', C.c_int32),
       ('kernel_uses_mlp', C.c_int32), ('n_layers', C.c_int32), ('features', C.c_int32 * MAX_MLP_LAYERS),
-      ('n_lengthscale', C.c_int32), ('reserved0', C.c_int32),
+      ('n_lengthscale', C.c_int32), ('input_warp', C.c_int32),
       ('eps', C.c_double), ('signal_variance', C.c_double), ('noise_variance', C.c_double),
       ('constant', C.c_double), ('dot_prod_sigma', C.c_double), ('dot_prod_bias', C.c_double),
       ('linear_bias', C.c_double),
@@ -44,6 +45,11 @@ class Model(C.Structure):
       ('mlp_kernel', C.c_void_p * MAX_MLP_LAYERS), ('mlp_bias', C.c_void_p * MAX_MLP_LAYERS),
       ('linear_kernel', C.c_void_p),
   ]
+
+
+class ModelKumar(C.Structure):
+  """hbo_model_kumar: an hbo_model with input_warp = WARP_KUMAR followed by the squareplus-warped a, b ([input_dim] each)."""
+  _fields_ = [('base', Model), ('kumar_a', C.c_void_p), ('kumar_b', C.c_void_p)]
 
 
 class GradLayout(C.Structure):
@@ -70,6 +76,7 @@ SIGNATURES = {
     'hbo_version': (C.c_char_p, []),
     'hbo_device_count': (C.c_int, []),
     'hbo_grad_layout_of': (C.c_int, [C.POINTER(Model), C.POINTER(GradLayout)]),
+    'hbo_grad_layout_kumar_of': (C.c_int, [C.POINTER(Model), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     'hbo_gram': (C.c_int, [_P, C.POINTER(Model), _P, C.c_int64, _P, C.c_int64, C.c_int, _P]),
     'hbo_mean': (C.c_int, [_P, C.POINTER(Model), _P, C.c_int64, _P]),
     'hbo_dataset_create': (C.c_int, [_P, C.c_int, C.c_int, C.POINTER(Task), C.c_int, C.POINTER(_P)]),

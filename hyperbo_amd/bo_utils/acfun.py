@@ -191,6 +191,8 @@ def _hgp_value_and_grad(model, sub_dataset_key, x_queries, acq_id, acfun_param):
   HGP (acfun.py:72-82 under bayesopt.py:116-125).  One hbo_acq_grad per sample against that sample's cached factor (samples
   beyond the cache budget: factorised, used and released on the spot)."""
   from hyperbo_amd.basics import linalg
+  if getattr(model.cov_func, 'uses_kumar', False):   # (as hbo_acq_samples: HGP over Kumaraswamy kernels is out of scope)
+    raise nat.HboError(nat.HBO_ERR_UNSUPPORTED, 'HGP acquisition over a Kumaraswamy kernel is not supported')
   samples = model.get_model_params_samples()
   has_obs = model.has_observations(sub_dataset_key)
   dtype = _model.infer_dtype(model.dataset[sub_dataset_key].x, model.dataset[sub_dataset_key].y) if has_obs \

@@ -200,6 +200,8 @@ extern "C" int hbo_profile_get(hbo_ctx* c, char names[][32], double* ms, int32_t
 
 extern "C" int hbo_grad_layout_of(const hbo_model* m, hbo_grad_layout* out) {
   if (!m || !out) return HBO_ERR_ARG;
+  const char* why = nullptr;
+  if (int rc = check_input_warp(m, &why)) { hbo_g_err = std::string("hbo_grad_layout_of: ") + why; return rc; }
   int pos = 0;
   const bool dot = m->kernel_id == HBO_KERNEL_DOT;
   out->lengthscale = dot ? -1 : pos; if (!dot) pos += m->n_lengthscale;
@@ -220,7 +222,16 @@ extern "C" int hbo_grad_layout_of(const hbo_model* m, hbo_grad_layout* out) {
       fin = m->features[l];
     }
   }
+  if (is_kumar(m)) pos += 2 * m->input_dim;   // d/da, d/db at the end (hbo_grad_layout_kumar_of)
   out->total = pos;
+  return HBO_OK;
+}
+extern "C" int hbo_grad_layout_kumar_of(const hbo_model* m, int32_t* a_off, int32_t* b_off) {
+  if (!m || !a_off || !b_off) return HBO_ERR_ARG;
+  hbo_grad_layout lay;
+  if (int rc = hbo_grad_layout_of(m, &lay)) return rc;
+  *a_off = is_kumar(m) ? lay.total - 2 * m->input_dim : -1;
+  *b_off = is_kumar(m) ? lay.total - m->input_dim : -1;
   return HBO_OK;
 }
 
@@ -447,19 +458,29 @@ extern "C" int hbo_gram(hbo_ctx* c, const hbo_model* m, const void* x1, int64_t 
   hipStream_t st = c->stream;
   if (!x2) n2 = n1;
   if (n2 <= 0) return HBO_OK;
-  void *d1 = nullptr, *d2 = nullptr, *dout = nullptr;
+  void *d1 = nullptr, *d2 = nullptr, *dout = nullptr, *w1 = nullptr, *w2 = nullptr;
   FeatBuf f1, f2;
-  auto cleanup = [&]() { for (void* p : {d1, d2, dout}) if (p) hipFree(p); };
+  auto cleanup = [&]() { for (void* p : {d1, d2, dout, w1, w2}) if (p) hipFree(p); };
 #define HIPCHK_G(call) do { hipError_t e__ = (call); if (e__ != hipSuccess) { c->err = std::string(#call " failed: ") + hipGetErrorString(e__); cleanup(); return HBO_ERR_HIP; } } while (0)
   HIPCHK_G(hbo_malloc(c, &d1, (size_t)n1 * m->input_dim * es));
   HIPCHK_G(hipMemcpyAsync(d1, x1, (size_t)n1 * m->input_dim * es, hipMemcpyHostToDevice, st));
   const void* F1 = d1; const void* F2 = d1;
   if (m->kernel_uses_mlp) { rc = f1.ensure(c, m, n1); if (rc) { cleanup(); return rc; } run_mlp(c, m, d1, n1, f1.acts.data()); F1 = F2 = f1.acts[m->n_layers - 1]; }
+  if (is_kumar(m)) {   // kernel.py:190-217: K(w(x1), w(x2))
+    HIPCHK_G(hbo_malloc(c, &w1, (size_t)n1 * m->input_dim * es));
+    launch_kumar_forward(dtype, nullptr, 0, 0, d1, w1, nullptr, n1, m->input_dim, c->d_model, st);
+    F1 = F2 = w1;
+  }
   if (x2) {
     HIPCHK_G(hbo_malloc(c, &d2, (size_t)n2 * m->input_dim * es));
     HIPCHK_G(hipMemcpyAsync(d2, x2, (size_t)n2 * m->input_dim * es, hipMemcpyHostToDevice, st));
     F2 = d2;
     if (m->kernel_uses_mlp) { rc = f2.ensure(c, m, n2); if (rc) { cleanup(); return rc; } run_mlp(c, m, d2, n2, f2.acts.data()); F2 = f2.acts[m->n_layers - 1]; }
+    if (is_kumar(m)) {
+      HIPCHK_G(hbo_malloc(c, &w2, (size_t)n2 * m->input_dim * es));
+      launch_kumar_forward(dtype, nullptr, 0, 0, d2, w2, nullptr, n2, m->input_dim, c->d_model, st);
+      F2 = w2;
+    }
   }
   const int fdim = feature_dim(m);
   if (diag) {

@@ -29,6 +29,23 @@ static int mean_feature_dim(const hbo_model* m) {
   return 0;
 }
 static bool needs_mlp(const hbo_model* m) { return m->kernel_uses_mlp || m->mean_id == HBO_MEAN_LINEAR_MLP; }
+// Kumaraswamy input warp (hbo.h hbo_model_kumar): the covariance reads w(x) from a buffer of its own, the mean the raw x
+static bool is_kumar(const hbo_model* m) { return m->input_warp == HBO_WARP_KUMAR; }
+static const hbo_model_kumar* as_kumar(const hbo_model* m) { return reinterpret_cast<const hbo_model_kumar*>(m); }
+// host-only part of the check (no context needed: hbo_grad_layout_of runs it too)
+static int check_input_warp(const hbo_model* m, const char** why) {
+  if (m->input_warp == HBO_WARP_NONE) return HBO_OK;
+  if (m->input_warp != HBO_WARP_KUMAR) { *why = "unknown input_warp"; return HBO_ERR_UNSUPPORTED; }
+  if (m->kernel_uses_mlp) { *why = "a Kumaraswamy warp together with an MLP basis is not supported"; return HBO_ERR_UNSUPPORTED; }
+  if (!as_kumar(m)->kumar_a || !as_kumar(m)->kumar_b) { *why = "kumar_a / kumar_b missing"; return HBO_ERR_ARG; }
+  return HBO_OK;
+}
+// an hbo_model, or the hbo_model_kumar it heads, copied whole (callers that modify a copy of the model must not drop a, b)
+struct ModelCopy {
+  hbo_model_kumar k;
+  explicit ModelCopy(const hbo_model* m) { memset(&k, 0, sizeof k); if (is_kumar(m)) k = *as_kumar(m); else k.base = *m; }
+  hbo_model* get() { return &k.base; }
+};
 
 static int validate_model(hbo_ctx* c, const hbo_model* m) {
   if (!m) return fail(c, HBO_ERR_ARG, "model is null");
@@ -36,6 +53,8 @@ static int validate_model(hbo_ctx* c, const hbo_model* m) {
   if (m->kernel_id < 0 || m->kernel_id > HBO_KERNEL_DOT) return fail(c, HBO_ERR_ARG, "bad kernel_id");
   if (m->mean_id < 0 || m->mean_id > HBO_MEAN_LINEAR_MLP) return fail(c, HBO_ERR_ARG, "bad mean_id");
   if (m->input_dim <= 0 || m->input_dim > HBO_MAX_FEATURE_DIM) return fail(c, HBO_ERR_ARG, "bad input_dim");
+  const char* why = nullptr;   // (before the MLP fields: a Kumaraswamy model with an MLP basis is UNSUPPORTED, whatever they hold)
+  if (int rc = check_input_warp(m, &why)) return fail(c, rc, why);
   if (needs_mlp(m)) {
     if (m->n_layers <= 0 || m->n_layers > HBO_MAX_MLP_LAYERS) return fail(c, HBO_ERR_ARG, "bad n_layers");
     for (int l = 0; l < m->n_layers; ++l) {
@@ -85,6 +104,9 @@ static void fill_model_dev(ModelDev& h, const hbo_model* m) {
   }
   const int fm = mean_feature_dim(m);
   for (int d = 0; d < fm; ++d) h.lin_w[d] = host_elem(m->linear_kernel, m->dtype, d);
+  h.input_warp = m->input_warp;
+  if (is_kumar(m))
+    for (int d = 0; d < m->input_dim; ++d) { h.kumar_a[d] = host_elem(as_kumar(m)->kumar_a, m->dtype, d); h.kumar_b[d] = host_elem(as_kumar(m)->kumar_b, m->dtype, d); }
 }
 // fills ctx->h_model, uploads it and the MLP weights
 static int upload_model(hbo_ctx* c, const hbo_model* m) {
@@ -159,6 +181,8 @@ struct TaskHost {
   double* dmu = nullptr; double* fnorm = nullptr;
   double* dF = nullptr; double* dtmp = nullptr; size_t dF_elems = 0;   // MLP backward workspaces
   FeatBuf feat;
+  void* KW = nullptr; size_t kw_bytes = 0;     // Kumaraswamy: w(X), the covariance's features
+  double* KH = nullptr; size_t kh_bytes = 0;   // Kumaraswamy gradient: dw/da, dw/db (n x D doubles each)
 };
 struct hbo_dataset {
   int dtype = 0, D = 0, ntasks = 0, max_nblk = 0;
@@ -184,7 +208,7 @@ static void free_task(hbo_ctx* c, TaskHost* t) {
   if (!t) return;
   if (t->owns_inputs) for (void* p : {t->X, t->ysum, t->ydiv}) dev_free(c, p);
   for (void* p : {t->A, t->W, t->S, t->wscr, t->svec_shared ? nullptr : t->svec, (void*)t->dmu, (void*)t->fnorm}) dev_free(c, p);
-  for (void* p : {(void*)t->dF, (void*)t->dtmp}) dev_free(c, p);
+  for (void* p : {(void*)t->dF, (void*)t->dtmp, t->KW, (void*)t->KH}) dev_free(c, p);
   delete t;
 }
 
@@ -237,7 +261,8 @@ static void fill_desc(TaskDesc& d, TaskHost* t, const hbo_model* m, int dtype, i
   if ((role == OBJ_EKL || role == OBJ_EUC) && t->m + 1 > HBO_TILE) { d.naug = 1; d.last_src = t->m; d.nvec = t->m + 1; }   // see TaskDesc::nvec
   d.n = (int)t->n; d.npad = t->npad; d.nblk = t->nblk; d.m = t->m; d.ld = t->ld;
   const void* last = needs_mlp(m) ? t->feat.acts[m->n_layers - 1] : nullptr;
-  d.F = m->kernel_uses_mlp ? last : t->X;
+  d.F = m->kernel_uses_mlp ? last : (is_kumar(m) ? t->KW : t->X);
+  d.kh = is_kumar(m) ? t->KH : nullptr;
   d.fdim = feature_dim(m);
   d.fmean = mean_feature_dim(m);
   d.Fm = (m->mean_id == HBO_MEAN_LINEAR) ? t->X : (m->mean_id == HBO_MEAN_LINEAR_MLP ? last : nullptr);
@@ -245,9 +270,19 @@ static void fill_desc(TaskDesc& d, TaskHost* t, const hbo_model* m, int dtype, i
   (void)dtype;
 }
 
+// Kumaraswamy buffers of a task: w(X) for `rows` rows, and (want_h) dw/da, dw/db for its n rows
+static int ensure_kumar_buffers(hbo_ctx* c, const hbo_model* m, TaskHost* t, int64_t rows, bool want_h) {
+  const size_t wb = (size_t)std::max<int64_t>(rows, 1) * m->input_dim * esize(m->dtype);
+  if (t->kw_bytes < wb) { dev_free(c, t->KW); t->KW = nullptr; t->kw_bytes = 0; HIPCHK(c, dev_alloc(c, &t->KW, wb)); t->kw_bytes = wb; }
+  const size_t hb = want_h ? (size_t)2 * std::max<int64_t>(t->n, 1) * m->input_dim * sizeof(double) : 0;
+  if (t->kh_bytes < hb) { dev_free(c, t->KH); t->KH = nullptr; t->kh_bytes = 0; HIPCHK(c, dev_alloc(c, (void**)&t->KH, hb)); t->kh_bytes = hb; }
+  return HBO_OK;
+}
+
 // ---- GPCache -----------------------------------------------------------------------------
 struct hbo_cache {
   int dtype = 0, D = 0, m = 0;
+  int input_warp = 0;      // the cached inputs were warped (hbo_model::input_warp of the factorising model): appends warp the new rows
   TaskHost* t = nullptr;
   TaskDesc h_desc; TaskDesc* d_desc = nullptr;
   int* d_info = nullptr; int info = INT_MAX;

@@ -14,7 +14,7 @@ extern "C" int hbo_factor(hbo_ctx* c, const hbo_model* m, const void* x, int64_t
   const size_t es = esize(dtype);
   hipStream_t st = c->stream;
   hbo_cache* k = new hbo_cache();
-  k->dtype = dtype; k->D = m->input_dim; k->m = mcols;
+  k->dtype = dtype; k->D = m->input_dim; k->m = mcols; k->input_warp = m->input_warp;
   TaskHost* t = k->t = new TaskHost();
   t->n = n; t->m = mcols; t->npad = round_up(n, HBO_TILE); t->nblk = t->npad / HBO_TILE; t->ld = padded_ld(t->npad, dtype);
   auto bail = [&](int code) { hbo_cache_free(c, k); return code; };
@@ -30,6 +30,7 @@ extern "C" int hbo_factor(hbo_ctx* c, const hbo_model* m, const void* x, int64_t
   rc = ensure_task_workspace(c, dtype, t, true, mcols);
   if (rc) return bail(rc);
   if (needs_mlp(m)) { rc = t->feat.ensure(c, m, t->npad); if (rc) return bail(rc); }
+  if (is_kumar(m)) { rc = ensure_kumar_buffers(c, m, t, t->npad, false); if (rc) return bail(rc); }   // capacity npad rows (row appends)
   fill_desc(k->h_desc, t, m, dtype, ROLE_FACTOR);
   HIPCHK_K(hbo_malloc(c, (void**)&k->d_desc, sizeof(TaskDesc)));
   HIPCHK_K(hbo_malloc(c, (void**)&k->d_info, sizeof(int)));
@@ -42,6 +43,7 @@ extern "C" int hbo_factor(hbo_ctx* c, const hbo_model* m, const void* x, int64_t
   if (c->opt_poison) launch_poison(dtype, k->d_desc, 1, t->npad, st);
   { ProfScope ps(c, "features", 1);
     if (needs_mlp(m)) run_mlp(c, m, t->X, n, t->feat.acts.data());
+    if (is_kumar(m)) launch_kumar_forward(dtype, nullptr, 0, 0, t->X, t->KW, nullptr, n, m->input_dim, c->d_model, st);
     launch_aug_rows(dtype, k->d_desc, 1, t->npad, c->d_model, st); }
   HIPCHK_K(hipMemcpy2DAsync(k->resid, (size_t)t->npad * es, (char*)t->A + (size_t)t->npad * t->ld * es, (size_t)t->ld * es, (size_t)t->npad * es, mcols, hipMemcpyDeviceToDevice, st));
   { ProfScope ps(c, "gram", 1);
@@ -124,6 +126,7 @@ extern "C" int hbo_cache_append(hbo_ctx* c, const hbo_model* m, hbo_cache* k, co
   HIPCHK(c, hipSetDevice(c->device));
   TaskHost* t = k->t;
   if (k->dtype != m->dtype || k->D != m->input_dim) return fail(c, HBO_ERR_ARG, "hbo_cache_append: cache/model mismatch");
+  if (k->input_warp != m->input_warp) return fail(c, HBO_ERR_ARG, "hbo_cache_append: the cache was factorised with another input warp");
   if (k->info != INT_MAX) return HBO_NOT_PD;
   if (t->n + n_new > t->npad) return fail(c, HBO_ERR_UNSUPPORTED, "hbo_cache_append: capacity exhausted (re-factorise)");
   k->w3_valid = false;   // W changes: its bf16 planes are rebuilt at the next posterior call
@@ -155,6 +158,11 @@ extern "C" int hbo_cache_append(hbo_ctx* c, const hbo_model* m, hbo_cache* k, co
       flast = rows[m->n_layers - 1];
     }
     const void* Fq = m->kernel_uses_mlp ? flast : xrow;
+    if (is_kumar(m)) {   // the cached inputs are warped: so is the new row (the mean keeps reading the raw one)
+      void* wrow = (char*)t->KW + (size_t)n * m->input_dim * es;
+      launch_kumar_forward(dtype, nullptr, 0, 0, xrow, wrow, nullptr, 1, m->input_dim, c->d_model, st);
+      Fq = wrow;
+    }
     const void* Fmq = (m->mean_id == HBO_MEAN_LINEAR) ? xrow : (m->mean_id == HBO_MEAN_LINEAR_MLP ? flast : nullptr);
     launch_mean(dtype, Fmq, 1, fm, c->d_model, d_mu, st);
     launch_kdiag(dtype, Fq, 1, fdim, c->d_model, d_kd, st);
@@ -209,6 +217,7 @@ static int posterior(hbo_ctx* c, const hbo_model* m, hbo_cache* k, const void* x
   void* const* const mb = ov ? ov->mlp_b : c->d_mlp_b;
   const int dtype = m->dtype;
   if (k && (k->dtype != dtype || k->D != m->input_dim)) return fail(c, HBO_ERR_ARG, "posterior: cache/model mismatch");
+  if (k && k->input_warp != m->input_warp) return fail(c, HBO_ERR_ARG, "posterior: the cache was factorised with another input warp");
   const size_t es = esize(dtype);
   const int fdim = feature_dim(m), fm = mean_feature_dim(m);
   // Candidates are STREAMED: chunks of `CH` queries, so that the cross-Gram workspace (npad x CH) does not grow with M
@@ -245,6 +254,8 @@ static int posterior(hbo_ctx* c, const hbo_model* m, hbo_cache* k, const void* x
   { d_var = ws_get(c, WS_VAR + wso, (size_t)M * es); if (!d_var) return HBO_ERR_HIP; }
   if (ov) d_acq = ov->acq_dev;
   else if (acq_out) { d_acq = ws_get(c, WS_ACQ + wso, (size_t)M * es); if (!d_acq) return HBO_ERR_HIP; }
+  char* d_kwq = nullptr; const size_t kwq_b = al((size_t)mc_max * m->input_dim * es);   // Kumaraswamy: w(queries) per workspace
+  if (is_kumar(m)) { d_kwq = (char*)ws_get(c, WS_KW_Q + wso, kwq_b * nbuf); if (!d_kwq) return HBO_ERR_HIP; }
   if (needs_mlp(m)) for (int l = 0; l < m->n_layers; ++l) {
     fq_stride[l] = al((size_t)mc_max * m->features[l] * es);
     fq_acts[l] = (char*)ws_get(c, WS_FQ0 + l + wso, fq_stride[l] * nbuf); if (!fq_acts[l]) return HBO_ERR_HIP;
@@ -341,6 +352,11 @@ static int posterior(hbo_ctx* c, const hbo_model* m, hbo_cache* k, const void* x
         fq_last = acts[m->n_layers - 1];
       } }
     const void* Fq = m->kernel_uses_mlp ? fq_last : xq_d;
+    if (d_kwq) {
+      ProfScope ps(c, "kumar_forward", 1, sb);
+      launch_kumar_forward(dtype, nullptr, 0, 0, xq_d, d_kwq + b * kwq_b, nullptr, mc, m->input_dim, md, sb);
+      Fq = d_kwq + b * kwq_b;
+    }
     const void* Fmq = (m->mean_id == HBO_MEAN_LINEAR) ? (const void*)xq_d : (m->mean_id == HBO_MEAN_LINEAR_MLP ? fq_last : nullptr);
     launch_mean(dtype, Fmq, mc, fm, md, mu0_d, sb);
     launch_kdiag(dtype, Fq, mc, fdim, md, kd_d, sb);
@@ -488,6 +504,9 @@ extern "C" int hbo_acq_samples(hbo_ctx* c, const hbo_model* models, int32_t S, c
   const hbo_model* m0 = &models[0];
   for (int s = 0; s < S; ++s) {
     const hbo_model* m = &models[s];
+    // (before validate_model: a packed array element has no hbo_model_kumar tail to read)
+    if (m->input_warp != HBO_WARP_NONE)
+      return fail(c, HBO_ERR_UNSUPPORTED, "hbo_acq_samples: input-warped (Kumaraswamy) models are not supported; evaluate the samples with hbo_acq");
     int rc = validate_model(c, m);
     if (rc) return rc;
     bool same = m->dtype == m0->dtype && m->kernel_id == m0->kernel_id && m->mean_id == m0->mean_id && m->input_dim == m0->input_dim &&
@@ -627,6 +646,8 @@ extern "C" int hbo_acq_grad(hbo_ctx* c, const hbo_model* m, hbo_cache* k, const 
   if (rc) return rc;
   const int dtype = m->dtype;
   if (k && (k->dtype != dtype || k->D != m->input_dim)) return fail(c, HBO_ERR_ARG, "hbo_acq_grad: cache/model mismatch");
+  if (k && k->input_warp != m->input_warp) return fail(c, HBO_ERR_ARG, "hbo_acq_grad: the cache was factorised with another input warp");
+  const bool kumar = is_kumar(m);
   const size_t es = esize(dtype);
   hipStream_t st = c->stream;
   const int D = m->input_dim, fdim = feature_dim(m), fm = mean_feature_dim(m);
@@ -650,6 +671,8 @@ extern "C" int hbo_acq_grad(hbo_ctx* c, const hbo_model* m, hbo_cache* k, const 
   double* d_t1 = (double*)ws_get(c, WS_AG_T1, (size_t)mc_max * maxf * sizeof(double));
   double* d_dw = (double*)ws_get(c, WS_AG_DW, nparam * sizeof(double));   // weight-gradient sink of the shared MLP backward
   if (!d_xq || !d_mu0 || !d_kd || !d_acq || !d_gf || !d_dmu || !d_gx || !d_t0 || !d_t1 || !d_dw) return HBO_ERR_HIP;
+  void* d_kwq = kumar ? ws_get(c, WS_KW_Q, (size_t)mc_max * D * es) : nullptr;
+  if (kumar && !d_kwq) return HBO_ERR_HIP;
   void *d_K = nullptr, *d_L = nullptr, *d_B = nullptr;
   if (t) {
     d_K = ws_get(c, WS_AG_K, (size_t)mc_max * t->npad * es); d_L = ws_get(c, WS_AG_L, (size_t)mc_max * t->npad * es);
@@ -666,6 +689,7 @@ extern "C" int hbo_acq_grad(hbo_ctx* c, const hbo_model* m, hbo_cache* k, const 
     const void* fq_last = nullptr;
     if (mlp) { run_mlp(c, m, d_xq, mc, fq_acts); fq_last = fq_acts[L - 1]; }
     const void* Fq = m->kernel_uses_mlp ? fq_last : d_xq;
+    if (kumar) { launch_kumar_forward(dtype, nullptr, 0, 0, d_xq, d_kwq, nullptr, mc, D, c->d_model, st); Fq = d_kwq; }
     const void* Fmq = (m->mean_id == HBO_MEAN_LINEAR) ? d_xq : (m->mean_id == HBO_MEAN_LINEAR_MLP ? fq_last : nullptr);
     launch_mean(dtype, Fmq, mc, fm, c->d_model, d_mu0, st);
     launch_kdiag(dtype, Fq, mc, fdim, c->d_model, d_kd, st);
@@ -690,7 +714,8 @@ extern "C" int hbo_acq_grad(hbo_ctx* c, const hbo_model* m, hbo_cache* k, const 
       HIPCHK_D(hipMemsetAsync(d_gx, 0, (size_t)mc * D * sizeof(double), st));
       if (m->mean_id == HBO_MEAN_LINEAR) launch_acq_grad_mean(d_dmu, c->d_model, mc, D, d_gx, 1, st);
     } else {
-      HIPCHK_D(hipMemcpyAsync(d_gx, d_gf, (size_t)mc * D * sizeof(double), hipMemcpyDeviceToDevice, st));
+      if (kumar) launch_kumar_chain_dx(dtype, d_xq, mc, D, c->d_model, d_gf, d_gx, st);   // d acq / d w(x) * dw/dx
+      else HIPCHK_D(hipMemcpyAsync(d_gx, d_gf, (size_t)mc * D * sizeof(double), hipMemcpyDeviceToDevice, st));
       if (m->mean_id == HBO_MEAN_LINEAR) launch_acq_grad_mean(d_dmu, c->d_model, mc, D, d_gx, 1, st);
       if (m->mean_id == HBO_MEAN_LINEAR_MLP) { gmlp = d_t0; launch_acq_grad_mean(d_dmu, c->d_model, mc, flast, gmlp, 0, st); }
     }

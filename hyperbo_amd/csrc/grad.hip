@@ -16,17 +16,6 @@ namespace {
 // accumulators: SE/Matern: [0] sum G K, [1] tr G, [2+d] sum G dk/du ds_d^2, [2+fdim] sum G^2
 //               dot      : [0] sum G <fi,fj>, [1] tr G, [2] sum G,          [3] sum G^2
 // ---------------------------------------------------------------------------------------
-// outer-product vectors of a task: (pointer, row stride, count)
-template <typename T>
-__device__ __forceinline__ const T* outer_vecs(const TaskDesc& t, int obj, int64_t& stride, int& count) {
-  if (obj == OBJ_EUC) {
-    if (t.nvec) { stride = t.npad; count = t.nvec - 1; return static_cast<const T*>(t.svec) + t.npad; }   // data rows in svec columns 1..m
-    stride = t.ld; count = t.naug - 1;
-    return static_cast<const T*>(t.A) + (int64_t)t.npad * t.ld;
-  }
-  stride = t.npad; count = t.nvec ? t.nvec : t.naug;
-  return static_cast<const T*>(t.svec);
-}
 // MULTI = false: the NLL fast path (one outer-product vector, no Frobenius accumulator)
 template <typename T, bool MULTI, int KID>
 __global__ __launch_bounds__(256) void grad_contract_kernel(const TaskDesc* tasks, const ModelDev* __restrict__ md,

@@ -48,6 +48,8 @@ struct TaskDesc {
   double e_last, e_all, coef_c, coef_lh, coef_const;
   void* dmu;         // npad doubles: d f / d mu_i
   double* fnorm;     // 2 doubles: [0] |C0 - K1|_F, [1] |mu1 - mu0|  (EUC)
+  // Kumaraswamy input warp (kumar.hip): F holds w(X); kh (gradient calls) holds dw/da then dw/db, n x fdim doubles each
+  double* kh;
 };
 
 enum ObjectiveId { OBJ_NLL = 0, OBJ_EKL = 1, OBJ_EUC = 2 };
@@ -58,6 +60,9 @@ struct ModelDev {
   double sv, noise, eps, constant, dot_sigma, dot_bias, linear_bias;
   double inv_ls[HBO_MAX_FEATURE_DIM];   // 1/lengthscale per feature (broadcast if n_ls==1)
   double lin_w[HBO_MAX_FEATURE_DIM];    // linear mean weights
+  int input_warp;                       // HBO_WARP_NONE / HBO_WARP_KUMAR
+  double kumar_a[HBO_MAX_FEATURE_DIM];  // squareplus-warped Kumaraswamy a, b per input column (kumar.hip)
+  double kumar_b[HBO_MAX_FEATURE_DIM];
 };
 
 enum GemmMode {
@@ -254,6 +259,17 @@ void launch_mlp_zero_dF_batch(const MlpTaskDev* mt, int ntasks, int64_t max_n, i
 // over rows and tasks (fp64 atomics), d input into the other buffer when want_din
 void launch_dense_bwd_batch(int dtype, const MlpTaskDev* mt, int ntasks, int64_t max_n, int layer, int cur_is_dF, const void* w, double* dW,
                             double* db, int fin, int fout, int want_din, hipStream_t st);
+// ---- Kumaraswamy input warp (kumar.hip) ---------------------------------------------------------
+// w = 1 - (1 - x^a)^b per column of x (n x D) -> w; h (nullable, n x D doubles each): dw/da at h, dw/db at h + n D.
+// tasks != null: every task of the batch at once, x = tasks[z].X, w = tasks[z].F, h = tasks[z].kh (grid.y = task)
+void launch_kumar_forward(int dtype, const TaskDesc* tasks, int ntasks, int64_t max_n, const void* x, void* w, double* h, int64_t n, int D,
+                          const ModelDev* md, hipStream_t st);
+// d f / d a, d f / d b of a batch after the objective's inverse: per lower tile 2 D partial sums into partials
+// [task][max_nblk^2][2 D] (no atomics), then one ordered sum over tasks and tiles into out[2 D]
+void launch_kumar_grad(int dtype, const TaskDesc* tasks, int ntasks, int max_nblk, const ModelDev* md, int kernel_id, int D, int obj,
+                       double* partials, double* out, hipStream_t st);
+// gx[q][d] = gf[q][d] * dw/dx(xq[q][d])  (hbo_acq_grad)
+void launch_kumar_chain_dx(int dtype, const void* xq, int64_t M, int D, const ModelDev* md, const double* gf, double* gx, hipStream_t st);
 struct PostArgs {
   const void* Kxq; int64_t ldq; int npad; int n; int nblk;   // cross Gram (npad x ldq)
   const void* alpha;    // kinvy [npad] (first column)

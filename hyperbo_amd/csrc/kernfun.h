@@ -84,6 +84,18 @@ __device__ __forceinline__ T dk_du(int kid, T u, T k, T sv, const C& ec) {
   }
 }
 
+// outer-product vectors of a task: (pointer, row stride, count)
+template <typename T>
+__device__ __forceinline__ const T* outer_vecs(const TaskDesc& t, int obj, int64_t& stride, int& count) {
+  if (obj == OBJ_EUC) {
+    if (t.nvec) { stride = t.npad; count = t.nvec - 1; return static_cast<const T*>(t.svec) + t.npad; }   // data rows in svec columns 1..m
+    stride = t.ld; count = t.naug - 1;
+    return static_cast<const T*>(t.A) + (int64_t)t.npad * t.ld;
+  }
+  stride = t.npad; count = t.nvec ? t.nvec : t.naug;
+  return static_cast<const T*>(t.svec);
+}
+
 constexpr int DC = 16;     // feature chunk staged in LDS
 constexpr int SXS = 132;   // LDS row stride of a staged [DC][128] block
 

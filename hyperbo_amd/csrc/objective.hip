@@ -28,9 +28,10 @@ static int objective_local(hbo_ctx* c, const hbo_model* m_in, hbo_dataset* ds, i
   if (!c || !nll_sum || !m_in || (!ds && !sh)) return fail(c, HBO_ERR_ARG, "hbo_objective: null argument");
   if (objective != HBO_OBJ_NLL && objective != HBO_OBJ_EKL && objective != HBO_OBJ_EUC) return fail(c, HBO_ERR_ARG, "hbo_objective: unknown objective id");
   HIPCHK(c, hipSetDevice(c->device));
-  hbo_model mcopy = *m_in;
-  if (objective != HBO_OBJ_NLL) mcopy.eps = 0.0;   // objectives.py:63-65: cov_model = K + noise I, no jitter
-  const hbo_model* m = &mcopy;
+  ModelCopy mcopy(m_in);   // (a Kumaraswamy model keeps its a, b)
+  if (objective != HBO_OBJ_NLL) mcopy.get()->eps = 0.0;   // objectives.py:63-65: cov_model = K + noise I, no jitter
+  const hbo_model* m = mcopy.get();
+  const bool kumar = is_kumar(m);
   CholBoundScope bound_scope(c, 0.0);   // (set where the factorisation starts; cleared on every way out)
   const int obj = objective;
   const bool euc = obj == OBJ_EUC;
@@ -78,7 +79,7 @@ static int objective_local(hbo_ctx* c, const hbo_model* m_in, hbo_dataset* ds, i
   // (the single-workgroup evaluation needs 132 KB (fp64) / 68 KB (fp32) of LDS in one workgroup: a device that cannot give it -- any
   //  ARCH other than gfx950 the Makefile is pointed at -- takes the blocked pipeline instead of failing at launch)
   const bool small_ok = c->opt_small_fused && ds && small_eval_lds(ds->dtype) <= c->lds_per_block;
-  const bool lds_only = obj == OBJ_NLL && ds->max_nblk == 1 && small_ok && !needs_mlp(m);
+  const bool lds_only = obj == OBJ_NLL && ds->max_nblk == 1 && small_ok && !needs_mlp(m) && !(kumar && want_grad);
   void* small_scratch = nullptr;
   if (lds_only) {
     small_scratch = ws_get(c, WS_SMALL_W, (size_t)HBO_TILE * padded_ld(HBO_TILE, ds->dtype) * esize(ds->dtype));
@@ -112,6 +113,7 @@ static int objective_local(hbo_ctx* c, const hbo_model* m_in, hbo_dataset* ds, i
       if (rc) return rc;
     }
     if (needs_mlp(m)) { rc = t->feat.ensure(c, m, t->n); if (rc) return rc; }
+    if (kumar) { rc = ensure_kumar_buffers(c, m, t, t->n, want_grad); if (rc) return rc; }
     if (needs_mlp(m) && want_grad) {
       int maxf = m->input_dim;
       for (int l = 0; l < m->n_layers; ++l) maxf = std::max(maxf, (int)m->features[l]);
@@ -182,11 +184,14 @@ static int objective_local(hbo_ctx* c, const hbo_model* m_in, hbo_dataset* ds, i
       fin = m->features[l];
     }
   };
+  // Kumaraswamy: w(X) (and dw/da, dw/db) of every task in one launch, before the Gram -- the fused path stays the fused path
+  auto kumar_forward = [&]() { launch_kumar_forward(dtype, ds->d_desc, T, max_n, nullptr, nullptr, nullptr, 0, m->input_dim, c->d_model, st); };
   if (fused_small) {
     if (needs_mlp(m)) { ProfScope ps(c, "features", 1); mlp_forward(); }
+    if (kumar) { ProfScope ps(c, "kumar_forward", 1); kumar_forward(); }
     ProfScope ps(c, "small_eval", 1);
     launch_small_eval(dtype, ds->d_desc, T, c->d_model, m->kernel_id, feature_dim(m), ds->d_info, ds->d_nll,
-                      want_grad ? ds->d_gradout : nullptr, out_stride, want_grad && needs_mlp(m), st);
+                      want_grad ? ds->d_gradout : nullptr, out_stride, want_grad && (needs_mlp(m) || kumar), st);
   } else {
   if (c->opt_poison) launch_poison(dtype, ds->d_desc, T, max_npad, st);
   {
@@ -194,6 +199,7 @@ static int objective_local(hbo_ctx* c, const hbo_model* m_in, hbo_dataset* ds, i
     if (needs_mlp(m)) mlp_forward();
     launch_aug_rows(dtype, ds->d_desc, T, max_npad, c->d_model, st);
   }
+  if (kumar) { ProfScope ps(c, "kumar_forward", 1); kumar_forward(); }
   int max_naug = 1;
   for (int k = 0; k < T; ++k) max_naug = std::max(max_naug, ds->h_desc[k].naug);
   TrtriProgress trtri_pg;
@@ -292,6 +298,16 @@ static int objective_local(hbo_ctx* c, const hbo_model* m_in, hbo_dataset* ds, i
                            ds->d_partials + stride_task * T, max_nblk); }
   }
   }   // !fused_small
+  if (want_grad && kumar) {
+    // d f / d a, d f / d b (kumar.hip): per-tile partials, one ordered sum over tiles and tasks -> ds->d_mlpgrad[0, 2D)
+    ProfScope ps(c, "kumar_backward", 1);
+    const int D = m->input_dim;
+    const size_t tot = (size_t)2 * D;
+    if (ds->mlpgrad_elems < tot) { if (ds->d_mlpgrad) dev_free(c, ds->d_mlpgrad); HIPCHK(c, dev_alloc(c, (void**)&ds->d_mlpgrad, tot * sizeof(double))); ds->mlpgrad_elems = tot; }
+    double* part = static_cast<double*>(ws_get(c, WS_KU_PART, sizeof(double) * (size_t)T * max_nblk * max_nblk * 2 * D));
+    if (!part) return HBO_ERR_HIP;
+    launch_kumar_grad(dtype, ds->d_desc, T, max_nblk, c->d_model, m->kernel_id, D, obj, part, ds->d_mlpgrad, st);
+  }
   if (want_grad && needs_mlp(m)) {
     // d nll / d features -> MLP backward (hyperbo/gp_utils/basis_functions.py:24-36), summed over tasks; every pass one launch
     // for the whole batch (mlp.hip)
@@ -328,6 +344,12 @@ static int objective_local(hbo_ctx* c, const hbo_model* m_in, hbo_dataset* ds, i
       hmap[n_ls + 5 + fm] = lay.linear_bias;
     }
     int nseg = 0;
+    if (want_grad && kumar) {   // the 2 D Kumaraswamy leaves, already summed over the tasks
+      int32_t ao = -1, bo = -1;
+      hbo_grad_layout_kumar_of(m, &ao, &bo);
+      int* sg = hmap.data() + out_stride;
+      sg[0] = ao; sg[1] = 0; sg[2] = m->input_dim; sg[3] = bo; sg[4] = m->input_dim; sg[5] = m->input_dim; nseg = 2;
+    }
     if (want_grad && needs_mlp(m)) {
       int pos = 0, fin0 = m->input_dim;
       for (int l = 0; l < m->n_layers; ++l) {
@@ -358,7 +380,7 @@ static int objective_local(hbo_ctx* c, const hbo_model* m_in, hbo_dataset* ds, i
   const double* h_grad = h_nll + T;
   const int* h_info = reinterpret_cast<const int*>(h_grad + (size_t)T * out_stride);
   std::vector<double> h_mlp;
-  if (want_grad && needs_mlp(m)) {
+  if (want_grad && (needs_mlp(m) || kumar)) {
     h_mlp.resize(ds->mlpgrad_elems);
     HIPCHK(c, hipMemcpyAsync(h_mlp.data(), ds->d_mlpgrad, sizeof(double) * ds->mlpgrad_elems, hipMemcpyDeviceToHost, st));
   }
@@ -396,6 +418,14 @@ static int objective_local(hbo_ctx* c, const hbo_model* m_in, hbo_dataset* ds, i
         pos += wn;
         for (size_t i = 0; i < bn; ++i) grad_sum[lay.mlp_bias[l] + i] = notpd ? NAN : h_mlp[pos + i];
         pos += bn; fin0 = m->features[l];
+      }
+    }
+    if (kumar) {
+      int32_t ao = -1, bo = -1;
+      hbo_grad_layout_kumar_of(m, &ao, &bo);
+      for (int d = 0; d < m->input_dim; ++d) {
+        grad_sum[ao + d] = notpd ? NAN : h_mlp[d];
+        grad_sum[bo + d] = notpd ? NAN : h_mlp[m->input_dim + d];
       }
     }
   }

@@ -13,7 +13,7 @@ from hyperbo_amd import _native as nat
 from hyperbo_amd.gp_utils import mean as _mean
 
 
-def _make(kernel_id, name, uses_mlp):
+def _make(kernel_id, name, uses_mlp, uses_kumar=False):
   def matrix_map(params, vx1, vx2=None, warp_func=None, diag=False):
     """Returns the (n1, n2) kernel matrix; diag=True (with vx2=None) returns the (n1,) diagonal."""
     vx1 = np.asarray(vx1)
@@ -37,6 +37,7 @@ def _make(kernel_id, name, uses_mlp):
   matrix_map.__qualname__ = name
   matrix_map.kernel_id = kernel_id
   matrix_map.uses_mlp = uses_mlp
+  matrix_map.uses_kumar = uses_kumar
   return matrix_map
 
 
@@ -59,3 +60,18 @@ dot_product_mlp = _make(nat.KERNEL_DOT, 'kernel_mlp', True)
 squared_exponential_mlp = _make(nat.KERNEL_SE, 'kernel_mlp', True)
 matern32_mlp = _make(nat.KERNEL_MATERN32, 'kernel_mlp', True)
 matern52_mlp = _make(nat.KERNEL_MATERN52, 'kernel_mlp', True)
+
+# hyperbo/gp_utils/kernel.py:186-222 with_kumar_bases: the base kernel on Kumaraswamy-warped inputs (kumar.hip).  functools.wraps
+# gives the wrapper the base kernel's __name__, so 'mlp' in __name__ stays false (GP.initialize_params creates no MLP for them).
+squared_exponential_kumar = _make(nat.KERNEL_SE, 'squared_exponential', False, True)
+matern32_kumar = _make(nat.KERNEL_MATERN32, 'matern32', False, True)
+matern52_kumar = _make(nat.KERNEL_MATERN52, 'matern52', False, True)
+dot_product_kumar = _make(nat.KERNEL_DOT, 'dot_product', False, True)
+
+
+def init_kumar_warp_with_shape(key, params, input_shape):
+  """hyperbo/gp_utils/basis_functions.py:64-70: kumar_params = {'a': zeros(D), 'b': zeros(D)} (raw; squareplus(0) = 1, so the
+  warp starts as the identity).  `key` is unused (the flax initialiser is zeros); `input_shape` is (..., D)."""
+  del key
+  dim = int(input_shape[-1])
+  params.model['kumar_params'] = {'a': np.zeros((dim,), dtype=np.float64), 'b': np.zeros((dim,), dtype=np.float64)}

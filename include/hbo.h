@@ -59,7 +59,7 @@ typedef struct hbo_model {
   int32_t n_layers;         /* MLP depth (0 if unused) */
   int32_t features[HBO_MAX_MLP_LAYERS]; /* params.config['mlp_features'] */
   int32_t n_lengthscale;    /* 1 (broadcast) or the kernel's feature dimension */
-  int32_t reserved0;
+  int32_t input_warp;       /* 0: none; HBO_WARP_KUMAR: the pointer is really an hbo_model_kumar (below) */
   double eps;
   double signal_variance;
   double noise_variance;
@@ -73,8 +73,31 @@ typedef struct hbo_model {
   const void* linear_kernel;                     /* [Fin] (linear_mean['kernel'][:,0]) */
 } hbo_model;
 
+/* Kumaraswamy input warping (hyperbo/gp_utils/kernel.py:186-222 with_kumar_bases, basis_functions.py:48-70 KumarWarp): the
+ * *_kumar kernels evaluate the base kernel on w(x) = 1 - (1 - x^a)^b, per input column, a = squareplus(a_raw),
+ * b = squareplus(b_raw) (utils.py:59-71; the squareplus stays with the caller, as every other warp).  Only the covariance sees w(x):
+ * a linear mean still reads the raw x, as in the reference.  Inputs are not clamped (x < 0 gives NaN, as the formula does).
+ *   An hbo_model with input_warp = HBO_WARP_KUMAR is the first member of an hbo_model_kumar; kumar_a / kumar_b hold input_dim
+ *   elements of the model dtype each, ALREADY squareplus-warped.  Exactly a == 1 evaluates x^a as x and exactly b == 1 evaluates
+ *   w as x^a (1 - (1 - u) == u in exact arithmetic), so raw zeros give the plain kernel bit for bit.
+ *   Not supported (HBO_ERR_UNSUPPORTED): together with kernel_uses_mlp (not a reference combination), any other input_warp value,
+ *   and hbo_acq_samples.
+ *   Gradient: the layout of such a model ends with 2 D more doubles, d/da at [total - 2D, total - D) and d/db at [total - D, total)
+ *   (hbo_grad_layout_kumar_of), summed over rows and tasks in a fixed order (per-workgroup partials, one ordered finalisation):
+ *   dw/da = b (1 - x^a)^(b-1) x^a ln x,  dw/db = -(1 - x^a)^b ln(1 - x^a).  At x = 0 and x = 1 both are DEFINED as their limit 0
+ *   (a deliberate choice: 0 ln 0 never enters the sum; the reference's autodiff value at these endpoints has not been compared).
+ *   hbo_acq_grad chains d acq / d w(x) with dw/dx = a b x^(a-1) (1 - x^a)^(b-1), evaluated as written in the model dtype. */
+#define HBO_WARP_NONE 0
+#define HBO_WARP_KUMAR 1
+typedef struct hbo_model_kumar {
+  hbo_model base;
+  const void* kumar_a;   /* [input_dim], squareplus(a_raw) */
+  const void* kumar_b;   /* [input_dim], squareplus(b_raw) */
+} hbo_model_kumar;
+
 /* Flat layout (in doubles) of the gradient w.r.t. the WARPED parameters written by hbo_nll / hbo_objective.
- * Offsets of absent parameters are -1.  total = number of doubles. */
+ * Offsets of absent parameters are -1.  total = number of doubles (for a Kumaraswamy model: including the 2 D doubles of a, b
+ * at the end, which this struct has no field for -- hbo_grad_layout_kumar_of). */
 typedef struct hbo_grad_layout {
   int32_t lengthscale;      /* n_lengthscale entries */
   int32_t signal_variance;
@@ -107,6 +130,8 @@ int hbo_device_count(void);
 int hbo_device_info(int device, char* name_out, int32_t cap, int32_t* cus, int64_t* mem_bytes);
 
 int hbo_grad_layout_of(const hbo_model* model, hbo_grad_layout* out);
+/* offsets of d/da and d/db (input_dim doubles each) in the gradient of a Kumaraswamy model; -1 / -1 for a model without warp */
+int hbo_grad_layout_kumar_of(const hbo_model* model, int32_t* a_off, int32_t* b_off);
 
 /* ---- kernel.py:33-58 cov_func(params, vx1, vx2=None, diag=False) ------------------------ */
 /* out: [n1,n2] (x2 may be NULL -> x2 = x1), or [n1] when diag != 0 (requires x2 == NULL). */
