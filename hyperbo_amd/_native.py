@@ -13,6 +13,7 @@ import numpy as np
 
 HBO_OK, HBO_ERR_ARG, HBO_ERR_HIP, HBO_ERR_NODEV, HBO_ERR_UNSUPPORTED, HBO_ERR_COMM = 0, -1, -2, -3, -4, -5
 HBO_NOT_PD = 1
+HBO_NOT_CONVERGED = 2
 KERNEL_SE, KERNEL_MATERN32, KERNEL_MATERN52, KERNEL_DOT = 0, 1, 2, 3
 MEAN_ZERO, MEAN_CONSTANT, MEAN_LINEAR, MEAN_LINEAR_MLP = 0, 1, 2, 3
 F32, F64 = 0, 1
@@ -104,6 +105,10 @@ SIGNATURES = {
     'hbo_profile_get': (C.c_int, [_P, _P, C.POINTER(C.c_double), C.POINTER(C.c_int32),
                                   C.POINTER(C.c_int32)]),
     'hbo_set_option': (C.c_int, [_P, C.c_char_p, C.c_int64]),
+    'hbo_get_option': (C.c_int, [_P, C.c_char_p, C.POINTER(C.c_int64)]),
+    'hbo_sym_eig': (C.c_int, [_P, C.c_int, _P, C.c_int64, C.c_int32, _P, _P]),
+    'hbo_nll_spectral': (C.c_int, [_P, C.POINTER(Model), _P, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                   C.POINTER(C.c_double)]),
     'hbo_tune': (C.c_int, [_P, C.c_char_p, C.c_int64]),   # include/hbo_tune.h: measurement hooks, not the boundary
     'hbo_mfma_peak_probe': (C.c_int, [_P, C.c_double, C.POINTER(C.c_double)]),   # include/hbo_tune.h
     'hbo_comm_unique_id': (C.c_int, [_P]),
@@ -176,12 +181,20 @@ class Context:
       lib().hbo_ctx_destroy(self._h)
       self._h = _P()
 
+  # (the routing switch 'spectral' of hbo_set_option is documented on its own in include/hbo.h, not among these six tuning options;
+  #  set_option reaches it through hbo_tune, which passes every name it does not know to hbo_set_option)
   PUBLIC_OPTIONS = ('potrf_group', 'lookahead', 'small_nblk', 'pool_cap_mb', 'post_chunk', 'bf16x3')
 
   def set_option(self, name, value):
     """The options of include/hbo.h; any other name goes to the measurement hook hbo_tune (include/hbo_tune.h)."""
     f = lib().hbo_set_option if name in self.PUBLIC_OPTIONS else lib().hbo_tune
     self.check(f(self._h, name.encode(), int(value)))
+
+  def get_option(self, name):
+    """An option of include/hbo.h read back (also the read-only 'eig_sweeps'); unknown names raise."""
+    out = C.c_int64(0)
+    self.check(lib().hbo_get_option(self._h, name.encode(), C.byref(out)), allow_not_pd=False)
+    return out.value
 
   def profile_enable(self, level):
     self.check(lib().hbo_profile_enable(self._h, int(level)))
@@ -202,6 +215,12 @@ class Context:
 
 
 _default_ctx = None
+
+
+def spectral_enabled():
+  """True when the default context has the option 'spectral' set (include/hbo.h): the reference's SVD call sites then run on
+  hbo_sym_eig / hbo_nll_spectral.  Without a default context nothing can have set it (and nothing touches the GPU)."""
+  return _default_ctx is not None and bool(_default_ctx._h) and _default_ctx.get_option('spectral') == 1
 
 
 def default_context():

@@ -57,10 +57,40 @@ def inverse_spdmatrix_vector_product(spd_matrix, x, cached_cholesky=None):
   return solve_linear_system(spd_matrix, x)[1]
 
 
+def eigh(a):
+  """numpy.linalg.eigh on the device (hbo_sym_eig, fp64 Jacobi): (w, v) of a symmetric [n, n] or [count, n, n] array, only its
+  lower triangle read; w ascending, v[..., :, j] belongs to w[..., j]; both float64.  A matrix that held NaN / inf or did not
+  converge comes back NaN (the library's HBO_NOT_CONVERGED)."""
+  a = np.asarray(a)
+  dtype = np.float32 if a.dtype == np.float32 else np.float64
+  if a.ndim not in (2, 3) or a.shape[-1] != a.shape[-2]:
+    raise ValueError(f'eigh takes [n, n] or [count, n, n] matrices, got shape {a.shape}')
+  a3 = np.ascontiguousarray(a.reshape((-1,) + a.shape[-2:]), dtype=dtype)
+  count, n = a3.shape[0], a3.shape[-1]
+  w = np.empty((count, n), dtype=np.float64)
+  v = np.empty((count, n, n), dtype=np.float64)
+  ctx = nat.default_context()
+  rc = nat.lib().hbo_sym_eig(ctx.handle, nat.dtype_code(dtype), nat.ptr(a3), n, count, nat.ptr(w), nat.ptr(v))
+  if rc != nat.HBO_NOT_CONVERGED:
+    ctx.check(rc, allow_not_pd=False)
+  return (w[0], v[0]) if a.ndim == 2 else (w, v)
+
+
 def svd_matrix_sqrt(cov):
   """linalg.py:113-126: A with A A^T = cov, columns truncated to the numerical rank (host LAPACK; only used
-  by the non-partial KL, outside the device hot path)."""
+  by the non-partial KL, outside the device hot path).  With the context option 'spectral' on, the decomposition is the device's
+  eigh: cov = V diag(w) V^T, A = V sqrt(|w|) ordered by |w| descending -- the SVD's column space, with the same rank tolerance
+  computed from s = |w| (the KL that uses A does not depend on the columns' signs or order)."""
   cov = np.asarray(cov)
+  if nat.spectral_enabled():
+    w, v = eigh(cov)
+    s = np.abs(w)
+    order = np.argsort(-s, kind='stable')
+    s, v = s[order], v[:, order]
+    out_dtype = cov.dtype if cov.dtype in (np.float32, np.float64) else np.float64
+    tol = s.max() * np.finfo(out_dtype).eps / 2. * np.sqrt(2 * cov.shape[0] + 1.)
+    rank = np.count_nonzero(s > tol)
+    return (v * np.sqrt(s)[None, :])[:, :rank].astype(out_dtype)
   u, s, _ = np.linalg.svd(cov)
   factor_ = u * np.sqrt(s[..., None, :])
   tol = s.max() * np.finfo(s.dtype).eps / 2. * np.sqrt(2 * cov.shape[0] + 1.)

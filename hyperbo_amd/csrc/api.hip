@@ -86,7 +86,7 @@ extern "C" int hbo_ctx_destroy(hbo_ctx* c) {
   delete c;
   return HBO_OK;
 }
-// The six options of the boundary (include/hbo.h).
+// The seven options of the boundary (include/hbo.h).
 extern "C" int hbo_set_option(hbo_ctx* c, const char* name, int64_t value) {
   if (!c || !name) return HBO_ERR_ARG;
   if (!strcmp(name, "potrf_group")) { if (value < 0 || value > 16) return fail(c, HBO_ERR_ARG, "potrf_group in 0..16 (0: auto)"); c->opt_group = (int)value; return HBO_OK; }
@@ -103,6 +103,20 @@ extern "C" int hbo_set_option(hbo_ctx* c, const char* name, int64_t value) {
   }
   if (!strcmp(name, "post_chunk")) { if (value < 128 || value > 65536) return fail(c, HBO_ERR_ARG, "post_chunk in 128..65536"); c->opt_post_chunk = (int)value; return HBO_OK; }
   if (!strcmp(name, "bf16x3")) { c->opt_post_bf16x3 = c->opt_syrk_bf16x3 = c->opt_trtri_bf16x3 = c->opt_lauum_bf16x3 = value != 0; return HBO_OK; }
+  if (!strcmp(name, "spectral")) { if (value < 0 || value > 1) return fail(c, HBO_ERR_ARG, "spectral is 0 or 1"); c->opt_spectral = (int)value; return HBO_OK; }
+  return fail(c, HBO_ERR_ARG, std::string("unknown option ") + name);
+}
+// The same options read back (plus the read-only eig_sweeps).  bf16x3 reads as 1 only when all four of its legs are on.
+extern "C" int hbo_get_option(hbo_ctx* c, const char* name, int64_t* out) {
+  if (!c || !name || !out) return fail(c, HBO_ERR_ARG, "hbo_get_option: null argument");
+  if (!strcmp(name, "potrf_group")) { *out = c->opt_group; return HBO_OK; }
+  if (!strcmp(name, "lookahead")) { *out = c->opt_lookahead; return HBO_OK; }
+  if (!strcmp(name, "small_nblk")) { *out = c->opt_small_nblk; return HBO_OK; }
+  if (!strcmp(name, "pool_cap_mb")) { *out = (int64_t)(c->pool_cap >> 20); return HBO_OK; }
+  if (!strcmp(name, "post_chunk")) { *out = c->opt_post_chunk; return HBO_OK; }
+  if (!strcmp(name, "bf16x3")) { *out = c->opt_post_bf16x3 && c->opt_syrk_bf16x3 && c->opt_trtri_bf16x3 && c->opt_lauum_bf16x3; return HBO_OK; }
+  if (!strcmp(name, "spectral")) { *out = c->opt_spectral; return HBO_OK; }
+  if (!strcmp(name, "eig_sweeps")) { *out = c->eig_last_sweeps; return HBO_OK; }
   return fail(c, HBO_ERR_ARG, std::string("unknown option ") + name);
 }
 // Measurement hooks (include/hbo_tune.h): placement and overlap knobs of the schedules, for the A/B tools under tools/ and

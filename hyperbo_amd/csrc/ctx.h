@@ -97,6 +97,8 @@ struct hbo_ctx {
   int lds_per_block = 160 * 1024;   // hipDeviceProp_t::sharedMemPerBlock of the context's device (hbo_ctx_create)
   int opt_gram_mfma = 32;      // hbo_tune("gram_mfma"): fp32 Gram matrices of the stationary covariances with at least this many features take gram_mfma_kernel (0: never)
   int opt_small_fused = 1;     // hbo_tune("small_fused"): batches whose tasks all have n <= 128 take the single-workgroup evaluation (small.hip)
+  int opt_spectral = 0;        // hbo_set_option("spectral"): stored for the Python layer, which routes its SVD call sites by it (hbo.h)
+  int eig_last_sweeps = 0;     // outer Jacobi sweeps of the last hbo_sym_eig / hbo_nll_spectral (largest over its batches; eig.hip)
   int opt_post_serial = 0;     // hbo_tune("post_serial"): the streamed posterior's producer side (cross Gram) on the SAME stream as its products: isolated stage times
   int opt_fault_shard = 0;     // hbo_tune("fault_shard"): ONE-SHOT fault injection for the tests of the sharded objective's failure paths
   bool comm_aborted = false;   // set by comm_abort: sharded calls fail with HBO_ERR_COMM until hbo_comm_init builds a new communicator

@@ -71,6 +71,12 @@ def sample_from_gp(key, mean_func, cov_func, params, x, warp_func=None, num_samp
   cov = cov + np.eye(n) * (float(np.squeeze(noise_variance)) + eps)
   if method == 'cholesky':
     factor, _ = linalg.solve_linear_system(cov, np.zeros((n, 1)))
+  elif nat.spectral_enabled():
+    # context option 'spectral': the factor from the device eigensolver, V sqrt(|w|) ('svd') or V sqrt(w) ('eigh', NaN columns for
+    # negative w as jax's multivariate_normal gives)
+    w, v = linalg.eigh(cov)
+    with np.errstate(invalid='ignore'):
+      factor = v * np.sqrt(np.abs(w) if method == 'svd' else w)[None, :]
   elif method == 'svd':
     u, sv, _ = np.linalg.svd(cov)
     factor = u * np.sqrt(sv[None, :])

@@ -113,6 +113,22 @@ class DeviceDataset:
     except Exception:  # pylint: disable=broad-except
       pass
 
+  def evaluate_spectral(self, mean_func, cov_func, params, warp_func=None):
+    """The SVD variant of the NLL on the device (hbo_nll_spectral): (per-task dict, per-task min |eigenvalue| dict), keyed like
+    self.keys.  Tasks that held NaN / inf or did not converge are NaN."""
+    if self.num_tasks == 0:
+      return {}, {}
+    bm = _model.BuiltModel(mean_func, cov_func, params, warp_func, self.dtype, self.input_dim)
+    nll = C.c_double(0.0)
+    pt = (C.c_double * self.num_tasks)()
+    mn = (C.c_double * self.num_tasks)()
+    rc = nat.lib().hbo_nll_spectral(self.ctx.handle, bm.ref(), self._h, C.byref(nll), pt, mn)
+    if rc != nat.HBO_NOT_CONVERGED:
+      self.ctx.check(rc, allow_not_pd=False)
+    vals = dict(zip(self.device_order_keys, list(pt)))
+    mins = dict(zip(self.device_order_keys, list(mn)))
+    return {k: vals[k] for k in self.keys}, {k: mins[k] for k in self.keys}
+
   def evaluate_sharded(self, mean_func, cov_func, params, warp_func=None, objective=OBJ_NLL, comm=None):
     """This rank's shard through hbo_objective_sharded: the sums over ALL ranks of `comm`'s communicator, reduced on the device
     and all-reduced in place (RCCL over xGMI).  Returns (value_sum, task_count, flat grad_sum (warped), BuiltModel)."""
@@ -241,6 +257,20 @@ def neg_log_marginal_likelihood(mean_func, cov_func, params, dataset, warp_func=
                                 return_key2nll=False, use_cholesky=True):
   """Negative log marginal likelihood of a (multi-task) GP: mean over included sub-datasets
   (objectives.py:109-210).  use_cholesky=False is the SVD variant (objectives.py:157-176)."""
+  if not use_cholesky and nat.spectral_enabled():
+    # context option 'spectral': the same value from the device eigensolver over the resident tasks (hbo_nll_spectral)
+    dev, owned = _as_device(dataset, exclude_aligned)
+    try:
+      key2nll, key2min = dev.evaluate_spectral(mean_func, cov_func, params, warp_func)
+    finally:
+      if owned:
+        dev.close()
+    for k, s_min in key2min.items():
+      if s_min <= 0:
+        logging.warning('Covariance matrix is low rank. min |eigenvalue| = %s (sub-dataset %s)', s_min, k)
+    total = sum(key2nll.values()) / len(key2nll) if key2nll else 0.
+    total = _apply_priors(total, params, warp_func)
+    return (total, key2nll) if return_key2nll else total
   if not use_cholesky:
     if isinstance(dataset, (DeviceDataset, DeviceBatch)):
       raise TypeError('use_cholesky=False takes the host dataset dict (the SVD runs on host LAPACK)')

@@ -33,6 +33,7 @@ extern "C" {
 #define HBO_ERR_UNSUPPORTED (-4)
 #define HBO_ERR_COMM (-5)
 #define HBO_NOT_PD 1
+#define HBO_NOT_CONVERGED 2   /* hbo_sym_eig / hbo_nll_spectral: the sweep cap was hit or the input held NaN / inf (outputs NaN-filled) */
 
 /* closed registries: hyperbo/bo_utils/const.py:22-50 */
 enum hbo_kernel_id { HBO_KERNEL_SE = 0, HBO_KERNEL_MATERN32 = 1, HBO_KERNEL_MATERN52 = 2, HBO_KERNEL_DOT = 3 };
@@ -257,6 +258,36 @@ int hbo_profile_get(hbo_ctx* ctx, char names[][32], double* ms, int32_t* launche
  *                         the fp32-MFMA product) -- cfg 3's EI 97 -> 59 ms; and so do the factorisation's trailing updates, the inverse's
  *                         upper levels and K^-1 = W^T W of those covariances (hbo_tune chol_f16x2, default on: cfg 3's factor 21.5 -> 17.6 ms) */
 int hbo_set_option(hbo_ctx* ctx, const char* name, int64_t value);
+/*   spectral        0/1   (default 0) route the reference's SVD call sites -- neg_log_marginal_likelihood(use_cholesky=False),
+ *                         GP / HGP.stats, svd_matrix_sqrt, sample_from_gp(method='svd' | 'eigh') -- to hbo_sym_eig / hbo_nll_spectral
+ *                         instead of host LAPACK.  The library only stores it: the Python layer reads it back and routes its calls.
+ * hbo_get_option reads an option back (the same names; unknown names are an error), and the read-only eig_sweeps: the outer Jacobi
+ * sweeps of the last hbo_sym_eig / hbo_nll_spectral call (largest over its batches). */
+int hbo_get_option(hbo_ctx* ctx, const char* name, int64_t* out);
+
+/* ---- symmetric eigensolver: the device form of the reference's SVD routines (objectives.py:157-176, linalg.py:113-126,
+ *      gp.py:198-240 multivariate_normal 'svd' / 'eigh').  fp64 two-sided Jacobi (csrc/eig.hip): the matrix is padded to a multiple
+ *      of 64 and cut into blocks of 32; a sweep pairs the blocks round-robin, each pair's 64 x 64 sub-matrix is diagonalised in LDS
+ *      by one workgroup (32 disjoint rotations per step, Rutishauser's formulas, exact-zero rotations skipped so padding never
+ *      couples) and the two-sided update J_k^T A_(k,l) J_l is applied tile by tile.  A problem stops when off(A) = |A - diag A|_F
+ *      <= sqrt(npad) eps |A|_F (per-tile partials, one fixed-order sum: identical calls are bit-identical) or after a sweep without
+ *      any rotation; at most 40 sweeps (over the cap: HBO_NOT_CONVERGED).  Each diagonalised pair leaves its eigenvalues sorted, the
+ *      larger ones in the lower block, which halves the sweep count on Gram matrices.  All arithmetic is fp64; an fp32 input is promoted first.
+ *      Matrices of the same padded order run as one batch.  What stays on the host: the promotion, the exact power-of-two scaling
+ *      of the input (max |a| into [0.5, 1)), the ordering of the eigenvalues and the O(n) sums of the NLL. */
+/* a: [count, n, n] (dtype), only the lower triangle is read.  w_out: [count, n] ascending (numpy.linalg.eigh).  v_out (nullable):
+ * [count, n, n], column j belongs to w[j].  w_out does not depend on whether v_out is given (bit for bit).  A matrix that did not
+ * converge or held NaN / inf gets NaN outputs and the call returns HBO_NOT_CONVERGED. */
+int hbo_sym_eig(hbo_ctx* ctx, int dtype, const void* a, int64_t n, int32_t count, double* w_out, double* v_out);
+/* The SVD variant of the NLL (objectives.py:157-176) over the device-resident tasks of `ds`: per task, K = Gram + (noise + eps) I
+ * (built on the device exactly as hbo_gram, the diagonal added in the model dtype, then promoted to fp64) = Q diag(w) Q^T, the
+ * column y~ = (Y - mu) 1 carried through the rotations (no eigenvectors are formed), and
+ *   nll = 0.5 (sum_i (Q^T y~)_i^2 / w_i + m^2 (sum_i log |w_i| + n log 2 pi))
+ * -- the reference's value incl. the (m,m)+scalar broadcast for m > 1 (s = |w|; K^-1 keeps the sign of w as the SVD's V S^-1 U^T
+ * does; an exact zero eigenvalue gives the IEEE result, inf or NaN, as its 1/s).  Output conventions of hbo_nll (sums over tasks,
+ * per task in the dataset's order); abs_eig_min_per_task (nullable): min |w_i|, the reference's s[-1].  No gradient. */
+int hbo_nll_spectral(hbo_ctx* ctx, const hbo_model* model, hbo_dataset* ds, double* nll_sum, double* nll_per_task,
+                     double* abs_eig_min_per_task);
 
 /* ---- multi-GPU: one process per GPU; sum-all-reduce of [nll, grads] over RCCL (xGMI) ------ */
 #define HBO_UNIQUE_ID_BYTES 128
