@@ -98,6 +98,7 @@ SIGNATURES = {
                           C.c_double, _P]),
     'hbo_acq_samples': (C.c_int, [_P, _P, C.c_int32, _P, C.c_int64, _P, C.c_int32, _P, C.c_int64, C.c_int, C.POINTER(C.c_double),
                                   C.POINTER(C.c_double), C.c_double, _P]),
+    'hbo_nll_samples': (C.c_int, [_P, _P, C.c_int32, _P, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     'hbo_spd_solve': (C.c_int, [_P, C.c_int, _P, C.c_int64, _P, C.c_int32, _P, _P, _P,
                                 C.POINTER(C.c_double)]),
     'hbo_chol_solve': (C.c_int, [_P, C.c_int, _P, C.c_int64, _P, C.c_int32, _P]),

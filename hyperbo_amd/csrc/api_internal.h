@@ -72,6 +72,15 @@ static int validate_model(hbo_ctx* c, const hbo_model* m) {
   return HBO_OK;
 }
 
+// S hyper-parameter samples of ONE model family (hbo_acq_samples, hbo_nll_samples): same dtype, covariance, mean, input_dim and
+// MLP architecture -- everything that shapes a launch; only the values differ
+static bool same_model_family(const hbo_model* m, const hbo_model* m0) {
+  bool same = m->dtype == m0->dtype && m->kernel_id == m0->kernel_id && m->mean_id == m0->mean_id && m->input_dim == m0->input_dim &&
+              m->kernel_uses_mlp == m0->kernel_uses_mlp && m->n_lengthscale == m0->n_lengthscale && needs_mlp(m) == needs_mlp(m0);
+  if (same && needs_mlp(m0)) { same = m->n_layers == m0->n_layers; for (int l = 0; same && l < m0->n_layers; ++l) same = m->features[l] == m0->features[l]; }
+  return same;
+}
+
 static double host_elem(const void* p, int dtype, int64_t i) {
   return dtype == HBO_F64 ? ((const double*)p)[i] : (double)((const float*)p)[i];
 }
@@ -260,7 +269,8 @@ static void fill_desc(TaskDesc& d, TaskHost* t, const hbo_model* m, int dtype, i
   d.last_src = d.naug - 1;
   if ((role == OBJ_EKL || role == OBJ_EUC) && t->m + 1 > HBO_TILE) { d.naug = 1; d.last_src = t->m; d.nvec = t->m + 1; }   // see TaskDesc::nvec
   d.n = (int)t->n; d.npad = t->npad; d.nblk = t->nblk; d.m = t->m; d.ld = t->ld;
-  const void* last = needs_mlp(m) ? t->feat.acts[m->n_layers - 1] : nullptr;
+  // (a task whose activations were never allocated -- hbo_nll_samples keeps its own -- gets null; the caller sets F / Fm)
+  const void* last = (needs_mlp(m) && (int)t->feat.acts.size() >= m->n_layers) ? t->feat.acts[m->n_layers - 1] : nullptr;
   d.F = m->kernel_uses_mlp ? last : (is_kumar(m) ? t->KW : t->X);
   d.kh = is_kumar(m) ? t->KH : nullptr;
   d.fdim = feature_dim(m);

@@ -509,10 +509,7 @@ extern "C" int hbo_acq_samples(hbo_ctx* c, const hbo_model* models, int32_t S, c
       return fail(c, HBO_ERR_UNSUPPORTED, "hbo_acq_samples: input-warped (Kumaraswamy) models are not supported; evaluate the samples with hbo_acq");
     int rc = validate_model(c, m);
     if (rc) return rc;
-    bool same = m->dtype == m0->dtype && m->kernel_id == m0->kernel_id && m->mean_id == m0->mean_id && m->input_dim == m0->input_dim &&
-                m->kernel_uses_mlp == m0->kernel_uses_mlp && m->n_lengthscale == m0->n_lengthscale && needs_mlp(m) == needs_mlp(m0);
-    if (same && needs_mlp(m0)) { same = m->n_layers == m0->n_layers; for (int l = 0; same && l < m0->n_layers; ++l) same = m->features[l] == m0->features[l]; }
-    if (!same) return fail(c, HBO_ERR_ARG, "hbo_acq_samples: the samples must share dtype, covariance, mean and MLP architecture");
+    if (!same_model_family(m, m0)) return fail(c, HBO_ERR_ARG, "hbo_acq_samples: the samples must share dtype, covariance, mean and MLP architecture");
   }
   prof_begin(c);
   const int dtype = m0->dtype;

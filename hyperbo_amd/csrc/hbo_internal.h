@@ -243,17 +243,21 @@ void launch_dense_bwd(int dtype, const void* in, const void* out, const void* w,
 // write_back: also store K^-1 (full n x n square in S), s = K^-1 r (svec) and d f / d mu (dmu) for the feature-gradient kernels of
 // an MLP model (grad_feat_kernel, grad_feat_mean_kernel), which follow as launches of their own
 int small_eval_lds(int dtype);
+// tasks_per_model > 0: md holds one model per run of that many consecutive tasks (hbo_nll_samples: sample-major S x T batch)
 void launch_small_eval(int dtype, const TaskDesc* tasks, int ntasks, const ModelDev* md, int kernel_id, int fdim, int* info,
-                       double* nll_out, double* grad_out, int out_stride, int write_back, hipStream_t st);
+                       double* nll_out, double* grad_out, int out_stride, int write_back, hipStream_t st, int tasks_per_model = 0);
 // MLP basis of a whole batch, one launch per layer (mlp.hip): per-task pointers
 struct MlpTaskDev {
   const void* x;                        // n x D inputs
   void* acts[HBO_MAX_MLP_LAYERS];       // n x f_l activations
   double* dF; double* dtmp;             // backward: gradient w.r.t. a layer's output, ping-pong
   int64_t n;
+  int64_t model;                        // forward: the task reads the weights at w + model * fin * fout, b + model * fout (0: shared)
 };
+// model_weights != 0: w / b hold one weight set per model, back to back ([models][fin][fout], [models][fout]), and task t uses set
+// mt[t].model (hbo_nll_samples: S parameter samples over T tasks in one launch per layer); 0: one set for every task
 void launch_mlp_forward_batch(int dtype, const MlpTaskDev* mt, int ntasks, int64_t max_n, int layer, const void* w, const void* b, int fin,
-                              int fout, hipStream_t st);
+                              int fout, hipStream_t st, int model_weights = 0);
 void launch_mlp_zero_dF_batch(const MlpTaskDev* mt, int ntasks, int64_t max_n, int flast, hipStream_t st);
 // one layer of the backward pass for every task: dz in place on the current buffer (dF when cur_is_dF, else dtmp), dW / db summed
 // over rows and tasks (fp64 atomics), d input into the other buffer when want_din

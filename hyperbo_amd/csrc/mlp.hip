@@ -9,10 +9,11 @@ namespace {
 // out[i][o] = tanh(sum_k in[i][k] w[k][o] + b[o]) for every task of the batch; grid.y = task
 template <typename T>
 __global__ void dense_tanh_batch_kernel(const MlpTaskDev* __restrict__ mt, int layer, const T* __restrict__ w, const T* __restrict__ b,
-                                        int fin, int fout) {
+                                        int fin, int fout, int model_weights) {
   const MlpTaskDev& t = mt[blockIdx.y];
   const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= t.n * fout) return;
+  if (model_weights) { w += t.model * fin * fout; b += t.model * fout; }   // (this task's weight set)
   const T* in = static_cast<const T*>(layer ? t.acts[layer - 1] : t.x);
   T* out = static_cast<T*>(t.acts[layer]);
   const int64_t i = idx / fout;
@@ -69,11 +70,11 @@ __global__ void dense_bwd_in_batch_kernel(const MlpTaskDev* __restrict__ mt, int
 }  // namespace
 
 void launch_mlp_forward_batch(int dtype, const MlpTaskDev* mt, int ntasks, int64_t max_n, int layer, const void* w, const void* b, int fin,
-                              int fout, hipStream_t st) {
+                              int fout, hipStream_t st, int model_weights) {
   if (ntasks <= 0 || max_n <= 0) return;
   dim3 grid((unsigned)((max_n * fout + 255) / 256), (unsigned)ntasks);
-  if (dtype == HBO_F64) hipLaunchKernelGGL((dense_tanh_batch_kernel<double>), grid, dim3(256), 0, st, mt, layer, (const double*)w, (const double*)b, fin, fout);
-  else hipLaunchKernelGGL((dense_tanh_batch_kernel<float>), grid, dim3(256), 0, st, mt, layer, (const float*)w, (const float*)b, fin, fout);
+  if (dtype == HBO_F64) hipLaunchKernelGGL((dense_tanh_batch_kernel<double>), grid, dim3(256), 0, st, mt, layer, (const double*)w, (const double*)b, fin, fout, model_weights);
+  else hipLaunchKernelGGL((dense_tanh_batch_kernel<float>), grid, dim3(256), 0, st, mt, layer, (const float*)w, (const float*)b, fin, fout, model_weights);
 }
 void launch_mlp_zero_dF_batch(const MlpTaskDev* mt, int ntasks, int64_t max_n, int flast, hipStream_t st) {
   if (ntasks <= 0 || max_n <= 0) return;

@@ -43,6 +43,7 @@ struct SmallArgs {
   int out_stride;
   int fdim;
   int write_back;      // MLP models: K^-1 (full square) -> S, s -> svec, d f / d mu -> dmu for the feature-gradient kernels that follow
+  int tasks_per_model; // 0: md is the model of every task; > 0: workgroup b reads md + b / tasks_per_model (hbo_nll_samples: S samples x T tasks)
 };
 
 template <typename T, int KID>
@@ -61,7 +62,7 @@ __global__ __launch_bounds__(SMALL_THREADS) void small_eval_kernel(SmallArgs g) 
   double* s_tot = swred + SMALL_WAVES * (DC + 4);             // [SM_RED]
 
   const TaskDesc& t = g.tasks[blockIdx.x];
-  const ModelDev* md = g.md;
+  const ModelDev* md = g.tasks_per_model ? g.md + blockIdx.x / g.tasks_per_model : g.md;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int l15 = lane & 15, lq = lane >> 4;
   const int n = t.n, fdim = g.fdim;
@@ -478,8 +479,8 @@ void small_eval_t(const SmallArgs& a, int ntasks, int kernel_id, hipStream_t st)
 int small_eval_lds(int dtype) { return dtype == HBO_F64 ? small_lds_bytes<double>() : small_lds_bytes<float>(); }
 // NLL (+ gradient block) of every task of a batch whose tasks all have n <= 128, one workgroup per task, one launch.
 void launch_small_eval(int dtype, const TaskDesc* tasks, int ntasks, const ModelDev* md, int kernel_id, int fdim, int* info,
-                       double* nll_out, double* grad_out, int out_stride, int write_back, hipStream_t st) {
-  SmallArgs a = {tasks, md, info, nll_out, grad_out, out_stride, fdim, write_back};
+                       double* nll_out, double* grad_out, int out_stride, int write_back, hipStream_t st, int tasks_per_model) {
+  SmallArgs a = {tasks, md, info, nll_out, grad_out, out_stride, fdim, write_back, tasks_per_model};
   if (dtype == HBO_F64) small_eval_t<double>(a, ntasks, kernel_id, st);
   else small_eval_t<float>(a, ntasks, kernel_id, st);
 }

@@ -129,6 +129,34 @@ class DeviceDataset:
     mins = dict(zip(self.device_order_keys, list(mn)))
     return {k: vals[k] for k in self.keys}, {k: mins[k] for k in self.keys}
 
+  def evaluate_samples(self, mean_func, cov_func, config, model_samples, warp_func=None, per_task=False):
+    """Value-only NLL sums over this dataset's tasks of every parameter sample in `model_samples` (params.model dicts of one
+    model family, with `config`), from one hbo_nll_samples call per 4096 samples.  Returns an (S,) float64 array -- entry s is
+    what evaluate() returns for sample s -- and, with per_task, a list of per-task dicts keyed like self.keys.  A sample whose Gram
+    matrix is not PD is NaN."""
+    from hyperbo_amd.basics import definitions as defs
+    count = len(model_samples)
+    totals = np.zeros(count, dtype=np.float64)
+    pt = np.zeros((count, max(self.num_tasks, 1)), dtype=np.float64) if per_task else None
+    if self.num_tasks and count:
+      built = [_model.BuiltModel(mean_func, cov_func, defs.GPParams(model=smp, config=config), warp_func, self.dtype, self.input_dim)
+               for smp in model_samples]
+      for s0 in range(0, count, 4096):
+        part = built[s0:s0 + 4096]
+        structs = (nat.Model * len(part))(*[b.struct for b in part])
+        out = totals[s0:s0 + len(part)]
+        tp = pt[s0:s0 + len(part)] if per_task else None
+        self.ctx.check(nat.lib().hbo_nll_samples(self.ctx.handle, structs, len(part), self._h,
+                                                 out.ctypes.data_as(C.POINTER(C.c_double)),
+                                                 tp.ctypes.data_as(C.POINTER(C.c_double)) if per_task else None))
+    if not per_task:
+      return totals
+    rows = []
+    for s in range(count):
+      vals = dict(zip(self.device_order_keys, pt[s, :self.num_tasks]))
+      rows.append({k: float(vals[k]) for k in self.keys})
+    return totals, rows
+
   def evaluate_sharded(self, mean_func, cov_func, params, warp_func=None, objective=OBJ_NLL, comm=None):
     """This rank's shard through hbo_objective_sharded: the sums over ALL ranks of `comm`'s communicator, reduced on the device
     and all-reduced in place (RCCL over xGMI).  Returns (value_sum, task_count, flat grad_sum (warped), BuiltModel)."""
@@ -290,6 +318,26 @@ def neg_log_marginal_likelihood(mean_func, cov_func, params, dataset, warp_func=
   if return_key2nll:
     return total, (key2nll or {})
   return total
+
+
+def nll_log_densities(mean_func, cov_func, config, model_samples, dataset, warp_func=None, exclude_aligned=True):
+  """(S,) log densities of the slice sampler's target, one per params.model dict in `model_samples`:
+  -(neg_log_marginal_likelihood - sum of log priors), the NLL a mean over the tasks as neg_log_marginal_likelihood takes it and
+  the priors of config['priors'] applied per sample exactly as there (objectives.py:198-207).  The S NLLs come from one batched
+  device call (DeviceDataset.evaluate_samples, hbo_nll_samples).  NaN where a sample's Gram matrix is not PD."""
+  from hyperbo_amd.basics import definitions as defs
+  dev, owned = _as_device(dataset, exclude_aligned)
+  try:
+    totals = dev.evaluate_samples(mean_func, cov_func, config, model_samples, warp_func)
+    num_tasks = dev.num_tasks
+  finally:
+    if owned:
+      dev.close()
+  out = np.empty(len(model_samples), dtype=np.float64)
+  for s, smp in enumerate(model_samples):
+    total = 0. if num_tasks == 0 else totals[s] / num_tasks
+    out[s] = -_apply_priors(total, defs.GPParams(model=smp, config=config), warp_func)
+  return out
 
 
 def nll_value_and_grad(mean_func, cov_func, params, dataset, warp_func=None, exclude_aligned=True,

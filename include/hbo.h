@@ -209,6 +209,19 @@ int hbo_acq(hbo_ctx* ctx, const hbo_model* model, hbo_cache* cache, const void* 
 int hbo_acq_samples(hbo_ctx* ctx, const hbo_model* models, int32_t S, const void* x, int64_t n, const void* y, int32_t m,
                     const void* xq, int64_t M, int acq_id, const double* params, const double* add_noise, double scale, void* out);
 
+/* ---- the value-only NLL of S hyper-parameter samples of one model family over every task of a resident dataset: the log
+ *      density of the slice sampler config['method'] = 'slice_sample' asks for (hyperbo/bo_utils/bayesopt.py:247-255 -- HBO_SS:
+ *      burnin 50, nsamples 50, NLL objective, DEFAULT_PRIORS; hyperbo/gp_utils/slice_sampling_test.py:56-153), which calls it for the
+ *      pending points of all its chains at once.  nll_sum[s] = what hbo_nll(ctx, &models[s], ds, ...) returns (a sum over the tasks;
+ *      the caller divides by the task count), nll_per_task (nullable): [S][n_tasks] in the dataset's order.  The samples share dtype,
+ *      covariance, mean, input_dim and MLP architecture (HBO_ERR_ARG otherwise, the rule of hbo_acq_samples); an input-warped
+ *      (Kumaraswamy) sample gives HBO_ERR_UNSUPPORTED before any device work.  A task whose Gram matrix is not PD is NaN, and so is its
+ *      sample's sum; the call returns HBO_NOT_PD and the other samples are unaffected.  Every task of n <= 128: one launch of the
+ *      single-workgroup evaluation over the S x T pairs, each pair's value independent of the other samples in the call (bit for
+ *      bit); otherwise Gram -> factorisation -> reduction as one batch per chunk of samples that fits half the free device memory.
+ *      No float atomics: identical calls are bit-identical. */
+int hbo_nll_samples(hbo_ctx* ctx, const hbo_model* models, int32_t S, hbo_dataset* ds, double* nll_sum, double* nll_per_task);
+
 /* ---- d acquisition / d x_query: the gradient jaxopt.ScipyBoundedMinimize(L-BFGS-B) takes of
  *      f(x) = -ac_func(model, key, x[None]) in bayesopt() (hyperbo/bo_utils/bayesopt.py:116-125).
  *      Queries are independent rows: out [M,1] (model dtype) as hbo_acq, grad_out [M, input_dim] doubles.
