@@ -201,6 +201,84 @@ class BuiltModel:
     return grads
 
 
+_TRAIN_WARPS = ((gp_utils_utils.identity_warp, nat.TRAIN_WARP_IDENTITY), (gp_utils_utils.softplus_warp, nat.TRAIN_WARP_SOFTPLUS),
+                (gp_utils_utils.DEFAULT_SOFTPLUS, nat.TRAIN_WARP_SOFTPLUS_EPS), (gp_utils_utils.squareplus_warp, nat.TRAIN_WARP_SQUAREPLUS))
+
+
+def train_warp_code(fn):
+  """hbo_train_warp of a warp function of the closed set, None for any other callable."""
+  for f, code in _TRAIN_WARPS:
+    if fn is f:
+      return code
+  return None
+
+
+def train_leaf_map(bm, model):
+  """hbo_train_leaf of every element of lbfgs.tree_flatten(model) (sorted keys, row-major leaves), for the model family of `bm` (a
+  BuiltModel of `model`): which field of hbo_model the element becomes, through which warp -- what BuiltModel reads (warped values)
+  and what its unflatten_grad chains.  A leaf the model does not read gets HBO_TRAIN_NONE.  Raises ValueError for a warp outside
+  the closed set on a leaf the model reads."""
+  lay = bm.layout
+  wf = bm.warp_func or {}
+  scalar_targets = {'signal_variance': (nat.TRAIN_SIGNAL_VARIANCE, lay.signal_variance),
+                    'noise_variance': (nat.TRAIN_NOISE_VARIANCE, lay.noise_variance),
+                    'constant': (nat.TRAIN_CONSTANT, lay.constant),
+                    'dot_prod_sigma': (nat.TRAIN_DOT_PROD_SIGMA, lay.dot_prod_sigma),
+                    'dot_prod_bias': (nat.TRAIN_DOT_PROD_BIAS, lay.dot_prod_bias)}
+  rows = []
+
+  def warp_of(key):
+    if key not in wf:
+      return nat.TRAIN_WARP_IDENTITY
+    code = train_warp_code(wf[key])
+    if code is None:
+      raise ValueError(f"adam_on_device: warp_func['{key}'] = {wf[key]!r} is outside the closed set (identity, softplus, "
+                       'DEFAULT_SOFTPLUS, squareplus)')
+    return code
+
+  def emit(leaf, target, warp=nat.TRAIN_WARP_IDENTITY, layer=0):
+    a = np.asarray(leaf)
+    f32 = int(a.dtype == np.float32)
+    for i in range(a.size):
+      rows.append((warp, target, layer, i, f32) if target != nat.TRAIN_NONE else (nat.TRAIN_WARP_IDENTITY, nat.TRAIN_NONE, 0, 0, f32))
+
+  def rec_none(t):
+    if isinstance(t, dict):
+      for k in sorted(t):
+        rec_none(t[k])
+    else:
+      emit(t, nat.TRAIN_NONE)
+
+  for key in sorted(model):
+    val = model[key]
+    if key == 'lengthscale' and lay.lengthscale >= 0:
+      emit(val, nat.TRAIN_LENGTHSCALE, warp_of(key))
+    elif key in scalar_targets and scalar_targets[key][1] >= 0:
+      emit(val, scalar_targets[key][0], warp_of(key))
+    elif key == 'linear_mean' and lay.linear_kernel >= 0:
+      for sub in sorted(val):
+        emit(val[sub], nat.TRAIN_LINEAR_BIAS if sub == 'bias' else nat.TRAIN_LINEAR_KERNEL if sub == 'kernel' else nat.TRAIN_NONE)
+    elif key == 'mlp_params' and bm.mlp_shapes:
+      for name in sorted(val):
+        layer = int(name[len('Dense_'):]) if name.startswith('Dense_') and name[len('Dense_'):].isdigit() else -1
+        if not 0 <= layer < len(bm.mlp_shapes):
+          rec_none(val[name])
+          continue
+        for sub in sorted(val[name]):
+          tgt = nat.TRAIN_MLP_BIAS if sub == 'bias' else nat.TRAIN_MLP_KERNEL if sub == 'kernel' else nat.TRAIN_NONE
+          emit(val[name][sub], tgt, layer=layer)
+    elif key == 'kumar_params' and bm.uses_kumar:
+      for sub in sorted(val):
+        tgt = nat.TRAIN_KUMAR_A if sub == 'a' else nat.TRAIN_KUMAR_B if sub == 'b' else nat.TRAIN_NONE
+        emit(val[sub], tgt, nat.TRAIN_WARP_SQUAREPLUS)
+    else:
+      rec_none(val)
+  leaves = (nat.TrainLeaf * max(len(rows), 1))()
+  for i, r in enumerate(rows):
+    leaves[i].warp, leaves[i].target, leaves[i].layer, leaves[i].index, leaves[i].round_f32 = r
+  return leaves, len(rows)
+
+
 def infer_dtype(*arrays):
   """Computation dtype for the given inputs, following JAX's promotion under JAX_ENABLE_X64: float32 only when every
   FLOATING input is float32; any float64 input -- and integer / bool / list inputs, which x64 JAX widens -- gives

@@ -68,6 +68,17 @@ class Task(C.Structure):
               ('reserved0', C.c_int32)]
 
 
+class TrainLeaf(C.Structure):
+  """hbo_train_leaf: how one element of the flat raw vector becomes a field of the model (hbo_train_adam)."""
+  _fields_ = [('warp', C.c_int32), ('target', C.c_int32), ('layer', C.c_int32), ('index', C.c_int32), ('round_f32', C.c_int32)]
+
+
+# hbo_train_warp / hbo_train_target
+TRAIN_WARP_IDENTITY, TRAIN_WARP_SOFTPLUS, TRAIN_WARP_SOFTPLUS_EPS, TRAIN_WARP_SQUAREPLUS = 0, 1, 2, 3
+(TRAIN_NONE, TRAIN_LENGTHSCALE, TRAIN_SIGNAL_VARIANCE, TRAIN_NOISE_VARIANCE, TRAIN_CONSTANT, TRAIN_DOT_PROD_SIGMA, TRAIN_DOT_PROD_BIAS,
+ TRAIN_LINEAR_KERNEL, TRAIN_LINEAR_BIAS, TRAIN_MLP_KERNEL, TRAIN_MLP_BIAS, TRAIN_KUMAR_A, TRAIN_KUMAR_B) = range(13)
+
+
 # every symbol include/hbo.h declares: name -> (restype, argtypes)
 _P = C.c_void_p
 SIGNATURES = {
@@ -118,6 +129,8 @@ SIGNATURES = {
     'hbo_comm_destroy': (C.c_int, [_P]),
     'hbo_objective_sharded': (C.c_int, [_P, C.POINTER(Model), _P, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double),
                                         C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    'hbo_train_adam': (C.c_int, [_P, C.POINTER(Model), _P, C.POINTER(TrainLeaf), C.c_int32, _P, _P, _P, _P, _P, C.c_int32,
+                                 C.c_double, C.c_double, C.c_double, C.c_double, _P, _P, _P, _P, C.POINTER(C.c_int32)]),
     'hbo_device_info': (C.c_int, [C.c_int, C.c_char_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
 }
 

@@ -341,7 +341,6 @@ extern "C" int hbo_dataset_create(hbo_ctx* c, int dtype, int input_dim, const hb
 }
 
 namespace {
-struct GatherTask { const void* sx; const void* sys; const void* syd; void* dx; void* dys; void* dyd; int64_t n_src, n_dst, idx_off; int m, has_idx; };
 // row r of task blockIdx.y of the sub-sample = row idx[idx_off + r] (or r) of the resident task: inputs, column sum of y, divergence rows
 template <typename T>
 __global__ __launch_bounds__(256) void gather_rows_kernel(const GatherTask* __restrict__ tasks, const int32_t* __restrict__ idx, int D) {
@@ -355,6 +354,11 @@ __global__ __launch_bounds__(256) void gather_rows_kernel(const GatherTask* __re
   if (t.syd) for (int a = 0; a <= t.m; ++a) static_cast<T*>(t.dyd)[(int64_t)a * t.n_dst + r] = static_cast<const T*>(t.syd)[(int64_t)a * t.n_src + s];
 }
 }  // namespace
+void launch_gather_rows(int dtype, const GatherTask* tasks, const int32_t* idx, int T, int64_t max_dst, int D, hipStream_t st) {
+  const dim3 grid((unsigned)((max_dst + 255) / 256), (unsigned)T);
+  if (dtype == HBO_F64) hipLaunchKernelGGL(gather_rows_kernel<double>, grid, dim3(256), 0, st, tasks, idx, D);
+  else hipLaunchKernelGGL(gather_rows_kernel<float>, grid, dim3(256), 0, st, tasks, idx, D);
+}
 
 extern "C" int hbo_dataset_subsample(hbo_ctx* c, const hbo_dataset* src, const int64_t* counts, const int32_t* idx, hbo_dataset** out) {
   if (!c || !src || !counts || !out) return fail(c, HBO_ERR_ARG, "hbo_dataset_subsample: null argument");
@@ -405,9 +409,7 @@ extern "C" int hbo_dataset_subsample(hbo_ctx* c, const hbo_dataset* src, const i
   e = hipMemcpyAsync(d_args, stage, desc_b + idx_b, hipMemcpyHostToDevice, st);
   if (e == hipSuccess) e = hipEventRecord(c->ev_upload, st);
   if (e == hipSuccess) {
-    const dim3 grid((unsigned)((max_dst + 255) / 256), (unsigned)T);
-    if (dtype == HBO_F64) hipLaunchKernelGGL(gather_rows_kernel<double>, grid, dim3(256), 0, st, reinterpret_cast<const GatherTask*>(d_args), reinterpret_cast<const int32_t*>(d_args + desc_b), D);
-    else hipLaunchKernelGGL(gather_rows_kernel<float>, grid, dim3(256), 0, st, reinterpret_cast<const GatherTask*>(d_args), reinterpret_cast<const int32_t*>(d_args + desc_b), D);
+    launch_gather_rows(dtype, reinterpret_cast<const GatherTask*>(d_args), reinterpret_cast<const int32_t*>(d_args + desc_b), T, max_dst, D, st);
     e = hipGetLastError();
   }
   if (e != hipSuccess) { hbo_dataset_free(c, ds); return fail(c, HBO_ERR_HIP, std::string("hbo_dataset_subsample: ") + hipGetErrorString(e)); }

@@ -97,26 +97,28 @@ struct CholBoundScope {   // valid from run_potrf to the last product of the inv
   CholBoundScope(hbo_ctx* ctx, double b) : c(ctx) { c->chol_diag_bound = b; }
   ~CholBoundScope() { c->chol_diag_bound = 0; }
 };
-// the device-side form of an (already warped) model
+// the device-side form of an (already warped) model (model_dev_fill: the same code fills it on the device in hbo_train_adam)
 static void fill_model_dev(ModelDev& h, const hbo_model* m) {
   memset(&h, 0, sizeof h);
-  h.kernel_id = m->kernel_id; h.mean_id = m->mean_id; h.fdim = feature_dim(m);
-  h.n_ls = (m->kernel_id == HBO_KERNEL_DOT) ? 0 : m->n_lengthscale;
-  h.sv = m->signal_variance; h.noise = m->noise_variance; h.eps = m->eps; h.constant = m->constant;
-  h.dot_sigma = m->dot_prod_sigma; h.dot_bias = m->dot_prod_bias; h.linear_bias = m->linear_bias;
-  if (m->kernel_id == HBO_KERNEL_DOT) { if (h.dot_sigma == 0) h.dot_sigma = 1; }
-  else { h.dot_sigma = 1; }
-  for (int d = 0; d < h.fdim; ++d) {
-    double ls = 1.0;
-    if (m->kernel_id != HBO_KERNEL_DOT) ls = host_elem(m->lengthscale, m->dtype, m->n_lengthscale == 1 ? 0 : d);
-    h.inv_ls[d] = 1.0 / ls;
-  }
-  const int fm = mean_feature_dim(m);
-  for (int d = 0; d < fm; ++d) h.lin_w[d] = host_elem(m->linear_kernel, m->dtype, d);
-  h.input_warp = m->input_warp;
-  if (is_kumar(m))
-    for (int d = 0; d < m->input_dim; ++d) { h.kumar_a[d] = host_elem(as_kumar(m)->kumar_a, m->dtype, d); h.kumar_b[d] = host_elem(as_kumar(m)->kumar_b, m->dtype, d); }
+  model_dev_fill(h, m, 0, 1);
 }
+// hbo_objective's per-call work up to the copy back (objective.hip).  With `sh` set it reduces [nll, count, grad] on the device into
+// ShardOut::d_red with the scatter map it uploads (launch_shard_reduce) and returns without waiting: the sharded objective all-reduces
+// that buffer, hbo_train_adam (train.hip) queues its first Adam step behind it and reuses the map for the steps after it.
+struct ShardReq { double* count; double* timing; };
+struct ShardOut { double* d_red = nullptr; hipEvent_t ev0 = nullptr, ev1 = nullptr; int red_count = 0; int* d_map = nullptr; int nseg = 0; int out_stride = 0; };
+int objective_local(hbo_ctx* c, const hbo_model* m_in, hbo_dataset* ds, int objective, double* nll_sum, double* nll_per_task,
+                    double* grad_sum, const ShardReq* sh, ShardOut* so);
+// one row gather of hbo_dataset_subsample (api.hip): row r of task blockIdx.y of the destination = row idx[idx_off + r] (or r) of
+// the source task; hbo_train_adam points the destinations at a batch that already exists and overwrites its rows in place
+struct GatherTask { const void* sx; const void* sys; const void* syd; void* dx; void* dys; void* dyd; int64_t n_src, n_dst, idx_off; int m, has_idx; };
+void launch_gather_rows(int dtype, const GatherTask* tasks, const int32_t* idx, int T, int64_t max_dst, int D, hipStream_t st);
+// the launches of one single-workgroup evaluation (forward) and of the backward passes, without any host-side set-up
+void enqueue_fused_forward(hbo_ctx* c, const hbo_model* m, hbo_dataset* ds, int64_t max_n, int out_stride, bool want_grad);
+int enqueue_backward(hbo_ctx* c, const hbo_model* m, hbo_dataset* ds, int64_t max_n, int obj, bool want_grad);
+void launch_shard_reduce(const double* nll, const double* grad, const int* info, int T, int out_stride, const int* map,
+                         const double* mlp, const int* mlp_seg, int n_mlp_seg, double* out, int out_count, hipStream_t st);   // grad.hip
+
 // fills ctx->h_model, uploads it and the MLP weights
 static int upload_model(hbo_ctx* c, const hbo_model* m) {
   int rc = validate_model(c, m);

@@ -65,6 +65,41 @@ struct ModelDev {
   double kumar_b[HBO_MAX_FEATURE_DIM];
 };
 
+// Fills the device form of an (already warped) model: fill_model_dev (host, after zeroing the struct) and the Adam step of
+// hbo_train_adam (train.hip, one workgroup, on the device) run this same code.  Thread `tid` of `nthr` writes its share of the
+// per-feature arrays (every entry, zeros beyond the used ones), thread 0 the scalars.  Array parameters are read in the model dtype.
+__host__ __device__ inline double model_elem(const void* p, int dtype, int i) {
+  return dtype == HBO_F64 ? static_cast<const double*>(p)[i] : (double)static_cast<const float*>(p)[i];
+}
+__host__ __device__ inline void model_dev_fill(ModelDev& h, const hbo_model* m, int tid, int nthr) {
+  const int flast = m->n_layers > 0 ? m->features[m->n_layers - 1] : 0;
+  const int fdim = m->kernel_uses_mlp ? flast : m->input_dim;
+  const int fm = m->mean_id == HBO_MEAN_LINEAR ? m->input_dim : (m->mean_id == HBO_MEAN_LINEAR_MLP ? flast : 0);
+  const bool dot = m->kernel_id == HBO_KERNEL_DOT, kumar = m->input_warp == HBO_WARP_KUMAR;
+  const hbo_model_kumar* mk = reinterpret_cast<const hbo_model_kumar*>(m);
+  if (tid == 0) {
+    h.kernel_id = m->kernel_id; h.mean_id = m->mean_id; h.fdim = fdim;
+    h.n_ls = dot ? 0 : m->n_lengthscale;
+    h.sv = m->signal_variance; h.noise = m->noise_variance; h.eps = m->eps; h.constant = m->constant;
+    h.dot_sigma = m->dot_prod_sigma; h.dot_bias = m->dot_prod_bias; h.linear_bias = m->linear_bias;
+    if (dot) { if (h.dot_sigma == 0) h.dot_sigma = 1; }
+    else { h.dot_sigma = 1; }
+    h.input_warp = m->input_warp;
+  }
+  for (int d = tid; d < HBO_MAX_FEATURE_DIM; d += nthr) {
+    double inv = 0.0;
+    if (d < fdim) {
+      double ls = 1.0;
+      if (!dot) ls = model_elem(m->lengthscale, m->dtype, m->n_lengthscale == 1 ? 0 : d);
+      inv = 1.0 / ls;
+    }
+    h.inv_ls[d] = inv;
+    h.lin_w[d] = d < fm ? model_elem(m->linear_kernel, m->dtype, d) : 0.0;
+    h.kumar_a[d] = kumar && d < m->input_dim ? model_elem(mk->kumar_a, m->dtype, d) : 0.0;
+    h.kumar_b[d] = kumar && d < m->input_dim ? model_elem(mk->kumar_b, m->dtype, d) : 0.0;
+  }
+}
+
 enum GemmMode {
   GEMM_SYRK = 0,     // A[r,c] -= P[r,:] P[c,:]^T over panel columns (trailing / look-ahead update)
   GEMM_TRTRI_A = 1,  // S21 = L21 * W11

@@ -11,20 +11,77 @@ extern "C" int hbo_nll(hbo_ctx* c, const hbo_model* m, hbo_dataset* ds, double* 
 
 // Task-sharded form (hbo_objective_sharded): the sums over this rank's tasks are formed on the device, all-reduced in place
 // over the context's RCCL communicator and copied to the host once.
-struct ShardReq { double* count; double* timing; };
 int comm_allreduce_device(hbo_ctx* c, double* d_buf, int count, hipStream_t st);   // comm.hip
-void launch_shard_reduce(const double* nll, const double* grad, const int* info, int T, int out_stride, const int* map,
-                         const double* mlp, const int* mlp_seg, int n_mlp_seg, double* out, int out_count, hipStream_t st);   // gram.hip
 
 // The sharded form never leaves its peers alone in the collective: objective_local does everything up to (not including) the
 // all-reduce and hands back the device buffer [nll, count, grad]; whatever it returns, objective_impl then takes part in the ONE
 // all-reduce of the evaluation -- with NaN in every slot after a local failure (the peers see a NaN objective, not a hang) --
 // and only if not even that buffer can be had does it abort the communicator, so that the peers' collective fails too.
-struct ShardOut { double* d_red = nullptr; hipEvent_t ev0 = nullptr, ev1 = nullptr; int red_count = 0; };
 int comm_abort(hbo_ctx* c);   // comm.hip
 
-static int objective_local(hbo_ctx* c, const hbo_model* m_in, hbo_dataset* ds, int objective, double* nll_sum,
-                           double* nll_per_task, double* grad_sum, const ShardReq* sh, ShardOut* so) {
+// The launches of one evaluation that do not depend on the path taken (objective_local) or that hbo_train_adam (train.hip) queues once
+// per step without the host-side set-up: the batched MLP basis (one launch per layer), the Kumaraswamy forward (w(X) and dw/da, dw/db
+// of every task in one launch, before the Gram -- the fused path stays the fused path), the single-workgroup evaluation of a batch
+// whose tasks all fit one 128-block (small.hip) and the backward passes of both paths.
+static void enqueue_mlp_forward(hbo_ctx* c, const hbo_model* m, hbo_dataset* ds, int64_t max_n) {
+  int fin = m->input_dim;
+  for (int l = 0; l < m->n_layers; ++l) {
+    launch_mlp_forward_batch(ds->dtype, ds->d_mlp, ds->ntasks, max_n, l, c->d_mlp_w[l], c->d_mlp_b[l], fin, m->features[l], c->stream);
+    fin = m->features[l];
+  }
+}
+static void enqueue_kumar_forward(hbo_ctx* c, const hbo_model* m, hbo_dataset* ds, int64_t max_n) {
+  launch_kumar_forward(ds->dtype, ds->d_desc, ds->ntasks, max_n, nullptr, nullptr, nullptr, 0, m->input_dim, c->d_model, c->stream);
+}
+void enqueue_fused_forward(hbo_ctx* c, const hbo_model* m, hbo_dataset* ds, int64_t max_n, int out_stride, bool want_grad) {
+  const bool kumar = is_kumar(m);
+  if (needs_mlp(m)) { ProfScope ps(c, "features", 1); enqueue_mlp_forward(c, m, ds, max_n); }
+  if (kumar) { ProfScope ps(c, "kumar_forward", 1); enqueue_kumar_forward(c, m, ds, max_n); }
+  ProfScope ps(c, "small_eval", 1);
+  launch_small_eval(ds->dtype, ds->d_desc, ds->ntasks, c->d_model, m->kernel_id, feature_dim(m), ds->d_info, ds->d_nll,
+                    want_grad ? ds->d_gradout : nullptr, out_stride, want_grad && (needs_mlp(m) || kumar), c->stream);
+}
+int enqueue_backward(hbo_ctx* c, const hbo_model* m, hbo_dataset* ds, int64_t max_n, int obj, bool want_grad) {
+  const int dtype = ds->dtype, T = ds->ntasks, max_nblk = ds->max_nblk, max_npad = max_nblk * HBO_TILE;
+  const bool kumar = is_kumar(m), euc = obj == OBJ_EUC;
+  hipStream_t st = c->stream;
+  if (want_grad && kumar) {
+    // d f / d a, d f / d b (kumar.hip): per-tile partials, one ordered sum over tiles and tasks -> ds->d_mlpgrad[0, 2D)
+    ProfScope ps(c, "kumar_backward", 1);
+    const int D = m->input_dim;
+    const size_t tot = (size_t)2 * D;
+    if (ds->mlpgrad_elems < tot) { if (ds->d_mlpgrad) dev_free(c, ds->d_mlpgrad); HIPCHK(c, dev_alloc(c, (void**)&ds->d_mlpgrad, tot * sizeof(double))); ds->mlpgrad_elems = tot; }
+    double* part = static_cast<double*>(ws_get(c, WS_KU_PART, sizeof(double) * (size_t)T * max_nblk * max_nblk * 2 * D));
+    if (!part) return HBO_ERR_HIP;
+    launch_kumar_grad(dtype, ds->d_desc, T, max_nblk, c->d_model, m->kernel_id, D, obj, part, ds->d_mlpgrad, st);
+  }
+  if (want_grad && needs_mlp(m)) {
+    // d nll / d features -> MLP backward (hyperbo/gp_utils/basis_functions.py:24-36), summed over tasks; every pass one launch
+    // for the whole batch (mlp.hip)
+    ProfScope ps(c, "mlp_backward", 1);
+    const int L = m->n_layers, flast = m->features[L - 1];
+    size_t tot = 0; int fin0 = m->input_dim;
+    std::vector<size_t> woff(L), boff(L);
+    for (int l = 0; l < L; ++l) { woff[l] = tot; tot += (size_t)fin0 * m->features[l]; boff[l] = tot; tot += m->features[l]; fin0 = m->features[l]; }
+    if (ds->mlpgrad_elems < tot) { if (ds->d_mlpgrad) dev_free(c, ds->d_mlpgrad); HIPCHK(c, dev_alloc(c, (void**)&ds->d_mlpgrad, tot * sizeof(double))); ds->mlpgrad_elems = tot; }
+    HIPCHK(c, hipMemsetAsync(ds->d_mlpgrad, 0, tot * sizeof(double), st));
+    launch_mlp_zero_dF_batch(ds->d_mlp, T, max_n, flast, st);
+    if (m->kernel_uses_mlp) {
+      launch_grad_feat(dtype, ds->d_desc, T, max_nblk, c->d_model, m->kernel_id, flast, obj, st);
+      if (euc) launch_scale_dF(ds->d_desc, T, (int64_t)max_npad, flast, st);
+    }
+    if (m->mean_id == HBO_MEAN_LINEAR_MLP) launch_grad_feat_mean(dtype, ds->d_desc, T, (int64_t)max_npad, c->d_model, flast, st);
+    for (int l = L - 1; l >= 0; --l) {
+      const int fin = l ? m->features[l - 1] : m->input_dim;
+      launch_dense_bwd_batch(dtype, ds->d_mlp, T, max_n, l, ((L - 1 - l) % 2) == 0, c->d_mlp_w[l], ds->d_mlpgrad + woff[l], ds->d_mlpgrad + boff[l],
+                             fin, m->features[l], l > 0, st);
+    }
+  }
+  return HBO_OK;
+}
+
+int objective_local(hbo_ctx* c, const hbo_model* m_in, hbo_dataset* ds, int objective, double* nll_sum,
+                    double* nll_per_task, double* grad_sum, const ShardReq* sh, ShardOut* so) {
   if (!c || !nll_sum || !m_in || (!ds && !sh)) return fail(c, HBO_ERR_ARG, "hbo_objective: null argument");
   if (objective != HBO_OBJ_NLL && objective != HBO_OBJ_EKL && objective != HBO_OBJ_EUC) return fail(c, HBO_ERR_ARG, "hbo_objective: unknown objective id");
   HIPCHK(c, hipSetDevice(c->device));
@@ -177,21 +234,10 @@ static int objective_local(hbo_ctx* c, const hbo_model* m_in, hbo_dataset* ds, i
   // every task fits one 128-block (the reference's training regime: sub-sampled tasks of 50-100 points): ONE launch, one workgroup
   // per task does Gram -> factorisation -> inverse -> K^-1 -> contraction in LDS (small.hip) instead of the 13 launches below
   const bool fused_small = obj == OBJ_NLL && max_nblk == 1 && small_ok;
-  auto mlp_forward = [&]() {   // the basis of every task, one launch per layer
-    int fin = m->input_dim;
-    for (int l = 0; l < m->n_layers; ++l) {
-      launch_mlp_forward_batch(dtype, ds->d_mlp, T, max_n, l, c->d_mlp_w[l], c->d_mlp_b[l], fin, m->features[l], st);
-      fin = m->features[l];
-    }
-  };
-  // Kumaraswamy: w(X) (and dw/da, dw/db) of every task in one launch, before the Gram -- the fused path stays the fused path
-  auto kumar_forward = [&]() { launch_kumar_forward(dtype, ds->d_desc, T, max_n, nullptr, nullptr, nullptr, 0, m->input_dim, c->d_model, st); };
+  auto mlp_forward = [&]() { enqueue_mlp_forward(c, m, ds, max_n); };
+  auto kumar_forward = [&]() { enqueue_kumar_forward(c, m, ds, max_n); };
   if (fused_small) {
-    if (needs_mlp(m)) { ProfScope ps(c, "features", 1); mlp_forward(); }
-    if (kumar) { ProfScope ps(c, "kumar_forward", 1); kumar_forward(); }
-    ProfScope ps(c, "small_eval", 1);
-    launch_small_eval(dtype, ds->d_desc, T, c->d_model, m->kernel_id, feature_dim(m), ds->d_info, ds->d_nll,
-                      want_grad ? ds->d_gradout : nullptr, out_stride, want_grad && (needs_mlp(m) || kumar), st);
+    enqueue_fused_forward(c, m, ds, max_n, out_stride, want_grad);
   } else {
   if (c->opt_poison) launch_poison(dtype, ds->d_desc, T, max_npad, st);
   {
@@ -298,38 +344,8 @@ static int objective_local(hbo_ctx* c, const hbo_model* m_in, hbo_dataset* ds, i
                            ds->d_partials + stride_task * T, max_nblk); }
   }
   }   // !fused_small
-  if (want_grad && kumar) {
-    // d f / d a, d f / d b (kumar.hip): per-tile partials, one ordered sum over tiles and tasks -> ds->d_mlpgrad[0, 2D)
-    ProfScope ps(c, "kumar_backward", 1);
-    const int D = m->input_dim;
-    const size_t tot = (size_t)2 * D;
-    if (ds->mlpgrad_elems < tot) { if (ds->d_mlpgrad) dev_free(c, ds->d_mlpgrad); HIPCHK(c, dev_alloc(c, (void**)&ds->d_mlpgrad, tot * sizeof(double))); ds->mlpgrad_elems = tot; }
-    double* part = static_cast<double*>(ws_get(c, WS_KU_PART, sizeof(double) * (size_t)T * max_nblk * max_nblk * 2 * D));
-    if (!part) return HBO_ERR_HIP;
-    launch_kumar_grad(dtype, ds->d_desc, T, max_nblk, c->d_model, m->kernel_id, D, obj, part, ds->d_mlpgrad, st);
-  }
-  if (want_grad && needs_mlp(m)) {
-    // d nll / d features -> MLP backward (hyperbo/gp_utils/basis_functions.py:24-36), summed over tasks; every pass one launch
-    // for the whole batch (mlp.hip)
-    ProfScope ps(c, "mlp_backward", 1);
-    const int L = m->n_layers, flast = m->features[L - 1];
-    size_t tot = 0; int fin0 = m->input_dim;
-    std::vector<size_t> woff(L), boff(L);
-    for (int l = 0; l < L; ++l) { woff[l] = tot; tot += (size_t)fin0 * m->features[l]; boff[l] = tot; tot += m->features[l]; fin0 = m->features[l]; }
-    if (ds->mlpgrad_elems < tot) { if (ds->d_mlpgrad) dev_free(c, ds->d_mlpgrad); HIPCHK(c, dev_alloc(c, (void**)&ds->d_mlpgrad, tot * sizeof(double))); ds->mlpgrad_elems = tot; }
-    HIPCHK(c, hipMemsetAsync(ds->d_mlpgrad, 0, tot * sizeof(double), st));
-    launch_mlp_zero_dF_batch(ds->d_mlp, T, max_n, flast, st);
-    if (m->kernel_uses_mlp) {
-      launch_grad_feat(dtype, ds->d_desc, T, max_nblk, c->d_model, m->kernel_id, flast, obj, st);
-      if (euc) launch_scale_dF(ds->d_desc, T, (int64_t)max_npad, flast, st);
-    }
-    if (m->mean_id == HBO_MEAN_LINEAR_MLP) launch_grad_feat_mean(dtype, ds->d_desc, T, (int64_t)max_npad, c->d_model, flast, st);
-    for (int l = L - 1; l >= 0; --l) {
-      const int fin = l ? m->features[l - 1] : m->input_dim;
-      launch_dense_bwd_batch(dtype, ds->d_mlp, T, max_n, l, ((L - 1 - l) % 2) == 0, c->d_mlp_w[l], ds->d_mlpgrad + woff[l], ds->d_mlpgrad + boff[l],
-                             fin, m->features[l], l > 0, st);
-    }
-  }
+  rc = enqueue_backward(c, m, ds, max_n, obj, want_grad);
+  if (rc) return rc;
   if (sh) {
     // [nll, count, grad] of this rank's tasks in the caller's gradient layout, on the device: entry j of a task's gradient block
     // goes to map[j] (the scatter the host loop below does), the MLP gradient -- already summed over the tasks -- by segments
@@ -373,6 +389,7 @@ static int objective_local(hbo_ctx* c, const hbo_model* m_in, hbo_dataset* ds, i
     HIPCHK(c, hipEventRecord(ev1, st));
     HIPCHK(c, hipGetLastError());
     so->d_red = d_red; so->ev0 = ev_sh0; so->ev1 = ev1;
+    so->d_map = d_map; so->nseg = nseg; so->out_stride = out_stride;
     return HBO_OK;
   }
   HIPCHK(c, hipMemcpyAsync(stage, ds->d_pack, pack_bytes, hipMemcpyDeviceToHost, st));

@@ -116,6 +116,8 @@ def infer_parameters(mean_func, cov_func, init_params, dataset, warp_func=None,
   def make_device(batch):
     return obj.DeviceBatch(batch) if getattr(vg, 'accepts_device_batch', False) else batch
 
+  if method == 'adam' and params.config.get('adam_on_device', False):
+    return _infer_adam_on_device(mean_func, cov_func, params, dataset, warp_func, objective, rng, callback)
   if method == 'adam':
     needs_resample = any(s.x.shape[0] >= batch_size for s in dataset.values())
     # native objectives: the dataset stays resident in HBM and every step's batch is gathered there from freshly drawn row
@@ -180,6 +182,112 @@ def infer_parameters(mean_func, cov_func, init_params, dataset, warp_func=None,
       dev.close()
   else:
     raise ValueError(f'Optimization method {method} is not supported.')
+  params.cache = {}
+  return params
+
+
+ADAM_SEGMENT = 256   # Adam steps per hbo_train_adam call
+
+
+def _adam_on_device_unmet(mean_func, cov_func, params, dataset, warp_func, objective):
+  """The first condition that keeps config['adam_on_device'] from running (a message), or None.  Host-side checks only: the
+  library adds its own (small_fused off, the device's LDS) when it is called."""
+  if isinstance(objective, str):
+    objective = getattr(obj, objective, objective)
+  if objective is not obj.neg_log_marginal_likelihood:
+    return f'the objective is {getattr(objective, "__name__", objective)!r}, not obj.nll'
+  if 'priors' in params.config:
+    return "config has 'priors'"
+  wf = warp_func or {}
+  for key in sorted(params.model):
+    if key in wf and (isinstance(params.model[key], dict) or _model.train_warp_code(wf[key]) is None):
+      return f"warp_func['{key}'] is outside the closed set (identity, softplus, DEFAULT_SOFTPLUS, squareplus on array leaves)"
+  if params.config.get('comm') is not None:
+    return 'a comm is given (the sharded objective)'
+  batch_size = params.config['batch_size']
+  for key, sd in obj.included_sub_datasets(dataset):
+    n = sd.x.shape[0]
+    if (batch_size if n >= batch_size else n) > 128:
+      return f'task {key!r} of the batch has {min(n, batch_size)} > 128 points'
+  return None
+
+
+def _infer_adam_on_device(mean_func, cov_func, params, dataset, warp_func, objective, rng, callback):
+  """infer_parameters(method='adam') with config['adam_on_device'] = True: the steps run in segments of up to ADAM_SEGMENT on the
+  device (hbo_train_adam: evaluation, reduction and Adam update queued back to back, one synchronisation per segment).  Same batches
+  (the index draws of data_utils.sub_sample_index_iterator, a segment's up front), losses, parameters and callbacks as the host loop
+  above; the callbacks of a segment are replayed after it.  Only the fused regime (every batch task n <= 128, NLL, no priors, warps of
+  the closed set): anything else raises ValueError naming the first unmet condition."""
+  from hyperbo_amd.basics import data_utils, lbfgs as lbfgs_lib
+  why = _adam_on_device_unmet(mean_func, cov_func, params, dataset, warp_func, objective)
+  if why is not None:
+    raise ValueError(f'adam_on_device: {why}.')
+  config = params.config
+  batch_size, max_steps = config['batch_size'], config['max_training_step']
+  opt = _Adam(config['learning_rate'])
+  x, unflatten = lbfgs_lib.tree_flatten(params.model)
+  vg = _value_and_grad_of(objective)
+  full = obj.DeviceDataset(dataset)
+  ctx = full.ctx
+  needs_resample = any(s.x.shape[0] >= batch_size for s in dataset.values())
+  index_iter = data_utils.sub_sample_index_iterator(rng, dataset, batch_size) if needs_resample else None
+  order = full.device_order_keys
+  am, av = np.zeros_like(x), np.zeros_like(x)
+  last_ix = None
+  step = 0
+  try:
+    if full.num_tasks == 0:
+      raise ValueError('adam_on_device: the dataset has no task the NLL includes.')
+    while step < max_steps:
+      k = min(ADAM_SEGMENT, max_steps - step)
+      bm = _model.BuiltModel(mean_func, cov_func, GPParams(model=unflatten(x), config=config), warp_func, full.dtype, full.input_dim)
+      leaves, P = _model.train_leaf_map(bm, params.model)
+      if P != x.size:
+        raise ValueError(f'adam_on_device: the leaf map has {P} entries for {x.size} parameters')
+      counts = rows = None
+      ixs = None
+      if needs_resample:
+        ixs = [next(index_iter) for _ in range(k)]
+        counts = np.ascontiguousarray([[(-1 if ix.get(key) is None else len(ix[key])) for key in order] for ix in ixs], dtype=np.int64)
+        parts = [ix[key] for ix in ixs for key in order if ix.get(key) is not None]
+        rows = np.ascontiguousarray(np.concatenate(parts) if parts else np.zeros(1), dtype=np.int32)
+      t = np.arange(step + 1, step + k + 1)
+      bias1 = np.array([1 - opt.b1**int(i) for i in t], dtype=np.float64)
+      bias2 = np.array([1 - opt.b2**int(i) for i in t], dtype=np.float64)
+      losses = np.empty(k, dtype=np.float64)
+      trace = np.empty((k, x.size), dtype=np.float64)
+      done = C.c_int32(0)
+      rc = nat.lib().hbo_train_adam(ctx.handle, bm.ref(), full._h, leaves, P, nat.ptr(x), nat.ptr(am), nat.ptr(av), nat.ptr(bias1),
+                                    nat.ptr(bias2), k, float(opt.lr), float(opt.b1), float(opt.b2), float(opt.eps),
+                                    nat.ptr(counts), nat.ptr(rows), nat.ptr(losses), nat.ptr(trace), C.byref(done))
+      if rc == nat.HBO_ERR_UNSUPPORTED:
+        raise ValueError('adam_on_device: ' + (nat.lib().hbo_last_error(ctx.handle) or b'').decode())
+      ctx.check(rc, allow_not_pd=False)
+      done = done.value
+      for j in range(done):
+        params.model = unflatten(trace[j])
+        if callback:
+          callback(step + j, params.model, float(losses[j]))
+      if ixs is not None:
+        last_ix = ixs[min(done, k - 1)]
+      if done < k:
+        if step + done == 0 and np.isnan(losses[0]):
+          raise ValueError(f'Encountered NaN in loss function. current_loss = {losses[0]}.')
+        step += done
+        break
+      step += k
+    # the final evaluation at the updated x, on the batch of the last step evaluated (gp.py:135-142 keeps x only if it is finite)
+    dev = full.subsample(last_ix) if last_ix is not None else full
+    try:
+      final_loss, _ = vg(mean_func=mean_func, cov_func=cov_func, params=GPParams(model=unflatten(x), config=config), dataset=dev,
+                         warp_func=warp_func)
+    finally:
+      if dev is not full:
+        dev.close()
+    if np.isfinite(final_loss):
+      params.model = unflatten(x)
+  finally:
+    full.close()
   params.cache = {}
   return params
 

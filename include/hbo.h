@@ -318,6 +318,49 @@ int hbo_comm_destroy(hbo_ctx* ctx);
 int hbo_objective_sharded(hbo_ctx* ctx, const hbo_model* model, hbo_dataset* ds, int objective, double* value_sum,
                           double* count, double* grad_sum, double* timing);
 
+/* ---- gp.py:53-195 infer_parameters(method='adam'): K Adam steps queued on the device ------------------------------------
+ * Each step is stream-ordered launches with no host wait: [gather this step's rows] -> the single-workgroup evaluation (with the
+ * MLP / Kumaraswamy forward and backward passes around it) -> the reduction of [nll_sum, T, grad] in the caller's layout (the order
+ * of summation of hbo_objective) -> one Adam step in one workgroup, which chains the gradient through the warps, updates x and
+ * writes the next (warped) model where the following step's launches read it.  One copy back and one synchronisation per call.
+ *
+ * The raw parameter vector x is lbfgs.tree_flatten(params.model); leaves[i] says how x[i] becomes a field of the model:
+ *   warp      hbo_train_warp (utils.py:28-81, the closed set the host chain rule knows)
+ *   target    hbo_train_target; NONE = the model does not read it (zero gradient: Adam leaves it where it is)
+ *   layer     MLP layer of an MLP_KERNEL / MLP_BIAS leaf, else 0
+ *   index     element within the target ([in, out] row-major for MLP_KERNEL); 0 for the scalar targets
+ *   round_f32 1: the leaf is float32 in params.model (the host rounds x to float32 before the warp, and the warp result too)
+ * Array targets (lengthscale, linear kernel, MLP weights, Kumaraswamy a, b) are rounded to the model dtype as the host's copy is.
+ * `model` supplies the family and the starting values (its warped fields must be the ones x gives); fields no leaf targets keep
+ * the model's value.  x, adam_m, adam_v [P]: in / out, the Adam state carried from call to call.  bias1[s], bias2[s]: 1 - b1**t,
+ * 1 - b2**t of step s as the host computes them.  Adam is evaluated operation by operation as gp.py:_Adam.step (no contraction):
+ * from the same gradient the update is bit-identical to the host's.
+ *   batch_counts / batch_rows (both null: the whole of `ds` every step): per step, hbo_dataset_subsample's counts [T] and rows
+ *   (steps x T counts, the rows of the steps back to back); every step must keep the same counts (only the rows change).
+ *   losses [steps]: nll_sum / T of each step (written up to and including the first non-finite one).  x_trace (nullable)
+ *   [steps][P]: x as evaluated at each step.  *steps_done: the first step whose loss was not finite (x, adam_m, adam_v are then
+ *   the ones evaluated there, not updated), or `steps`.
+ * Only the fused regime is accepted: every task of the batch has n <= 128, the hbo_tune option small_fused is on and the device
+ * gives the single-workgroup evaluation its LDS; otherwise HBO_ERR_UNSUPPORTED.  The arguments are checked before any HIP call
+ * (HBO_ERR_ARG, hbo_last_error names the argument). */
+enum hbo_train_warp { HBO_TRAIN_WARP_IDENTITY = 0, HBO_TRAIN_WARP_SOFTPLUS = 1, HBO_TRAIN_WARP_SOFTPLUS_EPS = 2, HBO_TRAIN_WARP_SQUAREPLUS = 3 };
+enum hbo_train_target {
+  HBO_TRAIN_NONE = 0, HBO_TRAIN_LENGTHSCALE = 1, HBO_TRAIN_SIGNAL_VARIANCE = 2, HBO_TRAIN_NOISE_VARIANCE = 3, HBO_TRAIN_CONSTANT = 4,
+  HBO_TRAIN_DOT_PROD_SIGMA = 5, HBO_TRAIN_DOT_PROD_BIAS = 6, HBO_TRAIN_LINEAR_KERNEL = 7, HBO_TRAIN_LINEAR_BIAS = 8,
+  HBO_TRAIN_MLP_KERNEL = 9, HBO_TRAIN_MLP_BIAS = 10, HBO_TRAIN_KUMAR_A = 11, HBO_TRAIN_KUMAR_B = 12
+};
+typedef struct hbo_train_leaf {
+  int32_t warp;
+  int32_t target;
+  int32_t layer, index;
+  int32_t round_f32;
+} hbo_train_leaf;
+int hbo_train_adam(hbo_ctx* ctx, const hbo_model* model, hbo_dataset* ds, const hbo_train_leaf* leaves, int32_t P,
+                   double* x, double* adam_m, double* adam_v, const double* bias1, const double* bias2,
+                   int32_t steps, double lr, double b1, double b2, double adam_eps,
+                   const int64_t* batch_counts, const int32_t* batch_rows,
+                   double* losses, double* x_trace, int32_t* steps_done);
+
 #ifdef __cplusplus
 }
 #endif
