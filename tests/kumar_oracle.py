@@ -44,3 +44,32 @@ def kumar_kernel(base):
     return base(params, w(vx1), None if vx2 is None else w(vx2), warp_func=warp_func, diag=diag)
   matrix_map.__name__ = base.__name__
   return matrix_map
+
+
+def se_nll_ab_grad(model, ds):
+  """Analytic d mean-NLL / d (raw a, b) of the SE kernel on warped inputs with a constant / zero mean (the oracle's
+  dnll/dK = 1/2 (m^2 K^-1 - s s^T), chained through dK/dw and dw/da, dw/db).  fp64 NumPy."""
+  from oracle import hyperbo_oracle as o
+  kp = model['kumar_params']
+  a, b = squareplus(kp['a']), squareplus(kp['b'])
+  ls = o.default_softplus(model['lengthscale']); sv = o.default_softplus(model['signal_variance'])
+  noise = o.default_softplus(model['noise_variance']); c = float(model.get('constant', 0.0))
+  ga, gb = np.zeros_like(a), np.zeros_like(b)
+  for s in ds.values():
+    w = warp(s.x, kp['a'], kp['b'])
+    ws = w / ls
+    sq = np.sum(ws * ws, 1)
+    K = sv * np.exp(-0.5 * np.maximum(sq[:, None] + sq[None, :] - 2 * ws @ ws.T, 0))
+    A = K + (noise + 1e-6) * np.eye(len(w))
+    Ainv = np.linalg.inv(A)
+    m = s.y.shape[1]
+    r = np.sum(s.y - c, axis=1)
+    sv_ = Ainv @ r
+    G = 0.5 * (m * m * Ainv - np.outer(sv_, sv_))
+    M = G * K
+    M = 0.5 * (M + M.T)
+    dw = -2.0 * (M.sum(1)[:, None] * w - M @ w) / (ls * ls)      # d nll / d w
+    da, db = dw_dab(s.x, a, b)
+    ga += np.sum(dw * da, 0); gb += np.sum(dw * db, 0)
+  n = len(ds)
+  return ga / n * squareplus_grad(kp['a']), gb / n * squareplus_grad(kp['b'])

@@ -348,9 +348,8 @@ def test_single_workgroup_evaluation_vs_blocked_path_and_oracle(gpu_ctx, dtype, 
     gpu_ctx.set_option('small_fused', 1)
     gpu_ctx.profile_enable(0)
     dev.close()
-  f1, f0 = helpers.flatten(g1), helpers.flatten(g0)
   assert abs(v1 - v0) <= tol_blocked * abs(v0), (v1, v0)
-  assert np.max(np.abs(f1 - f0)) <= tol_blocked * 10 * np.max(np.abs(f0)), np.max(np.abs(f1 - f0)) / np.max(np.abs(f0))
+  helpers.assert_grad_close(g1, g0, tol_blocked * 10, label='small vs blocked')
   assert abs(t1 - t0) <= tol_blocked * abs(t0) and abs(t1 - v1) <= tol_blocked * abs(v1)
   for k in k0:
     assert abs(k1[k] - k0[k]) <= tol_blocked * max(abs(k0[k]), 1.0)
@@ -358,9 +357,8 @@ def test_single_workgroup_evaluation_vs_blocked_path_and_oracle(gpu_ctx, dtype, 
                            for k_, v_ in model.items()})
   dso64 = {k: o.SubDataset(np.asarray(v.x, np.float64), np.asarray(v.y, np.float64)) for k, v in dso.items()}
   vo, go = o.nll_value_and_grad(mo, ko, po64, dso64, WFO)
-  fo = helpers.flatten(go)
   assert abs(v1 - vo) <= tol_oracle * abs(vo)
-  assert np.max(np.abs(f1 - fo)) <= tol_oracle * 10 * np.max(np.abs(fo))
+  helpers.assert_grad_close(g1, go, tol_oracle * 10, label='small vs oracle')
   # one task beyond 128 points: the whole batch takes the blocked pipeline
   x, y = helpers.synthetic_task(rng, 129, d, dtype=dtype)
   dsn[99] = defs.SubDataset(x, y); dso64[99] = o.SubDataset(np.asarray(x, np.float64), np.asarray(y, np.float64))

@@ -100,34 +100,6 @@ def test_gram_vs_oracle_on_warped_inputs(gpu_ctx, base, d, dtype, tol):
 
 
 # ---- objectives ------------------------------------------------------------------------------------------------------
-def _se_kumar_nll_ab_grad(model, ds):
-  """Analytic d mean-NLL / d (raw a, b) of the SE kernel on warped inputs with a constant / zero mean (the oracle's
-  dnll/dK = 1/2 (m^2 K^-1 - s s^T), chained through dK/dw and dw/da, dw/db).  fp64 NumPy."""
-  kp = model['kumar_params']
-  a, b = ko.squareplus(kp['a']), ko.squareplus(kp['b'])
-  ls = o.default_softplus(model['lengthscale']); sv = o.default_softplus(model['signal_variance'])
-  noise = o.default_softplus(model['noise_variance']); c = float(model.get('constant', 0.0))
-  ga, gb = np.zeros_like(a), np.zeros_like(b)
-  for s in ds.values():
-    w = ko.warp(s.x, kp['a'], kp['b'])
-    ws = w / ls
-    sq = np.sum(ws * ws, 1)
-    K = sv * np.exp(-0.5 * np.maximum(sq[:, None] + sq[None, :] - 2 * ws @ ws.T, 0))
-    A = K + (noise + 1e-6) * np.eye(len(w))
-    Ainv = np.linalg.inv(A)
-    m = s.y.shape[1]
-    r = np.sum(s.y - c, axis=1)
-    sv_ = Ainv @ r
-    G = 0.5 * (m * m * Ainv - np.outer(sv_, sv_))
-    M = G * K
-    M = 0.5 * (M + M.T)
-    dw = -2.0 * (M.sum(1)[:, None] * w - M @ w) / (ls * ls)      # d nll / d w
-    da, db = ko.dw_dab(s.x, a, b)
-    ga += np.sum(dw * da, 0); gb += np.sum(dw * db, 0)
-  n = len(ds)
-  return ga / n * ko.squareplus_grad(kp['a']), gb / n * ko.squareplus_grad(kp['b'])
-
-
 def _fd_ab(fn, model, h=1e-5):
   out = {}
   for key in ('a', 'b'):
@@ -160,7 +132,7 @@ def test_nll_value_and_grad_se_kumar_fp64(gpu_ctx, sizes):
   po = o.GPParams(model=_without_kumar(model))
   vo, go = o.nll_value_and_grad(o.constant, o.squared_exponential, po, _warped_dataset(dso, model['kumar_params']), WFO)
   assert abs(vn - vo) <= 1e-10 * abs(vo)
-  ga, gb = _se_kumar_nll_ab_grad(model, dso)
+  ga, gb = ko.se_nll_ab_grad(model, dso)
   go['kumar_params'] = {'a': ga, 'b': gb}
   helpers.assert_grad_close(gn, go, FP64_GRAD_TOL)
 
@@ -252,7 +224,7 @@ def test_cfg2_full_size_se_kumar_and_bit_identical_repeats(gpu_ctx):
   vo, go = o.nll_value_and_grad(o.constant, o.squared_exponential, o.GPParams(model=_without_kumar(model)),
                                 _warped_dataset(dso, model['kumar_params']), WFO)
   assert abs(v1 - vo) <= 1e-10 * abs(vo)
-  ga, gb = _se_kumar_nll_ab_grad(model, dso)
+  ga, gb = ko.se_nll_ab_grad(model, dso)
   go['kumar_params'] = {'a': ga, 'b': gb}
   helpers.assert_grad_close(g1, go, FP64_GRAD_TOL)
 
@@ -372,7 +344,7 @@ def test_gp_train_adam_moves_kumar_params_like_the_numpy_loop(gpu_ctx):
   for t in range(1, steps + 1):
     _, go = o.nll_value_and_grad(o.constant, o.squared_exponential, o.GPParams(model=_without_kumar(params)),
                                  _warped_dataset(dso, params['kumar_params']), WFO)
-    ga, gb = _se_kumar_nll_ab_grad(params, dso)
+    ga, gb = ko.se_nll_ab_grad(params, dso)
     go['kumar_params'] = {'a': ga, 'b': gb}
     g = leaves(go)
     mom = b1 * mom + (1 - b1) * g; vel = b2 * vel + (1 - b2) * g * g

@@ -54,11 +54,13 @@ def _compare(host, dev, rtol, atol=1e-12):
   np.testing.assert_allclose(dfin, hfin, rtol=rtol, atol=atol)
 
 
-@pytest.mark.parametrize('kname,mname', cases.FAMILIES)
-def test_device_adam_matches_host_driver_fp64(gpu_ctx, kname, mname):
-  data = cases.dataset(_sizes())
-  host = _run(kname, mname, data, False)
-  dev = _run(kname, mname, data, True)
+@pytest.mark.parametrize('kname,mname,d,feats', [pytest.param(k, mu, cases.D, cases.FEATS, id=f'{k}-{mu}') for k, mu in cases.FAMILIES] +
+                         [pytest.param(k, mu, d, f, id=f'{k}-{mu}-d{d}-f{f[-1]}') for k, mu, d, f in cases.WIDE_FAMILIES])
+def test_device_adam_matches_host_driver_fp64(gpu_ctx, kname, mname, d, feats):
+  data = cases.dataset(_sizes(), d=d)
+  model = cases.model_of(kname, mname, d=d, feats=feats)
+  host = _run(kname, mname, data, False, model=model)
+  dev = _run(kname, mname, data, True, model=model)
   assert len(host[0]) == 200
   mlp = kname.endswith('_mlp') or mname == 'linear_mlp'
   _compare(host, dev, RTOL64_MLP if mlp else RTOL64, atol=1e-10 if mlp else 1e-12)

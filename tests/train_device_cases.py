@@ -7,7 +7,8 @@ FEATS = (6, 5)
 
 
 def model_of(kernel_name, mean_name, d=D, feats=FEATS, seed=0, dtype=np.float64):
-  """params.model for one kernel x mean of the closed registry, DEFAULT_WARP_FUNC-style raw values."""
+  """params.model for one kernel x mean of the closed registry, DEFAULT_WARP_FUNC-style raw values.  Beyond 16 features the
+  length-scales grow with sqrt(features / 16), so that the covariance of a wide feature space does not decay to the diagonal."""
   rng = np.random.default_rng(seed)
   mlp = kernel_name.endswith('_mlp') or mean_name == 'linear_mlp'
   kumar = kernel_name.endswith('_kumar')
@@ -17,7 +18,10 @@ def model_of(kernel_name, mean_name, d=D, feats=FEATS, seed=0, dtype=np.float64)
     m['dot_prod_sigma'] = np.array(-0.5, dtype=dtype)
     m['dot_prod_bias'] = np.array(0.3, dtype=dtype)
   else:
-    m['lengthscale'] = (rng.uniform(-0.5, 0.5, size=fdim)).astype(dtype)
+    ls = rng.uniform(-0.5, 0.5, size=fdim)
+    if fdim > 16:
+      ls = np.log(np.expm1(np.log1p(np.exp(ls)) * np.sqrt(fdim / 16)))
+    m['lengthscale'] = ls.astype(dtype)
   if mean_name == 'constant':
     m['constant'] = np.array(0.1, dtype=dtype)
   if mlp:
@@ -45,6 +49,10 @@ FAMILIES = [(k, mu) for k in ('squared_exponential', 'matern32', 'matern52', 'do
            [(k + '_mlp', mu) for k in ('squared_exponential', 'matern52', 'dot_product') for mu in ('constant', 'linear_mlp')] + \
            [('matern32_mlp', 'linear_mlp'), ('squared_exponential', 'linear_mlp'),
             ('squared_exponential_kumar', 'constant'), ('matern52_kumar', 'linear')]
+
+# (kernel, mean, input dim, MLP features): feature spaces wider than the 16-feature chunk of the single-workgroup evaluation
+# (small.hip), which every step of the device loop runs.  GPU tier only.
+WIDE_FAMILIES = [('matern52', 'linear', 33, FEATS), ('squared_exponential_mlp', 'linear_mlp', D, (6, 33))]
 
 
 def dataset(sizes, d=D, dtype=np.float64, seed=1):
