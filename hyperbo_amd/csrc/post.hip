@@ -47,7 +47,7 @@ __global__ __launch_bounds__(256) void acq_grad_kernel(AcqGradArgs a, const Mode
     double val, amu, asd;
     if (a.acq_id == HBO_ACQ_UCB) { val = mu + a.param * sd; amu = 1.0; asd = a.param; }
     else if (a.acq_id == HBO_ACQ_PI) { val = (mu - a.param) / sd; amu = 1.0 / sd; asd = -(mu - a.param) / (sd * sd); }
-    else { const double u = (mu - a.param) / sd; val = sd * (norm_pdf(u) + u * norm_cdf(u)); amu = norm_cdf(u); asd = norm_pdf(u); }
+    else { const double u = (mu - a.param) / sd; val = sd * ei_over_sd(u); amu = norm_cdf(u); asd = norm_pdf(u); }
     s_amu = amu; s_avar = asd / (2.0 * sd) * a.scale;
     static_cast<T*>(a.acq_out)[q] = (T)val;
     a.dmu[q] = amu;
@@ -160,7 +160,7 @@ __global__ void post_epilogue_kernel(PostArgs a) {
     else {
       const T gamma = ((T)a.param - mu) / sd;
       if (a.acq_id == HBO_ACQ_PI) r = -gamma;
-      else r = (T)((norm_pdf((double)gamma) - (double)gamma * (1.0 - norm_cdf((double)gamma)))) * sd;
+      else r = (T)ei_over_sd(-(double)gamma) * sd;
     }
     static_cast<T*>(a.acq_out)[q] = r;
   }

@@ -195,7 +195,9 @@ int hbo_cache_append(hbo_ctx* ctx, const hbo_model* model, hbo_cache* cache, con
 int hbo_predict(hbo_ctx* ctx, const hbo_model* model, hbo_cache* cache, const void* xq, int64_t M,
                 int full_cov, void* mu_out, void* var_out);
 /* ---- acfun.py:51-142 acquisition on top of GP.predict(full_cov=False) ------------------- */
-/* var' = (var + add_noise) * scale (gp.py:607-619); EI/PI: param = target; UCB: param = beta. */
+/* var' = (var + add_noise) * scale (gp.py:607-619); EI/PI: param = target; UCB: param = beta.
+ * EI equals the reference's formula (acfun.py:108-110), evaluated without its `1 - cdf(gamma)` cancellation (cdf(-gamma) from erfc):
+ * it differs from a literal evaluation only where that one has lost its digits (gamma = (target - mu) / sd > ~5 in fp64). */
 int hbo_acq(hbo_ctx* ctx, const hbo_model* model, hbo_cache* cache, const void* xq, int64_t M,
             int acq_id, double param, double add_noise, double scale, void* out);
 
