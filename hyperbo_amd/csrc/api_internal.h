@@ -94,8 +94,8 @@ static inline double chol_diag_bound_of(const hbo_model* m) {
 }
 struct CholBoundScope {   // valid from run_potrf to the last product of the inverse / K^-1 of the same matrices
   hbo_ctx* c;
-  CholBoundScope(hbo_ctx* ctx, double b) : c(ctx) { c->chol_diag_bound = b; }
-  ~CholBoundScope() { c->chol_diag_bound = 0; }
+  CholBoundScope(hbo_ctx* ctx, double b) : c(ctx) { c->run.chol_diag_bound = b; }
+  ~CholBoundScope() { c->run.chol_diag_bound = 0; }
 };
 // the device-side form of an (already warped) model (model_dev_fill: the same code fills it on the device in hbo_train_adam)
 static void fill_model_dev(ModelDev& h, const hbo_model* m) {

@@ -51,7 +51,7 @@ extern "C" int hbo_factor(hbo_ctx* c, const hbo_model* m, const void* x, int64_t
     launch_gram(dtype, g, c->d_model, dim3(t->nblk, t->nblk, 1), st); }
   // the inverse W = L^-1 (kept for the posterior products) starts beside the panel chain, as in the objective path
   TrtriProgress trtri_pg;
-  const bool early_trtri = use_lookahead(c, 1, t->nblk) && c->opt_overlap_trtri && t->nblk >= 4;
+  const bool early_trtri = use_early_trtri(c, 1, t->nblk);
   c->trtri_host_task = k->h_desc;
   CholBoundScope bound_scope(c, chol_diag_bound_of(m));
   { ProfScope ps(c, "potrf", 1); run_potrf(c, dtype, k->d_desc, 1, t->nblk, k->d_info, early_trtri ? &trtri_pg : nullptr); }
@@ -591,7 +591,7 @@ extern "C" int hbo_acq_samples(hbo_ctx* c, const hbo_model* models, int32_t S, c
     GramArgs g = {}; g.kernel_id = m0->kernel_id; g.mfma_min_f = c->opt_gram_mfma; g.tasks = d_batch; g.fdim = feature_dim(m0); g.symmetric = 1; g.padded = 1; g.model_stride = 1;
     launch_gram(dtype, g, d_models, dim3(nblk, nblk, S), st); }
   TrtriProgress trtri_pg;
-  const bool early_trtri = use_lookahead(c, S, nblk) && c->opt_overlap_trtri && nblk >= 4;
+  const bool early_trtri = use_early_trtri(c, S, nblk);
   c->trtri_host_task = S == 1 ? h_batch[0] : TaskDesc{};
   double bound_all = chol_diag_bound_of(&models[0]);
   for (int s = 1; s < S; ++s) { const double b = chol_diag_bound_of(&models[s]); bound_all = (b > 0 && bound_all > 0) ? std::max(bound_all, b) : 0.0; }

@@ -280,8 +280,7 @@ __device__ __forceinline__ int strict_index(int I, int J) { return I * (I - 1) /
 // L_pp and its leaf inverses into LDS first -- a caller that walks several row groups of the same panel (chain.hip)
 // stages once.
 template <typename T, bool IDENT>
-__device__ __forceinline__ void trsm_body(const TaskDesc& t, int p, int64_t row0, unsigned char* smem, bool stage,
-                                          unsigned short* xp = nullptr, int nkb = 0, int kb_off = 0) {
+__device__ __forceinline__ void trsm_body(const TaskDesc& t, int p, int64_t row0, unsigned char* smem, bool stage) {
   typedef typename Mma<T>::acc_t acc_t;
   constexpr int TE = trsm_tile<T>();
   T* sLt = reinterpret_cast<T*>(smem);          // 28 packed strictly-lower tiles of L_pp
@@ -369,15 +368,6 @@ __device__ __forceinline__ void trsm_body(const TaskDesc& t, int p, int64_t row0
         if (rg != jb) gst(Wout + (int64_t)(jb * 16 + l15) * ld + rg * 16 + row, x[r]);
       } else {
         gst(Ap + (int64_t)row * ld + jb * 16 + l15, x[r]);
-        if constexpr (sizeof(T) == 4) {
-          if (xp) {   // the same value as three bf16 planes (see SplitOut)
-            const int64_t grow = wrow0 + row;
-            unsigned short h, m, l;
-            hbo_split3((float)x[r], h, m, l);
-            unsigned short* o = xp + ((grow / NB * nkb + kb_off + jb) * 3) * (int64_t)(NB * 16) + (grow % NB) * 16 + l15;
-            o[0] = h; o[NB * 16] = m; o[2 * NB * 16] = l;
-          }
-        }
       }
     }
     if (jb < 7) {
@@ -392,7 +382,7 @@ __device__ __forceinline__ void trsm_body(const TaskDesc& t, int p, int64_t row0
   }
 }
 template <typename T, bool IDENT>
-__global__ __launch_bounds__(256) void trsm_kernel(const TaskDesc* tasks, int p_arg, int* yield_tab, SplitOut so, unsigned long long* tl) {
+__global__ __launch_bounds__(256) void trsm_kernel(const TaskDesc* tasks, int p_arg, int* yield_tab, unsigned long long* tl) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   __builtin_amdgcn_s_setprio(3);                // critical path: outrank co-resident GEMM waves
   const TaskDesc& t = tasks[blockIdx.z];
@@ -422,7 +412,7 @@ __global__ __launch_bounds__(256) void trsm_kernel(const TaskDesc* tasks, int p_
   int tok = 0;
   tl_begin(tl);
   if (yield_tab && threadIdx.x == 0) tok = yield_enter(yield_tab);
-  trsm_body<T, IDENT>(t, p, row0, smem, true, so.xp ? so.xp + (int64_t)blockIdx.z * so.task_stride : nullptr, so.nkb, so.kb_off);
+  trsm_body<T, IDENT>(t, p, row0, smem, true);
   if (yield_tab) {
     __syncthreads();
     if (threadIdx.x == 0) yield_leave(yield_tab, tok);
@@ -453,20 +443,19 @@ void potf2_t(const TaskDesc* tasks, int ntasks, int p, int* info, hipStream_t st
                      yield_flag, tl);
 }
 template <typename T>
-void trsm_t(const TaskDesc* tasks, int ntasks, int p, int max_nblk, hipStream_t st, int* yield_tab, const SplitOut& so, unsigned long long* tl) {
+void trsm_t(const TaskDesc* tasks, int ntasks, int p, int max_nblk, hipStream_t st, int* yield_tab, unsigned long long* tl) {
   set_attrs<T>();
   const int nrows = (max_nblk + 1 - (p + 1)) * NB;
   if (nrows <= 0) return;
   hipLaunchKernelGGL((trsm_kernel<T, false>), dim3(nrows / 64, 1, ntasks), dim3(256), trsm_lds_bytes<T>(), st,
-                     tasks, p, yield_tab, so, tl);
+                     tasks, p, yield_tab, tl);
 }
 template <typename T>
 void trtri_diag_t(const TaskDesc* tasks, int ntasks, int p_lo, int p_hi, hipStream_t st) {
   set_attrs<T>();
   if (p_hi <= p_lo) return;
-  SplitOut none; memset(&none, 0, sizeof none);
   hipLaunchKernelGGL((trsm_kernel<T, true>), dim3(2, p_hi - p_lo, ntasks), dim3(256), trsm_lds_bytes<T>(), st,
-                     tasks, p_lo, (int*)nullptr, none, (unsigned long long*)nullptr);
+                     tasks, p_lo, (int*)nullptr, (unsigned long long*)nullptr);
 }
 
 #endif  // HBO_DEVICE_ONLY
@@ -485,12 +474,9 @@ void launch_potf2(int dtype, const TaskDesc* tasks, int ntasks, int p, int* info
   if (dtype == HBO_F64) potf2_t<double>(tasks, ntasks, p, info, st, yield_flag, tl);
   else potf2_t<float>(tasks, ntasks, p, info, st, yield_flag, tl);
 }
-void launch_trsm(int dtype, const TaskDesc* tasks, int ntasks, int p, int max_nblk, hipStream_t st, int* yield_tab, const SplitOut* so,
-                 unsigned long long* tl) {
-  SplitOut o; memset(&o, 0, sizeof o);
-  if (so) o = *so;
-  if (dtype == HBO_F64) trsm_t<double>(tasks, ntasks, p, max_nblk, st, yield_tab, o, tl);
-  else trsm_t<float>(tasks, ntasks, p, max_nblk, st, yield_tab, o, tl);
+void launch_trsm(int dtype, const TaskDesc* tasks, int ntasks, int p, int max_nblk, hipStream_t st, int* yield_tab, unsigned long long* tl) {
+  if (dtype == HBO_F64) trsm_t<double>(tasks, ntasks, p, max_nblk, st, yield_tab, tl);
+  else trsm_t<float>(tasks, ntasks, p, max_nblk, st, yield_tab, tl);
 }
 void launch_trtri_diag(int dtype, const TaskDesc* tasks, int ntasks, int p_lo, int p_hi, hipStream_t st) {
   if (dtype == HBO_F64) trtri_diag_t<double>(tasks, ntasks, p_lo, p_hi, st);

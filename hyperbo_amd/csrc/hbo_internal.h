@@ -216,13 +216,10 @@ static inline bool hbo_first_use_on_device(unsigned long long& seen) {
 // ---- launchers (defined in the .hip files) ---------------------------------------------
 void launch_gemm(int dtype, const GemmArgs& a, dim3 grid, hipStream_t st);
 
-// fp32: the panel solve also writes the solved panel as three bf16 planes (the operand of the bf16x3 trailing updates, post3.hip):
-// element (row, k) of panel block column kb_off.. -> ((row / 128 * nkb + kb_off + k / 16) * 3 + plane) * 2048 + (row % 128) * 16 + k % 16
-struct SplitOut { unsigned short* xp; int64_t task_stride; int nkb, kb_off; };
 void launch_potf2(int dtype, const TaskDesc* tasks, int ntasks, int p, int* info, hipStream_t st, int* yield_flag = nullptr,
                   unsigned long long* tl = nullptr);
 void launch_trsm(int dtype, const TaskDesc* tasks, int ntasks, int p, int max_nblk, hipStream_t st, int* yield_tab = nullptr,
-                 const SplitOut* so = nullptr, unsigned long long* tl = nullptr);
+                 unsigned long long* tl = nullptr);
 // HBO_TIMELINE builds: the slot pair of the next tagged launch (sched.hip), null when no recording is on
 unsigned long long* tl_slot(const char* name, int p);
 // inverses of the diagonal blocks p in [p_lo, p_hi)

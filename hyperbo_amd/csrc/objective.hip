@@ -256,7 +256,7 @@ int objective_local(hbo_ctx* c, const hbo_model* m_in, hbo_dataset* ds, int obje
   // inverse started beside the chain and K^-1 = W^T W after it
   const bool sweep = want_grad && !euc && use_sweep(c, dtype, T, max_nblk);
   if (sweep) sweep_st.qs = c->opt_sweep_qs > 0 ? c->opt_sweep_qs : sweep_group(T, max_nblk);
-  const bool early_trtri = !sweep && want_grad && la && c->opt_overlap_trtri && max_nblk >= 4;
+  const bool early_trtri = !sweep && want_grad && use_early_trtri(c, T, max_nblk);
   if (!euc) {
     {
       ProfScope ps(c, "gram", 1);
@@ -266,7 +266,7 @@ int objective_local(hbo_ctx* c, const hbo_model* m_in, hbo_dataset* ds, int obje
     {
       c->trtri_host_task = TaskDesc{};
       if (T == 1) c->trtri_host_task = ds->h_desc[0];
-      c->chol_diag_bound = chol_diag_bound_of(m);   // (cleared where the evaluation leaves: bound_scope)
+      c->run.chol_diag_bound = chol_diag_bound_of(m);   // (cleared where the evaluation leaves: bound_scope)
       ProfScope ps(c, "potrf", 1); run_potrf(c, dtype, ds->d_desc, T, max_nblk, ds->d_info, early_trtri ? &trtri_pg : nullptr, sweep ? &sweep_st : nullptr);
     }
     // the small reductions (log-determinant + quadratic form now, alpha = W^T z and d nll / d mu after the inverse) run on

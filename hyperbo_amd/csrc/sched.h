@@ -29,6 +29,25 @@ static inline bool use_lookahead(const hbo_ctx* c, int ntasks, int max_nblk) {
   if (c->opt_lookahead >= 2) return true;
   return max_nblk > 4 && (max_nblk >= 18 || (int64_t)ntasks * max_nblk >= 80);
 }
+// The block-recursive inverse starts beside the panel chain (run_potrf's `early`) where there is a chain to run beside and at least
+// one early piece (four final panels) to hand over.  Option overlap_trtri: 0 = never.
+static inline bool use_early_trtri(const hbo_ctx* c, int ntasks, int max_nblk) {
+  return use_lookahead(c, ntasks, max_nblk) && c->opt_overlap_trtri && max_nblk >= 4;
+}
+// Every decision of one blocked factorisation (sched.hip: potrf_plan has the measurements behind each value).
+enum YieldMode { YIELD_NONE, YIELD_POTF2, YIELD_CHAIN };     // who announces itself in the per-CU yield table: nobody / potf2 / the chain's wide kernels too
+enum Fp32Form { FORM_MFMA, FORM_BF16X3, FORM_F16X2 };        // trailing updates: fp32 MFMA (and all of fp64) / three-way bf16 split / two-way fp16 split
+struct PotrfPlan {
+  bool la;            // look-ahead: the panel chain on its own stream, the bulk update beside it
+  int q, q_inner;     // panels per trailing update; panels per inner group of the chain's column updates (0: one level)
+  int persist_free;   // CUs the resident bulk update leaves to the panel chain
+  int tgran, early_at;   // the early inverse gets its work after every tgran-th panel, and after panel early_at (-1: never)
+  YieldMode yield;
+  bool split_f1;      // F1's later block columns on the third stream
+  Fp32Form form;
+  bool h2_scales;     // the f16x2 products of the inverse and of K^-1 = W^T W get their measured-maximum words
+};
+PotrfPlan potrf_plan(const hbo_ctx* c, int dtype, int ntasks, int max_nblk, bool sweep);
 void run_potrf(hbo_ctx* c, int dtype, const TaskDesc* d_tasks, int ntasks, int max_nblk, int* d_info, TrtriProgress* early = nullptr,
                SweepState* sweep = nullptr);
 // does the objective pipeline of this shape take the one-sweep inverse?  (sched.hip)

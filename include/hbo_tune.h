@@ -10,8 +10,7 @@
  *   trtri_free    0..200   CUs the co-running inverse products leave with one workgroup
  *   post_bf16x3 / syrk_bf16x3 / trtri_bf16x3 / lauum_bf16x3  0/1   the four parts of option bf16x3 separately
  *   trtri3_min_s  >=1      lowest level (in blocks) of the inverse that runs on the bf16 cores
- *   syrk3_col / syrk3_sep / syrk3_free       fp32 trailing updates: column updates on the bf16 cores too / panels split by
- *                          their own kernel instead of inside the panel solve / CUs the bulk update leaves with one workgroup
+ *   syrk3_free    0..200   fp32 trailing updates on the bf16 / fp16 cores: CUs the bulk update leaves with one workgroup (32)
  *   sweep         0..2     one-sweep inverse (W = L^-1 and K^-1 = W^T W row group by row group behind the panel chain): 0 never,
  *                          1 where measured faster (default: batches with look-ahead, one fp64 matrix of 17-48 blocks;
  *                          profiles/r04_chain_and_sweep.md, r04_gemm_pipeline.md), 2 wherever look-ahead is on
@@ -43,9 +42,6 @@
  *                          paths): 1 = the rank's local part counts as failed -> it joins the all-reduce with NaN in every slot;
  *                          2 = and it cannot produce that buffer either -> ncclCommAbort, the peers' all-reduce fails, later sharded
  *                          calls return HBO_ERR_COMM until hbo_comm_init
- *   f2_split      0..2     round 6: the bulk trailing update's leading block columns -- at least the next group's, about one resident round of tiles --
- *                          as a launch of their own with the event the next F1 waits for behind THAT launch (1: one matrix, 2: batches too).
- *                          Identical values; measured neutral (N = 8192 10.51 -> 10.57 ms: profiles/r06_f2_split.md); default 0
  *   gram_mfma     0..4096  per context: fp32 Gram matrices of the stationary covariances with at least this many features take gram_mfma_kernel
  *                          (u = |a|^2 + |b|^2 - 2 a.b with a = (x - x_c) / l centred on a row of the tile, the dot product from exact
  *                          three-way bf16 splits on the matrix cores; tiles where that may be off by more than 1e-6 sv are computed again
