@@ -423,7 +423,6 @@ __global__ __launch_bounds__(256) void trsm_kernel(const TaskDesc* tasks, int p_
 #endif
 }
 
-#ifndef HBO_DEVICE_ONLY
 template <typename T>
 void set_attrs() {
   static unsigned long long seen = 0;
@@ -458,10 +457,8 @@ void trtri_diag_t(const TaskDesc* tasks, int ntasks, int p_lo, int p_hi, hipStre
                      tasks, p_lo, (int*)nullptr, (unsigned long long*)nullptr);
 }
 
-#endif  // HBO_DEVICE_ONLY
 }  // namespace
 
-#ifndef HBO_DEVICE_ONLY
 #ifdef HBO_POTF2_TIMING
 void dbg_read_stamps(unsigned long long* host) { hipMemcpyFromSymbol(host, HIP_SYMBOL(hbo_dbg_stamps), sizeof(unsigned long long) * 64); }
 extern "C" void hbo_dbg_trsm_wall(unsigned long long* host, int panel) {
@@ -482,4 +479,3 @@ void launch_trtri_diag(int dtype, const TaskDesc* tasks, int ntasks, int p_lo, i
   if (dtype == HBO_F64) trtri_diag_t<double>(tasks, ntasks, p_lo, p_hi, st);
   else trtri_diag_t<float>(tasks, ntasks, p_lo, p_hi, st);
 }
-#endif  // HBO_DEVICE_ONLY

@@ -1,15 +1,16 @@
 // MFMA tile GEMM for gfx950 (CDNA4): the workhorse behind the trailing update of the blocked
 // Cholesky (syrk), the recursive triangular inverse (trtri), K^-1 = W^T W (lauum) and the
 // posterior V = L^-1 Kxq.  128x128 output tile per 256-thread workgroup (4 waves as 2x2, each
-// wave 64x64 = 4x4 v_mfma_{f64,f32}_16x16x4 accumulators), K stepped in 128-byte slabs,
-// global -> register -> LDS staging with a two-deep LDS ring (one barrier per K step).
+// wave 64x64 = 4x4 v_mfma_{f64,f32}_16x16x4 accumulators) or 64x64 tile (each wave 32x32 = 2x2), K stepped in
+// 128-byte slabs.  Two tile cores, gemm_tile2 (128-tile) and gemm_tile3 (64-tile), of one scheme: global -> register
+// -> LDS staging with ONE LDS stage per operand and two barriers per slab, the next slab(s) prefetched into registers,
+// the next k step's fragments read between the MFMAs of the current one, the order pinned with sched_barrier.
 // Every matrix is padded to a multiple of 128 with zeros / identity, so the core has no edge
 // predicates; triangular structure is exploited by per-tile K ranges, never by masking.
 //
 // Replaces, for the reference, what XLA lowers jax.scipy.linalg.cholesky / cho_solve /
 // solve_triangular to (hyperbo/basics/linalg.py:29-33,139-145; hyperbo/gp_utils/gp.py:297).
 #include "hbo_internal.h"
-#include <cstdlib>
 
 namespace {
 
@@ -42,52 +43,7 @@ template <int TM> __device__ __host__ constexpr int smc() { return TM + 16; }   
 constexpr int OPERAND_BYTES = 18432;  // >= 128*skc*sizeof(T) and BKE*SMC*sizeof(T)
 constexpr int OPERAND_BYTES_64 = 10240;   // 64-tiles: max(64*skc, BKE*80) elements
 constexpr int GEMM_LDS_BYTES_64 = 4 * OPERAND_BYTES_64;
-constexpr int GEMM_LDS_BYTES = 4 * OPERAND_BYTES;  // A,B x 2 stages (128-tiles; 64-tiles use half)
-
-template <typename T, bool KC, int TM>
-__device__ __forceinline__ void stage_load(const T* __restrict__ g, int64_t ld, int kt,
-                                           typename Mma<T>::vec_t (&r)[TM / 32], int tid) {
-  typedef typename Mma<T>::vec_t vec_t;
-  constexpr int VEC = 16 / sizeof(T);
-  constexpr int BKE = 128 / sizeof(T);
-  if (KC) {
-    const int c = tid & 7, row = tid >> 3;
-    const T* p = g + (int64_t)row * ld + (int64_t)kt * BKE + c * VEC;
-#pragma unroll
-    for (int q = 0; q < TM / 32; ++q) r[q] = gld(reinterpret_cast<const vec_t*>(p + (int64_t)(32 * q) * ld));
-  } else {
-    constexpr int CPR = TM / VEC;   // 16-byte chunks per TM-element row
-    constexpr int RPP = 256 / CPR;  // k rows per pass
-    const int c = tid % CPR, kr = tid / CPR;
-    const T* p = g + ((int64_t)kt * BKE + kr) * ld + c * VEC;
-#pragma unroll
-    for (int q = 0; q < TM / 32; ++q) r[q] = gld(reinterpret_cast<const vec_t*>(p + (int64_t)(RPP * q) * ld));
-  }
-}
-
-template <typename T, bool KC, int TM>
-__device__ __forceinline__ void stage_store(T* s, const typename Mma<T>::vec_t (&r)[TM / 32], int tid) {
-  typedef typename Mma<T>::vec_t vec_t;
-  constexpr int VEC = 16 / sizeof(T);
-  if (KC) {
-    const int c = tid & 7, row = tid >> 3;
-#pragma unroll
-    for (int q = 0; q < TM / 32; ++q) {
-      if ((skc<T>() * sizeof(T)) % 16 == 0) {
-        *reinterpret_cast<vec_t*>(s + (row + 32 * q) * skc<T>() + c * VEC) = r[q];
-      } else {
-#pragma unroll
-        for (int e = 0; e < VEC; ++e) s[(row + 32 * q) * skc<T>() + c * VEC + e] = r[q][e];
-      }
-    }
-  } else {
-    constexpr int CPR = TM / VEC;
-    constexpr int RPP = 256 / CPR;
-    const int c = tid % CPR, kr = tid / CPR;
-#pragma unroll
-    for (int q = 0; q < TM / 32; ++q) *reinterpret_cast<vec_t*>(s + (kr + RPP * q) * smc<TM>() + c * VEC) = r[q];
-  }
-}
+constexpr int GEMM_LDS_BYTES = 4 * OPERAND_BYTES;  // ceiling the 128-tile kernels are registered with; what a launch asks for: gemm_plan
 
 template <typename T, bool KC, int TM>
 __device__ __forceinline__ T frag_read(const T* s, int mn, int k) {
@@ -340,145 +296,12 @@ __device__ __forceinline__ bool decode_job(const GemmArgs& g, TileJob<T>& j, con
   return false;
 }
 
-template <typename T, bool AKC, bool BKC, int TM>
-__device__ __forceinline__ void gemm_tile(const TileJob<T>& job, unsigned char* smem) {
-  typedef typename Mma<T>::acc_t acc_t;
-  typedef typename Mma<T>::vec_t vec_t;
-  constexpr int BKE = 128 / sizeof(T);
-  constexpr int MI = TM / 32;            // 16x16 MFMA tiles per wave and dimension (wave tile TM/2)
-  constexpr int WT = TM / 2;             // wave tile edge
-  constexpr int OPB = TM == 128 ? OPERAND_BYTES : OPERAND_BYTES_64;
-
-  T* sA0 = reinterpret_cast<T*>(smem);
-  T* sA1 = reinterpret_cast<T*>(smem + OPB);
-  T* sB0 = reinterpret_cast<T*>(smem + 2 * OPB);
-  T* sB1 = reinterpret_cast<T*>(smem + 3 * OPB);
-
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wm = wave >> 1, wn = wave & 1;
-  const int l15 = lane & 15, lq = lane >> 4;
-
-  // accumulators start from C/alpha when the tile is accumulated into C (beta = 1): the C tile is
-  // fetched together with the first operand slabs instead of in a read-modify-write epilogue
-  acc_t acc[MI][MI];
-  if (job.beta) {
-    const T inv_alpha = (T)1 / job.alpha;
-#pragma unroll
-    for (int a = 0; a < MI; ++a)
-#pragma unroll
-      for (int b = 0; b < MI; ++b)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int row = wm * WT + a * 16 + Mma<T>::crow(lane, r);
-          const int col = wn * WT + b * 16 + l15;
-          acc[a][b][r] = gld(job.C + (int64_t)row * job.ldc + col) * inv_alpha;
-        }
-  } else {
-#pragma unroll
-    for (int a = 0; a < MI; ++a)
-#pragma unroll
-      for (int b = 0; b < MI; ++b) acc[a][b] = (acc_t){0, 0, 0, 0};
-  }
-
-  const int nk = job.ksteps;
-  vec_t ra[MI], rb[MI];
-  stage_load<T, AKC, TM>(job.A, job.lda, 0, ra, tid);
-  stage_load<T, BKC, TM>(job.B, job.ldb, 0, rb, tid);
-  stage_store<T, AKC, TM>(sA0, ra, tid);
-  stage_store<T, BKC, TM>(sB0, rb, tid);
-  __syncthreads();
-
-  // Yield poll, software-pipelined: the table entry of this CU is loaded at the top of a K step -- ahead of the slab
-  // prefetch, so it has arrived, at no cost, by the time the prefetch is waited for -- and looked at at the top of the
-  // NEXT step (a poll that is waited for on the spot costs an L2 round trip per K step: N = 16384 lost 0.9 % to it).
-  const int* const yslot = job.yield_flag ? job.yield_flag + cu_token() : nullptr;
-  int ypoll = 0;
-  for (int kt = 0; kt < nk; ++kt) {
-    if (yslot) {
-      // a panel-chain workgroup is running on this CU: stay off its MFMA / LDS paths until it is done (bounded wait)
-      if (ypoll != 0)
-        for (int spin = 0; spin < 256 && __hip_atomic_load(yslot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0; ++spin)
-          __builtin_amdgcn_s_sleep(16);
-      ypoll = __hip_atomic_load(yslot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    const T* cA = (kt & 1) ? sA1 : sA0;
-    const T* cB = (kt & 1) ? sB1 : sB0;
-    const bool more = (kt + 1 < nk);
-    if (more) {
-      stage_load<T, AKC, TM>(job.A, job.lda, kt + 1, ra, tid);
-      stage_load<T, BKC, TM>(job.B, job.ldb, kt + 1, rb, tid);
-    }
-#pragma unroll
-    for (int kk = 0; kk < BKE / 4; ++kk) {
-      const int k = kk * 4 + lq;
-      T af[MI], bf[MI];
-#pragma unroll
-      for (int a = 0; a < MI; ++a) af[a] = frag_read<T, AKC, TM>(cA, wm * WT + a * 16 + l15, k);
-#pragma unroll
-      for (int b = 0; b < MI; ++b) bf[b] = frag_read<T, BKC, TM>(cB, wn * WT + b * 16 + l15, k);
-#pragma unroll
-      for (int a = 0; a < MI; ++a)
-#pragma unroll
-        for (int b = 0; b < MI; ++b) acc[a][b] = Mma<T>::mma(af[a], bf[b], acc[a][b]);
-      // the LDS stores of the prefetched slab go in the middle of the MFMA stream
-      if (kk == BKE / 4 - 2 && more) {
-        __builtin_amdgcn_sched_barrier(0);
-        stage_store<T, AKC, TM>((kt & 1) ? sA0 : sA1, ra, tid);
-        stage_store<T, BKC, TM>((kt & 1) ? sB0 : sB1, rb, tid);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-    }
-    __syncthreads();
-  }
-
-  // epilogue: C = alpha * acc (the old C, if any, is already inside acc)
-  if (job.C) {
-#pragma unroll
-    for (int a = 0; a < MI; ++a)
-#pragma unroll
-      for (int b = 0; b < MI; ++b)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int row = wm * WT + a * 16 + Mma<T>::crow(lane, r);
-          const int col = wn * WT + b * 16 + l15;
-          gst(job.C + (int64_t)row * job.ldc + col, job.alpha * acc[a][b][r]);
-        }
-  }
-  if (TM == 128 && job.colsq) {
-    // sum over this tile's 128 rows of acc^2, per column
-    T* red = reinterpret_cast<T*>(smem);  // [4 waves][64]
-    T part[MI];
-#pragma unroll
-    for (int b = 0; b < MI; ++b) {
-      T s = 0;
-#pragma unroll
-      for (int a = 0; a < MI; ++a)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) s += acc[a][b][r] * acc[a][b][r];
-      s += __shfl_xor(s, 16);
-      s += __shfl_xor(s, 32);
-      part[b] = s;
-    }
-    // (the k-loop ended with a barrier, so smem is free)
-    if (lq == 0) {
-#pragma unroll
-      for (int b = 0; b < MI; ++b) red[wave * 64 + b * 16 + l15] = part[b];
-    }
-    __syncthreads();
-    if (tid < 128) {
-      const int wn2 = tid >> 6, c = tid & 63;
-      // waves (wm=0,wn2) and (wm=1,wn2)
-      gst(job.colsq + wn2 * 64 + c, red[(0 * 2 + wn2) * 64 + c] + red[(1 * 2 + wn2) * 64 + c]);
-    }
-  }
-}
-
-// ---- the pipelined tile core (round 4) ------------------------------------------------------------------------------------------
-// Same tile, same LDS layouts, same arithmetic (every accumulator receives its products in ascending k: bit-identical results) --
-// a different pipeline.  gemm_tile issues the LDS fragment reads of a k step right before the 16 MFMAs that consume them, stores a
-// whole slab to LDS in one run of instructions and keeps two LDS stages per operand; in its K loop a wave has stretches of 40-60
-// instructions without an MFMA, and it reaches 0.80-0.85 of the fp64 MFMA peak where a vendor kernel of the same macro tile
-// (rocBLAS dgemm, 128 x 128 x 16, 256 threads) sustains the peak (profiles/r04_gemm_pipeline.md).  What this core does instead:
+// ---- the 128-tile core ----------------------------------------------------------------------------------------------------------
+// Every accumulator receives its products in ascending k.  Measured and not adopted (profiles/r04_gemm_pipeline.md; removed from the
+// tree, profiles/gemm_refactor.md): the first core, bit-identical, which issued the LDS fragment reads of a k step right before the 16
+// MFMAs that consume them, stored a whole slab to LDS in one run of instructions and kept two LDS stages per operand with one barrier
+// per K step; in its K loop a wave had stretches of 40-60 instructions without an MFMA, and it reached 0.80-0.85 of the fp64 MFMA peak
+// where a vendor kernel of the same macro tile (rocBLAS dgemm, 128 x 128 x 16, 256 threads) sustains the peak.  What this core does:
 //   * the fragments of k step i + 1 are read (into a second register set) between the first MFMAs of step i;
 //   * ONE LDS stage per operand and two barriers per slab: after the last fragment read of a slab every wave passes a barrier,
 //     the next slab is written from the prefetch registers, a second barrier, then its first fragments are read -- every one of
@@ -549,6 +372,8 @@ __device__ __forceinline__ void gemm_tile2(const TileJob<T>& job, unsigned char*
   const int wm = wave >> 1, wn = wave & 1;
   const int l15 = lane & 15, lq = lane >> 4;
 
+  // accumulators start from C/alpha when the tile is accumulated into C (beta = 1): the C tile is
+  // fetched together with the first operand slabs instead of in a read-modify-write epilogue
   acc_t acc[MI][MI];
   if (job.beta) {
     const T inv_alpha = (T)1 / job.alpha;
@@ -618,11 +443,14 @@ __device__ __forceinline__ void gemm_tile2(const TileJob<T>& job, unsigned char*
 #pragma unroll
   for (int i = 0; i < 2 * MI; ++i) frag(0, 0, i);
 
+  // Yield poll, software-pipelined: the table entry of this CU is loaded at the top of a slab -- ahead of the slab
+  // prefetch, so it has arrived, at no cost, by the time the prefetch is waited for -- and looked at at the top of the
+  // NEXT slab (a poll that is waited for on the spot costs an L2 round trip per slab: N = 16384 lost 0.9 % to it).
   const int* const yslot = job.yield_flag ? job.yield_flag + cu_token() : nullptr;
   int ypoll = 0;
   for (int kt = 0; kt + 1 < nk; ++kt) {
     if (yslot) {
-      // a panel-chain workgroup is running on this CU: stay off its MFMA / LDS paths until it is done (bounded wait; see gemm_tile)
+      // a panel-chain workgroup is running on this CU: stay off its MFMA / LDS paths until it is done (bounded wait)
       if (ypoll != 0)
         for (int spin = 0; spin < 256 && __hip_atomic_load(yslot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0; ++spin)
           __builtin_amdgcn_s_sleep(16);
@@ -665,6 +493,7 @@ __device__ __forceinline__ void gemm_tile2(const TileJob<T>& job, unsigned char*
 #undef HBO_SB
   if (yslot) __syncthreads();   // (uniform exit of the K loop for the LDS reuse of the epilogue below)
 
+  // epilogue: C = alpha * acc (the old C, if any, is already inside acc)
   if (job.C) {
 #pragma unroll
     for (int a = 0; a < MI; ++a)
@@ -678,6 +507,7 @@ __device__ __forceinline__ void gemm_tile2(const TileJob<T>& job, unsigned char*
         }
   }
   if (TM == 128 && job.colsq) {
+    // sum over this tile's 128 rows of acc^2, per column
     __syncthreads();   // every wave is done with the last slab's fragments: the LDS is free for the reduction
     T* red = reinterpret_cast<T*>(smem);  // [4 waves][64]
     T part[MI];
@@ -698,22 +528,18 @@ __device__ __forceinline__ void gemm_tile2(const TileJob<T>& job, unsigned char*
     }
     __syncthreads();
     if (tid < 128) {
-      const int wn2 = tid >> 6, c = tid & 63;
+      const int wn2 = tid >> 6, c = tid & 63;   // waves (wm = 0, wn2) and (wm = 1, wn2)
       gst(job.colsq + wn2 * 64 + c, red[(0 * 2 + wn2) * 64 + c] + red[(1 * 2 + wn2) * 64 + c]);
     }
   }
 }
-// ---- the 64-tile core (round 4) ------------------------------------------------------------------------------------------------
+// ---- the 64-tile core -----------------------------------------------------------------------------------------------------------
 // The single-stage scheme of gemm_tile2 for the 64 x 64 tile: 4 MFMAs and 4 fragment reads per wave and k step, two barriers per
 // slab, fragment reads of the next k step beside the MFMAs of the current one, and a ring of PF slabs prefetched into registers
 // (16 VGPRs per slab and thread).  PF = 2: a lone workgroup's slabs come from L2 at ~1 us each, a deeper ring buys nothing and
 // costs the fourth workgroup per CU (profiles/r04_gemm_pipeline.md, section 4).  Same ascending-k arithmetic: identical results.
-#ifndef HBO_PF64
-#define HBO_PF64 2
-#endif
-#ifndef HBO_LB64
-#define HBO_LB64 4
-#endif
+constexpr int PF64 = 2;   // slabs in the register ring
+constexpr int LB64 = 4;   // workgroups per CU the 64-tile kernels are bounded for (__launch_bounds__)
 template <typename T, bool AKC, bool BKC, int TM, int PF>
 __device__ __forceinline__ void gemm_tile3(const TileJob<T>& job, unsigned char* smem) {
   typedef typename Mma<T>::acc_t acc_t;
@@ -835,22 +661,11 @@ __device__ __forceinline__ void gemm_tile3(const TileJob<T>& job, unsigned char*
         }
   }
 }
-// which core a tile takes: the pipelined ones (128-tile: gemm_tile2, 64-tile: gemm_tile3; fp32 has 8 k steps per slab where fp64
-// has 4, everything else is the same); gemm_tile stays for the A/B builds (-DHBO_GEMM_V1, -DHBO_GEMM_F32_V1, -DHBO_GEMM_NO64)
+// which core a tile takes (fp32 has 8 k steps per slab where fp64 has 4, everything else is the same)
 template <typename T, bool AKC, bool BKC, int TM>
 __device__ __forceinline__ void run_tile(const TileJob<T>& job, unsigned char* smem) {
-#ifndef HBO_GEMM_V1
-#ifdef HBO_GEMM_F32_V1
-  if constexpr (sizeof(T) == 4) gemm_tile<T, AKC, BKC, TM>(job, smem);
-  else
-#endif
   if constexpr (TM == 128) gemm_tile2<T, AKC, BKC, TM>(job, smem);
-#ifndef HBO_GEMM_NO64
-  else if constexpr (TM == 64) gemm_tile3<T, AKC, BKC, TM, HBO_PF64>(job, smem);
-#endif
-  else
-#endif
-    gemm_tile<T, AKC, BKC, TM>(job, smem);
+  else gemm_tile3<T, AKC, BKC, TM, PF64>(job, smem);
 }
 
 // SYRK tiles by linear index (column-major over the trapezoid c in [c_lo,c_hi), r in [c,nrt)): used by
@@ -973,166 +788,115 @@ __device__ __forceinline__ void gemm_kernel_body(const GemmArgs& g, unsigned cha
 }
 
 template <typename T, bool AKC, bool BKC, int TM>
-__global__ __launch_bounds__(256, TM == 64 ? (sizeof(T) == 8 ? HBO_LB64 : 4) : 2) void gemm_kernel(GemmArgs g) {
+__global__ __launch_bounds__(256, TM == 64 ? LB64 : 2) void gemm_kernel(GemmArgs g) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   tl_begin(g.tl);
   gemm_kernel_body<T, AKC, BKC, TM>(g, smem);
   tl_end(g.tl);
 }
 
-#ifndef HBO_DEVICE_ONLY
-template <typename T, bool AKC, bool BKC>
-void launch_tile64(dim3 grid, int lds64, hipStream_t st, const GemmArgs& a) {
-  // (round 6: the same tile on ONE wave -- a 64-thread workgroup with the 128-tile's 4 x 4 accumulator block, LDS-DMA staging, no barrier --
-  //  was built, bit-identical, and slower everywhere: these launches are bound by the latency of a tile, and one SIMD then executes all
-  //  64 MFMAs of a slab: N = 4096 2.57 -> 4.58 ms, N = 8192 10.65 -> 13.5, shard of 8 2.45 -> 3.55; profiles/r06_tile64_one_wave.md)
-  hipLaunchKernelGGL((gemm_kernel<T, AKC, BKC, 64>), grid, dim3(256), lds64, st, a);
-}
-template <typename T>
-void launch_gemm_t(const GemmArgs& a_in, dim3 grid, hipStream_t st) {
-  GemmArgs a = a_in;
-  // the persistent forms: SYRK (any tile size); TRTRI of a single matrix and the SWEEP modes (also over a batch) with a tile counter
-  const bool sweep_mode = a.mode == GEMM_SWEEP_B || a.mode == GEMM_SWEEP_T || a.mode == GEMM_SWEEP_C;
-  if (a.mode != GEMM_SYRK && !((a.mode == GEMM_TRTRI_A || a.mode == GEMM_TRTRI_B) && a.work_counter && grid.z == 1) && !(sweep_mode && a.work_counter) &&
-      !(a.mode == GEMM_LAUUM && a.work_counter && grid.z == 1 && !a.small_tiles) && !(a.mode == GEMM_POST && a.work_counter && grid.z == 1))
-    a.persistent = 0;
+// ---- host side: what a launch of each mode looks like ----------------------------------------------------------------------------
+// The caller's grid is in 128-tile units: (x, y) tiles x z tasks.
+enum Operands { OPS_KK, OPS_KM, OPS_MM };   // LDS layout of A and B, k- or m-contiguous: gemm_kernel<T, AKC, BKC> = <1,1>, <1,0>, <0,0>
+enum TileGrid {
+  TILES_XY,    // the grid as given; both dimensions x 2 on 64-tiles
+  TILES_TRI,   // 1-D over the lower tiles of grid.x blocks (the largest task's): n (n + 1) / 2, on 64-tiles 2 n (n + 1) -- decode_job, LAUUM
+};
+struct ModeRow {
+  Operands ops;
+  TileGrid tiles;
+  // small_tiles selects 64-tiles (elsewhere it is ignored): 4x the workgroups, a quarter of the per-tile latency -- for the skinny
+  // updates on the critical path (next block column), small trailing matrices and batches
+  bool tiles64;
+  // `persistent` workgroups that loop over the tiles may replace the tile grid -- the same tiles in the same order, drawn from a
+  // counter: the hardware deals the workgroups of a plain grid to the 8 XCDs in turn and waits when the next one's XCD is full; with
+  // LAUUM's tiles of 1 to 64 K blocks a tenth of the slots stood empty in the middle of the launch (in-kernel stamps: 459 of 512 busy
+  // on average).  POST draws its (row tile, column tile) pairs the same way, long rows first.  Conditions on top of that:
+  bool resident;
+  bool needs_counter;   // only with a work_counter (SYRK without one strides over its tiles)
+  bool one_task;        // only for grid.z == 1
+  bool only128;         // only on 128-tiles
+  bool over_tasks;      // the resident launch draws over tiles x tasks from one counter (GemmArgs::ptasks), not one grid per task
+};
+constexpr ModeRow MODE_TABLE[] = {
+  //                  operands tile grid  tiles64 resident counter one task 128 only over tasks
+  /* GEMM_SYRK    */ {OPS_KK, TILES_XY,  true,  true,  false, false, false, false},
+  /* GEMM_TRTRI_A */ {OPS_KM, TILES_XY,  true,  true,  true,  true,  false, false},
+  /* GEMM_TRTRI_B */ {OPS_KM, TILES_XY,  true,  true,  true,  true,  false, false},
+  /* GEMM_LAUUM   */ {OPS_MM, TILES_TRI, true,  true,  true,  true,  true,  false},
+  /* GEMM_POST    */ {OPS_KM, TILES_XY,  false, true,  true,  true,  false, false},
+  /* GEMM_VTV     */ {OPS_MM, TILES_XY,  false, false, false, false, false, false},
+  /* GEMM_SWEEP_B */ {OPS_KM, TILES_XY,  true,  true,  true,  false, false, true},
+  /* GEMM_SWEEP_T */ {OPS_KM, TILES_XY,  true,  true,  true,  false, false, true},
+  /* GEMM_SWEEP_C */ {OPS_MM, TILES_TRI, true,  true,  true,  false, false, true},   // grid.x = leading blocks b1 of the largest task
+};
+constexpr int N_MODES = sizeof(MODE_TABLE) / sizeof(ModeRow);
+static_assert(GEMM_SYRK == 0 && GEMM_TRTRI_A == 1 && GEMM_TRTRI_B == 2 && GEMM_LAUUM == 3 && GEMM_POST == 4 && GEMM_VTV == 5 &&
+              GEMM_SWEEP_B == 6 && GEMM_SWEEP_T == 7 && GEMM_SWEEP_C == 8 && N_MODES == 9, "one row per GemmMode, in its order");
+
+// dynamic LDS of a launch.  64-tiles ask for four operand stages although gemm_tile3 uses two: measured equal or better (N = 4096: 2.76
+// against 2.81 ms with 20 KB, profiles/r04_gemm_pipeline.md).  128-tiles: one stage per operand, and not less than the 64-tile request --
+// the persistent update runs its last round on 64-tiles inside the 128-tile kernel (n_big)
+constexpr int LDS_64 = GEMM_LDS_BYTES_64;
+constexpr int LDS_128 = 2 * OPERAND_BYTES > LDS_64 ? 2 * OPERAND_BYTES : LDS_64;
+
+// the whole launch decision (pure: no HIP call) for a mode of the table; a = the caller's arguments with persistent / work_counter /
+// pgx / pgy / ptasks as the kernel is to see them, tm = 128 or 64
+struct GemmPlan { GemmArgs a; Operands ops; int tm; dim3 grid; int lds; };
+GemmPlan gemm_plan(const GemmArgs& a_in, dim3 grid) {
+  const ModeRow& row = MODE_TABLE[a_in.mode];
+  GemmPlan p = {a_in, row.ops, row.tiles64 && a_in.small_tiles ? 64 : 128, grid, 0};
+  GemmArgs& a = p.a;
+  const bool resident_ok = row.resident && (!row.needs_counter || a.work_counter) && (!row.one_task || grid.z == 1) && (!row.only128 || p.tm == 128);
   // a resident grid needs at least one workgroup: on a small device / partition (or with a placement knob >= the CU count) the
   // callers' 2*(CUs - free) is <= 0 -- fall back to the plain grid AND drop the counter, or the kernel would take the counter branch
   // of a launch whose resident size is zero and compute no tile
-  if (a.persistent <= 0) { a.persistent = 0; a.work_counter = nullptr; }
+  if (!resident_ok || a.persistent <= 0) { a.persistent = 0; a.work_counter = nullptr; }
+  const unsigned u = p.tm == 64 ? 2 : 1, n = grid.x;
+  const dim3 tiles = row.tiles == TILES_TRI ? dim3(u == 2 ? 2 * n * (n + 1) : n * (n + 1) / 2, 1, grid.z) : dim3(grid.x * u, grid.y * u, grid.z);
   a.ptasks = 0;
-  // dynamic LDS of a 128-tile workgroup: one stage per operand for the pipelined cores, two for gemm_tile
-#ifdef HBO_GEMM_V1
-  int lds128 = GEMM_LDS_BYTES;
-#else
-#ifdef HBO_GEMM_F32_V1
-  int lds128 = sizeof(T) == 8 ? 2 * OPERAND_BYTES : GEMM_LDS_BYTES;
-#else
-  int lds128 = 2 * OPERAND_BYTES;
-#endif
-#endif
-  // 64-tiles keep the two-stage request although gemm_tile3 uses one: measured equal or better (N = 4096: 2.76 against 2.81 ms with
-  // 20 KB, profiles/r04_gemm_pipeline.md); the persistent update runs its last round on 64-tiles inside the 128-tile kernel (n_big)
-  const int lds64 = GEMM_LDS_BYTES_64;
-  if (lds128 < lds64) lds128 = lds64;
-#ifdef HBO_GEMM_DEBUG
-  // HBO_GEMM_LDS=<bytes>: ask for more LDS than the kernel needs (above 80 KB: one workgroup per CU instead of two)
-  static const int dbg_lds = getenv("HBO_GEMM_LDS") ? atoi(getenv("HBO_GEMM_LDS")) : 0;
-  if (dbg_lds > lds128) lds128 = dbg_lds;
-  const int attr128 = dbg_lds > GEMM_LDS_BYTES ? dbg_lds : GEMM_LDS_BYTES;
-#else
-  const int attr128 = GEMM_LDS_BYTES;
-#endif
+  if (a.persistent > 0) {
+    // (the <1,1> kernel, SYRK, walks its own linear tile order -- decode_syrk_linear -- and reads no pgx / pgy)
+    if (row.ops != OPS_KK) { a.pgx = (int)tiles.x; a.pgy = (int)tiles.y; }
+    if (row.over_tasks) a.ptasks = (int)grid.z;
+    p.grid = dim3(a.persistent, 1, row.over_tasks ? 1 : grid.z);
+  } else {
+    p.grid = tiles;
+  }
+  p.lds = p.tm == 64 ? LDS_64 : LDS_128;
+  return p;
+}
+
+template <typename T, bool AKC, bool BKC>
+void launch_plan(const GemmPlan& p, hipStream_t st) {
+  // (round 6: the 64-tile on ONE wave -- a 64-thread workgroup with the 128-tile's 4 x 4 accumulator block, LDS-DMA staging, no barrier --
+  //  was built, bit-identical, and slower everywhere: these launches are bound by the latency of a tile, and one SIMD then executes all
+  //  64 MFMAs of a slab: N = 4096 2.57 -> 4.58 ms, N = 8192 10.65 -> 13.5, shard of 8 2.45 -> 3.55; profiles/r06_tile64_one_wave.md)
+  if (p.tm == 64) hipLaunchKernelGGL((gemm_kernel<T, AKC, BKC, 64>), p.grid, dim3(256), p.lds, st, p.a);
+  else hipLaunchKernelGGL((gemm_kernel<T, AKC, BKC, 128>), p.grid, dim3(256), p.lds, st, p.a);
+}
+template <typename T>
+void launch_gemm_t(const GemmArgs& a, dim3 grid, hipStream_t st) {
   static unsigned long long attr_seen = 0;
   if (hbo_first_use_on_device(attr_seen)) {
     hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_kernel<T, true, true, 128>),
-                        hipFuncAttributeMaxDynamicSharedMemorySize, attr128);
+                        hipFuncAttributeMaxDynamicSharedMemorySize, GEMM_LDS_BYTES);
     hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_kernel<T, true, false, 128>),
-                        hipFuncAttributeMaxDynamicSharedMemorySize, attr128);
+                        hipFuncAttributeMaxDynamicSharedMemorySize, GEMM_LDS_BYTES);
     hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_kernel<T, false, false, 128>),
-                        hipFuncAttributeMaxDynamicSharedMemorySize, attr128);
+                        hipFuncAttributeMaxDynamicSharedMemorySize, GEMM_LDS_BYTES);
   }
-  switch (a.mode) {
-    case GEMM_SYRK:
-      if (a.persistent > 0) {
-        dim3 gp(a.persistent, 1, grid.z);
-        if (a.small_tiles) launch_tile64<T, true, true>(gp, lds64, st, a);
-        else hipLaunchKernelGGL((gemm_kernel<T, true, true, 128>), gp, dim3(256), lds128, st, a);
-      } else if (a.small_tiles) {
-        // 64x64 tiles: 4x the workgroups, a quarter of the per-tile latency -- for the skinny
-        // updates on the critical path (next block column) and small trailing matrices
-        dim3 g2(grid.x * 2, grid.y * 2, grid.z);
-        launch_tile64<T, true, true>(g2, lds64, st, a);
-      } else {
-        hipLaunchKernelGGL((gemm_kernel<T, true, true, 128>), grid, dim3(256), lds128, st, a);
-      }
-      break;
-    case GEMM_TRTRI_A:
-    case GEMM_TRTRI_B:
-      if (a.small_tiles && a.persistent > 0) {
-        GemmArgs b = a; b.pgx = (int)grid.x * 2; b.pgy = (int)grid.y * 2;
-        launch_tile64<T, true, false>(dim3(a.persistent, 1, 1), lds64, st, b);
-      } else if (a.small_tiles) {
-        dim3 g2(grid.x * 2, grid.y * 2, grid.z);
-        launch_tile64<T, true, false>(g2, lds64, st, a);
-      } else if (a.persistent > 0) {
-        GemmArgs b = a; b.pgx = (int)grid.x; b.pgy = (int)grid.y;
-        hipLaunchKernelGGL((gemm_kernel<T, true, false, 128>), dim3(a.persistent, 1, 1), dim3(256), lds128, st, b);
-      } else {
-        hipLaunchKernelGGL((gemm_kernel<T, true, false, 128>), grid, dim3(256), lds128, st, a);
-      }
-      break;
-    case GEMM_SWEEP_B:
-    case GEMM_SWEEP_T:
-      // grid = tiles in 128-units (x, y) x tasks
-      if (a.persistent > 0) {
-        GemmArgs b = a; const int u = a.small_tiles ? 2 : 1;
-        b.pgx = (int)grid.x * u; b.pgy = (int)grid.y * u; b.ptasks = (int)grid.z;
-        if (a.small_tiles) launch_tile64<T, true, false>(dim3(a.persistent, 1, 1), lds64, st, b);
-        else hipLaunchKernelGGL((gemm_kernel<T, true, false, 128>), dim3(a.persistent, 1, 1), dim3(256), lds128, st, b);
-      } else if (a.small_tiles) {
-        launch_tile64<T, true, false>(dim3(grid.x * 2, grid.y * 2, grid.z), lds64, st, a);
-      } else {
-        hipLaunchKernelGGL((gemm_kernel<T, true, false, 128>), grid, dim3(256), lds128, st, a);
-      }
-      break;
-    case GEMM_SWEEP_C: {
-      // grid.x = leading blocks b1 of the largest task: 1-D over their lower tiles
-      const unsigned nt = a.small_tiles ? 2 * grid.x * (grid.x + 1) : grid.x * (grid.x + 1) / 2;
-      if (a.persistent > 0) {
-        GemmArgs b = a; b.pgx = (int)nt; b.pgy = 1; b.ptasks = (int)grid.z;
-        if (a.small_tiles) launch_tile64<T, false, false>(dim3(a.persistent, 1, 1), lds64, st, b);
-        else hipLaunchKernelGGL((gemm_kernel<T, false, false, 128>), dim3(a.persistent, 1, 1), dim3(256), lds128, st, b);
-      } else if (a.small_tiles) {
-        launch_tile64<T, false, false>(dim3(nt, 1, grid.z), lds64, st, a);
-      } else {
-        hipLaunchKernelGGL((gemm_kernel<T, false, false, 128>), dim3(nt, 1, grid.z), dim3(256), lds128, st, a);
-      }
-      break;
-    }
-    case GEMM_POST:
-      if (a.persistent > 0) {   // (row tile, column tile) pairs drawn from a counter, long rows first -- see LAUUM
-        GemmArgs b = a; b.pgx = (int)grid.x; b.pgy = (int)grid.y;
-        hipLaunchKernelGGL((gemm_kernel<T, true, false, 128>), dim3(a.persistent, 1, 1), dim3(256), lds128, st, b);
-      } else
-      hipLaunchKernelGGL((gemm_kernel<T, true, false, 128>), grid, dim3(256), lds128, st, a);
-      break;
-    case GEMM_VTV:
-#ifdef HBO_GEMM_DEBUG
-      {
-        // HBO_BENCH_VTV_KC=1 / 2: the same square launch through the <true,false> / <true,true> cores (operands read as k-contiguous
-        // rows of the same buffer: meaningless numbers, the loop's rate for those LDS layouts)
-        static const int kc = getenv("HBO_BENCH_VTV_KC") ? atoi(getenv("HBO_BENCH_VTV_KC")) : 0;
-        if (kc == 1) { hipLaunchKernelGGL((gemm_kernel<T, true, false, 128>), grid, dim3(256), lds128, st, a); break; }
-        if (kc == 2) { hipLaunchKernelGGL((gemm_kernel<T, true, true, 128>), grid, dim3(256), lds128, st, a); break; }
-      }
-#endif
-      hipLaunchKernelGGL((gemm_kernel<T, false, false, 128>), grid, dim3(256), lds128, st, a);
-      break;
-    case GEMM_LAUUM:
-      if (a.small_tiles) {
-        dim3 g2(2 * grid.x * (grid.x + 1), 1, grid.z);
-        launch_tile64<T, false, false>(g2, lds64, st, a);
-      } else {
-        // 1-D grid over the lower tiles (grid.x = block count of the largest task)
-        dim3 g1(grid.x * (grid.x + 1) / 2, 1, grid.z);
-        if (a.persistent > 0) {
-          // the same tiles in the same order, drawn from a counter by a resident grid: the hardware deals the workgroups of a
-          // plain grid to the 8 XCDs in turn and waits when the next one's XCD is full -- with tiles of 1 to 64 K blocks a tenth
-          // of the slots stood empty in the middle of the launch (in-kernel stamps: 459 of 512 busy on average)
-          GemmArgs b = a; b.pgx = (int)g1.x; b.pgy = 1;
-          hipLaunchKernelGGL((gemm_kernel<T, false, false, 128>), dim3(a.persistent, 1, 1), dim3(256), lds128, st, b);
-        } else
-        hipLaunchKernelGGL((gemm_kernel<T, false, false, 128>), g1, dim3(256), lds128, st, a);
-      }
-      break;
+  if (a.mode < 0 || a.mode >= N_MODES) return;   // not a GemmMode: nothing to launch
+  const GemmPlan p = gemm_plan(a, grid);
+  switch (p.ops) {
+    case OPS_KK: launch_plan<T, true, true>(p, st); break;
+    case OPS_KM: launch_plan<T, true, false>(p, st); break;
+    case OPS_MM: launch_plan<T, false, false>(p, st); break;
   }
 }
 
-#endif  // HBO_DEVICE_ONLY
 }  // namespace
 
-#ifndef HBO_DEVICE_ONLY
 #ifdef HBO_GEMM_TIMING
 extern "C" void hbo_dbg_gemm_wall(unsigned long long* host, int mode, int index) {
   if (host) { hipMemcpyFromSymbol(host, HIP_SYMBOL(hbo_dbg_gemm), sizeof(unsigned long long) * 4 * 8192); return; }
@@ -1150,4 +914,3 @@ void launch_gemm(int dtype, const GemmArgs& a_in, dim3 grid, hipStream_t st) {
   if (dtype == HBO_F64) launch_gemm_t<double>(a, grid, st);
   else launch_gemm_t<float>(a, grid, st);
 }
-#endif  // HBO_DEVICE_ONLY

@@ -122,11 +122,12 @@ struct GemmArgs {
   int c_lo;      // SYRK: first updated tile column;   TRTRI_A: tile rows launched for the last group
   int c_hi;      // SYRK: end (exclusive) of updated tile columns;   TRTRI_A: index of the last group
   int aug;       // SYRK: 1 -> include the augmented tile-row
-  int small_tiles;  // 1 -> 64x64 output tiles (SYRK / TRTRI / LAUUM; grid is given in 128-tile units)
-  int persistent;   // >0 -> that many persistent workgroups loop over the tiles (SYRK; TRTRI on 128-tiles with a work_counter)
+  int small_tiles;  // 1 -> 64x64 output tiles (every mode but POST / VTV; grid is given in 128-tile units)
+  int persistent;   // >0 -> that many persistent workgroups loop over the tiles, where the mode's row of gemm.hip: MODE_TABLE
+                    // allows it (SYRK always; the others with a work_counter, most of them for one task only); else ignored
   int n_big;        // persistent SYRK on 128-tiles: tiles [0, n_big) of the linear order run as 128-tiles, the rest as four 64-tiles
                     // each (0 = all of them as 128-tiles): the last, partly filled round of a launch balances at a quarter of the grain
-  int pgx, pgy;     // persistent TRTRI / SWEEP: the tile grid the workgroups walk (set by launch_gemm)
+  int pgx, pgy;     // persistent form of every mode but SYRK: the tile grid the workgroups walk (set by launch_gemm)
   int ptasks;       // persistent form over a batch: tiles x tasks are drawn from ONE counter (tile-major, so that equal-K tiles of
                     // all tasks are neighbours); 0: the task is blockIdx.z
   int* work_counter; // persistent SYRK: zero-initialised tile counter -> workgroups draw tiles dynamically (a faster
