@@ -295,7 +295,7 @@ static int posterior(hbo_ctx* c, const hbo_model* m, hbo_cache* k, const void* x
   unsigned short* d_K3 = nullptr; size_t k3_b = 0;
   const int nkb = k ? t->npad / 16 : 0;
   // stationary covariances (|k| <= signal variance: the cross Gram's scale is known without a pass over it): two-way fp16 split,
-  // three MFMAs per product instead of six (post2h.hip)
+  // three MFMAs per product instead of six (post3.hip, H2)
   const bool use2h = use3 && c->opt_post_f16x2 && m->kernel_id != HBO_KERNEL_DOT;
   const int planes = use2h ? 2 : 3;
   const float kscale = use2h ? post2h_scale_for(m->signal_variance) : 1.f;
@@ -312,12 +312,10 @@ static int posterior(hbo_ctx* c, const hbo_model* m, hbo_cache* k, const void* x
     }
     if (use3) {
       ProfScope ps(c, "split_w", 1, sa);
-      if (use2h) {
-        launch_absmax_lower(static_cast<const float*>(t->W), t->ld, t->nblk, k->d_wmax, sa);
-        launch_split2h_rows(static_cast<const float*>(t->W), t->ld, t->nblk, k->w3, nkb, k->d_wmax, sa);
-      } else {
-        launch_split3_rows(static_cast<const float*>(t->W), t->ld, t->nblk, k->w3, nkb, sa);
-      }
+      Split3Block sw = {}; sw.in = static_cast<const float*>(t->W); sw.ld = t->ld; sw.out = k->w3; sw.row_tiles = sw.last_rows = t->nblk;
+      sw.nkb = nkb; sw.last_krows = t->npad; sw.tri = 1;
+      if (use2h) { (void)hipMemsetAsync(k->d_wmax, 0, sizeof(unsigned int), sa); sw.h2 = 1; sw.max_out = k->d_wmax; }   // max |W| first, then the split
+      launch_split3_block(sw, 1, false, sa);
       k->w3_valid = true; k->w3_planes = planes;
     }
   }
@@ -390,24 +388,16 @@ static int posterior(hbo_ctx* c, const hbo_model* m, hbo_cache* k, const void* x
     unsigned short* K3_d = use3 ? d_K3 + (size_t)b * (k3_b / sizeof(unsigned short)) : nullptr;
     if (use3) {
       ProfScope ps(c, "split_kxq", 1, sb);
-      if (use2h) launch_split2h_transpose(reinterpret_cast<const float*>(K_d), ldq, t->npad, mpad, K3_d, nkb, kscale, sb);
-      else launch_split3_transpose(reinterpret_cast<const float*>(K_d), ldq, t->npad, mpad, K3_d, nkb, sb);
+      Split3Block sk = {}; sk.in = reinterpret_cast<const float*>(K_d); sk.ld = ldq; sk.out = K3_d; sk.row_tiles = sk.last_rows = mpad / HBO_TILE;
+      sk.nkb = nkb; sk.last_krows = t->npad; sk.h2 = use2h; sk.scale = kscale;
+      launch_split3_block(sk, 1, true, sb);
     }
     if (nbuf == 2) { ev_ready[b] = pool_event(c, evi++); hipEventRecord(ev_ready[b], sb); hipStreamWaitEvent(sa, ev_ready[b], 0); }
     // ---- consumer side (sa): V = L^-1 Kxq on MFMA (column sums of squares), then mean / variance / acquisition ----
-    if (use3 && use2h) {
+    if (use3) {
       ProfScope ps(c, "post_gemm", 1, sa);
-      Post2hArgs a = {}; a.Wp = k->w3; a.Kp = K3_d; a.nkb = nkb; a.wmax_bits = k->d_wmax; a.kscale = kscale;
+      Post3Args a = {}; a.Wp = k->w3; a.Kp = K3_d; a.nkb = nkb; a.h2 = use2h; a.wmax_bits = k->d_wmax; a.kscale = kscale;
       a.colsq = reinterpret_cast<float*>(colsq_d); a.ldc = ldq; a.nblk = t->nblk;
-      if (c->opt_lauum_persist && !ov) {
-        int* counters = (int*)ws_get(c, WS_COUNTERS, sizeof(int) * HBO_N_COUNTERS);
-        if (counters) { a.work_counter = counters + HBO_N_COUNTERS - 8 + (b & 1); hipMemsetAsync(a.work_counter, 0, sizeof(int), sa); }
-      }
-      launch_post2h(a, mpad / HBO_TILE, sa);
-    } else if (use3) {
-      ProfScope ps(c, "post_gemm", 1, sa);
-      Post3Args a = {}; a.Wp = k->w3; a.Kp = K3_d; a.nkb = nkb;
-      a.colsq = reinterpret_cast<float*>(colsq_d); a.ldc = ldq; a.V = nullptr; a.ldv = 0; a.nblk = t->nblk;
       if (c->opt_lauum_persist && !ov) {   // (a resident grid with a tile counter for the large products; one counter per chunk in flight)
         int* counters = (int*)ws_get(c, WS_COUNTERS, sizeof(int) * HBO_N_COUNTERS);
         if (counters) { a.work_counter = counters + HBO_N_COUNTERS - 8 + (b & 1); hipMemsetAsync(a.work_counter, 0, sizeof(int), sa); }

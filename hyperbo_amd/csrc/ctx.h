@@ -70,7 +70,7 @@ struct hbo_ctx {
   int opt_poison = 0;          // tests: every evaluation first fills what it is about to recompute with NaN (gram.hip: poison_kernel)
   // ---- posterior options ----
   int opt_post_chunk = 8192;   // posterior / acquisition: candidates per pass (the cross-Gram workspace is npad x this, whatever M)
-  int opt_post_f16x2 = 1;      // fp32 posterior product of the stationary covariances: two-way fp16 split, three MFMAs per product (post2h.hip) instead of bf16x3's six
+  int opt_post_f16x2 = 1;      // fp32 posterior product of the stationary covariances: two-way fp16 split, three MFMAs per product (post3.hip: post2h_kernel) instead of bf16x3's six
   int opt_post_bf16x3 = 1;     // fp32 posterior product on the bf16 matrix cores (three-way exact split of both operands, post3.hip); 0: fp32 MFMA
   int n_cus = 256;
   std::vector<hipEvent_t> ev_pool;

@@ -167,7 +167,7 @@ __device__ __forceinline__ void hbo_split3(float x, unsigned short& h, unsigned 
   h = __builtin_bit_cast(unsigned short, bh); m = __builtin_bit_cast(unsigned short, bm); l = __builtin_bit_cast(unsigned short, bl);
 }
 // x s = h + l + r, |r| <= 2^-22 |x s|: two fp16 numbers (the caller scales by a power of two so that the operand's largest magnitude
-// lands in [2^13, 2^14), hbo_h2_scale_for) -- the operand form of the fp32 products on the fp16 matrix cores (post2h.hip, post3.hip)
+// lands in [2^13, 2^14), hbo_h2_scale_for) -- the operand form of the fp32 products on the fp16 matrix cores (post3.hip)
 __device__ __forceinline__ void hbo_split2h(float x, unsigned short& h, unsigned short& l) {
   const _Float16 hh = (_Float16)x;
   const _Float16 ll = (_Float16)(x - (float)hh);
@@ -322,34 +322,22 @@ void launch_post_epilogue(int dtype, const PostArgs& a, hipStream_t st);
 // colsq[i][col] = sum over the 128 rows of row block i of (sum_ch Vpart[ch][row][col])^2, chunks ch < ceil((i + 1) / kchunk)
 void launch_post_colsq_split(int dtype, const void* vpart, int npad, int64_t ldq, int mpad, int nblk, int kchunk, void* colsq, hipStream_t st);
 
-// ---- fp32 posterior product on the bf16 matrix cores (post3.hip) --------------------------------
+// ---- fp32 posterior product on the 16-bit matrix cores from split operands (post3.hip) ----------
 struct Post3Args {
-  const unsigned short* Wp;   // W = L^-1 split into bf16 panel blocks (layout: post3.hip), npad rows, k up to npad
+  const unsigned short* Wp;   // W = L^-1 split into panel blocks (layout: post3.hip), npad rows, k up to npad
   const unsigned short* Kp;   // Kxq^T split the same way: rows = candidates of the chunk, k = training points
   int nkb;                    // npad / 16: blocks of k per 128-row tile (both operands)
   float* colsq; int64_t ldc;  // [nblk][ldc] per-row-block column sums of V^2 (may be null)
-  float* V; int64_t ldv;      // optional V output (npad x ldv)
   int nblk;
   int col_tiles;              // (set by launch_post3)
   int* work_counter;          // non-null: a resident grid draws the (row tile, column tile) pairs from this zeroed counter, long rows first
-};
-// fp32 posterior product on the fp16 matrix cores from two-way splits (post2h.hip): operands scaled by powers of two into fp16's range
-struct Post2hArgs {
-  const unsigned short* Wp;   // W = L^-1 split into fp16 panel blocks (two planes; layout: post2h.hip), scaled by scale_for(*wmax_bits)
-  const unsigned short* Kp;   // Kxq^T split the same way, scaled by kscale
-  int nkb;
-  float* colsq; int64_t ldc;  // [nblk][ldc] per-row-block column sums of V^2
-  int nblk;
-  int col_tiles;              // (set by launch_post2h)
-  int* work_counter;          // as Post3Args
-  const unsigned int* wmax_bits;   // device: bits of max |W| (launch_absmax_lower)
+  // h2 = 0: three bf16 planes per operand, exact (post3_kernel).  h2 = 1: two fp16 planes (post2h_kernel), W scaled by the power of
+  // two that follows from *wmax_bits (device: bits of max |W|, measured by the split of W), Kxq^T by the host-known kscale
+  int h2;
+  const unsigned int* wmax_bits;
   float kscale;
 };
-void launch_absmax_lower(const float* in, int64_t ld, int nblk, unsigned int* out, hipStream_t st);
-void launch_split2h_rows(const float* in, int64_t ld, int row_tiles, unsigned short* out, int nkb, const unsigned int* amax_bits, hipStream_t st);
-void launch_split2h_transpose(const float* in, int64_t ld, int krows, int jcols, unsigned short* out, int nkb, float scale, hipStream_t st);
 float post2h_scale_for(double bound);
-void launch_post2h(const Post2hArgs& a, int col_tiles, hipStream_t st);
 // fp32 trailing updates of the blocked Cholesky on the bf16 matrix cores (post3.hip: split3_panel_kernel, syrk3_kernel)
 struct Syrk3Args {
   const TaskDesc* tasks;
@@ -393,13 +381,11 @@ struct Split3Block { const float* in; int64_t ld, gstep; unsigned short* out; in
                      int last_rows, last_krows;   // the LAST group: operand row tiles / k rows that exist (a cut lower half)
                      // h2: two fp16 planes scaled by `scale` (host-known) -- or by the scale of a measured maximum: *scale_bits,
                      // or (max_out) taken by a first pass over the same elements into *max_out (zeroed by the caller, or extended)
-                     int h2; float scale; const unsigned int* scale_bits; unsigned int* max_out; };
+                     int h2; float scale; const unsigned int* scale_bits; unsigned int* max_out;
+                     int lower_only; };   // transposed: `in` is lower triangular by 128-blocks, the blocks above the diagonal are skipped
 void launch_split3_block(const Split3Block& a, int ngrp, bool transposed, hipStream_t st);
 void launch_split3_panel(const Syrk3Args& a, int row_tiles, int ntasks, hipStream_t st);
 void launch_syrk3(const Syrk3Args& a, int ntiles, int ntasks, hipStream_t st);
-void launch_split3_rows(const float* in, int64_t ld, int row_tiles, unsigned short* out, int nkb, hipStream_t st);
-void launch_split3_transpose(const float* in, int64_t ld, int krows, int jcols, unsigned short* out, int nkb, hipStream_t st, int lower_only = 0);
-void launch_split2h_transpose_measured(const float* in, int64_t ld, int krows, int jcols, unsigned short* out, int nkb, unsigned int* amax_bits, hipStream_t st, int lower_only);
 void launch_post3(const Post3Args& a, int col_tiles, hipStream_t st);
 
 struct AcqGradArgs {

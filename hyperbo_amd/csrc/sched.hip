@@ -685,11 +685,14 @@ void run_lauum(hbo_ctx* c, int dtype, const TaskDesc* d_tasks, int ntasks, int m
       hipStream_t s = st ? st : c->stream;
       const int n = max_nblk * HBO_TILE;
       Syrk3Args g = {}; g.tasks = d_tasks; g.Xp = xp; g.nkb = nkb; g.mode = 3;
+      Split3Block sw = {}; sw.in = static_cast<const float*>(h.W); sw.ld = h.ld; sw.out = xp; sw.row_tiles = sw.last_rows = max_nblk;
+      sw.nkb = nkb; sw.last_krows = n; sw.lower_only = 1;
       if (c->run.h2_words) {   // the f16x2 form: max |W| by one pass, W^T as two fp16 planes, three MFMAs per product
         unsigned int* word = c->run.h2_words + HBO_H2_WORDS - 1;
-        launch_split2h_transpose_measured(static_cast<const float*>(h.W), h.ld, n, n, xp, nkb, word, s, 1);
+        sw.h2 = 1; sw.max_out = word;
         g.h2 = 1; g.sx_bits = g.sy_bits = word;
-      } else launch_split3_transpose(static_cast<const float*>(h.W), h.ld, n, n, xp, nkb, s, 1);
+      }
+      launch_split3_block(sw, 1, true, s);
       r.whole = c->opt_lauum_persist;
       resident_grid(c, g, r, nt, s);
       launch_syrk3(g, nt, 1, s);

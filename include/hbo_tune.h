@@ -22,7 +22,7 @@
  *   split_f1      0..2     the update of the next group's block columns (F1): only the next column on the panel stream, the later
  *                          ones on a third stream -- 0 never, 1 batches (default: 64 tasks 14.32 -> 14.12 ms), 2 always
  *   sweep_big     >=0      sweep launches of small / batched shapes with at least this many 128-tiles (x tasks) use 128-tiles (4000)
- *   post_f16x2    0/1      fp32 posterior product of the stationary covariances on the fp16 matrix cores from two-way splits (post2h.hip;
+ *   post_f16x2    0/1      fp32 posterior product of the stationary covariances on the fp16 matrix cores from two-way splits (post3.hip: post2h_kernel;
  *                          default 1; 0 = bf16x3's exact three-way split)
  *   group_inner   -1..16   two-level panel groups: the chain's left-looking column updates stay inside inner groups of this many panels, one
  *                          update per inner boundary brings the rest of the (outer, potrf_group) group up to date; 0 = one level, -1 = auto

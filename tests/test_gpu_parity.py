@@ -2503,11 +2503,22 @@ def test_fp32_posterior_on_bf16_matrix_cores_is_as_accurate_as_fp32_mfma(gpu_ctx
     assert not np.array_equal(out['f16x2'][1], out['bf16x3'][1])                      # the other path did run
 
 
+# (n, M) at which the matrix-core product itself is chosen (hbo_predict keeps it for nblk >= 2 only from 2 x CUs = 512 tiles of
+# ceil(M / 128) x nblk on): run with post_chunk = 8192.
+#   (129, 32641): two blocks, one point past a block; 256 column tiles in all; four chunks, the last of 8065 candidates (one past
+#                 63 column tiles); 64 x 2 tiles per chunk: a plain grid
+#   (2049, 8000): 17 blocks; 63 column tiles in one chunk = 1071 tiles > 4 x CUs: the resident grid draws them from the counter
+_POST3_MATRIX_CORE_CASES = [(129, 32641), (2049, 8000)]
+
+
 @pytest.mark.gpu
-@pytest.mark.parametrize('n,M', [(1, 1), (5, 3), (128, 128), (129, 1), (130, 257), (511, 130), (2049, 129)])
+@pytest.mark.parametrize('n,M', [(1, 1), (5, 3), (128, 128), (129, 1), (130, 257), (511, 130), (2049, 129)] + _POST3_MATRIX_CORE_CASES)
 def test_fp32_posterior_bf16x3_edge_sizes(gpu_ctx, n, M):
-  """Block-boundary sizes of the bf16 matrix-core product (one training point, exactly one 128-block, one past a block, a single
-  candidate, ragged chunks): same mean, variance and EI as the fp32-MFMA product to fp32 rounding."""
+  """Block-boundary sizes of the fp32 posterior in its three forms -- fp32 MFMA (post_bf16x3 = 0), bf16x3 (post_f16x2 = 0) and
+  f16x2 (the default for a stationary kernel): same mean, variance and EI from both matrix-core forms as from the fp32-MFMA
+  product, to fp32 rounding.  One block (n <= 128: one training point, exactly one block, ragged 128-candidate chunks) runs
+  post3_kernel / post2h_kernel on a plain grid; _POST3_MATRIX_CORE_CASES run them over several blocks, on a plain grid and on the
+  resident grid with the tile counter, and also check that the three forms really ran."""
   defs, _, acfun, gp, kernel, mean, _, utils = _native()
   rng = np.random.default_rng(1000 * n + M)
   d = 3
@@ -2516,18 +2527,28 @@ def test_fp32_posterior_bf16x3_edge_sizes(gpu_ctx, n, M):
            {'lengthscale': isp(np.full(d, 0.6)), 'signal_variance': isp(1.0), 'noise_variance': isp(1e-2), 'constant': np.array(0.1)}.items()}
   x = rng.uniform(size=(n, d)).astype(np.float32); y = np.sin(x.sum(1, keepdims=True)).astype(np.float32)
   xq = rng.uniform(size=(M, d)).astype(np.float32)
+  matrix_core = (n, M) in _POST3_MATRIX_CORE_CASES
+  # (the other cases with n > 128 -- (129, 1), (130, 257), (511, 130), (2049, 129) -- have two blocks or more and few candidates:
+  #  every form takes the split-K fp32 route there, so they exercise that route under the three option settings)
   out = []
   try:
-    gpu_ctx.set_option('post_chunk', 128)
-    for opt in (0, 1):
-      gpu_ctx.set_option('post_bf16x3', opt)
+    gpu_ctx.set_option('post_chunk', 8192 if matrix_core else 128)
+    for bf16x3, f16x2 in ((0, 1), (1, 0), (1, 1)):
+      gpu_ctx.set_option('post_bf16x3', bf16x3)
+      gpu_ctx.set_option('post_f16x2', f16x2)
       g = gp.GP({0: defs.SubDataset(x, y)}, mean.constant, kernel.matern52, defs.GPParams(model=model), utils.DEFAULT_WARP_FUNC)
       mu, var = g.predict(xq, 0)
       ei = acfun.expected_improvement(model=g, sub_dataset_key=0, x_queries=xq)
       out.append([np.asarray(a, np.float64).ravel() for a in (mu, var, ei)])
   finally:
     gpu_ctx.set_option('post_bf16x3', 1)
+    gpu_ctx.set_option('post_f16x2', 1)
     gpu_ctx.set_option('post_chunk', 8192)
-  for a, b, what in zip(out[0], out[1], ('mean', 'variance', 'EI')):
-    assert np.isfinite(b).all(), what
-    assert np.abs(a - b).max() <= 2e-5 * max(1.0, np.abs(a).max()), (what, np.abs(a - b).max())
+  for form, res in (('bf16x3', out[1]), ('f16x2', out[2])):
+    for a, b, what in zip(out[0], res, ('mean', 'variance', 'EI')):
+      print('edge_sizes n=%d M=%d %s %s: max |diff| %.3e, bound %.3e' % (n, M, form, what, np.abs(a - b).max(), 2e-5 * max(1.0, np.abs(a).max())))
+      assert np.isfinite(b).all(), (form, what)
+      assert np.abs(a - b).max() <= 2e-5 * max(1.0, np.abs(a).max()), (form, what, np.abs(a - b).max())
+  if matrix_core:   # (Matern is stationary, so f16x2 applies: three different products)
+    assert not np.array_equal(out[2][1], out[1][1])
+    assert not np.array_equal(out[1][1], out[0][1])
