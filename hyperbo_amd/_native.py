@@ -123,6 +123,7 @@ SIGNATURES = {
                                    C.POINTER(C.c_double)]),
     'hbo_tune': (C.c_int, [_P, C.c_char_p, C.c_int64]),   # include/hbo_tune.h: measurement hooks, not the boundary
     'hbo_mfma_peak_probe': (C.c_int, [_P, C.c_double, C.POINTER(C.c_double)]),   # include/hbo_tune.h
+    'hbo_probe_post_product': (C.c_int, [_P, C.c_int, _P, C.c_int64, _P, C.c_int64, C.c_double, C.c_int, _P]),   # include/hbo_tune.h (test hook)
     'hbo_comm_unique_id': (C.c_int, [_P]),
     'hbo_comm_init': (C.c_int, [_P, C.c_int, C.c_int, _P]),
     'hbo_comm_allreduce_sum': (C.c_int, [_P, C.POINTER(C.c_double), C.c_int32]),
@@ -205,7 +206,7 @@ class Context:
     self.check(f(self._h, name.encode(), int(value)))
 
   def get_option(self, name):
-    """An option of include/hbo.h read back (also the read-only 'eig_sweeps'); unknown names raise."""
+    """An option of include/hbo.h read back (also the read-only 'eig_sweeps', 'chol_form' and 'inv_forms'); unknown names raise."""
     out = C.c_int64(0)
     self.check(lib().hbo_get_option(self._h, name.encode(), C.byref(out)), allow_not_pd=False)
     return out.value

@@ -106,7 +106,7 @@ extern "C" int hbo_set_option(hbo_ctx* c, const char* name, int64_t value) {
   if (!strcmp(name, "spectral")) { if (value < 0 || value > 1) return fail(c, HBO_ERR_ARG, "spectral is 0 or 1"); c->opt_spectral = (int)value; return HBO_OK; }
   return fail(c, HBO_ERR_ARG, std::string("unknown option ") + name);
 }
-// The same options read back (plus the read-only eig_sweeps).  bf16x3 reads as 1 only when all four of its legs are on.
+// The same options read back (plus the read-only eig_sweeps, chol_form and inv_forms).  bf16x3 reads as 1 only when all four of its legs are on.
 extern "C" int hbo_get_option(hbo_ctx* c, const char* name, int64_t* out) {
   if (!c || !name || !out) return fail(c, HBO_ERR_ARG, "hbo_get_option: null argument");
   if (!strcmp(name, "potrf_group")) { *out = c->opt_group; return HBO_OK; }
@@ -117,6 +117,8 @@ extern "C" int hbo_get_option(hbo_ctx* c, const char* name, int64_t* out) {
   if (!strcmp(name, "bf16x3")) { *out = c->opt_post_bf16x3 && c->opt_syrk_bf16x3 && c->opt_trtri_bf16x3 && c->opt_lauum_bf16x3; return HBO_OK; }
   if (!strcmp(name, "spectral")) { *out = c->opt_spectral; return HBO_OK; }
   if (!strcmp(name, "eig_sweeps")) { *out = c->eig_last_sweeps; return HBO_OK; }
+  if (!strcmp(name, "chol_form")) { *out = c->last_chol_form; return HBO_OK; }   // (include/hbo_tune.h)
+  if (!strcmp(name, "inv_forms")) { *out = c->last_inv_forms; return HBO_OK; }
   return fail(c, HBO_ERR_ARG, std::string("unknown option ") + name);
 }
 // Measurement hooks (include/hbo_tune.h): placement and overlap knobs of the schedules, for the A/B tools under tools/ and
@@ -132,7 +134,7 @@ extern "C" int hbo_tune(hbo_ctx* c, const char* name, int64_t value) {
       {"post_bf16x3", &hbo_ctx::opt_post_bf16x3, 0, 1}, {"post_f16x2", &hbo_ctx::opt_post_f16x2, 0, 1}, {"chol_f16x2", &hbo_ctx::opt_chol_f16x2, 0, 1}, {"group_inner", &hbo_ctx::opt_group_inner, -1, 16}, {"syrk_bf16x3", &hbo_ctx::opt_syrk_bf16x3, 0, 1},
       {"trtri_bf16x3", &hbo_ctx::opt_trtri_bf16x3, 0, 1}, {"lauum_bf16x3", &hbo_ctx::opt_lauum_bf16x3, 0, 1}, {"trtri3_min_s", &hbo_ctx::opt_trtri3_min_s, 1, 1024},
       {"fault_shard", &hbo_ctx::opt_fault_shard, 0, 2}, {"small_fused", &hbo_ctx::opt_small_fused, 0, 1}, {"gram_mfma", &hbo_ctx::opt_gram_mfma, 0, 4096}, {"post_serial", &hbo_ctx::opt_post_serial, 0, 1},
-      {"syrk3_free", &hbo_ctx::opt_syrk3_free, 0, 200},
+      {"syrk3_free", &hbo_ctx::opt_syrk3_free, 0, 200}, {"spd_diag_bound", &hbo_ctx::opt_spd_diag_bound, 0, 1},
   };
   for (const Knob& k : knobs)
     if (!strcmp(name, k.name)) {
@@ -608,6 +610,11 @@ extern "C" int hbo_spd_solve(hbo_ctx* c, int dtype, const void* a, int64_t n, co
   HIPCHK_S(hipMemcpyAsync(d_info, &inf, sizeof(int), hipMemcpyHostToDevice, st));
   HIPCHK_S(hipStreamSynchronize(st));
   c->trtri_host_task = h;
+  // hbo_tune "spd_diag_bound" (test hook): max_i A_ii off the caller's matrix -- what potrf_plan, trtri_level3 and run_lauum need to
+  // take the f16x2 form, as hbo_factor does from the model's signal variance.  Default: 0 = unknown, the bf16x3 form
+  double diag_bound = 0;
+  if (c->opt_spd_diag_bound) for (int64_t i = 0; i < n; ++i) diag_bound = std::max(diag_bound, host_elem(a, dtype, i * n + i));
+  CholBoundScope bound_scope(c, diag_bound);
   { ProfScope ps(c, "potrf", 1); run_potrf(c, dtype, d_desc, 1, t->nblk, d_info); }
   if (need_inv) {
     { ProfScope ps(c, "trtri", 1); run_trtri(c, dtype, d_desc, 1, t->nblk); }

@@ -196,6 +196,33 @@ extern "C" int hbo_cache_append(hbo_ctx* c, const hbo_model* m, hbo_cache* k, co
   return status;
 }
 
+// ---- the three launches of the fp32 posterior product on the 16-bit matrix cores (post3.hip) -----------------------------------
+// Shared by the posterior below and by hbo_probe_post_product (include/hbo_tune.h), which feeds them caller-chosen operands.
+// W [nblk * 128 rows, ld], lower triangular: its split copy w3 (blocks up to each row tile's diagonal block).  h2: two fp16 planes
+// by the scale that follows from max |W|, measured first into *d_wmax; else three bf16 planes
+static void post3_split_w(const float* W, int64_t ld, int nblk, bool h2, unsigned short* w3, unsigned int* d_wmax, hipStream_t st) {
+  Split3Block sw = {}; sw.in = W; sw.ld = ld; sw.out = w3; sw.row_tiles = sw.last_rows = nblk;
+  sw.nkb = nblk * (HBO_TILE / 16); sw.last_krows = nblk * HBO_TILE; sw.tri = 1;
+  if (h2) { (void)hipMemsetAsync(d_wmax, 0, sizeof(unsigned int), st); sw.h2 = 1; sw.max_out = d_wmax; }   // max |W| first, then the split
+  launch_split3_block(sw, 1, false, st);
+}
+// the cross Gram of one chunk, Kxq [npad, ldq] with mpad candidates (columns), transposed on the way: K3 rows = candidates
+static void post3_split_kxq(const float* K, int64_t ldq, int mpad, int npad, bool h2, float kscale, unsigned short* K3, hipStream_t st) {
+  Split3Block sk = {}; sk.in = K; sk.ld = ldq; sk.out = K3; sk.row_tiles = sk.last_rows = mpad / HBO_TILE;
+  sk.nkb = npad / 16; sk.last_krows = npad; sk.h2 = h2; sk.scale = kscale;
+  launch_split3_block(sk, 1, true, st);
+}
+// colsq [nblk, ldc] = per row block of W the column sums of (W Kxq)^2.  counter (nullable): zeroed here and handed to launch_post3,
+// which turns a large product into a resident grid drawing its tiles from it
+static void post3_product(const unsigned short* w3, const unsigned short* K3, int nblk, int mpad, bool h2, const unsigned int* d_wmax,
+                          float kscale, float* colsq, int64_t ldc, int* counter, hipStream_t st) {
+  Post3Args a = {}; a.Wp = w3; a.Kp = K3; a.nkb = nblk * (HBO_TILE / 16); a.h2 = h2; a.wmax_bits = d_wmax; a.kscale = kscale;
+  a.colsq = colsq; a.ldc = ldc; a.nblk = nblk;
+  if (counter) { a.work_counter = counter; hipMemsetAsync(counter, 0, sizeof(int), st); }
+  launch_post3(a, mpad / HBO_TILE, st);
+}
+
+
 // ---- posterior / acquisition ---------------------------------------------------------------
 // `ov` (hbo_acq_samples): the model and its MLP weights are already on the device at ov->md / ov->mlp_w / ov->mlp_b, the queries at
 // ov->xq_dev; the acquisition values go to ov->acq_dev and stay there -- nothing is uploaded, copied back or waited for, so that
@@ -293,7 +320,6 @@ static int posterior(hbo_ctx* c, const hbo_model* m, hbo_cache* k, const void* x
   // fp32: the product runs on the bf16 matrix cores from exact three-way splits of both operands (post3.hip)
   bool use3 = k && dtype == HBO_F32 && c->opt_post_bf16x3 && !full_cov && kchunk == 0;
   unsigned short* d_K3 = nullptr; size_t k3_b = 0;
-  const int nkb = k ? t->npad / 16 : 0;
   // stationary covariances (|k| <= signal variance: the cross Gram's scale is known without a pass over it): two-way fp16 split,
   // three MFMAs per product instead of six (post3.hip, H2)
   const bool use2h = use3 && c->opt_post_f16x2 && m->kernel_id != HBO_KERNEL_DOT;
@@ -312,10 +338,7 @@ static int posterior(hbo_ctx* c, const hbo_model* m, hbo_cache* k, const void* x
     }
     if (use3) {
       ProfScope ps(c, "split_w", 1, sa);
-      Split3Block sw = {}; sw.in = static_cast<const float*>(t->W); sw.ld = t->ld; sw.out = k->w3; sw.row_tiles = sw.last_rows = t->nblk;
-      sw.nkb = nkb; sw.last_krows = t->npad; sw.tri = 1;
-      if (use2h) { (void)hipMemsetAsync(k->d_wmax, 0, sizeof(unsigned int), sa); sw.h2 = 1; sw.max_out = k->d_wmax; }   // max |W| first, then the split
-      launch_split3_block(sw, 1, false, sa);
+      post3_split_w(static_cast<const float*>(t->W), t->ld, t->nblk, use2h, k->w3, k->d_wmax, sa);
       k->w3_valid = true; k->w3_planes = planes;
     }
   }
@@ -388,21 +411,18 @@ static int posterior(hbo_ctx* c, const hbo_model* m, hbo_cache* k, const void* x
     unsigned short* K3_d = use3 ? d_K3 + (size_t)b * (k3_b / sizeof(unsigned short)) : nullptr;
     if (use3) {
       ProfScope ps(c, "split_kxq", 1, sb);
-      Split3Block sk = {}; sk.in = reinterpret_cast<const float*>(K_d); sk.ld = ldq; sk.out = K3_d; sk.row_tiles = sk.last_rows = mpad / HBO_TILE;
-      sk.nkb = nkb; sk.last_krows = t->npad; sk.h2 = use2h; sk.scale = kscale;
-      launch_split3_block(sk, 1, true, sb);
+      post3_split_kxq(reinterpret_cast<const float*>(K_d), ldq, mpad, t->npad, use2h, kscale, K3_d, sb);
     }
     if (nbuf == 2) { ev_ready[b] = pool_event(c, evi++); hipEventRecord(ev_ready[b], sb); hipStreamWaitEvent(sa, ev_ready[b], 0); }
     // ---- consumer side (sa): V = L^-1 Kxq on MFMA (column sums of squares), then mean / variance / acquisition ----
     if (use3) {
       ProfScope ps(c, "post_gemm", 1, sa);
-      Post3Args a = {}; a.Wp = k->w3; a.Kp = K3_d; a.nkb = nkb; a.h2 = use2h; a.wmax_bits = k->d_wmax; a.kscale = kscale;
-      a.colsq = reinterpret_cast<float*>(colsq_d); a.ldc = ldq; a.nblk = t->nblk;
+      int* counter = nullptr;
       if (c->opt_lauum_persist && !ov) {   // (a resident grid with a tile counter for the large products; one counter per chunk in flight)
         int* counters = (int*)ws_get(c, WS_COUNTERS, sizeof(int) * HBO_N_COUNTERS);
-        if (counters) { a.work_counter = counters + HBO_N_COUNTERS - 8 + (b & 1); hipMemsetAsync(a.work_counter, 0, sizeof(int), sa); }
+        if (counters) counter = counters + HBO_N_COUNTERS - 8 + (b & 1);
       }
-      launch_post3(a, mpad / HBO_TILE, sa);
+      post3_product(k->w3, K3_d, t->nblk, mpad, use2h, k->d_wmax, kscale, reinterpret_cast<float*>(colsq_d), ldq, counter, sa);
     } else {
       ProfScope ps(c, "post_gemm", 1, sa);
       GemmArgs a = {}; a.tasks = k->d_desc; a.mode = GEMM_POST; a.B = K_d; a.ldb = ldq; a.V = full_cov ? d_V : nullptr; a.colsq = colsq_d;
@@ -727,5 +747,46 @@ extern "C" int hbo_acq_grad(hbo_ctx* c, const hbo_model* m, hbo_cache* k, const 
     for (int64_t i = 0; i < M * D; ++i) grad_out[i] = NAN;
     return HBO_NOT_PD;
   }
+  return HBO_OK;
+}
+
+// Test hook (include/hbo_tune.h): the fp32 split-operand posterior product on caller-chosen operands -- W and Kxq go up padded as a
+// cache holds them, the three launches of the posterior above run once over all M candidates, the per-row-block column sums of V^2
+// come back.  The split buffers are filled with 0xFF (NaN in bf16 and fp16) first: a block the product reads but no split wrote shows.
+extern "C" int hbo_probe_post_product(hbo_ctx* c, int form, const float* W, int64_t n, const float* Kxq, int64_t M, double k_bound,
+                                      int use_counter, float* colsq_out) {
+  if (!c || !W || !Kxq || !colsq_out) return fail(c, HBO_ERR_ARG, "hbo_probe_post_product: null argument");
+  if (form != 0 && form != 1) return fail(c, HBO_ERR_ARG, "hbo_probe_post_product: form is 0 (bf16x3) or 1 (f16x2)");
+  if (n <= 0 || n > 16384 || M <= 0 || M > (1 << 20)) return fail(c, HBO_ERR_ARG, "hbo_probe_post_product: need 1 <= n <= 16384 and 1 <= M <= 2^20");
+  if (use_counter != 0 && use_counter != 1) return fail(c, HBO_ERR_ARG, "hbo_probe_post_product: use_counter is 0 or 1");
+  if (form == 1 && (!(k_bound > 0) || !(k_bound < 1e30))) return fail(c, HBO_ERR_ARG, "hbo_probe_post_product: f16x2 needs a positive finite k_bound");
+  HIPCHK(c, hipSetDevice(c->device));
+  const bool h2 = form == 1;
+  const int planes = h2 ? 2 : 3;
+  const int npad = round_up(n, HBO_TILE), nblk = npad / HBO_TILE, mpad = round_up(M, HBO_TILE);
+  const int64_t ld = padded_ld(npad, HBO_F32), ldq = padded_ld(mpad, HBO_F32);
+  const float kscale = h2 ? post2h_scale_for(k_bound) : 1.f;
+  const size_t w_b = (size_t)npad * ld * sizeof(float), k_b = (size_t)npad * ldq * sizeof(float), c_b = (size_t)nblk * ldq * sizeof(float);
+  const size_t w3_b = (size_t)npad * npad * planes * sizeof(unsigned short), k3_b = (size_t)mpad * npad * planes * sizeof(unsigned short);
+  hipStream_t st = c->stream;
+  void *d_w = nullptr, *d_k = nullptr, *d_c = nullptr, *d_w3 = nullptr, *d_k3 = nullptr, *d_words = nullptr;
+  auto cleanup = [&]() { for (void* p : {d_w, d_k, d_c, d_w3, d_k3, d_words}) if (p) hipFree(p); };
+#define HIPCHK_Q(call) do { hipError_t e__ = (call); if (e__ != hipSuccess) { c->err = std::string(#call " failed: ") + hipGetErrorString(e__); cleanup(); return HBO_ERR_HIP; } } while (0)
+  HIPCHK_Q(hbo_malloc(c, &d_w, w_b)); HIPCHK_Q(hbo_malloc(c, &d_k, k_b)); HIPCHK_Q(hbo_malloc(c, &d_c, c_b));
+  HIPCHK_Q(hbo_malloc(c, &d_w3, w3_b)); HIPCHK_Q(hbo_malloc(c, &d_k3, k3_b)); HIPCHK_Q(hbo_malloc(c, &d_words, 2 * sizeof(unsigned int)));
+  HIPCHK_Q(hipMemsetAsync(d_w, 0, w_b, st)); HIPCHK_Q(hipMemsetAsync(d_k, 0, k_b, st)); HIPCHK_Q(hipMemsetAsync(d_c, 0, c_b, st));
+  HIPCHK_Q(hipMemsetAsync(d_w3, 0xFF, w3_b, st)); HIPCHK_Q(hipMemsetAsync(d_k3, 0xFF, k3_b, st));
+  HIPCHK_Q(hipMemcpy2DAsync(d_w, (size_t)ld * sizeof(float), W, (size_t)n * sizeof(float), (size_t)n * sizeof(float), (size_t)n, hipMemcpyHostToDevice, st));
+  HIPCHK_Q(hipMemcpy2DAsync(d_k, (size_t)ldq * sizeof(float), Kxq, (size_t)M * sizeof(float), (size_t)M * sizeof(float), (size_t)n, hipMemcpyHostToDevice, st));
+  unsigned int* d_wmax = static_cast<unsigned int*>(d_words);
+  post3_split_w(static_cast<const float*>(d_w), ld, nblk, h2, static_cast<unsigned short*>(d_w3), d_wmax, st);
+  post3_split_kxq(static_cast<const float*>(d_k), ldq, mpad, npad, h2, kscale, static_cast<unsigned short*>(d_k3), st);
+  post3_product(static_cast<const unsigned short*>(d_w3), static_cast<const unsigned short*>(d_k3), nblk, mpad, h2, d_wmax, kscale,
+                static_cast<float*>(d_c), ldq, use_counter ? reinterpret_cast<int*>(d_wmax + 1) : nullptr, st);
+  HIPCHK_Q(hipMemcpy2DAsync(colsq_out, (size_t)M * sizeof(float), d_c, (size_t)ldq * sizeof(float), (size_t)M * sizeof(float), (size_t)nblk, hipMemcpyDeviceToHost, st));
+  HIPCHK_Q(hipStreamSynchronize(st));
+  HIPCHK_Q(hipGetLastError());
+#undef HIPCHK_Q
+  cleanup();
   return HBO_OK;
 }

@@ -109,6 +109,9 @@ struct hbo_ctx {
   int opt_spectral = 0;        // hbo_set_option("spectral"): stored for the Python layer, which routes its SVD call sites by it (hbo.h)
   int eig_last_sweeps = 0;     // outer Jacobi sweeps of the last hbo_sym_eig / hbo_nll_spectral (largest over its batches; eig.hip)
   int opt_post_serial = 0;     // hbo_tune("post_serial"): the streamed posterior's producer side (cross Gram) on the SAME stream as its products: isolated stage times
+  int opt_spd_diag_bound = 0;  // hbo_tune("spd_diag_bound"), test hook: hbo_spd_solve reads max_i A_ii off its host matrix, so that it can take the f16x2 form
+  int last_chol_form = 0;      // Fp32Form of the last run_potrf's trailing updates (hbo_get_option "chol_form")
+  int last_inv_forms = 0;      // since the last run_potrf: 1 / 2 a level of the inverse ran on bf16x3 / f16x2 (trtri_level3), 4 / 8 K^-1 = W^T W did (hbo_get_option "inv_forms")
   int opt_fault_shard = 0;     // hbo_tune("fault_shard"): ONE-SHOT fault injection for the tests of the sharded objective's failure paths
   bool comm_aborted = false;   // set by comm_abort: sharded calls fail with HBO_ERR_COMM until hbo_comm_init builds a new communicator
   double* d_comm_buf = nullptr;

@@ -393,6 +393,7 @@ void run_potrf(hbo_ctx* c, int dtype, const TaskDesc* d_tasks, int ntasks, int m
   PotrfState s = {c, dtype, d_tasks, ntasks, max_nblk, d_info, c->stream, pl.la ? c->stream2 : c->stream};
   if (pl.la) { hipEvent_t e = pool_event(c, s.evi++); hipEventRecord(e, s.sm); hipStreamWaitEvent(s.sp, e, 0); }   // fork
   potrf_setup(pl, s);
+  c->last_chol_form = (int)s.form; c->last_inv_forms = 0;
   for (int g0 = 0, grp = 0; g0 < max_nblk; g0 += pl.q, ++grp) {
     const int g1 = std::min(g0 + pl.q, max_nblk);
     const int g2 = std::min(g1 + pl.q, max_nblk);
@@ -465,6 +466,7 @@ static bool trtri_level3(hbo_ctx* c, const TaskDesc* d_tasks, const TaskDesc& h,
     resident_grid(c, g, r, ntiles, st);
     launch_syrk3(g, ntiles, 1, st);
   };
+  c->last_inv_forms |= h2 ? 2 : 1;
   ProfScope ps(c, "trtri_gemm", 2, st);
   if (do_a) {
     sb.in = L + (o0 + half) * ld + o0; sb.out = xp; sb.tri = 0; sb.last_rows = vlast; sb.last_krows = (int)half;
@@ -692,6 +694,7 @@ void run_lauum(hbo_ctx* c, int dtype, const TaskDesc* d_tasks, int ntasks, int m
         sw.h2 = 1; sw.max_out = word;
         g.h2 = 1; g.sx_bits = g.sy_bits = word;
       }
+      c->last_inv_forms |= g.h2 ? 8 : 4;
       launch_split3_block(sw, 1, true, s);
       r.whole = c->opt_lauum_persist;
       resident_grid(c, g, r, nt, s);

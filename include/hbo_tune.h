@@ -49,7 +49,16 @@
  *                          profiles/r06_gram_mfma.md)
  *   batch_bg      -1..2    batches: the sweep's launches beside the chain as plain grids (0), persistent over tiles x tasks
  *                          from one counter (1), and also polling the per-CU yield table the chain's kernels then fill (2);
- *                          -1 (default): 1 up to 8 tasks, 0 above (8 tasks 2.52 -> 2.44 ms, 64 tasks 14.13 / 14.31) */
+ *                          -1 (default): 1 up to 8 tasks, 0 above (8 tasks 2.52 -> 2.44 ms, 64 tasks 14.13 / 14.31)
+ *   spd_diag_bound 0/1     TEST HOOK (tests/test_gpu_split_products.py): with 1, hbo_spd_solve takes max_i A_ii from the host matrix it was given
+ *                          and holds it as the factorisation's diagonal bound for the call, so that an fp32 solve of a caller-chosen matrix
+ *                          takes the f16x2 form exactly as hbo_factor does (chol_f16x2); default 0: hbo_spd_solve stays on bf16x3
+ *
+ * Read-only, through hbo_get_option:
+ *   chol_form              form of the trailing updates of the context's last factorisation: 0 fp32 MFMA (and all of fp64), 1 bf16x3,
+ *                          2 f16x2 (the profile's stage names are the same for all three)
+ *   inv_forms              what ran on the 16-bit matrix cores since that factorisation, as bits: 1 / 2 a level of the inverse on bf16x3 /
+ *                          f16x2 (syrk3_kernel modes 1 and 2), 4 / 8 K^-1 = W^T W on bf16x3 / f16x2 (mode 3); 0: all on fp32 / fp64 MFMA */
 #ifndef HBO_TUNE_H_
 #define HBO_TUNE_H_
 #include "hbo.h"
@@ -60,6 +69,14 @@ int hbo_tune(hbo_ctx* ctx, const char* name, int64_t value);
 /* sustained fp64 MFMA rate of the device, measured now by ~ms milliseconds of back-to-back v_mfma_f64_16x16x4_f64 on every SIMD
  * (TFLOP/s): the roofline denominator bench.py reports beside the datasheet figure */
 int hbo_mfma_peak_probe(hbo_ctx* ctx, double ms, double* tflops_out);
+/* TEST HOOK: the fp32 posterior product V = W Kxq on the 16-bit matrix cores (form 0: bf16x3, 1: f16x2) on caller-chosen operands.
+ * W [n, n] row-major, lower triangular (zeros above the diagonal); Kxq [n, M]; k_bound (f16x2): a bound on |Kxq|, the role the signal
+ * variance plays in hbo_predict.  Both are padded as a cache pads them and go through the launches hbo_predict runs for an fp32 cache
+ * (split of W, transposed split of Kxq, product), one chunk of all M candidates; use_counter = 1 hands the product a zeroed tile
+ * counter as hbo_predict does (a resident grid once there are more than 4 tiles per CU).  colsq_out [ceil(n / 128), M]:
+ * colsq_out[i, j] = sum over the rows r of 128-row block i of V[r, j]^2.  HBO_ERR_ARG on a bad argument, before any device call. */
+int hbo_probe_post_product(hbo_ctx* ctx, int form, const float* W, int64_t n, const float* Kxq, int64_t M, double k_bound,
+                           int use_counter, float* colsq_out);
 #ifdef __cplusplus
 }
 #endif
