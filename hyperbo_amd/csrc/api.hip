@@ -479,41 +479,39 @@ extern "C" int hbo_gram(hbo_ctx* c, const hbo_model* m, const void* x1, int64_t 
   void *d1 = nullptr, *d2 = nullptr, *dout = nullptr, *w1 = nullptr, *w2 = nullptr;
   FeatBuf f1, f2;
   auto cleanup = [&]() { for (void* p : {d1, d2, dout, w1, w2}) if (p) hipFree(p); };
-#define HIPCHK_G(call) do { hipError_t e__ = (call); if (e__ != hipSuccess) { c->err = std::string(#call " failed: ") + hipGetErrorString(e__); cleanup(); return HBO_ERR_HIP; } } while (0)
-  HIPCHK_G(hbo_malloc(c, &d1, (size_t)n1 * m->input_dim * es));
-  HIPCHK_G(hipMemcpyAsync(d1, x1, (size_t)n1 * m->input_dim * es, hipMemcpyHostToDevice, st));
+  HIPCHK_OR(c, hbo_malloc(c, &d1, (size_t)n1 * m->input_dim * es), cleanup());
+  HIPCHK_OR(c, hipMemcpyAsync(d1, x1, (size_t)n1 * m->input_dim * es, hipMemcpyHostToDevice, st), cleanup());
   const void* F1 = d1; const void* F2 = d1;
   if (m->kernel_uses_mlp) { rc = f1.ensure(c, m, n1); if (rc) { cleanup(); return rc; } run_mlp(c, m, d1, n1, f1.acts.data()); F1 = F2 = f1.acts[m->n_layers - 1]; }
   if (is_kumar(m)) {   // kernel.py:190-217: K(w(x1), w(x2))
-    HIPCHK_G(hbo_malloc(c, &w1, (size_t)n1 * m->input_dim * es));
+    HIPCHK_OR(c, hbo_malloc(c, &w1, (size_t)n1 * m->input_dim * es), cleanup());
     launch_kumar_forward(dtype, nullptr, 0, 0, d1, w1, nullptr, n1, m->input_dim, c->d_model, st);
     F1 = F2 = w1;
   }
   if (x2) {
-    HIPCHK_G(hbo_malloc(c, &d2, (size_t)n2 * m->input_dim * es));
-    HIPCHK_G(hipMemcpyAsync(d2, x2, (size_t)n2 * m->input_dim * es, hipMemcpyHostToDevice, st));
+    HIPCHK_OR(c, hbo_malloc(c, &d2, (size_t)n2 * m->input_dim * es), cleanup());
+    HIPCHK_OR(c, hipMemcpyAsync(d2, x2, (size_t)n2 * m->input_dim * es, hipMemcpyHostToDevice, st), cleanup());
     F2 = d2;
     if (m->kernel_uses_mlp) { rc = f2.ensure(c, m, n2); if (rc) { cleanup(); return rc; } run_mlp(c, m, d2, n2, f2.acts.data()); F2 = f2.acts[m->n_layers - 1]; }
     if (is_kumar(m)) {
-      HIPCHK_G(hbo_malloc(c, &w2, (size_t)n2 * m->input_dim * es));
+      HIPCHK_OR(c, hbo_malloc(c, &w2, (size_t)n2 * m->input_dim * es), cleanup());
       launch_kumar_forward(dtype, nullptr, 0, 0, d2, w2, nullptr, n2, m->input_dim, c->d_model, st);
       F2 = w2;
     }
   }
   const int fdim = feature_dim(m);
   if (diag) {
-    HIPCHK_G(hbo_malloc(c, &dout, (size_t)n1 * es));
+    HIPCHK_OR(c, hbo_malloc(c, &dout, (size_t)n1 * es), cleanup());
     launch_kdiag(dtype, F1, n1, fdim, c->d_model, dout, st);
-    HIPCHK_G(hipMemcpyAsync(out, dout, (size_t)n1 * es, hipMemcpyDeviceToHost, st));
+    HIPCHK_OR(c, hipMemcpyAsync(out, dout, (size_t)n1 * es, hipMemcpyDeviceToHost, st), cleanup());
   } else {
-    HIPCHK_G(hbo_malloc(c, &dout, (size_t)n1 * n2 * es));
+    HIPCHK_OR(c, hbo_malloc(c, &dout, (size_t)n1 * n2 * es), cleanup());
     GramArgs g = {}; g.kernel_id = c->h_model->kernel_id; g.mfma_min_f = c->opt_gram_mfma; g.x1 = F1; g.x2 = F2; g.out = dout; g.n1 = n1; g.n2 = n2; g.ldo = n2; g.fdim = fdim;
     launch_gram(dtype, g, c->d_model, dim3((unsigned)((n2 + 127) / 128), (unsigned)((n1 + 127) / 128), 1), st);
-    HIPCHK_G(hipMemcpyAsync(out, dout, (size_t)n1 * n2 * es, hipMemcpyDeviceToHost, st));
+    HIPCHK_OR(c, hipMemcpyAsync(out, dout, (size_t)n1 * n2 * es, hipMemcpyDeviceToHost, st), cleanup());
   }
-  HIPCHK_G(hipStreamSynchronize(st));
-  HIPCHK_G(hipGetLastError());
-#undef HIPCHK_G
+  HIPCHK_OR(c, hipStreamSynchronize(st), cleanup());
+  HIPCHK_OR(c, hipGetLastError(), cleanup());
   cleanup();
   return HBO_OK;
 }
@@ -558,20 +556,18 @@ extern "C" int hbo_chol_solve(hbo_ctx* c, int dtype, const void* chol_lower, int
   const int64_t npad = round_up(n, 64);
   void *d_l = nullptr, *d_r = nullptr;
   auto cleanup = [&]() { for (void* p : {d_l, d_r}) if (p) hipFree(p); };
-#define HIPCHK_S(call) do { hipError_t e__ = (call); if (e__ != hipSuccess) { c->err = std::string(#call " failed: ") + hipGetErrorString(e__); cleanup(); return HBO_ERR_HIP; } } while (0)
   // right-hand sides as rows (m x npad, zero padding)
   std::vector<unsigned char> rt((size_t)mcols * npad * es, 0);
   for (int64_t i = 0; i < n; ++i)
     for (int a = 0; a < mcols; ++a) memcpy(rt.data() + ((size_t)a * npad + i) * es, (const unsigned char*)b + ((size_t)i * mcols + a) * es, es);
-  HIPCHK_S(hbo_malloc(c, &d_l, (size_t)n * n * es));
-  HIPCHK_S(hbo_malloc(c, &d_r, rt.size()));
-  HIPCHK_S(hipMemcpyAsync(d_l, chol_lower, (size_t)n * n * es, hipMemcpyHostToDevice, st));
-  HIPCHK_S(hipMemcpyAsync(d_r, rt.data(), rt.size(), hipMemcpyHostToDevice, st));
+  HIPCHK_OR(c, hbo_malloc(c, &d_l, (size_t)n * n * es), cleanup());
+  HIPCHK_OR(c, hbo_malloc(c, &d_r, rt.size()), cleanup());
+  HIPCHK_OR(c, hipMemcpyAsync(d_l, chol_lower, (size_t)n * n * es, hipMemcpyHostToDevice, st), cleanup());
+  HIPCHK_OR(c, hipMemcpyAsync(d_r, rt.data(), rt.size(), hipMemcpyHostToDevice, st), cleanup());
   launch_chol_solve(dtype, d_l, n, d_r, npad, mcols, st);
-  HIPCHK_S(hipMemcpyAsync(rt.data(), d_r, rt.size(), hipMemcpyDeviceToHost, st));
-  HIPCHK_S(hipStreamSynchronize(st));
-  HIPCHK_S(hipGetLastError());
-#undef HIPCHK_S
+  HIPCHK_OR(c, hipMemcpyAsync(rt.data(), d_r, rt.size(), hipMemcpyDeviceToHost, st), cleanup());
+  HIPCHK_OR(c, hipStreamSynchronize(st), cleanup());
+  HIPCHK_OR(c, hipGetLastError(), cleanup());
   for (int64_t i = 0; i < n; ++i)
     for (int a = 0; a < mcols; ++a) memcpy((unsigned char*)x_out + ((size_t)i * mcols + a) * es, rt.data() + ((size_t)a * npad + i) * es, es);
   cleanup();
@@ -592,23 +588,22 @@ extern "C" int hbo_spd_solve(hbo_ctx* c, int dtype, const void* a, int64_t n, co
   t->n = n; t->m = b ? mcols : 1; t->npad = round_up(n, HBO_TILE); t->nblk = t->npad / HBO_TILE; t->ld = padded_ld(t->npad, dtype);
   void *d_a = nullptr, *d_b = nullptr, *d_tmp = nullptr; TaskDesc* d_desc = nullptr; int* d_info = nullptr;
   auto cleanup = [&]() { free_task(c, t); for (void* p : {d_a, d_b, d_tmp, (void*)d_desc, (void*)d_info}) if (p) hipFree(p); };
-#define HIPCHK_S(call) do { hipError_t e__ = (call); if (e__ != hipSuccess) { c->err = std::string(#call " failed: ") + hipGetErrorString(e__); cleanup(); return HBO_ERR_HIP; } } while (0)
   const bool need_inv = inv_out != nullptr || x_out != nullptr;
   { int rc = ensure_task_workspace(c, dtype, t, need_inv, t->m); if (rc) { cleanup(); return rc; } }
-  HIPCHK_S(hbo_malloc(c, &d_a, (size_t)n * n * es));
-  HIPCHK_S(hipMemcpyAsync(d_a, a, (size_t)n * n * es, hipMemcpyHostToDevice, st));
-  if (b) { HIPCHK_S(hbo_malloc(c, &d_b, (size_t)n * mcols * es)); HIPCHK_S(hipMemcpyAsync(d_b, b, (size_t)n * mcols * es, hipMemcpyHostToDevice, st)); }
+  HIPCHK_OR(c, hbo_malloc(c, &d_a, (size_t)n * n * es), cleanup());
+  HIPCHK_OR(c, hipMemcpyAsync(d_a, a, (size_t)n * n * es, hipMemcpyHostToDevice, st), cleanup());
+  if (b) { HIPCHK_OR(c, hbo_malloc(c, &d_b, (size_t)n * mcols * es), cleanup()); HIPCHK_OR(c, hipMemcpyAsync(d_b, b, (size_t)n * mcols * es, hipMemcpyHostToDevice, st), cleanup()); }
   launch_fill_spd(dtype, d_a, n, t->A, t->ld, t->npad, st);
   launch_set_aug(dtype, d_b, n, b ? mcols : 0, t->A, t->ld, t->npad, st);
   TaskDesc h; memset(&h, 0, sizeof h);
   h.A = t->A; h.W = t->W; h.S = t->S; h.wscr = t->wscr; h.svec = t->svec; h.n = (int)n; h.npad = t->npad; h.nblk = t->nblk; h.m = t->m; h.ld = t->ld;
   h.naug = t->m;
-  HIPCHK_S(hbo_malloc(c, (void**)&d_desc, sizeof h));
-  HIPCHK_S(hbo_malloc(c, (void**)&d_info, sizeof(int)));
+  HIPCHK_OR(c, hbo_malloc(c, (void**)&d_desc, sizeof h), cleanup());
+  HIPCHK_OR(c, hbo_malloc(c, (void**)&d_info, sizeof(int)), cleanup());
   int inf = INT_MAX;
-  HIPCHK_S(hipMemcpyAsync(d_desc, &h, sizeof h, hipMemcpyHostToDevice, st));
-  HIPCHK_S(hipMemcpyAsync(d_info, &inf, sizeof(int), hipMemcpyHostToDevice, st));
-  HIPCHK_S(hipStreamSynchronize(st));
+  HIPCHK_OR(c, hipMemcpyAsync(d_desc, &h, sizeof h, hipMemcpyHostToDevice, st), cleanup());
+  HIPCHK_OR(c, hipMemcpyAsync(d_info, &inf, sizeof(int), hipMemcpyHostToDevice, st), cleanup());
+  HIPCHK_OR(c, hipStreamSynchronize(st), cleanup());
   c->trtri_host_task = h;
   // hbo_tune "spd_diag_bound" (test hook): max_i A_ii off the caller's matrix -- what potrf_plan, trtri_level3 and run_lauum need to
   // take the f16x2 form, as hbo_factor does from the model's signal variance.  Default: 0 = unknown, the bf16x3 form
@@ -621,31 +616,30 @@ extern "C" int hbo_spd_solve(hbo_ctx* c, int dtype, const void* a, int64_t n, co
     if (x_out && b) for (int col = 0; col < mcols; ++col) launch_wt_z(dtype, d_desc, 1, t->nblk, col, col, t->npad, st);
     if (inv_out) { ProfScope ps(c, "lauum", 1); run_lauum(c, dtype, d_desc, 1, t->nblk); }
   }
-  HIPCHK_S(hipMemcpyAsync(&inf, d_info, sizeof(int), hipMemcpyDeviceToHost, st));
-  HIPCHK_S(hbo_malloc(c, &d_tmp, (size_t)n * n * es));
+  HIPCHK_OR(c, hipMemcpyAsync(&inf, d_info, sizeof(int), hipMemcpyDeviceToHost, st), cleanup());
+  HIPCHK_OR(c, hbo_malloc(c, &d_tmp, (size_t)n * n * es), cleanup());
   std::vector<unsigned char> hchol;
   if (chol_out || logdet_half) {
     launch_extract_lower(dtype, t->A, t->ld, n, d_tmp, st);
     void* dst = chol_out;
     if (!dst) { hchol.resize((size_t)n * n * es); dst = hchol.data(); }
-    HIPCHK_S(hipMemcpyAsync(dst, d_tmp, (size_t)n * n * es, hipMemcpyDeviceToHost, st));
-    HIPCHK_S(hipStreamSynchronize(st));
+    HIPCHK_OR(c, hipMemcpyAsync(dst, d_tmp, (size_t)n * n * es, hipMemcpyDeviceToHost, st), cleanup());
+    HIPCHK_OR(c, hipStreamSynchronize(st), cleanup());
     if (logdet_half) { double s = 0; for (int64_t i = 0; i < n; ++i) s += log(host_elem(dst, dtype, i * n + i)); *logdet_half = s; }
   }
   if (inv_out) {
     launch_symmetrize_from_lower(dtype, t->S, t->ld, n, d_tmp, st);
-    HIPCHK_S(hipMemcpyAsync(inv_out, d_tmp, (size_t)n * n * es, hipMemcpyDeviceToHost, st));
+    HIPCHK_OR(c, hipMemcpyAsync(inv_out, d_tmp, (size_t)n * n * es, hipMemcpyDeviceToHost, st), cleanup());
   }
-  HIPCHK_S(hipStreamSynchronize(st));
+  HIPCHK_OR(c, hipStreamSynchronize(st), cleanup());
   if (x_out && b) {
     std::vector<unsigned char> buf((size_t)mcols * t->npad * es);
-    HIPCHK_S(hipMemcpy(buf.data(), t->svec, buf.size(), hipMemcpyDeviceToHost));
+    HIPCHK_OR(c, hipMemcpy(buf.data(), t->svec, buf.size(), hipMemcpyDeviceToHost), cleanup());
     for (int col = 0; col < mcols; ++col)
       for (int64_t i = 0; i < n; ++i)
         memcpy((unsigned char*)x_out + ((size_t)i * mcols + col) * es, buf.data() + ((size_t)col * t->npad + i) * es, es);
   }
-  HIPCHK_S(hipGetLastError());
-#undef HIPCHK_S
+  HIPCHK_OR(c, hipGetLastError(), cleanup());
   prof_collect(c);
   const bool bad = inf != INT_MAX;
   if (bad) {

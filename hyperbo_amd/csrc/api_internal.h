@@ -1,6 +1,7 @@
 // Host-side internals shared by the translation units of the C ABI (api.hip: context, options, datasets, dense entry points;
 // objective.hip: hbo_objective / hbo_objective_sharded; cache.hip: hbo_factor, row append, posterior, acquisition): model
-// validation and upload, the MLP feature pipeline, the per-task device buffers and the descriptors the kernels read.
+// validation and upload, the MLP feature pipeline and the query-side features of everything that reads a factor (query_features), the
+// per-task device buffers and the descriptors the kernels read, and the plan of a posterior call (post_plan: every decision, no HIP call).
 #pragma once
 #include "ctx.h"
 
@@ -147,16 +148,42 @@ static int upload_model(hbo_ctx* c, const hbo_model* m) {
 
 // ---- feature pipeline ----------------------------------------------------------------------
 // Computes the MLP activations of x (n x D, device) into acts[l] (allocated by the caller: n x f_l)
-// (w / b: the layers' device weights -- the context's own copy of the last uploaded model unless a caller keeps several)
-static void run_mlp(hbo_ctx* c, const hbo_model* m, const void* x, int64_t n, void* const* acts, void* const* w = nullptr, void* const* b = nullptr) {
+// (w / b: the layers' device weights -- the context's own copy of the last uploaded model unless a caller keeps several;
+//  st: the context's main stream unless given)
+static void run_mlp(hbo_ctx* c, const hbo_model* m, const void* x, int64_t n, void* const* acts, void* const* w = nullptr, void* const* b = nullptr,
+                    hipStream_t st = nullptr) {
   const void* in = x;
   int fin = m->input_dim;
   if (!w) { w = c->d_mlp_w; b = c->d_mlp_b; }
+  if (!st) st = c->stream;
   for (int l = 0; l < m->n_layers; ++l) {
-    launch_dense_tanh(m->dtype, in, w[l], b[l], acts[l], n, fin, m->features[l], c->stream);
+    launch_dense_tanh(m->dtype, in, w[l], b[l], acts[l], n, fin, m->features[l], st);
     in = acts[l];
     fin = m->features[l];
   }
+}
+
+// The query side of everything that reads a factor (row append, posterior, d acquisition / dx): for `n` rows xq (device) the MLP
+// activations into acts[l] (n x f_l each; unused without an MLP), the warped rows into `wq` (Kumaraswamy models; null otherwise), then
+// the prior mean into mu0 and k(x, x) into kd, all on `st`.  The mean reads the raw x (or the MLP output), the covariance w(x).
+// md / w / b: the model and its MLP weights on the device.  timed: the "features" / "kumar_forward" scopes of the profile.
+struct QueryFeat { const void* Fq; const void* fq_last; };   // what the covariance reads; the last MLP layer (null without an MLP)
+static QueryFeat query_features(hbo_ctx* c, const hbo_model* m, const ModelDev* md, void* const* w, void* const* b, const void* xq, int64_t n,
+                                void* const* acts, void* wq, void* mu0, void* kd, hipStream_t st, bool timed = false) {
+  const int lvl = timed ? 1 : INT_MAX;
+  QueryFeat f = {nullptr, nullptr};
+  { ProfScope ps(c, "features", lvl, st);
+    if (needs_mlp(m)) { run_mlp(c, m, xq, n, acts, w, b, st); f.fq_last = acts[m->n_layers - 1]; } }
+  f.Fq = m->kernel_uses_mlp ? f.fq_last : xq;
+  if (is_kumar(m)) {
+    ProfScope ps(c, "kumar_forward", lvl, st);
+    launch_kumar_forward(m->dtype, nullptr, 0, 0, xq, wq, nullptr, n, m->input_dim, md, st);
+    f.Fq = wq;
+  }
+  const void* Fmq = (m->mean_id == HBO_MEAN_LINEAR) ? xq : (m->mean_id == HBO_MEAN_LINEAR_MLP ? f.fq_last : nullptr);
+  launch_mean(m->dtype, Fmq, n, mean_feature_dim(m), md, mu0, st);
+  launch_kdiag(m->dtype, f.Fq, n, feature_dim(m), md, kd, st);
+  return f;
 }
 
 struct FeatBuf {   // device activations of one input matrix
@@ -311,3 +338,82 @@ static void fill_nan(void* p, size_t count, int dtype) {
   else for (size_t i = 0; i < count; ++i) ((float*)p)[i] = NAN;
 }
 
+// ---- posterior plan ------------------------------------------------------------------------
+// Every decision of one posterior / acquisition call (cache.hip: posterior), from sizes and options alone: no HIP call, no allocation.
+// nblk: 128-blocks of the cache (0: prior branch).  ov_lane: null for a call of its own, else the lane of the override (hbo_acq_samples).
+// deny: forms the caller could not get the memory for -- the plan without them.
+enum { POST_NO_SPLITK = 1, POST_NO_SPLIT3 = 2 };
+struct PostChunk {
+  int64_t q0, mc; int b;       // first query, queries, workspace
+  int mpad; int64_t ldq;       // the chunk's padded candidates and their leading dimension
+  int counter;                 // the product as a resident grid drawing its tiles from this word of the tile-counter array (-1: plain grid)
+};
+struct PostPlan {
+  int refuse;                  // not 0: the call is not run (HBO_ERR_UNSUPPORTED: full_cov beyond 65536 queries)
+  int dtype, nblk; bool full_cov;
+  int64_t M, CH, mc_max, nchunks; int nbuf;   // chunks of CH queries through nbuf alternating workspaces
+  int mpad_max; int64_t ldq_max;
+  int lane, wso;               // side-stream lane of an override's single-chunk pass; its workspace-slot offset
+  hipStream_t sa, sb;          // consumer (products, epilogue, copy back) and producer (features, cross Gram) streams
+  int kchunk, nch;             // split-K product: 128-blocks per K chunk (0: not split) and the chunks of the longest row
+  Fp32Form form; int planes; float kscale;   // the product's fp32 form (FORM_MFMA: also all of fp64), planes of its split operands, scale of Kxq's
+  bool direct_form;            // the producer's cross Gram in the direct form
+  bool own_counters; int n_cus;
+  // One rule for both products: a resident grid with a tile counter for calls of their own, with lauum_persist on, beyond `min_tiles` tiles
+  // (one counter per chunk in flight)
+  bool resident(int64_t tiles, int64_t min_tiles) const { return own_counters && tiles > min_tiles; }
+  PostChunk chunk(int64_t i) const {
+    PostChunk ch;
+    ch.q0 = i * CH; ch.mc = std::min<int64_t>(CH, M - ch.q0); ch.b = (int)(i % nbuf);
+    ch.mpad = round_up(ch.mc, HBO_TILE); ch.ldq = padded_ld(ch.mpad, dtype);
+    const int64_t tiles = (int64_t)(ch.mpad / HBO_TILE) * nblk;
+    // the bf16 / fp16 form hands launch_post3 a counter whatever the size (it decides); launch_gemm's takes one for the large products
+    const bool res = nblk && kchunk == 0 && resident(tiles, form != FORM_MFMA ? 0 : 4 * (int64_t)n_cus);
+    ch.counter = res ? HBO_N_COUNTERS - 8 + (ch.b & 1) : -1;
+    return ch;
+  }
+};
+static PostPlan post_plan(const hbo_ctx* c, const hbo_model* m, int64_t M, int nblk, bool full_cov, const int* ov_lane, int deny = 0) {
+  PostPlan p = {};
+  p.dtype = m->dtype; p.nblk = nblk; p.full_cov = full_cov; p.M = M; p.n_cus = c->n_cus;
+  // Candidates are STREAMED: chunks of `CH` queries, so that the cross-Gram workspace (npad x CH) does not grow with M
+  // (gp.py:295-305 materialises all of Kxq; at cfg 3 that is 16384 x 65536 fp32 = 4.3 GB).  Two workspaces alternate:
+  // upload + features + cross Gram of chunk i+1 run on a second stream beside the triangular product of chunk i; the
+  // results of all chunks are gathered in M-sized vectors and come back in one copy.  full_cov keeps a single pass.
+  p.CH = full_cov ? 65536 : std::max<int64_t>(c->opt_post_chunk, HBO_TILE);
+  if (full_cov && M > p.CH) p.refuse = HBO_ERR_UNSUPPORTED;
+  p.mc_max = std::min<int64_t>(M, p.CH);
+  p.nchunks = (M + p.CH - 1) / p.CH;
+  p.nbuf = (!full_cov && M > p.CH) ? 2 : 1;
+  p.mpad_max = round_up(p.mc_max, HBO_TILE);
+  p.ldq_max = padded_ld(p.mpad_max, p.dtype);
+  p.lane = (ov_lane && p.nbuf == 1) ? *ov_lane : 0;
+  p.wso = 4096 * p.lane;   // workspace slots of this lane
+  p.sa = p.lane == 1 ? c->stream2 : (p.lane == 2 ? c->stream4 : c->stream);
+  p.sb = (p.nbuf == 2 && !c->opt_post_serial) ? c->stream2 : p.sa;
+  // Few candidates (a BO step asks for tens of them): one workgroup per 128-row tile of W would walk a K range of up to N alone
+  // (N = 8192, 64 queries: 1.1 ms for 8.6 GFLOP); the K range is cut into chunks of `kchunk` blocks instead, one workgroup per
+  // (row tile, chunk), partial products to a workspace, summed and squared by a second small kernel (0.1-0.2 ms).
+  // (decided on the TOTAL number of candidates, not on the chunk: every post_chunk then gives the same bits)
+  if (nblk && !(deny & POST_NO_SPLITK) && !full_cov && nblk >= 2 && (int64_t)((M + HBO_TILE - 1) / HBO_TILE) * nblk < 2 * c->n_cus) {
+    p.kchunk = std::max(2, std::min(8, nblk / 8));   // N = 8100: 1 / 2 / 4 / 8 / 16 blocks per chunk: 0.81 / 0.48 / 0.35 / 0.35 / 0.35 ms; N = 2000: 2 / 4 / 8: 0.11 / 0.11 / 0.17
+    // (below 8 blocks one block per chunk: the lone 128-tile of the last row block of an N = 512 cache ran its K = 512 alone on a
+    //  CU for 75 us -- an HGP acquisition over 32 samples spent half its time there)
+    if (nblk < 8) p.kchunk = 1;
+    p.nch = (nblk + p.kchunk - 1) / p.kchunk;
+  }
+  // fp32: the product runs on the bf16 matrix cores from exact three-way splits of both operands (post3.hip)
+  const bool use3 = nblk && !(deny & POST_NO_SPLIT3) && p.dtype == HBO_F32 && c->opt_post_bf16x3 && !full_cov && p.kchunk == 0;
+  // stationary covariances (|k| <= signal variance: the cross Gram's scale is known without a pass over it): two-way fp16 split,
+  // three MFMAs per product instead of six (post3.hip, H2)
+  const bool use2h = use3 && c->opt_post_f16x2 && m->kernel_id != HBO_KERNEL_DOT;
+  p.form = use2h ? FORM_F16X2 : (use3 ? FORM_BF16X3 : FORM_MFMA);
+  p.planes = use2h ? 2 : 3;
+  p.kscale = use2h ? post2h_scale_for(m->signal_variance) : 1.f;
+  // the producer of a streamed posterior runs BESIDE the product of the previous chunk, in the slots its resident grid leaves: there the
+  // matrix-core form (38 KB of LDS per workgroup, the product's own MFMA pipes) is the slower one -- cfg 3: EI 58.5 ms with the direct
+  // form, 59.0 with it, although alone it takes 0.33 ms per chunk against 0.58 (round 6)
+  p.direct_form = p.nbuf == 2;
+  p.own_counters = c->opt_lauum_persist && !ov_lane;
+  return p;
+}

@@ -118,7 +118,9 @@ struct hbo_ctx {
   int comm_buf_count = 0;
 };
 
-#define HIPCHK(ctx, call)                                                                     \
+// The one error check of the host code: a failing HIP call leaves "<call> failed: <why> (<file>:<line>)" as the context's error (or as the
+// ctx-less one), runs `action` -- what the caller has to undo: cleanup(), bail(...), nothing -- and returns HBO_ERR_HIP.
+#define HIPCHK_OR(ctx, call, action)                                                          \
   do {                                                                                        \
     hipError_t e__ = (call);                                                                  \
     if (e__ != hipSuccess) {                                                                  \
@@ -126,9 +128,11 @@ struct hbo_ctx {
       snprintf(buf__, sizeof buf__, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e__),   \
                __FILE__, __LINE__);                                                           \
       if (ctx) (ctx)->err = buf__; else hbo_g_err = buf__;                                        \
+      action;                                                                                 \
       return HBO_ERR_HIP;                                                                     \
     }                                                                                         \
   } while (0)
+#define HIPCHK(ctx, call) HIPCHK_OR(ctx, call, (void)0)
 
 static inline int fail(hbo_ctx* ctx, int code, const std::string& msg) {
   if (ctx) ctx->err = msg; else hbo_g_err = msg;

@@ -319,6 +319,43 @@ def test_predict_append_and_acquisition(gpu_ctx, base):
       np.testing.assert_allclose(grad[:, j], fd[:, 0], rtol=1e-5, atol=1e-7 * max(1.0, np.max(np.abs(fd))), err_msg=f'{name} d{j}')
 
 
+def test_streamed_kumar_posterior_chunks_match_single_pass(gpu_ctx):
+  """A Kumaraswamy model streamed through two workspaces: the linear mean reads the raw queries, the covariance w(queries), which
+  lives per workspace.  post_chunk = 128 cuts 300 queries into three chunks (the last ragged) through two alternating workspaces:
+  mean, variance and EI with data, and mean, variance and UCB on the prior branch, must be finite and bit-identical to the
+  one-pass run, fp64 and fp32; the fp64 one-pass mean and variance are within 1e-9 of the oracle."""
+  nat, defs, acfun, gp, kernel, mean, _, utils = _native()
+  rng = np.random.default_rng(14)
+  d = 3
+  model = _model(rng, d, mname='linear', spread=1.0)
+  x, y = _x(rng, 200, d), rng.normal(size=(200, 1))
+  xq = rng.uniform(0.05, 0.95, size=(300, d))
+  muo, varo = o.predict(o.linear, ko.kumar_kernel(o.matern52), o.GPParams(model=model), x, y, xq, WFO)
+  for dtype in (np.float64, np.float32):
+    cast = lambda t: {k: cast(v) for k, v in t.items()} if isinstance(t, dict) else np.asarray(t, dtype=dtype)
+    g = gp.GP({0: defs.SubDataset(x.astype(dtype), y.astype(dtype)), 1: defs.SubDataset(np.zeros((0, d), dtype), np.zeros((0, 1), dtype))},
+              mean.linear, kernel.matern52_kumar, defs.GPParams(model=cast(model)), utils.DEFAULT_WARP_FUNC)
+    q = xq.astype(dtype)
+    ref = None
+    try:
+      for chunk in (65536, 128):
+        gpu_ctx.set_option('post_chunk', chunk)
+        p0, ei = g.predict(q, 0), acfun.expected_improvement(model=g, sub_dataset_key=0, x_queries=q)
+        p1, ucb = g.predict(q, 1), acfun.ucb(model=g, sub_dataset_key=1, x_queries=q)
+        flat = [p0[0], p0[1], ei, p1[0], p1[1], ucb]
+        assert all(np.isfinite(a).all() for a in flat), chunk
+        if ref is None:
+          ref = flat
+          if dtype == np.float64:
+            mu, var = g.predict(q, 0, with_noise=False, unbiased=False)
+            assert helpers.rel_err(mu, muo) < 1e-9 and helpers.rel_err(var, varo) < 1e-9
+        else:
+          for a, b in zip(flat, ref):
+            assert np.array_equal(a, b), chunk
+    finally:
+      gpu_ctx.set_option('post_chunk', 8192)
+
+
 # ---- training ------------------------------------------------------------------------------------------------------------
 def test_gp_train_adam_moves_kumar_params_like_the_numpy_loop(gpu_ctx):
   """GP.train (Adam, full batches) against the same Adam loop in NumPy on the oracle NLL's gradient (analytic SE-kumar a / b

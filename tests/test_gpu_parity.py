@@ -2341,8 +2341,6 @@ def test_streamed_posterior_chunks_match_single_pass(gpu_ctx):
             assert np.array_equal(a, b), chunk
     finally:
       gpu_ctx.set_option('post_chunk', 8192)
-  if dtype == np.float32:
-    pass
   # against the oracle (fp64) with small chunks
   gpu_ctx.set_option('post_chunk', 256)
   try:
