@@ -73,6 +73,21 @@ class TrainLeaf(C.Structure):
   _fields_ = [('warp', C.c_int32), ('target', C.c_int32), ('layer', C.c_int32), ('index', C.c_int32), ('round_f32', C.c_int32)]
 
 
+class LbfgsOpts(C.Structure):
+  """hbo_lbfgs_opts: the arguments of lbfgs.lbfgs and its line search (hbo_train_lbfgs)."""
+  _fields_ = [('memory', C.c_int32), ('ls_steps', C.c_int32), ('max_iters', C.c_int32), ('alpha', C.c_double), ('tol', C.c_double),
+              ('c1', C.c_double), ('c2', C.c_double), ('grow', C.c_double), ('tau', C.c_double)]
+
+
+class LbfgsEval(C.Structure):
+  """hbo_lbfgs_eval: one evaluation of the log of hbo_train_lbfgs."""
+  _fields_ = [('kind', C.c_int32), ('iter', C.c_int32), ('alpha', C.c_double), ('value', C.c_double)]
+
+
+# hbo_lbfgs_kind / hbo_lbfgs_status
+LBFGS_START, LBFGS_MAIN, LBFGS_LINE_SEARCH, LBFGS_IDLE = 0, 1, 2, 3
+(LBFGS_RUNNING, LBFGS_CONVERGED_AT_START, LBFGS_CONVERGED, LBFGS_NO_PROGRESS, LBFGS_INSTABILITY, LBFGS_STEPS_DONE) = range(6)
+
 # hbo_train_warp / hbo_train_target
 TRAIN_WARP_IDENTITY, TRAIN_WARP_SOFTPLUS, TRAIN_WARP_SOFTPLUS_EPS, TRAIN_WARP_SQUAREPLUS = 0, 1, 2, 3
 (TRAIN_NONE, TRAIN_LENGTHSCALE, TRAIN_SIGNAL_VARIANCE, TRAIN_NOISE_VARIANCE, TRAIN_CONSTANT, TRAIN_DOT_PROD_SIGMA, TRAIN_DOT_PROD_BIAS,
@@ -132,6 +147,11 @@ SIGNATURES = {
                                         C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     'hbo_train_adam': (C.c_int, [_P, C.POINTER(Model), _P, C.POINTER(TrainLeaf), C.c_int32, _P, _P, _P, _P, _P, C.c_int32,
                                  C.c_double, C.c_double, C.c_double, C.c_double, _P, _P, _P, _P, C.POINTER(C.c_int32)]),
+    'hbo_lbfgs_state_doubles': (C.c_int64, [C.c_int32, C.c_int32]),
+    'hbo_train_lbfgs': (C.c_int, [_P, C.POINTER(Model), _P, C.POINTER(TrainLeaf), C.c_int32, C.POINTER(LbfgsOpts), _P, _P, C.c_int32,
+                                  C.POINTER(LbfgsEval), _P, _P, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    'hbo_probe_lbfgs_ctl': (C.c_int, [_P, C.c_int32, C.POINTER(LbfgsOpts), _P, C.c_double, _P, _P, _P, C.POINTER(LbfgsEval),
+                                      C.POINTER(C.c_int32)]),   # include/hbo_tune.h (test hook)
     'hbo_device_info': (C.c_int, [C.c_int, C.c_char_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
 }
 

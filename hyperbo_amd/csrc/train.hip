@@ -2,7 +2,14 @@
 // whose tasks all fit one 128-block.  Per step: [gather the step's rows in place] -> single-workgroup evaluation and its backward
 // passes (objective.hip: enqueue_fused_forward / enqueue_backward) -> launch_shard_reduce ([nll_sum, T, grad] in the caller's
 // layout) -> adam_step_kernel.  No host wait between steps: one copy back and one synchronisation per call.
+//
+// hbo_train_lbfgs: the evaluations of infer_parameters(method='lbfgs') (basics/lbfgs.py) queued the same way on one resident batch:
+// evaluation -> launch_shard_reduce -> lbfgs_ctl_kernel, which runs the state machine of lbfgs_ctl.h on [nll_sum / T, grad / T]
+// chained through the warps and writes the model of the next point.  Both step kernels share the chain rule, the leaf -> model field
+// staging and the host-side leaf checks and packing below.
 #include "api_internal.h"
+#define HBO_LBFGS_FN static __host__ __device__ inline
+#include "lbfgs_ctl.h"
 
 #include <numeric>
 
@@ -42,93 +49,171 @@ __device__ void put_elem(void* p, int dtype, int i, double v) {
   else static_cast<float*>(p)[i] = (float)v;
 }
 
-struct AdamStepArgs {
+// What both step kernels read: the leaf map, where each leaf's gradient sits in the reduction, the starting model (its array pointers
+// point at device copies in the model dtype) and where the next model goes.
+struct TrainDev {
   const hbo_train_leaf* leaves; const int* goff; int P;
-  double* x; double* am; double* av;
-  const double* bias1; const double* bias2;
-  double lr, b1, b2, eps;
   const double* red;                 // [nll_sum, T, grad sum in the caller's layout]
-  double* losses; double* trace;     // trace nullable
-  int* halt; int* steps_done;
-  hbo_model_kumar init;              // the starting model; its array pointers point at device copies (model dtype)
+  hbo_model_kumar init;
   int n_ls, fm;
   void* mlp_w[HBO_MAX_MLP_LAYERS]; void* mlp_b[HBO_MAX_MLP_LAYERS];
   ModelDev* md;
 };
+// the warped fields of the next model while its leaves are written (arrays in the model dtype)
+struct ModelStage {
+  double ls[HBO_MAX_FEATURE_DIM], lin[HBO_MAX_FEATURE_DIM], ka[HBO_MAX_FEATURE_DIM], kb[HBO_MAX_FEATURE_DIM];
+  double sc[6];   // signal variance, noise variance, constant, dot sigma, dot bias, linear bias
+};
+// the starting model's fields into the stage (fields no leaf targets keep them); ends with a barrier
+__device__ void stage_load(const TrainDev& t, ModelStage& s, int tid, int nthr) {
+  const hbo_model& m0 = t.init.base;
+  const int dtype = m0.dtype, D = m0.input_dim;
+  for (int d = tid; d < HBO_MAX_FEATURE_DIM; d += nthr) {
+    if (d < t.n_ls) put_elem(s.ls, dtype, d, model_elem(m0.lengthscale, dtype, d));
+    if (d < t.fm) put_elem(s.lin, dtype, d, model_elem(m0.linear_kernel, dtype, d));
+    if (m0.input_warp == HBO_WARP_KUMAR && d < D) {
+      put_elem(s.ka, dtype, d, model_elem(t.init.kumar_a, dtype, d));
+      put_elem(s.kb, dtype, d, model_elem(t.init.kumar_b, dtype, d));
+    }
+  }
+  if (tid == 0) {
+    s.sc[0] = m0.signal_variance; s.sc[1] = m0.noise_variance; s.sc[2] = m0.constant;
+    s.sc[3] = m0.dot_prod_sigma; s.sc[4] = m0.dot_prod_bias; s.sc[5] = m0.linear_bias;
+  }
+  __syncthreads();
+}
+// d loss / d x[i] from the reduction: grad / count, then d warp / d raw (_model.BuiltModel.unflatten_grad; a leaf the model does not
+// read has gradient zero)
+__device__ double chained_grad(const TrainDev& t, const hbo_train_leaf& lf, int i, double x, double count) {
+  const double xr = lf.round_f32 ? (double)(float)x : x;
+  double g = 0.0;
+  if (t.goff[i] >= 0) g = (t.red[2 + t.goff[i]] / count) * warp_slope(lf.warp, xr);
+  return g;
+}
+// leaf value x -> its warped field of the next model
+__device__ void stage_put(const TrainDev& t, ModelStage& s, const hbo_train_leaf& lf, double x) {
+  const int dtype = t.init.base.dtype;
+  const double xr = lf.round_f32 ? (double)(float)x : x;
+  double w = warp_value(lf.warp, xr);
+  if (lf.round_f32) w = (double)(float)w;
+  switch (lf.target) {
+    case HBO_TRAIN_LENGTHSCALE: put_elem(s.ls, dtype, lf.index, w); break;
+    case HBO_TRAIN_SIGNAL_VARIANCE: s.sc[0] = w; break;
+    case HBO_TRAIN_NOISE_VARIANCE: s.sc[1] = w; break;
+    case HBO_TRAIN_CONSTANT: s.sc[2] = w; break;
+    case HBO_TRAIN_DOT_PROD_SIGMA: s.sc[3] = w; break;
+    case HBO_TRAIN_DOT_PROD_BIAS: s.sc[4] = w; break;
+    case HBO_TRAIN_LINEAR_BIAS: s.sc[5] = w; break;
+    case HBO_TRAIN_LINEAR_KERNEL: put_elem(s.lin, dtype, lf.index, w); break;
+    case HBO_TRAIN_MLP_KERNEL: put_elem(t.mlp_w[lf.layer], dtype, lf.index, w); break;
+    case HBO_TRAIN_MLP_BIAS: put_elem(t.mlp_b[lf.layer], dtype, lf.index, w); break;
+    case HBO_TRAIN_KUMAR_A: put_elem(s.ka, dtype, lf.index, w); break;
+    case HBO_TRAIN_KUMAR_B: put_elem(s.kb, dtype, lf.index, w); break;
+    default: break;
+  }
+}
+// the staged model into ModelDev (the MLP weights went to their buffers leaf by leaf); begins with a barrier
+__device__ void stage_store(const TrainDev& t, ModelStage& s, int tid, int nthr) {
+  __syncthreads();
+  hbo_model_kumar mk = t.init;
+  mk.base.signal_variance = s.sc[0]; mk.base.noise_variance = s.sc[1]; mk.base.constant = s.sc[2];
+  mk.base.dot_prod_sigma = s.sc[3]; mk.base.dot_prod_bias = s.sc[4]; mk.base.linear_bias = s.sc[5];
+  mk.base.lengthscale = s.ls; mk.base.linear_kernel = s.lin; mk.kumar_a = s.ka; mk.kumar_b = s.kb;
+  model_dev_fill(*t.md, &mk.base, tid, nthr);
+}
 
-// One step: loss check (gp.py:135-142), warp chain rule (_model.BuiltModel.unflatten_grad), Adam (gp.py:_Adam.step), then the
-// warped next model into ModelDev and the MLP weight buffers.  A non-finite loss sets the halt word: every later step returns here.
+struct AdamStepArgs {
+  TrainDev t;
+  double* x; double* am; double* av;
+  const double* bias1; const double* bias2;
+  double lr, b1, b2, eps;
+  double* losses; double* trace;     // trace nullable
+  int* halt; int* steps_done;
+};
+
+// One step: loss check (gp.py:135-142), warp chain rule, Adam (gp.py:_Adam.step), then the warped next model into ModelDev and the
+// MLP weight buffers.  A non-finite loss sets the halt word: every later step returns here.
 __global__ __launch_bounds__(ADAM_THREADS) void adam_step_kernel(AdamStepArgs a, int step) {
-  __shared__ double s_ls[HBO_MAX_FEATURE_DIM], s_lin[HBO_MAX_FEATURE_DIM], s_ka[HBO_MAX_FEATURE_DIM], s_kb[HBO_MAX_FEATURE_DIM];
-  __shared__ double s_sc[6];   // signal variance, noise variance, constant, dot sigma, dot bias, linear bias
+  __shared__ ModelStage s;
   __shared__ int s_halt;
   const int tid = threadIdx.x, nthr = blockDim.x;
   if (tid == 0) s_halt = *a.halt;
   __syncthreads();
   if (s_halt) return;
-  const double count = a.red[1];
-  const double loss = a.red[0] / count;
+  const double count = a.t.red[1];
+  const double loss = a.t.red[0] / count;
   if (tid == 0) a.losses[step] = loss;
   if (!isfinite(loss)) {
     if (tid == 0) { *a.halt = 1; *a.steps_done = step; }
     return;
   }
-  const hbo_model& m0 = a.init.base;
-  const int dtype = m0.dtype, D = m0.input_dim;
-  for (int d = tid; d < HBO_MAX_FEATURE_DIM; d += nthr) {
-    if (d < a.n_ls) put_elem(s_ls, dtype, d, model_elem(m0.lengthscale, dtype, d));
-    if (d < a.fm) put_elem(s_lin, dtype, d, model_elem(m0.linear_kernel, dtype, d));
-    if (m0.input_warp == HBO_WARP_KUMAR && d < D) {
-      put_elem(s_ka, dtype, d, model_elem(a.init.kumar_a, dtype, d));
-      put_elem(s_kb, dtype, d, model_elem(a.init.kumar_b, dtype, d));
-    }
-  }
-  if (tid == 0) {
-    s_sc[0] = m0.signal_variance; s_sc[1] = m0.noise_variance; s_sc[2] = m0.constant;
-    s_sc[3] = m0.dot_prod_sigma; s_sc[4] = m0.dot_prod_bias; s_sc[5] = m0.linear_bias;
-  }
-  __syncthreads();
+  stage_load(a.t, s, tid, nthr);
   const double b1 = a.b1, b2 = a.b2, c1 = 1 - b1, c2 = 1 - b2;
   const double bias1 = a.bias1[step], bias2 = a.bias2[step];
-  for (int i = tid; i < a.P; i += nthr) {
-    const hbo_train_leaf lf = a.leaves[i];
+  for (int i = tid; i < a.t.P; i += nthr) {
+    const hbo_train_leaf lf = a.t.leaves[i];
     const double x = a.x[i];
-    if (a.trace) a.trace[(size_t)step * a.P + i] = x;
-    const double xr = lf.round_f32 ? (double)(float)x : x;
-    // grad / count, then d warp / d raw (a leaf the model does not read has gradient zero)
-    double g = 0.0;
-    if (a.goff[i] >= 0) g = (a.red[2 + a.goff[i]] / count) * warp_slope(lf.warp, xr);
+    if (a.trace) a.trace[(size_t)step * a.t.P + i] = x;
+    const double g = chained_grad(a.t, lf, i, x, count);
     const double m = b1 * a.am[i] + c1 * g;
     const double v = b2 * a.av[i] + c2 * g * g;
     const double mhat = m / bias1;
     const double vhat = v / bias2;
     const double xn = x - a.lr * mhat / (sqrt(vhat) + a.eps);
     a.am[i] = m; a.av[i] = v; a.x[i] = xn;
-    const double xnr = lf.round_f32 ? (double)(float)xn : xn;
-    double w = warp_value(lf.warp, xnr);
-    if (lf.round_f32) w = (double)(float)w;
-    switch (lf.target) {
-      case HBO_TRAIN_LENGTHSCALE: put_elem(s_ls, dtype, lf.index, w); break;
-      case HBO_TRAIN_SIGNAL_VARIANCE: s_sc[0] = w; break;
-      case HBO_TRAIN_NOISE_VARIANCE: s_sc[1] = w; break;
-      case HBO_TRAIN_CONSTANT: s_sc[2] = w; break;
-      case HBO_TRAIN_DOT_PROD_SIGMA: s_sc[3] = w; break;
-      case HBO_TRAIN_DOT_PROD_BIAS: s_sc[4] = w; break;
-      case HBO_TRAIN_LINEAR_BIAS: s_sc[5] = w; break;
-      case HBO_TRAIN_LINEAR_KERNEL: put_elem(s_lin, dtype, lf.index, w); break;
-      case HBO_TRAIN_MLP_KERNEL: put_elem(a.mlp_w[lf.layer], dtype, lf.index, w); break;
-      case HBO_TRAIN_MLP_BIAS: put_elem(a.mlp_b[lf.layer], dtype, lf.index, w); break;
-      case HBO_TRAIN_KUMAR_A: put_elem(s_ka, dtype, lf.index, w); break;
-      case HBO_TRAIN_KUMAR_B: put_elem(s_kb, dtype, lf.index, w); break;
-      default: break;
-    }
+    stage_put(a.t, s, lf, xn);
+  }
+  stage_store(a.t, s, tid, nthr);
+}
+
+// ---- L-BFGS ----------------------------------------------------------------------------------------------------------------
+static_assert(sizeof(hbo_lbfgs_opts) == sizeof(hbo_lbfgs_opts_ctl) && sizeof(hbo_lbfgs_eval) == sizeof(hbo_lbfgs_eval_ctl), "lbfgs_ctl.h restates hbo.h");
+static_assert(HBO_LBFGS_START == HBO_LBFGS_CTL_START && HBO_LBFGS_MAIN == HBO_LBFGS_CTL_MAIN && HBO_LBFGS_LINE_SEARCH == HBO_LBFGS_CTL_LINE_SEARCH &&
+              HBO_LBFGS_IDLE == HBO_LBFGS_CTL_IDLE && HBO_LBFGS_STEPS_DONE == HBO_LBFGS_CTL_STEPS_DONE, "lbfgs_ctl.h restates hbo.h");
+
+struct LbfgsArgs {
+  TrainDev t;
+  hbo_lbfgs_opts_ctl o;
+  double* state;
+  hbo_lbfgs_eval_ctl* log;
+  double* trace;   // nullable
+};
+
+// the model of the point the state wants evaluated next
+__device__ void lbfgs_write_model(const LbfgsArgs& a, ModelStage& s, int tid, int nthr) {
+  const hbo_lbfgs_view v = hbo_lbfgs_view_of(a.state, a.t.P, a.o.memory);
+  stage_load(a.t, s, tid, nthr);
+  for (int i = tid; i < a.t.P; i += nthr) stage_put(a.t, s, a.t.leaves[i], v.xt[i]);
+  stage_store(a.t, s, tid, nthr);
+}
+// a call that continues a run: the model of the pending point with the device's warps, as every other evaluation of the run got it
+__global__ __launch_bounds__(ADAM_THREADS) void lbfgs_model_kernel(LbfgsArgs a) {
+  __shared__ ModelStage s;
+  lbfgs_write_model(a, s, threadIdx.x, blockDim.x);
+}
+// One evaluation: value and chained gradient of the point evaluated, the state machine, the next model, one log entry.  Once the run
+// has stopped every later slot logs IDLE and returns.
+__global__ __launch_bounds__(ADAM_THREADS) void lbfgs_ctl_kernel(LbfgsArgs a, int slot) {
+  __shared__ ModelStage s;
+  __shared__ double scratch[HBO_LBFGS_PARTIALS];
+  const int tid = threadIdx.x, nthr = blockDim.x, P = a.t.P;
+  const hbo_lbfgs_view v = hbo_lbfgs_view_of(a.state, P, a.o.memory);
+  if (v.hdr[HBO_LBFGS_S_STATUS] != (double)HBO_LBFGS_CTL_RUNNING) {   // (no thread of this launch writes the status before this read)
+    if (tid == 0) { hbo_lbfgs_eval_ctl e; e.kind = HBO_LBFGS_CTL_IDLE; e.iter = (int)v.hdr[HBO_LBFGS_S_ITER]; e.alpha = 0.0; e.value = NAN; a.log[slot] = e; }
+    return;
+  }
+  const double count = a.t.red[1];
+  const double value = a.t.red[0] / count;
+  for (int i = tid; i < P; i += nthr) {
+    const double x = v.xt[i];
+    if (a.trace) a.trace[(size_t)slot * P + i] = x;
+    v.g[i] = chained_grad(a.t, a.t.leaves[i], i, x, count);
   }
   __syncthreads();
-  hbo_model_kumar mk = a.init;
-  mk.base.signal_variance = s_sc[0]; mk.base.noise_variance = s_sc[1]; mk.base.constant = s_sc[2];
-  mk.base.dot_prod_sigma = s_sc[3]; mk.base.dot_prod_bias = s_sc[4]; mk.base.linear_bias = s_sc[5];
-  mk.base.lengthscale = s_ls; mk.base.linear_kernel = s_lin; mk.kumar_a = s_ka; mk.kumar_b = s_kb;
-  model_dev_fill(*a.md, &mk.base, tid, nthr);
+  hbo_lbfgs_eval_ctl ev;
+  hbo_lbfgs_ctl_step(a.state, P, a.o, value, tid, nthr, scratch, &ev);
+  if (tid == 0) a.log[slot] = ev;
+  if (v.hdr[HBO_LBFGS_S_STATUS] == (double)HBO_LBFGS_CTL_RUNNING) lbfgs_write_model(a, s, tid, nthr);
 }
 
 int train_gradient_offset(const hbo_model* m, const hbo_grad_layout& lay, int32_t ka, int32_t kb, const hbo_train_leaf& lf) {
@@ -162,6 +247,108 @@ int train_target_size(const hbo_model* m, const hbo_train_leaf& lf) {
   }
 }
 
+// The checks of model and leaf map that need neither the dataset nor the context; goff[i]: where leaf i's gradient sits in the layout
+int train_check_leaves(hbo_ctx* c, const std::string& fn, const hbo_model* m, const hbo_train_leaf* leaves, int32_t P, hbo_grad_layout& lay,
+                       std::vector<int>& goff) {
+  if (int rc = validate_model(c, m)) return rc;
+  if (m->n_lengthscale > HBO_MAX_FEATURE_DIM) return fail(c, HBO_ERR_ARG, fn + "bad n_lengthscale");
+  if (int rc = hbo_grad_layout_of(m, &lay)) return fail(c, rc, fn + "bad model");
+  int32_t ka = -1, kb = -1;
+  hbo_grad_layout_kumar_of(m, &ka, &kb);
+  goff.resize(P);
+  for (int i = 0; i < P; ++i) {
+    const hbo_train_leaf& lf = leaves[i];
+    if (lf.warp < HBO_TRAIN_WARP_IDENTITY || lf.warp > HBO_TRAIN_WARP_SQUAREPLUS)
+      return fail(c, HBO_ERR_ARG, fn + "leaf " + std::to_string(i) + ": unknown warp");
+    if (lf.target < HBO_TRAIN_NONE || lf.target > HBO_TRAIN_KUMAR_B)
+      return fail(c, HBO_ERR_ARG, fn + "leaf " + std::to_string(i) + ": unknown target");
+    if (lf.round_f32 != 0 && lf.round_f32 != 1) return fail(c, HBO_ERR_ARG, fn + "leaf " + std::to_string(i) + ": round_f32 is 0 or 1");
+    if (lf.index < 0 || lf.index >= train_target_size(m, lf))
+      return fail(c, HBO_ERR_ARG, fn + "leaf " + std::to_string(i) + ": layer / index outside its target");
+    goff[i] = train_gradient_offset(m, lay, ka, kb, lf);
+    if (lf.target != HBO_TRAIN_NONE && (goff[i] < 0 || goff[i] >= lay.total))
+      return fail(c, HBO_ERR_ARG, fn + "leaf " + std::to_string(i) + ": the model does not read its target");
+  }
+  return HBO_OK;
+}
+// the dataset against the model (after the caller has found it non-null)
+int train_check_dataset(hbo_ctx* c, const std::string& fn, const hbo_model* m, const hbo_dataset* ds) {
+  if (ds->ntasks <= 0) return fail(c, HBO_ERR_ARG, fn + "the dataset has no tasks");
+  if (m->dtype != ds->dtype || m->input_dim != ds->D) return fail(c, HBO_ERR_ARG, fn + "model/dataset dtype or input_dim mismatch");
+  return HBO_OK;
+}
+// the context, then the fused regime: every task of the batch in one 128-block, small_fused on, enough LDS
+int train_check_regime(hbo_ctx* c, const std::string& fn, int dtype, int64_t max_n) {
+  if (!c) return fail(c, HBO_ERR_ARG, fn + "context is null");
+  if (max_n > HBO_TILE) return fail(c, HBO_ERR_UNSUPPORTED, fn + "a task of the batch has more than 128 points (only the fused regime runs on the device)");
+  if (!c->opt_small_fused) return fail(c, HBO_ERR_UNSUPPORTED, fn + "small_fused is off (only the fused regime runs on the device)");
+  if (small_eval_lds(dtype) > c->lds_per_block) return fail(c, HBO_ERR_UNSUPPORTED, fn + "the device cannot give the single-workgroup evaluation its LDS");
+  return HBO_OK;
+}
+
+// The head of both loops' upload: [leaves | goff | the starting model's arrays (model dtype)].  `take(bytes)` hands out offsets.
+struct TrainPack { size_t o_leaf, o_goff, o_ls, o_lin, o_ka, o_kb; int n_ls, fm; };
+template <class Take>
+TrainPack train_pack_layout(Take&& take, const hbo_model* m, int32_t P) {
+  TrainPack p;
+  const size_t es = esize(m->dtype);
+  p.n_ls = m->kernel_id == HBO_KERNEL_DOT ? 0 : m->n_lengthscale; p.fm = mean_feature_dim(m);
+  p.o_leaf = take(sizeof(hbo_train_leaf) * P); p.o_goff = take(sizeof(int) * P);
+  p.o_ls = take(es * std::max(p.n_ls, 1)); p.o_lin = take(es * std::max(p.fm, 1));
+  p.o_ka = take(es * m->input_dim); p.o_kb = take(es * m->input_dim);
+  return p;
+}
+void train_pack_fill(unsigned char* h, const TrainPack& p, const hbo_model* m, const hbo_train_leaf* leaves, const std::vector<int>& goff, int32_t P) {
+  const size_t es = esize(m->dtype);
+  memcpy(h + p.o_leaf, leaves, sizeof(hbo_train_leaf) * P); memcpy(h + p.o_goff, goff.data(), sizeof(int) * P);
+  if (p.n_ls) memcpy(h + p.o_ls, m->lengthscale, es * p.n_ls);
+  if (p.fm) memcpy(h + p.o_lin, m->linear_kernel, es * p.fm);
+  if (is_kumar(m)) { memcpy(h + p.o_ka, as_kumar(m)->kumar_a, es * m->input_dim); memcpy(h + p.o_kb, as_kumar(m)->kumar_b, es * m->input_dim); }
+}
+// d: the device copy of the upload; red: the reduction the step kernels read
+void train_dev_set(TrainDev& t, hbo_ctx* c, const hbo_model* m, unsigned char* d, const TrainPack& p, int32_t P, const double* red) {
+  memset(&t, 0, sizeof t);
+  const bool kumar = is_kumar(m);
+  t.leaves = reinterpret_cast<const hbo_train_leaf*>(d + p.o_leaf); t.goff = reinterpret_cast<const int*>(d + p.o_goff); t.P = P;
+  t.red = red;
+  if (kumar) t.init = *as_kumar(m); else t.init.base = *m;
+  t.init.base.lengthscale = d + p.o_ls; t.init.base.linear_kernel = d + p.o_lin;
+  if (kumar) { t.init.kumar_a = d + p.o_ka; t.init.kumar_b = d + p.o_kb; }
+  for (int l = 0; l < HBO_MAX_MLP_LAYERS; ++l) { t.init.base.mlp_kernel[l] = nullptr; t.init.base.mlp_bias[l] = nullptr; }
+  t.n_ls = p.n_ls; t.fm = p.fm;
+  for (int l = 0; l < HBO_MAX_MLP_LAYERS; ++l) { t.mlp_w[l] = c->d_mlp_w[l]; t.mlp_b[l] = c->d_mlp_b[l]; }
+  t.md = c->d_model;
+}
+inline size_t train_align(size_t b) { return (b + 255) & ~(size_t)255; }
+
+int lbfgs_check_opts(hbo_ctx* c, const std::string& fn, const hbo_lbfgs_opts* o) {
+  if (!o) return fail(c, HBO_ERR_ARG, fn + "opts is null");
+  if (o->memory < 1) return fail(c, HBO_ERR_ARG, fn + "opts.memory must be at least 1");
+  if (o->ls_steps < 1) return fail(c, HBO_ERR_ARG, fn + "opts.ls_steps must be at least 1");
+  if (o->max_iters < 1) return fail(c, HBO_ERR_ARG, fn + "opts.max_iters must be at least 1");
+  if (!(o->alpha == o->alpha) || !(o->tol == o->tol) || !(o->c1 == o->c1) || !(o->c2 == o->c2) || !(o->grow == o->grow) || !(o->tau == o->tau))
+    return fail(c, HBO_ERR_ARG, fn + "opts.alpha, tol, c1, c2, grow and tau must be numbers");
+  return HBO_OK;
+}
+hbo_lbfgs_opts_ctl lbfgs_ctl_opts(const hbo_lbfgs_opts* o) {
+  hbo_lbfgs_opts_ctl r;
+  r.memory = o->memory; r.ls_steps = o->ls_steps; r.max_iters = o->max_iters;
+  r.alpha = o->alpha; r.tol = o->tol; r.c1 = o->c1; r.c2 = o->c2; r.grow = o->grow; r.tau = o->tau;
+  return r;
+}
+// A state the control code can index with: all zero (a fresh run), or a header hbo_lbfgs_ctl_step left.  *fresh: the run starts at x.
+int lbfgs_check_state(hbo_ctx* c, const std::string& fn, const double* state, const hbo_lbfgs_opts* o, bool* fresh) {
+  const double* h = state;
+  auto whole = [&](int k, double lo, double hi) { return h[k] >= lo && h[k] <= hi && h[k] == (double)(int64_t)h[k]; };
+  const bool ok = whole(HBO_LBFGS_S_PHASE, 0, 2) && whole(HBO_LBFGS_S_STATUS, 0, HBO_LBFGS_CTL_STEPS_DONE) && whole(HBO_LBFGS_S_ITER, 0, INT_MAX) &&
+                  whole(HBO_LBFGS_S_PROBES, 0, INT_MAX) && whole(HBO_LBFGS_S_NHIST, 0, o->memory) && whole(HBO_LBFGS_S_HEAD, 0, o->memory - 1) &&
+                  whole(HBO_LBFGS_S_EVALS, 0, INT_MAX);
+  *fresh = ok && h[HBO_LBFGS_S_PHASE] == HBO_LBFGS_PHASE_START && h[HBO_LBFGS_S_EVALS] == 0 && h[HBO_LBFGS_S_STATUS] == 0;
+  if (!ok || (h[HBO_LBFGS_S_PHASE] == HBO_LBFGS_PHASE_START && !*fresh && h[HBO_LBFGS_S_STATUS] == 0))
+    return fail(c, HBO_ERR_ARG, fn + "state is neither all zero nor one an earlier call with the same P and memory left");
+  return HBO_OK;
+}
+
 }  // namespace
 
 extern "C" int hbo_train_adam(hbo_ctx* c, const hbo_model* m, hbo_dataset* ds, const hbo_train_leaf* leaves, int32_t P,
@@ -170,39 +357,21 @@ extern "C" int hbo_train_adam(hbo_ctx* c, const hbo_model* m, hbo_dataset* ds, c
                               const int64_t* batch_counts, const int32_t* batch_rows,
                               double* losses, double* x_trace, int32_t* steps_done) {
   // ---- arguments: everything that does not need the context or the dataset first, then the dataset, then the context
-  const char* fn = "hbo_train_adam: ";
-  if (!m) return fail(c, HBO_ERR_ARG, std::string(fn) + "model is null");
-  if (P <= 0) return fail(c, HBO_ERR_ARG, std::string(fn) + "P must be positive");
-  if (steps <= 0) return fail(c, HBO_ERR_ARG, std::string(fn) + "steps must be positive");
+  const std::string fn = "hbo_train_adam: ";
+  if (!m) return fail(c, HBO_ERR_ARG, fn + "model is null");
+  if (P <= 0) return fail(c, HBO_ERR_ARG, fn + "P must be positive");
+  if (steps <= 0) return fail(c, HBO_ERR_ARG, fn + "steps must be positive");
   if (!leaves || !x || !adam_m || !adam_v || !bias1 || !bias2 || !losses || !steps_done)
-    return fail(c, HBO_ERR_ARG, std::string(fn) + "null array argument (leaves, x, adam_m, adam_v, bias1, bias2, losses, steps_done)");
-  if (!batch_counts != !batch_rows) return fail(c, HBO_ERR_ARG, std::string(fn) + "batch_counts and batch_rows are both given or both null");
+    return fail(c, HBO_ERR_ARG, fn + "null array argument (leaves, x, adam_m, adam_v, bias1, bias2, losses, steps_done)");
+  if (!batch_counts != !batch_rows) return fail(c, HBO_ERR_ARG, fn + "batch_counts and batch_rows are both given or both null");
   if (!(lr == lr) || !(b1 == b1) || !(b2 == b2) || !(adam_eps == adam_eps))
-    return fail(c, HBO_ERR_ARG, std::string(fn) + "lr, b1, b2 and adam_eps must be numbers");
-  if (int rc = validate_model(c, m)) return rc;
-  if (m->n_lengthscale > HBO_MAX_FEATURE_DIM) return fail(c, HBO_ERR_ARG, std::string(fn) + "bad n_lengthscale");
+    return fail(c, HBO_ERR_ARG, fn + "lr, b1, b2 and adam_eps must be numbers");
   hbo_grad_layout lay;
-  if (int rc = hbo_grad_layout_of(m, &lay)) return fail(c, rc, std::string(fn) + "bad model");
-  int32_t ka = -1, kb = -1;
-  hbo_grad_layout_kumar_of(m, &ka, &kb);
-  std::vector<int> goff(P);
-  for (int i = 0; i < P; ++i) {
-    const hbo_train_leaf& lf = leaves[i];
-    if (lf.warp < HBO_TRAIN_WARP_IDENTITY || lf.warp > HBO_TRAIN_WARP_SQUAREPLUS)
-      return fail(c, HBO_ERR_ARG, std::string(fn) + "leaf " + std::to_string(i) + ": unknown warp");
-    if (lf.target < HBO_TRAIN_NONE || lf.target > HBO_TRAIN_KUMAR_B)
-      return fail(c, HBO_ERR_ARG, std::string(fn) + "leaf " + std::to_string(i) + ": unknown target");
-    if (lf.round_f32 != 0 && lf.round_f32 != 1) return fail(c, HBO_ERR_ARG, std::string(fn) + "leaf " + std::to_string(i) + ": round_f32 is 0 or 1");
-    if (lf.index < 0 || lf.index >= train_target_size(m, lf))
-      return fail(c, HBO_ERR_ARG, std::string(fn) + "leaf " + std::to_string(i) + ": layer / index outside its target");
-    goff[i] = train_gradient_offset(m, lay, ka, kb, lf);
-    if (lf.target != HBO_TRAIN_NONE && (goff[i] < 0 || goff[i] >= lay.total))
-      return fail(c, HBO_ERR_ARG, std::string(fn) + "leaf " + std::to_string(i) + ": the model does not read its target");
-  }
-  if (!ds) return fail(c, HBO_ERR_ARG, std::string(fn) + "dataset is null");
+  std::vector<int> goff;
+  if (int rc = train_check_leaves(c, fn, m, leaves, P, lay, goff)) return rc;
+  if (!ds) return fail(c, HBO_ERR_ARG, fn + "dataset is null");
+  if (int rc = train_check_dataset(c, fn, m, ds)) return rc;
   const int T = ds->ntasks, D = ds->D, dtype = ds->dtype;
-  if (T <= 0) return fail(c, HBO_ERR_ARG, std::string(fn) + "the dataset has no tasks");
-  if (m->dtype != dtype || m->input_dim != D) return fail(c, HBO_ERR_ARG, std::string(fn) + "model/dataset dtype or input_dim mismatch");
   // the batch: its task sizes (the same every step), the rows a step consumes, and the order hbo_dataset_subsample keeps its tasks in
   std::vector<int64_t> nd(T);
   int64_t nidx = 0;
@@ -211,29 +380,26 @@ extern "C" int hbo_train_adam(hbo_ctx* c, const hbo_model* m, hbo_dataset* ds, c
     nd[k] = n;
     if (!batch_counts) continue;
     const int64_t ck = batch_counts[k];
-    if (ck == 0 || ck > n) return fail(c, HBO_ERR_ARG, std::string(fn) + "batch_counts[k] must be in 1..n_k (or negative: the whole task)");
+    if (ck == 0 || ck > n) return fail(c, HBO_ERR_ARG, fn + "batch_counts[k] must be in 1..n_k (or negative: the whole task)");
     if (ck > 0) { nd[k] = ck; nidx += ck; }
   }
   if (batch_counts) {
     for (int s = 1; s < steps; ++s)
       for (int k = 0; k < T; ++k)
         if ((batch_counts[(size_t)s * T + k] < 0) != (batch_counts[k] < 0) || (batch_counts[k] >= 0 && batch_counts[(size_t)s * T + k] != batch_counts[k]))
-          return fail(c, HBO_ERR_ARG, std::string(fn) + "batch_counts must be the same at every step");
+          return fail(c, HBO_ERR_ARG, fn + "batch_counts must be the same at every step");
     for (int s = 0; s < steps; ++s) {
       int64_t off = (int64_t)s * nidx;
       for (int k = 0; k < T; ++k) {
         if (batch_counts[k] < 0) continue;
         for (int64_t r = 0; r < batch_counts[k]; ++r, ++off)
-          if (batch_rows[off] < 0 || batch_rows[off] >= ds->tasks[k]->n) return fail(c, HBO_ERR_ARG, std::string(fn) + "batch_rows: index out of range");
+          if (batch_rows[off] < 0 || batch_rows[off] >= ds->tasks[k]->n) return fail(c, HBO_ERR_ARG, fn + "batch_rows: index out of range");
       }
     }
   }
-  if (!c) return fail(c, HBO_ERR_ARG, std::string(fn) + "context is null");
   int64_t max_n = 0;
   for (int k = 0; k < T; ++k) max_n = std::max(max_n, nd[k]);
-  if (max_n > HBO_TILE) return fail(c, HBO_ERR_UNSUPPORTED, std::string(fn) + "a task of the batch has more than 128 points (only the fused regime runs on the device)");
-  if (!c->opt_small_fused) return fail(c, HBO_ERR_UNSUPPORTED, std::string(fn) + "small_fused is off (only the fused regime runs on the device)");
-  if (small_eval_lds(dtype) > c->lds_per_block) return fail(c, HBO_ERR_UNSUPPORTED, std::string(fn) + "the device cannot give the single-workgroup evaluation its LDS");
+  if (int rc = train_check_regime(c, fn, dtype, max_n)) return rc;
 
   // ---- step 0: the batch, then everything hbo_objective does, up to the device-side reduction
   HIPCHK(c, hipSetDevice(c->device));
@@ -249,14 +415,10 @@ extern "C" int hbo_train_adam(hbo_ctx* c, const hbo_model* m, hbo_dataset* ds, c
   ShardReq sh{&count0, nullptr};
   ShardOut so;
   if (int rc = objective_local(c, m, batch, HBO_OBJ_NLL, &nll0, nullptr, grad0.data(), &sh, &so)) return rc;
-  if (!so.d_red || so.red_count != 2 + lay.total) return fail(c, HBO_ERR_HIP, std::string(fn) + "no reduction buffer");
+  if (!so.d_red || so.red_count != 2 + lay.total) return fail(c, HBO_ERR_HIP, fn + "no reduction buffer");
 
-  // ---- one upload: [leaves | goff | bias1 | bias2 | initial arrays | gather table | rows | x | m | v | halt, steps_done | losses],
+  // ---- one upload: [leaves | goff | initial arrays | bias1 | bias2 | gather table | rows | x | m | v | halt, steps_done | losses],
   //      then the trace; the copy back takes [x .. trace]
-  auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-  const size_t es = esize(dtype);
-  const int n_ls = m->kernel_id == HBO_KERNEL_DOT ? 0 : m->n_lengthscale, fm = mean_feature_dim(m);
-  const bool kumar = is_kumar(m);
   std::vector<int> perm(T);
   std::iota(perm.begin(), perm.end(), 0);
   std::stable_sort(perm.begin(), perm.end(), [&](int a, int b) { return nd[a] > nd[b]; });   // hbo_dataset_subsample's task order
@@ -272,11 +434,9 @@ extern "C" int hbo_train_adam(hbo_ctx* c, const hbo_model* m, hbo_dataset* ds, c
     }
   }
   size_t off = 0;
-  auto take = [&](size_t b) { const size_t o = off; off += al(b); return o; };
-  const size_t o_leaf = take(sizeof(hbo_train_leaf) * P), o_goff = take(sizeof(int) * P);
+  auto take = [&](size_t b) { const size_t o = off; off += train_align(b); return o; };
+  const TrainPack pack = train_pack_layout(take, m, P);
   const size_t o_b1 = take(sizeof(double) * steps), o_b2 = take(sizeof(double) * steps);
-  const size_t o_ls = take(es * std::max(n_ls, 1)), o_lin = take(es * std::max(fm, 1));
-  const size_t o_ka = take(es * D), o_kb = take(es * D);
   const size_t o_gt = take(sizeof(GatherTask) * std::max<size_t>(gt.size(), 1));
   const size_t o_rows = take(sizeof(int32_t) * std::max<int64_t>(batch_counts ? nidx * steps : 0, 1));
   const size_t o_x = take(sizeof(double) * P), o_m = take(sizeof(double) * P), o_v = take(sizeof(double) * P);
@@ -286,11 +446,8 @@ extern "C" int hbo_train_adam(hbo_ctx* c, const hbo_model* m, hbo_dataset* ds, c
   const size_t total = off;
   std::vector<unsigned char> h(total, 0);
   auto cp = [&](size_t o, const void* src, size_t b) { if (b) memcpy(h.data() + o, src, b); };
-  cp(o_leaf, leaves, sizeof(hbo_train_leaf) * P); cp(o_goff, goff.data(), sizeof(int) * P);
+  train_pack_fill(h.data(), pack, m, leaves, goff, P);
   cp(o_b1, bias1, sizeof(double) * steps); cp(o_b2, bias2, sizeof(double) * steps);
-  if (n_ls) cp(o_ls, m->lengthscale, es * n_ls);
-  if (fm) cp(o_lin, m->linear_kernel, es * fm);
-  if (kumar) { cp(o_ka, as_kumar(m)->kumar_a, es * D); cp(o_kb, as_kumar(m)->kumar_b, es * D); }
   cp(o_gt, gt.data(), sizeof(GatherTask) * gt.size());
   if (batch_counts) cp(o_rows, batch_rows, sizeof(int32_t) * nidx * steps);
   cp(o_x, x, sizeof(double) * P); cp(o_m, adam_m, sizeof(double) * P); cp(o_v, adam_v, sizeof(double) * P);
@@ -303,20 +460,12 @@ extern "C" int hbo_train_adam(hbo_ctx* c, const hbo_model* m, hbo_dataset* ds, c
 
   AdamStepArgs a;
   memset(&a, 0, sizeof a);
-  a.leaves = reinterpret_cast<const hbo_train_leaf*>(d + o_leaf); a.goff = reinterpret_cast<const int*>(d + o_goff); a.P = P;
+  train_dev_set(a.t, c, m, d, pack, P, so.d_red);
   a.x = reinterpret_cast<double*>(d + o_x); a.am = reinterpret_cast<double*>(d + o_m); a.av = reinterpret_cast<double*>(d + o_v);
   a.bias1 = reinterpret_cast<const double*>(d + o_b1); a.bias2 = reinterpret_cast<const double*>(d + o_b2);
   a.lr = lr; a.b1 = b1; a.b2 = b2; a.eps = adam_eps;
-  a.red = so.d_red;
   a.losses = reinterpret_cast<double*>(d + o_loss); a.trace = x_trace ? reinterpret_cast<double*>(d + o_trace) : nullptr;
   a.halt = reinterpret_cast<int*>(d + o_int); a.steps_done = a.halt + 1;
-  if (kumar) a.init = *as_kumar(m); else a.init.base = *m;
-  a.init.base.lengthscale = d + o_ls; a.init.base.linear_kernel = d + o_lin;
-  if (kumar) { a.init.kumar_a = d + o_ka; a.init.kumar_b = d + o_kb; }
-  for (int l = 0; l < HBO_MAX_MLP_LAYERS; ++l) { a.init.base.mlp_kernel[l] = nullptr; a.init.base.mlp_bias[l] = nullptr; }
-  a.n_ls = n_ls; a.fm = fm;
-  for (int l = 0; l < HBO_MAX_MLP_LAYERS; ++l) { a.mlp_w[l] = c->d_mlp_w[l]; a.mlp_b[l] = c->d_mlp_b[l]; }
-  a.md = c->d_model;
 
   const GatherTask* d_gt = reinterpret_cast<const GatherTask*>(d + o_gt);
   const int32_t* d_rows = reinterpret_cast<const int32_t*>(d + o_rows);
@@ -340,5 +489,137 @@ extern "C" int hbo_train_adam(hbo_ctx* c, const hbo_model* m, hbo_dataset* ds, c
   memcpy(losses, h.data() + o_loss, sizeof(double) * steps);
   if (x_trace) memcpy(x_trace, h.data() + o_trace, sizeof(double) * steps * (size_t)P);
   *steps_done = reinterpret_cast<const int*>(h.data() + o_int)[1];
+  return HBO_OK;
+}
+
+extern "C" int64_t hbo_lbfgs_state_doubles(int32_t P, int32_t memory) {
+  if (P <= 0 || memory < 1) return 0;
+  return hbo_lbfgs_state_size(P, memory);
+}
+
+extern "C" int hbo_train_lbfgs(hbo_ctx* c, const hbo_model* m, hbo_dataset* ds, const hbo_train_leaf* leaves, int32_t P,
+                               const hbo_lbfgs_opts* opts, double* x, double* state, int32_t evals, hbo_lbfgs_eval* log,
+                               double* x_trace, double* x_next, int32_t* evals_done, int32_t* status) {
+  // ---- arguments, in hbo_train_adam's order: what needs neither the dataset nor the context, the dataset, the context
+  const std::string fn = "hbo_train_lbfgs: ";
+  if (!m) return fail(c, HBO_ERR_ARG, fn + "model is null");
+  if (P <= 0) return fail(c, HBO_ERR_ARG, fn + "P must be positive");
+  if (evals <= 0) return fail(c, HBO_ERR_ARG, fn + "evals must be positive");
+  if (!leaves || !x || !state || !log || !evals_done || !status)
+    return fail(c, HBO_ERR_ARG, fn + "null array argument (leaves, x, state, log, evals_done, status)");
+  if (int rc = lbfgs_check_opts(c, fn, opts)) return rc;
+  bool fresh = false;
+  if (int rc = lbfgs_check_state(c, fn, state, opts, &fresh)) return rc;
+  hbo_grad_layout lay;
+  std::vector<int> goff;
+  if (int rc = train_check_leaves(c, fn, m, leaves, P, lay, goff)) return rc;
+  if (!ds) return fail(c, HBO_ERR_ARG, fn + "dataset is null");
+  if (int rc = train_check_dataset(c, fn, m, ds)) return rc;
+  const int T = ds->ntasks, dtype = ds->dtype;
+  int64_t max_n = 0;
+  for (int k = 0; k < T; ++k) max_n = std::max<int64_t>(max_n, ds->tasks[k]->n);
+  if (int rc = train_check_regime(c, fn, dtype, max_n)) return rc;
+
+  const int64_t ns = hbo_lbfgs_state_size(P, opts->memory);
+  hbo_lbfgs_view hv = hbo_lbfgs_view_of(state, P, opts->memory);
+  *evals_done = 0;
+  *status = (int32_t)state[HBO_LBFGS_S_STATUS];
+  if (*status != HBO_LBFGS_RUNNING) {   // a run that has stopped: nothing to queue
+    memcpy(x, hv.x, sizeof(double) * P);
+    if (x_next) memcpy(x_next, hv.xt, sizeof(double) * P);
+    return HBO_OK;
+  }
+  if (fresh) hbo_lbfgs_state_start(state, P, opts->memory, x);
+
+  // ---- the first evaluation: everything hbo_objective does, up to the device-side reduction
+  HIPCHK(c, hipSetDevice(c->device));
+  hipStream_t st = c->stream;
+  std::vector<double> grad0(std::max(lay.total, 1));
+  double nll0 = 0, count0 = 0;
+  ShardReq sh{&count0, nullptr};
+  ShardOut so;
+  if (int rc = objective_local(c, m, ds, HBO_OBJ_NLL, &nll0, nullptr, grad0.data(), &sh, &so)) return rc;
+  if (!so.d_red || so.red_count != 2 + lay.total) return fail(c, HBO_ERR_HIP, fn + "no reduction buffer");
+
+  // ---- one upload: [leaves | goff | initial arrays | state], then log and trace; the copy back takes [state .. trace]
+  size_t off = 0;
+  auto take = [&](size_t b) { const size_t o = off; off += train_align(b); return o; };
+  const TrainPack pack = train_pack_layout(take, m, P);
+  const size_t o_state = take(sizeof(double) * ns);
+  const size_t up_bytes = off;
+  const size_t o_log = take(sizeof(hbo_lbfgs_eval) * evals);
+  const size_t o_trace = take(x_trace ? sizeof(double) * evals * (size_t)P : 0);
+  const size_t total = off;
+  std::vector<unsigned char> h(total, 0);
+  train_pack_fill(h.data(), pack, m, leaves, goff, P);
+  memcpy(h.data() + o_state, state, sizeof(double) * ns);
+  unsigned char* d = static_cast<unsigned char*>(ws_get(c, WS_TRAIN, total));
+  if (!d) return HBO_ERR_HIP;
+  HIPCHK(c, hipMemcpyAsync(d, h.data(), up_bytes, hipMemcpyHostToDevice, st));
+
+  LbfgsArgs a;
+  memset(&a, 0, sizeof a);
+  train_dev_set(a.t, c, m, d, pack, P, so.d_red);
+  a.o = lbfgs_ctl_opts(opts);
+  a.state = reinterpret_cast<double*>(d + o_state);
+  a.log = reinterpret_cast<hbo_lbfgs_eval_ctl*>(d + o_log);
+  a.trace = x_trace ? reinterpret_cast<double*>(d + o_trace) : nullptr;
+
+  auto enqueue_eval = [&]() -> int {
+    enqueue_fused_forward(c, m, ds, max_n, so.out_stride, true);
+    if (int rc = enqueue_backward(c, m, ds, max_n, OBJ_NLL, true)) return rc;
+    launch_shard_reduce(ds->d_nll, ds->d_gradout, ds->d_info, T, so.out_stride, so.d_map, ds->d_mlpgrad, so.d_map + so.out_stride,
+                        so.nseg, so.d_red, so.red_count, st);
+    return HBO_OK;
+  };
+  if (!fresh) {
+    // A continued run: the pending point's model again with the device's warps (objective_local evaluated the caller's, whose host
+    // warps may differ in the last bit), so that a run gives the same bits however it is cut into calls.
+    { ProfScope ps(c, "lbfgs_ctl", 1);
+      hipLaunchKernelGGL(lbfgs_model_kernel, dim3(1), dim3(ADAM_THREADS), 0, st, a); }
+    if (int rc = enqueue_eval()) return rc;
+  }
+  for (int s = 0; s < evals; ++s) {
+    if (s > 0) { if (int rc = enqueue_eval()) return rc; }
+    { ProfScope ps(c, "lbfgs_ctl", 1);
+      hipLaunchKernelGGL(lbfgs_ctl_kernel, dim3(1), dim3(ADAM_THREADS), 0, st, a, s); }
+  }
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipMemcpyAsync(h.data() + o_state, d + o_state, total - o_state, hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipStreamSynchronize(st));
+  HIPCHK(c, hipGetLastError());
+  prof_collect(c);
+  memcpy(state, h.data() + o_state, sizeof(double) * ns);
+  memcpy(log, h.data() + o_log, sizeof(hbo_lbfgs_eval) * evals);
+  if (x_trace) memcpy(x_trace, h.data() + o_trace, sizeof(double) * evals * (size_t)P);
+  memcpy(x, hv.x, sizeof(double) * P);
+  if (x_next) memcpy(x_next, hv.xt, sizeof(double) * P);
+  int done = 0;
+  while (done < evals && log[done].kind != HBO_LBFGS_IDLE) ++done;
+  *evals_done = done;
+  *status = (int32_t)state[HBO_LBFGS_S_STATUS];
+  return HBO_OK;
+}
+
+// include/hbo_tune.h (TEST HOOK): the control code of lbfgs_ctl.h on the host, one thread, for one evaluation
+extern "C" int hbo_probe_lbfgs_ctl(double* state, int32_t P, const hbo_lbfgs_opts* opts, const double* x0, double value, const double* grad,
+                                   double* x_next, double* x_iter, hbo_lbfgs_eval* eval, int32_t* status) {
+  const std::string fn = "hbo_probe_lbfgs_ctl: ";
+  if (P <= 0) return fail(nullptr, HBO_ERR_ARG, fn + "P must be positive");
+  if (!state || !grad || !x_next || !eval || !status) return fail(nullptr, HBO_ERR_ARG, fn + "null argument (state, grad, x_next, eval, status)");
+  if (int rc = lbfgs_check_opts(nullptr, fn, opts)) return rc;
+  bool fresh = false;
+  if (int rc = lbfgs_check_state(nullptr, fn, state, opts, &fresh)) return rc;
+  if (fresh && !x0) return fail(nullptr, HBO_ERR_ARG, fn + "an all-zero state needs x0");
+  if (fresh) hbo_lbfgs_state_start(state, P, opts->memory, x0);
+  const hbo_lbfgs_view v = hbo_lbfgs_view_of(state, P, opts->memory);
+  memcpy(v.g, grad, sizeof(double) * P);
+  double scratch[HBO_LBFGS_PARTIALS];
+  hbo_lbfgs_eval_ctl ev;
+  hbo_lbfgs_ctl_step(state, P, lbfgs_ctl_opts(opts), value, 0, 1, scratch, &ev);
+  eval->kind = ev.kind; eval->iter = ev.iter; eval->alpha = ev.alpha; eval->value = ev.value;
+  memcpy(x_next, v.xt, sizeof(double) * P);
+  if (x_iter) memcpy(x_iter, v.x, sizeof(double) * P);
+  *status = (int32_t)state[HBO_LBFGS_S_STATUS];
   return HBO_OK;
 }

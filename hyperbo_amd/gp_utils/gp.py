@@ -172,6 +172,8 @@ def infer_parameters(mean_func, cov_func, init_params, dataset, warp_func=None,
         params.model = unflatten(x)
       if hasattr(dev, 'close'):
         dev.close()
+  elif method == 'lbfgs' and params.config.get('lbfgs_on_device', False):
+    return _infer_lbfgs_on_device(mean_func, cov_func, params, dataset, warp_func, objective, rng, callback)
   elif method == 'lbfgs':
     batch = next(data_utils.sub_sample_dataset_iterator(rng, dataset, batch_size))   # gp.py:102-107
     dev = make_device(batch)
@@ -190,8 +192,8 @@ ADAM_SEGMENT = 256   # Adam steps per hbo_train_adam call
 
 
 def _adam_on_device_unmet(mean_func, cov_func, params, dataset, warp_func, objective):
-  """The first condition that keeps config['adam_on_device'] from running (a message), or None.  Host-side checks only: the
-  library adds its own (small_fused off, the device's LDS) when it is called."""
+  """The first condition that keeps config['adam_on_device'] (and config['lbfgs_on_device'], which has the same rules) from running
+  (a message), or None.  Host-side checks only: the library adds its own (small_fused off, the device's LDS) when it is called."""
   if isinstance(objective, str):
     objective = getattr(obj, objective, objective)
   if objective is not obj.neg_log_marginal_likelihood:
@@ -287,6 +289,70 @@ def _infer_adam_on_device(mean_func, cov_func, params, dataset, warp_func, objec
     if np.isfinite(final_loss):
       params.model = unflatten(x)
   finally:
+    full.close()
+  params.cache = {}
+  return params
+
+
+LBFGS_SEGMENT = 32   # evaluations per hbo_train_lbfgs call (profiles/train_device.md: the slots queued behind a stop are wasted, 128 already loses to the host)
+
+
+def _infer_lbfgs_on_device(mean_func, cov_func, params, dataset, warp_func, objective, rng, callback):
+  """infer_parameters(method='lbfgs') with config['lbfgs_on_device'] = True: the evaluations of lbfgs.lbfgs (start, main steps, line
+  search probes) run in segments of LBFGS_SEGMENT on the device (hbo_train_lbfgs: evaluation, reduction and the L-BFGS control
+  workgroup queued back to back, one synchronisation per segment).  The same single sub-sample, options, decisions, parameters and
+  callbacks as the host branch; a segment's callbacks are replayed after it.  Python evaluates nothing (no DeviceDataset.evaluate call).
+  A dict under config['lbfgs_eval_log'] receives 'evals', the (kind, iter, alpha, value) of every evaluation (hbo_lbfgs_eval), and
+  'status' (hbo_lbfgs_status).
+  The rules of adam_on_device apply: anything else raises ValueError naming the first unmet condition."""
+  from hyperbo_amd.basics import data_utils, lbfgs as lbfgs_lib
+  why = _adam_on_device_unmet(mean_func, cov_func, params, dataset, warp_func, objective)
+  if why is not None:
+    raise ValueError(f'lbfgs_on_device: {why}.')
+  config = params.config
+  x, unflatten = lbfgs_lib.tree_flatten(params.model)
+  template = params.model
+  opts = nat.LbfgsOpts(memory=10, ls_steps=50, max_iters=int(config['max_training_step']), alpha=float(config.get('alpha', 1.0)),
+                       tol=1e-6, c1=1e-4, c2=0.9, grow=2.1, tau=0.5)   # lbfgs.lbfgs / backtracking_linesearch defaults
+  full = obj.DeviceDataset(dataset)
+  ctx = full.ctx
+  batch = None
+  try:
+    if full.num_tasks == 0:
+      raise ValueError('lbfgs_on_device: the dataset has no task the NLL includes.')
+    batch = full.subsample(next(data_utils.sub_sample_index_iterator(rng, dataset, config['batch_size'])))   # gp.py:102-107
+    state = np.zeros(nat.lib().hbo_lbfgs_state_doubles(x.size, opts.memory), dtype=np.float64)
+    x_next = x.copy()
+    status = nat.LBFGS_RUNNING
+    log_all = []
+    while status == nat.LBFGS_RUNNING:
+      k = int(LBFGS_SEGMENT)
+      bm = _model.BuiltModel(mean_func, cov_func, GPParams(model=unflatten(x_next), config=config), warp_func, batch.dtype, batch.input_dim)
+      leaves, P = _model.train_leaf_map(bm, template)
+      if P != x.size:
+        raise ValueError(f'lbfgs_on_device: the leaf map has {P} entries for {x.size} parameters')
+      log = (nat.LbfgsEval * k)()
+      trace = np.empty((k, x.size), dtype=np.float64)
+      done, st = C.c_int32(0), C.c_int32(0)
+      rc = nat.lib().hbo_train_lbfgs(ctx.handle, bm.ref(), batch._h, leaves, P, C.byref(opts), nat.ptr(x), nat.ptr(state), k, log,
+                                     nat.ptr(trace), nat.ptr(x_next), C.byref(done), C.byref(st))
+      if rc == nat.HBO_ERR_UNSUPPORTED:
+        raise ValueError('lbfgs_on_device: ' + (nat.lib().hbo_last_error(ctx.handle) or b'').decode())
+      ctx.check(rc, allow_not_pd=False)
+      status = st.value
+      for j in range(done.value):
+        e = log[j]
+        log_all.append((e.kind, e.iter, e.alpha, e.value))
+        # lbfgs() calls back at the start and at every main step it does not leave as converged
+        recorded = e.kind == nat.LBFGS_START or (e.kind == nat.LBFGS_MAIN and not (status == nat.LBFGS_CONVERGED and j == done.value - 1))
+        if recorded and callback:
+          callback(step=e.iter, model_params=unflatten(trace[j]), loss=float(e.value))
+    params.model = unflatten(x)
+    if isinstance(config.get('lbfgs_eval_log'), dict):   # a dict the caller left in config: every evaluation, and how the run ended
+      config['lbfgs_eval_log'].update(evals=log_all, status=status)
+  finally:
+    if batch is not None:
+      batch.close()
     full.close()
   params.cache = {}
   return params

@@ -363,6 +363,57 @@ int hbo_train_adam(hbo_ctx* ctx, const hbo_model* model, hbo_dataset* ds, const 
                    const int64_t* batch_counts, const int32_t* batch_rows,
                    double* losses, double* x_trace, int32_t* steps_done);
 
+/* ---- gp.py:53-195 infer_parameters(method='lbfgs'): the evaluations of basics/lbfgs.py queued on the device ----------------
+ * L-BFGS evaluates one batch over and over: at the start, once per main step, and up to ls_steps times per line search.  One call
+ * queues `evals` evaluations on the stream with no host wait between them; each is the launches of hbo_train_adam's resident batch
+ * (single-workgroup evaluation with its MLP / Kumaraswamy passes -> reduction of [nll_sum, T, grad]) followed by one control
+ * workgroup.  That workgroup chains [nll_sum / T, grad / T] through the leaves' warps (as the Adam step does, round_f32 included),
+ * runs the state machine of lbfgs.lbfgs / backtracking_linesearch / lbfgs_descent_dir_nocedal on it (csrc/lbfgs_ctl.h: every decision
+ * as the host takes it, NaN comparisons included; dot products in one fixed order, no fused multiply-adds, no atomics), writes the
+ * warped model of the next point where the following evaluation reads it, and appends one entry to the log.  One upload, one copy back
+ * and one synchronisation per call.
+ *
+ * leaves, P: as hbo_train_adam.  opts: lbfgs()'s memory, ls_steps, steps (max_iters), alpha, tol, and the line search's c1, c2, growth
+ * factor (2.1) and ls_tau.
+ *   state [hbo_lbfgs_state_doubles(P, memory)], in / out: the whole run -- iterate, pending point, old_x, old_g, direction, the
+ *     ring of s / y pairs, alpha, cur_val, g.d, phase and counters.  All zero: the run starts at x.  Otherwise the run continues
+ *     where the call that left the state stopped (same P and memory), and x is not read.
+ *   model: the family, and the warped fields of the point evaluated first -- x for a fresh state, the x_next of the previous call
+ *     otherwise.  A continued run evaluates that point again with the model the device derives from the state (the device's own
+ *     warps), so a run gives the same bits however it is cut into calls.
+ *   x [P]: in, the start (fresh state); out, the iterate lbfgs() would return if it stopped now.
+ *   log [evals]: one entry per queued evaluation, in order.  kind START (the first evaluation; iter 0), MAIN (the evaluation that
+ *     opens main step `iter`, 1..max_iters) or LINE_SEARCH (a probe of step `iter`'s search at x + alpha d); value = nll_sum / T there.
+ *     START and MAIN entries are lbfgs()'s callback points (step = iter, loss = value, the parameters = the point evaluated), with
+ *     one exception: the MAIN entry at which the run stops with CONVERGED (lbfgs() leaves its loop before the callback).  Once a stop
+ *     status is set every later slot is IDLE: its evaluation ran on the last model and was ignored.
+ *   x_trace (nullable) [evals][P]: the point of each evaluation (rows of IDLE slots are not written).
+ *   x_next (nullable) [P]: the point the next call evaluates first.
+ *   *evals_done: entries of the log before the first IDLE one.  *status: hbo_lbfgs_status after the last of them.
+ * A state that has already stopped returns at once with *evals_done = 0.  L-BFGS never fails on NaN: a NaN value at the start runs
+ * ls_steps probes and stops with NO_PROGRESS, x unchanged.
+ * NLL only, and only the fused regime (every task n <= 128, small_fused on, enough LDS; otherwise HBO_ERR_UNSUPPORTED).  The arguments
+ * are checked before any HIP call (HBO_ERR_ARG, hbo_last_error names the argument): those of hbo_train_adam, and memory < 1,
+ * ls_steps < 1, max_iters < 1, options that are not numbers, null state / log / evals_done / status, a state that is neither all zero
+ * nor one an earlier call left. */
+enum hbo_lbfgs_kind { HBO_LBFGS_START = 0, HBO_LBFGS_MAIN = 1, HBO_LBFGS_LINE_SEARCH = 2, HBO_LBFGS_IDLE = 3 };
+enum hbo_lbfgs_status {
+  HBO_LBFGS_RUNNING = 0, HBO_LBFGS_CONVERGED_AT_START = 1, HBO_LBFGS_CONVERGED = 2, HBO_LBFGS_NO_PROGRESS = 3, HBO_LBFGS_INSTABILITY = 4,
+  HBO_LBFGS_STEPS_DONE = 5
+};
+typedef struct hbo_lbfgs_opts {
+  int32_t memory, ls_steps, max_iters;
+  double alpha, tol, c1, c2, grow, tau;
+} hbo_lbfgs_opts;
+typedef struct hbo_lbfgs_eval {
+  int32_t kind, iter;
+  double alpha, value;
+} hbo_lbfgs_eval;
+int64_t hbo_lbfgs_state_doubles(int32_t P, int32_t memory);
+int hbo_train_lbfgs(hbo_ctx* ctx, const hbo_model* model, hbo_dataset* ds, const hbo_train_leaf* leaves, int32_t P,
+                    const hbo_lbfgs_opts* opts, double* x, double* state, int32_t evals, hbo_lbfgs_eval* log, double* x_trace,
+                    double* x_next, int32_t* evals_done, int32_t* status);
+
 #ifdef __cplusplus
 }
 #endif

@@ -77,6 +77,13 @@ int hbo_mfma_peak_probe(hbo_ctx* ctx, double ms, double* tflops_out);
  * colsq_out[i, j] = sum over the rows r of 128-row block i of V[r, j]^2.  HBO_ERR_ARG on a bad argument, before any device call. */
 int hbo_probe_post_product(hbo_ctx* ctx, int form, const float* W, int64_t n, const float* Kxq, int64_t M, double k_bound,
                            int use_counter, float* colsq_out);
+/* TEST HOOK: the control code of hbo_train_lbfgs (csrc/lbfgs_ctl.h, the text its control kernel compiles) on the host, one thread,
+ * for one evaluation; no context, no device.  `value` and `grad` [P] (raw space) belong to the point the state wants evaluated: x0 for
+ * an all-zero state (x0 is then required), the x_next of the previous call otherwise.  x_next [P]: the point to evaluate next;
+ * x_iter (nullable) [P]: the iterate lbfgs() would return now; *eval: the log entry of this evaluation; *status: hbo_lbfgs_status.
+ * HBO_ERR_ARG (hbo_last_error(NULL)) on a bad argument. */
+int hbo_probe_lbfgs_ctl(double* state, int32_t P, const hbo_lbfgs_opts* opts, const double* x0, double value, const double* grad,
+                        double* x_next, double* x_iter, hbo_lbfgs_eval* eval, int32_t* status);
 #ifdef __cplusplus
 }
 #endif

@@ -3,9 +3,13 @@ by side: se_constant and matern52_mlp_linear_mlp (24 tasks x 100 points, D = 4, 
 se_constant_resampled_400_to_100 (24 x 400 points, batch_size 100: a fresh batch per step).  A host clock around complete train()
 calls (each ends in a synchronisation); one warm-up call per setting, then `reps` interleaved rounds, median.
 
-  python tools/train_device_time.py [steps=200] [reps=5] [only=<workload>] [device_only]
+  python tools/train_device_time.py [steps=200] [reps=5] [only=<workload>] [device_only] [method=adam|lbfgs] [segment=]
 
-`device_only` with `only=` runs one device-loop train() and nothing else: the run to put under rocprofv3 --kernel-trace --stats."""
+`device_only` with `only=` runs one device-loop train() and nothing else: the run to put under rocprofv3 --kernel-trace --stats.
+
+`method=lbfgs` (steps defaults to 30): the same three workloads under L-BFGS, host driver vs config['lbfgs_on_device']
+(hbo_train_lbfgs); ms per train() call and ms per evaluation, the evaluations counted from the device loop's log and, for the host
+driver, around DeviceDataset.evaluate.  The resampled workload draws its one sub-sample per call.  `segment=` overrides gp.LBFGS_SEGMENT."""
 import json
 import os
 import sys
@@ -59,8 +63,66 @@ def run(w, steps, on_device, key):
   return (time.perf_counter() - t0) / steps * 1e3
 
 
+def run_lbfgs(w, steps, on_device, key):
+  """(ms per train() call, evaluations made)."""
+  data, mk, cov, mu, bs, feats = w
+  config = {'method': 'lbfgs', 'batch_size': bs, 'max_training_step': steps, 'objective': objectives.nll, 'mlp_features': feats}
+  if on_device:
+    config['lbfgs_on_device'] = True
+    config['lbfgs_eval_log'] = {}
+  g = gp.GP(data, mu, cov, defs.GPParams(model=mk(), config=config), utils.DEFAULT_WARP_FUNC)
+  calls = [0]
+  orig = objectives.DeviceDataset.evaluate
+
+  def counting(self, *a, **k):
+    calls[0] += 1
+    return orig(self, *a, **k)
+  objectives.DeviceDataset.evaluate = counting
+  try:
+    t0 = time.perf_counter()
+    g.train(key=key)
+    ms = (time.perf_counter() - t0) * 1e3
+  finally:
+    objectives.DeviceDataset.evaluate = orig
+  return ms, (len(config['lbfgs_eval_log']['evals']) if on_device else calls[0])
+
+
+def main_lbfgs(args):
+  steps, reps = int(args.get('steps', 30)), int(args.get('reps', 5))
+  if 'segment' in args:   # evaluations per hbo_train_lbfgs call, to compare against the default
+    gp.LBFGS_SEGMENT = int(args['segment'])
+  ws = workloads()
+  names = [args['only']] if 'only' in args else list(ws)
+  if 'device_only' in args:
+    ms, n = run_lbfgs(ws[names[0]], steps, True, 0)
+    print(json.dumps({names[0]: {'ms_per_call': ms, 'evaluations': n}}))
+    return
+  out = {}
+  for name in names:
+    for dev in (False, True):
+      run_lbfgs(ws[name], steps, dev, 0)   # warm-up
+    t = {False: [], True: []}
+    for r in range(reps):
+      for dev in (False, True):
+        t[dev].append(run_lbfgs(ws[name], steps, dev, r + 1))
+    res = {}
+    for dev, label in ((False, 'host'), (True, 'device')):
+      ms = [v for v, _ in t[dev]]
+      per = [v / n for v, n in t[dev]]
+      res[label + '_ms_per_call'] = round(float(np.median(ms)), 4)
+      res[label + '_ms_per_eval'] = round(float(np.median(per)), 4)
+      res[label + '_all_ms'] = [round(v, 4) for v in ms]
+      res[label + '_evals'] = [n for _, n in t[dev]]
+    res['device_faster'] = bool(max(res['device_all_ms']) < min(res['host_all_ms']))   # all five rounds below all five host rounds
+    out[name] = res
+    print(name, json.dumps(res), flush=True)
+  print(json.dumps({'method': 'lbfgs', 'steps': steps, 'reps': reps, 'segment': gp.LBFGS_SEGMENT, 'results': out}))
+
+
 def main():
   args = dict(a.split('=', 1) if '=' in a else (a, '1') for a in sys.argv[1:])
+  if args.get('method', 'adam') == 'lbfgs':
+    return main_lbfgs(args)
   steps, reps = int(args.get('steps', 200)), int(args.get('reps', 5))
   ws = workloads()
   names = [args['only']] if 'only' in args else list(ws)
