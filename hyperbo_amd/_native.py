@@ -119,6 +119,8 @@ SIGNATURES = {
     'hbo_cache_append': (C.c_int, [_P, C.POINTER(Model), _P, _P, C.c_int64, _P]),
     'hbo_acq_grad': (C.c_int, [_P, C.POINTER(Model), _P, _P, C.c_int64, C.c_int, C.c_double, C.c_double, C.c_double,
                                _P, C.POINTER(C.c_double)]),
+    'hbo_acq_grad_samples': (C.c_int, [_P, _P, C.c_int32, C.POINTER(_P), _P, C.c_int64, C.c_int, C.POINTER(C.c_double),
+                                       C.POINTER(C.c_double), C.c_double, _P, C.POINTER(C.c_double)]),
     'hbo_predict': (C.c_int, [_P, C.POINTER(Model), _P, _P, C.c_int64, C.c_int, _P, _P]),
     'hbo_acq': (C.c_int, [_P, C.POINTER(Model), _P, _P, C.c_int64, C.c_int, C.c_double, C.c_double,
                           C.c_double, _P]),
@@ -216,7 +218,7 @@ class Context:
       lib().hbo_ctx_destroy(self._h)
       self._h = _P()
 
-  # (the routing switch 'spectral' of hbo_set_option is documented on its own in include/hbo.h, not among these six tuning options;
+  # (the routing switches 'spectral' and 'acq_fused' of hbo_set_option are documented on their own in include/hbo.h, not among these six tuning options;
   #  set_option reaches it through hbo_tune, which passes every name it does not know to hbo_set_option)
   PUBLIC_OPTIONS = ('potrf_group', 'lookahead', 'small_nblk', 'pool_cap_mb', 'post_chunk', 'bf16x3')
 
@@ -256,6 +258,12 @@ def spectral_enabled():
   """True when the default context has the option 'spectral' set (include/hbo.h): the reference's SVD call sites then run on
   hbo_sym_eig / hbo_nll_spectral.  Without a default context nothing can have set it (and nothing touches the GPU)."""
   return _default_ctx is not None and bool(_default_ctx._h) and _default_ctx.get_option('spectral') == 1
+
+
+def acq_fused_enabled():
+  """True when the default context has the option 'acq_fused' set (include/hbo.h): value_and_grad calls over small caches then
+  run as one hbo_acq_grad_samples launch.  Without a default context nothing can have set it (and nothing touches the GPU)."""
+  return _default_ctx is not None and bool(_default_ctx._h) and _default_ctx.get_option('acq_fused') == 1
 
 
 def default_context():

@@ -189,10 +189,52 @@ def _hgp_sample_caches(model, sub_dataset_key, samples, dtype):
   return handles
 
 
+ACQ_FUSED_MAX_N = 128   # hbo_acq_grad_samples: one 128-block per cache
+
+
+def _acq_fused_unmet(model, sub_dataset_key, n_samples=1, n_kept=None, enabled=None):
+  """The first condition that keeps a value_and_grad call from the one-launch path (hbo_acq_grad_samples, context option
+  'acq_fused'), as a message, or None.  Host-side checks only.  n_kept: factor handles at hand for the n_samples parameter samples
+  (None: not known yet); enabled: the option's value (None: read from the default context)."""
+  if not (nat.acq_fused_enabled() if enabled is None else enabled):
+    return "the context option 'acq_fused' is off"
+  if not model.has_observations(sub_dataset_key):
+    return 'the sub-dataset has no observations (the prior branch)'
+  n = np.shape(model.dataset[sub_dataset_key].x)[0]
+  if n > ACQ_FUSED_MAX_N:
+    return f'the sub-dataset has {n} > {ACQ_FUSED_MAX_N} observations'
+  if getattr(model.cov_func, 'uses_mlp', False):
+    return 'the kernel runs on an MLP basis'
+  if getattr(model.mean_func, 'mean_id', None) == nat.MEAN_LINEAR_MLP:
+    return 'the mean is linear_mlp'
+  if getattr(model.cov_func, 'uses_kumar', False):
+    return 'the kernel is input-warped (Kumaraswamy)'
+  if n_kept is not None and n_kept < n_samples:
+    return f'only {n_kept} of the {n_samples} per-sample factors fit the device budget'
+  return None
+
+
+def _fused_value_and_grad(built, handles, noises, xq, acq_id, acfun_param, scale):
+  """((S, M, 1) values in the model dtype, (S, M, D) gradients in float64) of S models over their finished factors: one
+  hbo_acq_grad_samples call -- one upload, one launch, one copy back."""
+  s_count, (nq, d) = len(built), xq.shape
+  ctx = handles[0].ctx
+  structs = (nat.Model * s_count)(*[b.struct for b in built])
+  caches = (nat.C.c_void_p * s_count)(*[h.handle for h in handles])
+  prm = (nat.C.c_double * s_count)(*([float(acfun_param)] * s_count))
+  nse = (nat.C.c_double * s_count)(*[float(v) for v in noises])
+  out = np.empty((s_count, nq, 1), dtype=xq.dtype)
+  g = np.empty((s_count, nq, d), dtype=np.float64)
+  ctx.check(nat.lib().hbo_acq_grad_samples(ctx.handle, structs, s_count, caches, nat.ptr(xq), nq, int(acq_id), prm, nse, float(scale),
+                                           nat.ptr(out), g.ctypes.data_as(nat.C.POINTER(nat.C.c_double))))
+  return out, g
+
+
 def _hgp_value_and_grad(model, sub_dataset_key, x_queries, acq_id, acfun_param):
   """Mean over the parameter samples of (acquisition, d acquisition / d x): what jax differentiates when bayesopt() runs on an
   HGP (acfun.py:72-82 under bayesopt.py:116-125).  One hbo_acq_grad per sample against that sample's cached factor (samples
-  beyond the cache budget: factorised, used and released on the spot)."""
+  beyond the cache budget: factorised, used and released on the spot) -- or, with the context option 'acq_fused' on and a model
+  `_acq_fused_unmet` has nothing against, one hbo_acq_grad_samples call over all of them."""
   from hyperbo_amd.basics import linalg
   if getattr(model.cov_func, 'uses_kumar', False):   # (as hbo_acq_samples: HGP over Kumaraswamy kernels is out of scope)
     raise nat.HboError(nat.HBO_ERR_UNSUPPORTED, 'HGP acquisition over a Kumaraswamy kernel is not supported')
@@ -209,6 +251,14 @@ def _hgp_value_and_grad(model, sub_dataset_key, x_queries, acq_id, acfun_param):
   built, noises = _sample_models(model, samples, dtype)
   handles = _hgp_sample_caches(model, sub_dataset_key, samples, dtype) if has_obs else []
   _, scale = model.predict_noise_and_scale(True, True)
+  if _acq_fused_unmet(model, sub_dataset_key, len(samples), len(handles)) is None:
+    # option 'acq_fused': every sample's pass in ONE launch over the kept factors; the mean as the loop below takes it
+    outs, gs = _fused_value_and_grad(built, handles, noises, xq, acq_id, acfun_param, scale)
+    for out, g in zip(outs, gs):
+      val += out
+      grad += g
+    model.update_model_params(samples[-1])
+    return (val / len(samples)).astype(dtype), grad / len(samples)
   out = np.empty((nq, 1), dtype=dtype)
   g = np.zeros((nq, model.input_dim), dtype=np.float64)
   ctx = nat.default_context()
@@ -287,6 +337,9 @@ def acfun_wrapper(acfun_sub, acfun_callback_default):
     add_noise, scale = model.predict_noise_and_scale(True, True)
     bm = _model.BuiltModel(model.mean_func, model.cov_func, model.params, model.warp_func, dtype,
                            model.input_dim)
+    if _acq_fused_unmet(model, sub_dataset_key) is None:   # option 'acq_fused': the one-launch path with S = 1
+      outs, gs = _fused_value_and_grad([bm], [handle], [add_noise], xq, _NATIVE_ID[acfun_sub], acfun_param, scale)
+      return outs[0], gs[0]
     ctx = handle.ctx if handle is not None else nat.default_context()
     ctx.check(nat.lib().hbo_acq_grad(ctx.handle, bm.ref(), handle.handle if handle is not None else None,
                                      nat.ptr(xq), xq.shape[0], _NATIVE_ID[acfun_sub], float(acfun_param),

@@ -86,7 +86,7 @@ extern "C" int hbo_ctx_destroy(hbo_ctx* c) {
   delete c;
   return HBO_OK;
 }
-// The seven options of the boundary (include/hbo.h).
+// The eight options of the boundary (include/hbo.h).
 extern "C" int hbo_set_option(hbo_ctx* c, const char* name, int64_t value) {
   if (!c || !name) return HBO_ERR_ARG;
   if (!strcmp(name, "potrf_group")) { if (value < 0 || value > 16) return fail(c, HBO_ERR_ARG, "potrf_group in 0..16 (0: auto)"); c->opt_group = (int)value; return HBO_OK; }
@@ -104,6 +104,7 @@ extern "C" int hbo_set_option(hbo_ctx* c, const char* name, int64_t value) {
   if (!strcmp(name, "post_chunk")) { if (value < 128 || value > 65536) return fail(c, HBO_ERR_ARG, "post_chunk in 128..65536"); c->opt_post_chunk = (int)value; return HBO_OK; }
   if (!strcmp(name, "bf16x3")) { c->opt_post_bf16x3 = c->opt_syrk_bf16x3 = c->opt_trtri_bf16x3 = c->opt_lauum_bf16x3 = value != 0; return HBO_OK; }
   if (!strcmp(name, "spectral")) { if (value < 0 || value > 1) return fail(c, HBO_ERR_ARG, "spectral is 0 or 1"); c->opt_spectral = (int)value; return HBO_OK; }
+  if (!strcmp(name, "acq_fused")) { if (value < 0 || value > 1) return fail(c, HBO_ERR_ARG, "acq_fused is 0 or 1"); c->opt_acq_fused = (int)value; return HBO_OK; }
   return fail(c, HBO_ERR_ARG, std::string("unknown option ") + name);
 }
 // The same options read back (plus the read-only eig_sweeps, chol_form and inv_forms).  bf16x3 reads as 1 only when all four of its legs are on.
@@ -116,6 +117,7 @@ extern "C" int hbo_get_option(hbo_ctx* c, const char* name, int64_t* out) {
   if (!strcmp(name, "post_chunk")) { *out = c->opt_post_chunk; return HBO_OK; }
   if (!strcmp(name, "bf16x3")) { *out = c->opt_post_bf16x3 && c->opt_syrk_bf16x3 && c->opt_trtri_bf16x3 && c->opt_lauum_bf16x3; return HBO_OK; }
   if (!strcmp(name, "spectral")) { *out = c->opt_spectral; return HBO_OK; }
+  if (!strcmp(name, "acq_fused")) { *out = c->opt_acq_fused; return HBO_OK; }
   if (!strcmp(name, "eig_sweeps")) { *out = c->eig_last_sweeps; return HBO_OK; }
   if (!strcmp(name, "chol_form")) { *out = c->last_chol_form; return HBO_OK; }   // (include/hbo_tune.h)
   if (!strcmp(name, "inv_forms")) { *out = c->last_inv_forms; return HBO_OK; }

@@ -107,6 +107,7 @@ struct hbo_ctx {
   int opt_gram_mfma = 32;      // hbo_tune("gram_mfma"): fp32 Gram matrices of the stationary covariances with at least this many features take gram_mfma_kernel (0: never)
   int opt_small_fused = 1;     // hbo_tune("small_fused"): batches whose tasks all have n <= 128 take the single-workgroup evaluation (small.hip)
   int opt_spectral = 0;        // hbo_set_option("spectral"): stored for the Python layer, which routes its SVD call sites by it (hbo.h)
+  int opt_acq_fused = 0;      // hbo_set_option("acq_fused"): stored for the Python layer, which routes value_and_grad of small caches to hbo_acq_grad_samples (hbo.h)
   int eig_last_sweeps = 0;     // outer Jacobi sweeps of the last hbo_sym_eig / hbo_nll_spectral (largest over its batches; eig.hip)
   int opt_post_serial = 0;     // hbo_tune("post_serial"): the streamed posterior's producer side (cross Gram) on the SAME stream as its products: isolated stage times
   int opt_spd_diag_bound = 0;  // hbo_tune("spd_diag_bound"), test hook: hbo_spd_solve reads max_i A_ii off its host matrix, so that it can take the f16x2 form

@@ -402,6 +402,22 @@ void launch_acq_grad(int dtype, const AcqGradArgs& a, const ModelDev* md, hipStr
 void launch_acq_grad_mean(const double* dmu, const ModelDev* md, int64_t M, int fm, double* out, int accumulate,
                           hipStream_t st);
 void launch_add_inplace(double* dst, const double* src, int64_t count, hipStream_t st);
+// ---- d acquisition / d x of S samples x M queries in ONE launch, over caches of n <= 128 (acq_small.hip: one workgroup per pair) ----
+// What the kernel reads of one sample: the finished cache (features == inputs, W = L^-1, alpha) and the model's scalars; the per-feature
+// values (1 / lengthscale, then the linear mean's weights: 2 D doubles per sample) sit in AcqSmallArgs::vec.
+struct AcqSmallSample {
+  const void* F; const void* W; const void* alpha;   // [n][D], lower [n][ld], [n]  (model dtype)
+  int64_t ld;
+  int n, bad;                                        // bad: the cache is not positive definite -- the sample's rows are NaN
+  double sv, inv_sigma2, bias2, constant, linear_bias, param, add_noise;
+};
+struct AcqSmallArgs {
+  const AcqSmallSample* smp; const double* vec;      // [S], [S][2 D]
+  const void* xq; int D; int64_t M;                  // queries [M][D] (model dtype)
+  int kernel_id, mean_id, acq_id; double scale;
+  void* acq_out; double* grad_out;                   // [S][M] model dtype, [S][M][D]
+};
+void launch_acq_small(int dtype, const AcqSmallArgs& a, int S, hipStream_t st);
 void launch_extract_lower(int dtype, const void* A, int64_t ld, int64_t n, void* out, hipStream_t st);
 void launch_symmetrize_from_lower(int dtype, const void* S, int64_t ld, int64_t n, void* out, hipStream_t st);
 void launch_fill_spd(int dtype, const void* a_dense, int64_t n, void* A, int64_t ld, int npad, hipStream_t st);

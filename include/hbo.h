@@ -82,7 +82,7 @@ typedef struct hbo_model {
  *   elements of the model dtype each, ALREADY squareplus-warped.  Exactly a == 1 evaluates x^a as x and exactly b == 1 evaluates
  *   w as x^a (1 - (1 - u) == u in exact arithmetic), so raw zeros give the plain kernel bit for bit.
  *   Not supported (HBO_ERR_UNSUPPORTED): together with kernel_uses_mlp (not a reference combination), any other input_warp value,
- *   and hbo_acq_samples.
+ *   and hbo_acq_samples / hbo_acq_grad_samples.
  *   Gradient: the layout of such a model ends with 2 D more doubles, d/da at [total - 2D, total - D) and d/db at [total - D, total)
  *   (hbo_grad_layout_kumar_of), summed over rows and tasks in a fixed order (per-workgroup partials, one ordered finalisation):
  *   dw/da = b (1 - x^a)^(b-1) x^a ln x,  dw/db = -(1 - x^a)^b ln(1 - x^a).  At x = 0 and x = 1 both are DEFINED as their limit 0
@@ -231,6 +231,24 @@ int hbo_nll_samples(hbo_ctx* ctx, const hbo_model* models, int32_t S, hbo_datase
 int hbo_acq_grad(hbo_ctx* ctx, const hbo_model* model, hbo_cache* cache, const void* xq, int64_t M,
                  int acq_id, double param, double add_noise, double scale, void* out, double* grad_out);
 
+/* ---- the same for S hyper-parameter samples of ONE model family over their finished caches, in one launch: what bayesopt()'s inner
+ *      L-BFGS-B asks of an HGP at every evaluation (acfun.py:72-82 under bayesopt.py:116-125; the caller averages over s).
+ *      models[s] / caches[s]: sample s and the cache hbo_factor built for it (same observations or not: each pair is on its own);
+ *      acq_out [S,M] (model dtype) and grad_out [S,M,input_dim] doubles: row s is what
+ *      hbo_acq_grad(ctx, &models[s], caches[s], xq, M, acq_id, params[s], add_noise[s], scale, ...) returns, up to the order of
+ *      summation.  One upload, one launch (one workgroup per (sample, query) pair, csrc/acq_small.hip), one copy back and one
+ *      synchronisation whatever S is.  Every sum is fp64 in a fixed order and there are no atomics: a row does not depend on which
+ *      other samples or queries share the call (bit for bit), and identical calls are bit-identical.
+ *      HBO_ERR_ARG (before any device call): null arguments, S outside 1..4096, a bad acq_id, samples that do not share dtype /
+ *      covariance / mean / input_dim, a cache whose dtype / input_dim / input warp does not match its model.
+ *      HBO_ERR_UNSUPPORTED (before any device work; these stay with hbo_acq_grad): a cache with n > 128, a null or empty cache (the
+ *      prior branch), kernel_uses_mlp, a linear_mlp mean, an input-warped (Kumaraswamy) model (a packed array element has no
+ *      hbo_model_kumar tail, as in hbo_acq_samples).
+ *      A sample whose cache is not positive definite gets NaN rows and the call returns HBO_NOT_PD; the other samples are unaffected.
+ *      M == 0 returns HBO_OK. */
+int hbo_acq_grad_samples(hbo_ctx* ctx, const hbo_model* models, int32_t S, hbo_cache* const* caches, const void* xq, int64_t M,
+                         int acq_id, const double* params, const double* add_noise, double scale, void* acq_out, double* grad_out);
+
 /* ---- dense building blocks (linalg.py:29-33 solve_linear_system); host in/out ----------- */
 /* a: [n,n] SPD (only the lower triangle is read).  chol_out: lower factor (zeros above diag);
  * inv_out (nullable): full symmetric a^-1;  b/x_out (nullable): [n,m] solve a x = b. */
@@ -276,6 +294,11 @@ int hbo_set_option(hbo_ctx* ctx, const char* name, int64_t value);
 /*   spectral        0/1   (default 0) route the reference's SVD call sites -- neg_log_marginal_likelihood(use_cholesky=False),
  *                         GP / HGP.stats, svd_matrix_sqrt, sample_from_gp(method='svd' | 'eigh') -- to hbo_sym_eig / hbo_nll_spectral
  *                         instead of host LAPACK.  The library only stores it: the Python layer reads it back and routes its calls.
+ *   acq_fused       0/1   (default 0) route acquisition value_and_grad calls (bo_utils/acfun.py: an HGP's mean over its parameter samples,
+ *                         and a plain GP as S = 1) over caches of at most 128 observations to hbo_acq_grad_samples -- one launch per
+ *                         call instead of about eight launches and a host round trip per sample.  Models it does not cover (no
+ *                         observations, n > 128, an MLP basis, a linear_mlp mean, a Kumaraswamy kernel) keep the per-sample path.
+ *                         The library only stores it: the Python layer reads it back and routes its calls.
  * hbo_get_option reads an option back (the same names; unknown names are an error), and the read-only eig_sweeps: the outer Jacobi
  * sweeps of the last hbo_sym_eig / hbo_nll_spectral call (largest over its batches). */
 int hbo_get_option(hbo_ctx* ctx, const char* name, int64_t* out);
