@@ -19,6 +19,7 @@ MEAN_ZERO, MEAN_CONSTANT, MEAN_LINEAR, MEAN_LINEAR_MLP = 0, 1, 2, 3
 F32, F64 = 0, 1
 WARP_NONE, WARP_KUMAR = 0, 1
 ACQ_EI, ACQ_PI, ACQ_UCB = 0, 1, 2
+BO_PARAM_CONST, BO_PARAM_MAX_PLUS, BO_PARAM_MAX_PLUS_STD = 0, 1, 2
 MAX_MLP_LAYERS = 8
 MAX_FEATURE_DIM = 256
 MAX_PROFILE_STAGES = 32
@@ -66,6 +67,13 @@ class GradLayout(C.Structure):
 class Task(C.Structure):
   _fields_ = [('x', C.c_void_p), ('y', C.c_void_p), ('n', C.c_int64), ('m', C.c_int32),
               ('reserved0', C.c_int32)]
+
+
+class BoRun(C.Structure):
+  """hbo_bo_run: one run of hbo_bo_simulated (candidate pool, initial observations, acquisition and its per-iteration parameter)."""
+  _fields_ = [('xc', C.c_void_p), ('yc', C.c_void_p), ('M', C.c_int64), ('x0', C.c_void_p), ('y0', C.c_void_p), ('n0', C.c_int64),
+              ('acq_id', C.c_int32), ('param_mode', C.c_int32), ('param', C.c_double),
+              ('add_noise', C.c_double), ('scale0', C.c_double), ('scale', C.c_double)]
 
 
 class TrainLeaf(C.Structure):
@@ -121,6 +129,8 @@ SIGNATURES = {
                                _P, C.POINTER(C.c_double)]),
     'hbo_acq_grad_samples': (C.c_int, [_P, _P, C.c_int32, C.POINTER(_P), _P, C.c_int64, C.c_int, C.POINTER(C.c_double),
                                        C.POINTER(C.c_double), C.c_double, _P, C.POINTER(C.c_double)]),
+    'hbo_bo_simulated': (C.c_int, [_P, _P, C.POINTER(BoRun), C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_double), _P, _P,
+                                   C.POINTER(C.c_int32)]),
     'hbo_predict': (C.c_int, [_P, C.POINTER(Model), _P, _P, C.c_int64, C.c_int, _P, _P]),
     'hbo_acq': (C.c_int, [_P, C.POINTER(Model), _P, _P, C.c_int64, C.c_int, C.c_double, C.c_double,
                           C.c_double, _P]),

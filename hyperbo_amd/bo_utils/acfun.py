@@ -54,6 +54,9 @@ def ucb_sub(mu, std, beta=3.):
 
 _NATIVE_ID = {expected_improvement_sub: nat.ACQ_EI, probability_of_improvement_sub: nat.ACQ_PI,
               ucb_sub: nat.ACQ_UCB}
+# acquisition function object -> (acq_id, param_mode, param) of hbo_bo_simulated: the epilogue and the default callback's parameter
+# rule, which the device loop (bayesopt.py: bo_on_device) evaluates from the observed y itself.  Filled below, where the objects exist.
+_BO_DEVICE = {}
 
 
 def _leaves(t):
@@ -383,3 +386,13 @@ ucb3 = acfun_wrapper(acfun_sub=ucb_sub, acfun_callback_default=lambda a, b: 3.)
 ucb2 = acfun_wrapper(acfun_sub=ucb_sub, acfun_callback_default=lambda a, b: 2.)
 ucb = ucb3
 rand = random_search
+
+_BO_DEVICE.update({
+    expected_improvement: (nat.ACQ_EI, nat.BO_PARAM_MAX_PLUS, 0.0),        # ei_callback_default: max y
+    probability_of_improvement: (nat.ACQ_PI, nat.BO_PARAM_MAX_PLUS, 0.1),  # pi_callback_default: max y + zeta
+    pi2: (nat.ACQ_PI, nat.BO_PARAM_MAX_PLUS_STD, 0.1),                     # ... + zeta * np.std(y)
+    pi3: (nat.ACQ_PI, nat.BO_PARAM_MAX_PLUS, 0.05),
+    ucb2: (nat.ACQ_UCB, nat.BO_PARAM_CONST, 2.0),
+    ucb3: (nat.ACQ_UCB, nat.BO_PARAM_CONST, 3.0),
+    ucb4: (nat.ACQ_UCB, nat.BO_PARAM_CONST, 4.0),
+})

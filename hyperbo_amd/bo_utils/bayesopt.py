@@ -73,9 +73,103 @@ def bayesopt(key, model, sub_dataset_key, query_oracle, ac_func, iters, input_sa
   return model.dataset.get(sub_dataset_key, SubDataset(np.empty(0), np.empty(0)))
 
 
+def _bo_on_device_unmet(model, sub_dataset_key, queried_sub_dataset, ac_func):
+  """The first condition that keeps a simulated BO loop off the device loop (hbo_bo_simulated, config['bo_on_device']), as a
+  message, or None.  Host-side checks only."""
+  from hyperbo_amd.bo_utils import acfun
+  from hyperbo_amd.gp_utils import gp
+  if isinstance(model, gp.HGP):
+    return 'the model is an HGP (the acquisition is a mean over parameter samples)'
+  if (model.params.config or {}).get('retrain', 0) > 0:
+    return "config['retrain'] > 0 re-trains the model between iterations"
+  if getattr(ac_func, '__name__', '') in ('rand', 'random_search'):
+    return 'random search draws its selections on the host'
+  if ac_func not in acfun._BO_DEVICE:
+    return f'ac_func {ac_func!r} is not one of the native acquisition functions of bo_utils/acfun.py'
+  if getattr(model.cov_func, 'uses_kumar', False):
+    return 'the kernel is input-warped (Kumaraswamy)'
+  ys = [np.asarray(queried_sub_dataset.y)]
+  if sub_dataset_key in model.dataset:
+    ys.append(np.asarray(model.dataset[sub_dataset_key].y))
+  if any(y.ndim > 1 and y.shape[1] > 1 for y in ys):
+    return 'y has more than one column'
+  if np.shape(queried_sub_dataset.x)[0] == 0:
+    return 'the candidate pool is empty'
+  return None
+
+
+def _bo_scales(model, sub_dataset_key):
+  """(add_noise, scale of iteration 0, scale of the later ones) -- gp.py:607-619.  The first append creates a sub-dataset whose
+  key is not in model.dataset yet, and the unbiased T / (T - 1) then counts one more."""
+  add_noise, scale0 = model.predict_noise_and_scale(True, True)
+  if sub_dataset_key in model.dataset:
+    return add_noise, scale0, scale0
+  count = len([k for k, v in model.dataset.items() if v.aligned is None]) + 1
+  return add_noise, scale0, (count / (count - 1.) if count > 1 else 1.0)
+
+
+def simulated_bayesopt_batch(runs, iters):
+  """simulated_bayesopt for a sequence of (model, sub_dataset_key, queried_sub_dataset, ac_func) as ONE hbo_bo_simulated call: every
+  iteration of every run on the device (csrc/bo_loop.hip), one synchronisation.  The models must share a family
+  (dtype, covariance, mean, input_dim, MLP architecture).  Afterwards every selection is appended to its model's sub-dataset
+  (update_sub_dataset, as the host loop does); returns the list of resulting SubDatasets."""
+  from hyperbo_amd import _model
+  from hyperbo_amd import _native as nat
+  from hyperbo_amd.bo_utils import acfun
+  runs = list(runs)
+  empty = SubDataset(np.empty(0), np.empty(0))
+  if iters <= 0 or not runs:
+    return [model.dataset.get(key, empty) for model, key, _, _ in runs]
+  built, structs, keep, family = [], [], [], None
+  for model, key, pool, ac_func in runs:
+    unmet = _bo_on_device_unmet(model, key, pool, ac_func)
+    if unmet is not None:
+      raise ValueError('bo_on_device: ' + unmet)
+    has_obs = model.has_observations(key)
+    sd = model.dataset[key] if has_obs else None
+    dtype = _model.infer_dtype(pool.x, pool.y, *((sd.x, sd.y) if has_obs else ()))
+    bm = _model.BuiltModel(model.mean_func, model.cov_func, model.params, model.warp_func, dtype, model.input_dim)
+    fam = (bm.code, bm.kernel_id, bm.mean_id, model.input_dim, bm.uses_mlp_kernel, bm.struct.n_lengthscale, tuple(bm.mlp_shapes))
+    if family is None:
+      family = fam
+    elif fam != family:
+      raise ValueError('bo_on_device: the runs of one batch must share dtype, covariance, mean, input_dim and MLP architecture')
+    d = model.input_dim
+    xc = np.ascontiguousarray(np.asarray(pool.x).reshape(-1, d), dtype=dtype)
+    yc = np.ascontiguousarray(np.asarray(pool.y).reshape(-1), dtype=dtype)
+    x0 = np.ascontiguousarray(np.asarray(sd.x).reshape(-1, d), dtype=dtype) if has_obs else None
+    y0 = np.ascontiguousarray(np.asarray(sd.y).reshape(-1), dtype=dtype) if has_obs else None
+    acq_id, mode, param = acfun._BO_DEVICE[ac_func]
+    add_noise, scale0, scale = _bo_scales(model, key)
+    structs.append(nat.BoRun(nat.ptr(xc), nat.ptr(yc), xc.shape[0], nat.ptr(x0), nat.ptr(y0), 0 if x0 is None else x0.shape[0],
+                             acq_id, mode, param, add_noise, scale0, scale))
+    built.append(bm)
+    keep.append((xc, yc, x0, y0))
+  count = len(runs)
+  sel = np.zeros((count, iters), dtype=np.int32)
+  acq = np.zeros((count, iters), dtype=np.float64)
+  status = np.zeros(count, dtype=np.int32)
+  ctx = nat.default_context()
+  # (a run whose appended rows made the matrix numerically indefinite, status HBO_NOT_PD: its later selections are index 0 -- what
+  #  the host loop's np.argmax returns over the NaN values of a cache that failed to factorise; the rows are appended all the same)
+  ctx.check(nat.lib().hbo_bo_simulated(ctx.handle, (nat.Model * count)(*[b.struct for b in built]), (nat.BoRun * count)(*structs), count,
+                                       int(iters), sel.ctypes.data_as(nat.C.POINTER(nat.C.c_int32)),
+                                       acq.ctypes.data_as(nat.C.POINTER(nat.C.c_double)), None, None,
+                                       status.ctypes.data_as(nat.C.POINTER(nat.C.c_int32))))
+  out = []
+  for (model, key, pool, _), row in zip(runs, sel):
+    for idx in row:
+      model.update_sub_dataset((pool.x[idx], pool.y[idx]), sub_dataset_key=key, is_append=True)
+    out.append(model.dataset.get(key, empty))
+  return out
+
+
 def simulated_bayesopt(model, sub_dataset_key, queried_sub_dataset, ac_func, iters, random_key=None,
                        get_params_path=None, callback=None):
-  """bayesopt.py:136-190: BO restricted to a set of pre-evaluated candidates."""
+  """bayesopt.py:136-190: BO restricted to a set of pre-evaluated candidates.  With config['bo_on_device'] set the whole loop runs
+  on the device (simulated_bayesopt_batch with one run); a model or acquisition function it does not cover raises ValueError."""
+  if (model.params.config or {}).get('bo_on_device'):
+    return simulated_bayesopt_batch([(model, sub_dataset_key, queried_sub_dataset, ac_func)], iters)[0]
   rng = None if random_key is None else _rng(random_key)
   for _ in range(iters):
     retrain_model(model, sub_dataset_key=sub_dataset_key, random_key=rng, get_params_path=get_params_path,

@@ -829,6 +829,171 @@ extern "C" int hbo_acq_grad_samples(hbo_ctx* c, const hbo_model* models, int32_t
   return any_bad ? HBO_NOT_PD : HBO_OK;
 }
 
+// ---- the simulated BO loop of R runs in one call (bayesopt.py:136-190; kernels and the recurrence: bo_loop.hip) ----
+// Set-up once per call through the device code every posterior uses (query_features: MLP forward, mean, prior diagonal -- per run, with
+// its own model and weights), then the n0 + iters steps of every run as two stream-ordered launches each, all queued before the one
+// synchronisation.  The small records go up through the pinned stage, the pools straight from the caller's arrays, and the results
+// come back straight into the caller's arrays: no host-side copy of a pool.
+extern "C" int hbo_bo_simulated(hbo_ctx* c, const hbo_model* models, const hbo_bo_run* runs, int32_t R, int32_t iters, int32_t* sel_out,
+                                double* acq_out, void* mu_out, void* var_out, int32_t* status) {
+  if (!models || !runs || !sel_out || !acq_out || !status) return fail(c, HBO_ERR_ARG, "hbo_bo_simulated: null argument");
+  if (R <= 0 || R > 4096) return fail(c, HBO_ERR_ARG, "hbo_bo_simulated: 1 <= R <= 4096");
+  if (iters <= 0 || iters > 65536) return fail(c, HBO_ERR_ARG, "hbo_bo_simulated: 1 <= iters <= 65536");
+  const hbo_model* m0 = &models[0];
+  for (int r = 0; r < R; ++r) {
+    const hbo_model* m = &models[r];
+    const hbo_bo_run& u = runs[r];
+    // (before validate_model: a packed array element has no hbo_model_kumar tail to read)
+    if (m->input_warp != HBO_WARP_NONE)
+      return fail(c, HBO_ERR_UNSUPPORTED, "hbo_bo_simulated: input-warped (Kumaraswamy) models are not supported; run the host loop");
+    if (int rc = validate_model(c, m)) return rc;
+    if (!same_model_family(m, m0)) return fail(c, HBO_ERR_ARG, "hbo_bo_simulated: the runs' models must share dtype, covariance, mean, input_dim and MLP architecture");
+    if (u.M <= 0) return fail(c, HBO_ERR_ARG, "hbo_bo_simulated: a run has an empty candidate pool (M <= 0)");
+    if (u.n0 < 0 || u.M + u.n0 >= ((int64_t)1 << 31)) return fail(c, HBO_ERR_ARG, "hbo_bo_simulated: need n0 >= 0 and M + n0 < 2^31");
+    if (!u.xc || !u.yc || (u.n0 > 0 && (!u.x0 || !u.y0))) return fail(c, HBO_ERR_ARG, "hbo_bo_simulated: a run's pool or observations are null");
+    if (u.acq_id < 0 || u.acq_id > HBO_ACQ_UCB) return fail(c, HBO_ERR_ARG, "hbo_bo_simulated: bad acq_id");
+    if (u.param_mode < 0 || u.param_mode > HBO_BO_PARAM_MAX_PLUS_STD) return fail(c, HBO_ERR_ARG, "hbo_bo_simulated: bad param_mode");
+  }
+  const int dtype = m0->dtype, D = m0->input_dim, fdim = feature_dim(m0);
+  const size_t es = esize(dtype);
+  const bool mlp = needs_mlp(m0);
+  const int L = mlp ? m0->n_layers : 0;
+  auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+  // ---- sizes: [in] what goes up, [feat] set-up results (model dtype), [v] the fp64 state, [out] what comes back + the arg-max partials
+  size_t mlp_per = 0;
+  { int fin = D; for (int l = 0; l < L; ++l) { mlp_per += al((size_t)fin * m0->features[l] * es) + al((size_t)m0->features[l] * es); fin = m0->features[l]; } }
+  // (the head of [in] -- run records, pivots, 1 / lengthscale, models, MLP weights -- is staged in pinned memory; the pools go up straight from the caller's)
+  const size_t head_b = al(sizeof(BoRunDev) * R) + al(sizeof(BoPivot) * R) + al(sizeof(double) * fdim * R) + al(sizeof(ModelDev) * R) + mlp_per * R;
+  size_t in_b = head_b;
+  size_t feat_b = 0, v_b = 0, part_b = 0;
+  int64_t sum_M = 0, max_ncol = 0, max_steps = 0;
+  for (int r = 0; r < R; ++r) {
+    const int64_t ncol = runs[r].M + runs[r].n0, steps = runs[r].n0 + iters;
+    in_b += al((size_t)ncol * D * es) + al((size_t)ncol * es);
+    feat_b += 2 * al((size_t)ncol * es);
+    for (int l = 0; l < L; ++l) feat_b += al((size_t)ncol * m0->features[l] * es);
+    v_b += al(sizeof(double) * (size_t)steps * ncol) + 2 * al(sizeof(double) * ncol) + al(sizeof(double) * steps);
+    const size_t nch = (size_t)((runs[r].M + 255) / 256);
+    part_b += al(sizeof(double) * nch) + al(sizeof(int32_t) * nch);
+    sum_M += runs[r].M; max_ncol = std::max(max_ncol, ncol); max_steps = std::max(max_steps, steps);
+  }
+  const size_t acq_b = al(sizeof(double) * (size_t)R * iters), sel_b = al(sizeof(int32_t) * (size_t)R * iters), st_b = al(sizeof(int32_t) * R);
+  const size_t post_b = al((size_t)sum_M * es);
+  const size_t down_b = acq_b + sel_b + st_b + 2 * post_b, out_b = down_b + part_b;
+  if (!c) return fail(c, HBO_ERR_ARG, "hbo_bo_simulated: ctx is null");
+  HIPCHK(c, hipSetDevice(c->device));
+  { size_t total = 0;
+    HIPCHK(c, hipDeviceTotalMem(&total, c->device));
+    if (v_b > total / 2) return fail(c, HBO_ERR_UNSUPPORTED, "hbo_bo_simulated: the runs' workspaces ((n0 + iters) x (M + n0) doubles each) exceed half of the device memory; split the batch"); }
+  hipStream_t st = c->stream;
+  char* d_in = static_cast<char*>(ws_get(c, WS_BO_IN, in_b));
+  char* d_feat = static_cast<char*>(ws_get(c, WS_BO_FEAT, feat_b));
+  char* d_v = static_cast<char*>(ws_get(c, WS_BO_V, v_b));
+  char* d_out = static_cast<char*>(ws_get(c, WS_BO_OUT, out_b));
+  if (!d_in || !d_feat || !d_v || !d_out) return HBO_ERR_HIP;
+  // ---- the head of the block that goes up, and the device addresses of everything else
+  HIPCHK(c, hipEventSynchronize(c->ev_upload));   // the pinned buffer may still feed an earlier upload
+  char* h_in = static_cast<char*>(pinned_stage(c, head_b));
+  if (!h_in) return fail(c, HBO_ERR_HIP, "hbo_bo_simulated: no pinned staging memory");
+  memset(h_in, 0, head_b);
+  size_t off = 0;
+  auto take = [&](size_t bytes) { const size_t o = off; off += al(bytes); return o; };
+  const size_t o_runs = take(sizeof(BoRunDev) * R), o_piv = take(sizeof(BoPivot) * R), o_ils = take(sizeof(double) * fdim * R), o_md = take(sizeof(ModelDev) * R);
+  BoRunDev* h_runs = reinterpret_cast<BoRunDev*>(h_in + o_runs);
+  BoPivot* h_piv = reinterpret_cast<BoPivot*>(h_in + o_piv);
+  double* h_ils = reinterpret_cast<double*>(h_in + o_ils);
+  ModelDev* h_md = reinterpret_cast<ModelDev*>(h_in + o_md);
+  size_t xoff = head_b;   // the pools behind the head
+  std::vector<void*> w_dev((size_t)R * HBO_MAX_MLP_LAYERS, nullptr), b_dev((size_t)R * HBO_MAX_MLP_LAYERS, nullptr), acts((size_t)R * HBO_MAX_MLP_LAYERS, nullptr);
+  std::vector<const void*> d_x(R);
+  size_t foff = 0, voff = 0, poff = down_b, moff = 0;
+  for (int r = 0; r < R; ++r) {
+    const hbo_bo_run& u = runs[r];
+    const int64_t ncol = u.M + u.n0, steps = u.n0 + iters;
+    BoRunDev& q = h_runs[r];
+    fill_model_dev(h_md[r], &models[r]);
+    const ModelDev& md = h_md[r];
+    memcpy(h_ils + (size_t)r * fdim, md.inv_ls, sizeof(double) * fdim);
+    q.inv_ls = reinterpret_cast<const double*>(d_in + o_ils) + (size_t)r * fdim;
+    // inputs and values: the pool, then the initial observations (uploaded below)
+    d_x[r] = d_in + xoff; xoff += al((size_t)ncol * D * es);
+    q.y = d_in + xoff; xoff += al((size_t)ncol * es);
+    { int fin = D;
+      for (int l = 0; l < L; ++l) {
+        const size_t wb = (size_t)fin * m0->features[l] * es, bb = (size_t)m0->features[l] * es;
+        const size_t o_w = take(wb), o_b = take(bb);
+        memcpy(h_in + o_w, models[r].mlp_kernel[l], wb); memcpy(h_in + o_b, models[r].mlp_bias[l], bb);
+        w_dev[(size_t)r * HBO_MAX_MLP_LAYERS + l] = d_in + o_w; b_dev[(size_t)r * HBO_MAX_MLP_LAYERS + l] = d_in + o_b;
+        acts[(size_t)r * HBO_MAX_MLP_LAYERS + l] = d_feat + foff; foff += al((size_t)ncol * m0->features[l] * es);
+        fin = m0->features[l];
+      } }
+    q.F = m0->kernel_uses_mlp ? acts[(size_t)r * HBO_MAX_MLP_LAYERS + L - 1] : d_x[r];   // what query_features hands the covariance
+    q.mu0 = d_feat + foff; foff += al((size_t)ncol * es);
+    q.kd = d_feat + foff; foff += al((size_t)ncol * es);
+    q.V = reinterpret_cast<double*>(d_v + voff); voff += al(sizeof(double) * (size_t)steps * ncol);
+    q.sumsq = reinterpret_cast<double*>(d_v + voff); voff += al(sizeof(double) * ncol);
+    q.mu = reinterpret_cast<double*>(d_v + voff); voff += al(sizeof(double) * ncol);
+    q.yobs = reinterpret_cast<double*>(d_v + voff); voff += al(sizeof(double) * steps);
+    q.piv = reinterpret_cast<BoPivot*>(d_in + o_piv) + r;
+    const size_t nch = (size_t)((u.M + 255) / 256);
+    q.part_val = reinterpret_cast<double*>(d_out + poff); poff += al(sizeof(double) * nch);
+    q.part_idx = reinterpret_cast<int32_t*>(d_out + poff); poff += al(sizeof(int32_t) * nch);
+    q.acq = reinterpret_cast<double*>(d_out) + (size_t)r * iters;
+    q.sel = reinterpret_cast<int32_t*>(d_out + acq_b) + (size_t)r * iters;
+    q.status = reinterpret_cast<int32_t*>(d_out + acq_b + sel_b) + r;
+    q.mu_out = mu_out ? d_out + acq_b + sel_b + st_b + moff * es : nullptr;
+    q.var_out = var_out ? d_out + acq_b + sel_b + st_b + post_b + moff * es : nullptr;
+    moff += (size_t)u.M;
+    q.M = u.M; q.ncol = ncol; q.n0 = (int)u.n0; q.steps = (int)steps;
+    q.fdim = fdim; q.kernel_id = m0->kernel_id; q.acq_id = u.acq_id; q.param_mode = u.param_mode;
+    q.param = u.param; q.add_noise = u.add_noise; q.scale0 = u.scale0; q.scale = u.scale;
+    q.sv = md.sv; q.inv_sigma2 = 1.0 / (md.dot_sigma * md.dot_sigma); q.bias2 = md.dot_bias * md.dot_bias; q.noise_eps = md.noise + md.eps;
+    h_piv[r].p = 0; h_piv[r].l = NAN; h_piv[r].z = NAN; h_piv[r].ymax = NAN;
+    h_piv[r].param = u.param_mode == HBO_BO_PARAM_CONST ? u.param : 0.0;   // over an empty y (acfun.py:145-148, 160-166)
+  }
+  // (from the first queued copy on, an error waits for the stream before it returns: the copies read and write the caller's memory)
+  auto bail = [&]() { hipStreamSynchronize(st); };
+  HIPCHK_OR(c, hipMemcpyAsync(d_in, h_in, head_b, hipMemcpyHostToDevice, st), bail());
+  HIPCHK_OR(c, hipEventRecord(c->ev_upload, st), bail());
+  for (int r = 0; r < R; ++r) {
+    const hbo_bo_run& u = runs[r];
+    char* dx = static_cast<char*>(const_cast<void*>(d_x[r]));
+    char* dy = static_cast<char*>(const_cast<void*>(h_runs[r].y));
+    HIPCHK_OR(c, hipMemcpyAsync(dx, u.xc, (size_t)u.M * D * es, hipMemcpyHostToDevice, st), bail());
+    HIPCHK_OR(c, hipMemcpyAsync(dy, u.yc, (size_t)u.M * es, hipMemcpyHostToDevice, st), bail());
+    if (u.n0 > 0) {
+      HIPCHK_OR(c, hipMemcpyAsync(dx + (size_t)u.M * D * es, u.x0, (size_t)u.n0 * D * es, hipMemcpyHostToDevice, st), bail());
+      HIPCHK_OR(c, hipMemcpyAsync(dy + (size_t)u.M * es, u.y0, (size_t)u.n0 * es, hipMemcpyHostToDevice, st), bail());
+    }
+  }
+  HIPCHK_OR(c, hipMemsetAsync(d_out + acq_b + sel_b, 0, st_b, st), bail());
+  // ---- set-up: features of all columns, the mean and the prior diagonal at them, per run under its own model
+  const ModelDev* d_md = reinterpret_cast<const ModelDev*>(d_in + o_md);
+  for (int r = 0; r < R; ++r) {
+    const int64_t ncol = runs[r].M + runs[r].n0;
+    const BoRunDev& q = h_runs[r];
+    query_features(c, &models[r], d_md + r, mlp ? &w_dev[(size_t)r * HBO_MAX_MLP_LAYERS] : nullptr, mlp ? &b_dev[(size_t)r * HBO_MAX_MLP_LAYERS] : nullptr,
+                   d_x[r], ncol, &acts[(size_t)r * HBO_MAX_MLP_LAYERS], nullptr, const_cast<void*>(q.mu0), const_cast<void*>(q.kd), st);
+  }
+  // ---- the steps, all queued: row l (the prior at l = 0, the final posterior at l = steps), then the selection / forced pivot of row l
+  const BoRunDev* d_runs = reinterpret_cast<const BoRunDev*>(d_in + o_runs);
+  for (int l = 0; l <= (int)max_steps; ++l) {
+    launch_bo_row(dtype, d_runs, R, max_ncol, l, st);
+    if (l < (int)max_steps) launch_bo_select(dtype, d_runs, R, l, st);
+  }
+  // ---- the results straight into the caller's arrays (the device block holds them in the caller's layout), one wait
+  HIPCHK_OR(c, hipMemcpyAsync(acq_out, d_out, sizeof(double) * (size_t)R * iters, hipMemcpyDeviceToHost, st), bail());
+  HIPCHK_OR(c, hipMemcpyAsync(sel_out, d_out + acq_b, sizeof(int32_t) * (size_t)R * iters, hipMemcpyDeviceToHost, st), bail());
+  HIPCHK_OR(c, hipMemcpyAsync(status, d_out + acq_b + sel_b, sizeof(int32_t) * R, hipMemcpyDeviceToHost, st), bail());
+  if (mu_out) HIPCHK_OR(c, hipMemcpyAsync(mu_out, d_out + acq_b + sel_b + st_b, (size_t)sum_M * es, hipMemcpyDeviceToHost, st), bail());
+  if (var_out) HIPCHK_OR(c, hipMemcpyAsync(var_out, d_out + acq_b + sel_b + st_b + post_b, (size_t)sum_M * es, hipMemcpyDeviceToHost, st), bail());
+  HIPCHK(c, hipStreamSynchronize(st));
+  HIPCHK(c, hipGetLastError());
+  for (int r = 0; r < R; ++r) if (status[r] < 0) return fail(c, HBO_ERR_HIP, "hbo_bo_simulated: a selection left the candidate pool (internal error)");
+  for (int r = 0; r < R; ++r) if (status[r] != HBO_OK) return HBO_NOT_PD;
+  return HBO_OK;
+}
+
 // Test hook (include/hbo_tune.h): the fp32 split-operand posterior product on caller-chosen operands -- W and Kxq go up padded as a
 // cache holds them, the three launches of the posterior above run once over all M candidates, the per-row-block column sums of V^2
 // come back.  The split buffers are filled with 0xFF (NaN in bf16 and fp16) first: a block the product reads but no split wrote shows.

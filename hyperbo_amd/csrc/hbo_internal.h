@@ -418,6 +418,32 @@ struct AcqSmallArgs {
   void* acq_out; double* grad_out;                   // [S][M] model dtype, [S][M][D]
 };
 void launch_acq_small(int dtype, const AcqSmallArgs& a, int S, hipStream_t st);
+// ---- the simulated BO loop on the device (bo_loop.hip; host side: cache.hip: hbo_bo_simulated) ----
+// The pivot of the next row of a run: written by bo_select_kernel, read by the bo_row_kernel behind it.  Before the first selection
+// only `param` is read (set by the host: the acquisition parameter over an empty y).
+struct BoPivot {
+  int64_t p;                 // column of the observation
+  double l, z;               // l_pp, (y_p - mu_p) / l_pp  (NaN once a pivot was not positive)
+  double param;              // acquisition parameter of the next selection
+  double ymax;               // np.max of the observed y
+};
+// One run as the kernels see it.  Columns: the M candidates, then the n0 initial observations.
+struct BoRunDev {
+  const void* F; const void* mu0; const void* kd; const void* y;   // [ncol][fdim] kernel features, prior mean, k(c, c), values (model dtype)
+  const double* inv_ls;                                            // [fdim] 1 / lengthscale
+  double* V; double* sumsq; double* mu; double* yobs;              // [steps][ncol], [ncol], [ncol], [steps]
+  BoPivot* piv;
+  double* part_val; int32_t* part_idx;                             // arg-max partials, one per workgroup of candidates
+  int32_t* sel; double* acq; int32_t* status;                      // [iters], [iters], [1]
+  void* mu_out; void* var_out;                                     // [M] model dtype (nullable)
+  int64_t M, ncol;
+  int n0, steps;                                                   // steps = n0 + iters rows
+  int fdim, kernel_id, acq_id, param_mode;
+  double param, add_noise, scale0, scale;
+  double sv, inv_sigma2, bias2, noise_eps;
+};
+void launch_bo_row(int dtype, const BoRunDev* runs, int R, int64_t max_ncol, int step, hipStream_t st);
+void launch_bo_select(int dtype, const BoRunDev* runs, int R, int step, hipStream_t st);
 void launch_extract_lower(int dtype, const void* A, int64_t ld, int64_t n, void* out, hipStream_t st);
 void launch_symmetrize_from_lower(int dtype, const void* S, int64_t ld, int64_t n, void* out, hipStream_t st);
 void launch_fill_spd(int dtype, const void* a_dense, int64_t n, void* A, int64_t ld, int npad, hipStream_t st);

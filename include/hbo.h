@@ -249,6 +249,41 @@ int hbo_acq_grad(hbo_ctx* ctx, const hbo_model* model, hbo_cache* cache, const v
 int hbo_acq_grad_samples(hbo_ctx* ctx, const hbo_model* models, int32_t S, hbo_cache* const* caches, const void* xq, int64_t M,
                          int acq_id, const double* params, const double* add_noise, double scale, void* acq_out, double* grad_out);
 
+/* ---- the simulated BO loop over a pool of pre-evaluated candidates (hyperbo/bo_utils/bayesopt.py:136-190), every iteration of R
+ *      independent runs in ONE call: all launches are queued up front and the results come back behind them: one synchronisation, at the end.
+ *      Per iteration the host loop evaluates the acquisition function at the pool, takes np.argmax and appends the chosen (x, y); here
+ *      the posterior at the pool is carried along as one more row of forward substitution per appended observation
+ *      (csrc/bo_loop.hip; O(n M) per iteration, no factor, no limit on the number of observations).
+ *      models[r] may differ in values; they share dtype, covariance, mean, input_dim and MLP architecture (the rule of hbo_acq_samples).
+ *      Run r: pool xc [M, input_dim] with values yc [M], initial observations x0 [n0, input_dim] / y0 [n0] (n0 may be 0: the prior
+ *      branch; x0 / y0 may then be null), all in the model dtype.  add_noise, scale0, scale: GP.predict's post-processing
+ *      (gp.py:607-619), scale0 for iteration 0 and scale for the rest -- they differ when the first append creates the sub-dataset.
+ *      The acquisition parameter of an iteration comes from the observed y (initial and appended) on the device, as acfun.py's default
+ *      callbacks: CONST: param (ucb*: beta);  MAX_PLUS: max y + param (EI: 0, pi / pi3: zeta);  MAX_PLUS_STD: max y + param * np.std(y)
+ *      (pi2);  over an empty y the two MAX modes give 0.0.
+ *      Selection = np.argmax on the values rounded to the model dtype: the first index among equal values, the first NaN if there is
+ *      one; a selected candidate stays in the pool.
+ *      sel_out / acq_out [R][iters]: selected index and its acquisition value (NaN where np.argmax ran over NaN).  mu_out / var_out
+ *      (nullable): the runs' posteriors at their pools after the last append, before noise and scale, back to back ([sum of M], model
+ *      dtype).  status [R]: HBO_OK, or HBO_NOT_PD for a run one of whose pivots l_pp^2 was <= 0 or NaN -- from that row on its
+ *      values are NaN and its selections index 0, what the host loop gets from a cache that fails to factorise; the call then returns
+ *      HBO_NOT_PD and the other runs are unaffected.
+ *      No atomics; every sum is fp64 in a fixed order: identical calls are bit-identical, and a run does not depend on what shares
+ *      the call.
+ *      HBO_ERR_ARG (before any device work): null arguments, R outside 1..4096, iters outside 1..65536, a run with M <= 0, n0 < 0,
+ *      M + n0 >= 2^31, null pool or (n0 > 0) null observations, a bad acq_id / param_mode, models of different families.
+ *      HBO_ERR_UNSUPPORTED (before any device work): an input-warped (Kumaraswamy) model; a workspace ((n0 + iters) x (M + n0) doubles
+ *      per run) above half of the device memory. */
+enum hbo_bo_param_mode { HBO_BO_PARAM_CONST = 0, HBO_BO_PARAM_MAX_PLUS = 1, HBO_BO_PARAM_MAX_PLUS_STD = 2 };
+typedef struct hbo_bo_run {
+  const void* xc; const void* yc; int64_t M;      /* candidate pool [M, D], its pre-evaluated values [M] */
+  const void* x0; const void* y0; int64_t n0;     /* observations the sub-dataset starts with (n0 may be 0) */
+  int32_t acq_id; int32_t param_mode; double param;
+  double add_noise, scale0, scale;                /* gp.py:607-619; scale0 for iteration 0, scale for the rest */
+} hbo_bo_run;
+int hbo_bo_simulated(hbo_ctx* ctx, const hbo_model* models, const hbo_bo_run* runs, int32_t R, int32_t iters,
+                     int32_t* sel_out, double* acq_out, void* mu_out, void* var_out, int32_t* status);
+
 /* ---- dense building blocks (linalg.py:29-33 solve_linear_system); host in/out ----------- */
 /* a: [n,n] SPD (only the lower triangle is read).  chol_out: lower factor (zeros above diag);
  * inv_out (nullable): full symmetric a^-1;  b/x_out (nullable): [n,m] solve a x = b. */
