@@ -238,7 +238,7 @@ class Context:
     self.check(f(self._h, name.encode(), int(value)))
 
   def get_option(self, name):
-    """An option of include/hbo.h read back (also the read-only 'eig_sweeps', 'chol_form' and 'inv_forms'); unknown names raise."""
+    """An option of include/hbo.h read back (also the read-only 'eig_sweeps', 'chol_form', 'inv_forms' and 'post_resident'); unknown names raise."""
     out = C.c_int64(0)
     self.check(lib().hbo_get_option(self._h, name.encode(), C.byref(out)), allow_not_pd=False)
     return out.value

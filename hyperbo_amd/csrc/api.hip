@@ -107,7 +107,7 @@ extern "C" int hbo_set_option(hbo_ctx* c, const char* name, int64_t value) {
   if (!strcmp(name, "acq_fused")) { if (value < 0 || value > 1) return fail(c, HBO_ERR_ARG, "acq_fused is 0 or 1"); c->opt_acq_fused = (int)value; return HBO_OK; }
   return fail(c, HBO_ERR_ARG, std::string("unknown option ") + name);
 }
-// The same options read back (plus the read-only eig_sweeps, chol_form and inv_forms).  bf16x3 reads as 1 only when all four of its legs are on.
+// The same options read back (plus the read-only eig_sweeps, chol_form, inv_forms and post_resident).  bf16x3 reads as 1 only when all four of its legs are on.
 extern "C" int hbo_get_option(hbo_ctx* c, const char* name, int64_t* out) {
   if (!c || !name || !out) return fail(c, HBO_ERR_ARG, "hbo_get_option: null argument");
   if (!strcmp(name, "potrf_group")) { *out = c->opt_group; return HBO_OK; }
@@ -121,6 +121,7 @@ extern "C" int hbo_get_option(hbo_ctx* c, const char* name, int64_t* out) {
   if (!strcmp(name, "eig_sweeps")) { *out = c->eig_last_sweeps; return HBO_OK; }
   if (!strcmp(name, "chol_form")) { *out = c->last_chol_form; return HBO_OK; }   // (include/hbo_tune.h)
   if (!strcmp(name, "inv_forms")) { *out = c->last_inv_forms; return HBO_OK; }
+  if (!strcmp(name, "post_resident")) { *out = c->last_post_resident; return HBO_OK; }   // (include/hbo.h)
   return fail(c, HBO_ERR_ARG, std::string("unknown option ") + name);
 }
 // Measurement hooks (include/hbo_tune.h): placement and overlap knobs of the schedules, for the A/B tools under tools/ and

@@ -255,13 +255,13 @@ static void post3_split_kxq(const float* K, int64_t ldq, int mpad, int npad, boo
   launch_split3_block(sk, 1, true, st);
 }
 // colsq [nblk, ldc] = per row block of W the column sums of (W Kxq)^2.  counter (nullable): zeroed here and handed to launch_post3,
-// which turns a large product into a resident grid drawing its tiles from it
-static void post3_product(const unsigned short* w3, const unsigned short* K3, int nblk, int mpad, bool h2, const unsigned int* d_wmax,
+// which turns a large product into a resident grid drawing its tiles from it (returns whether it did)
+static bool post3_product(const unsigned short* w3, const unsigned short* K3, int nblk, int mpad, bool h2, const unsigned int* d_wmax,
                           float kscale, float* colsq, int64_t ldc, int* counter, hipStream_t st) {
   Post3Args a = {}; a.Wp = w3; a.Kp = K3; a.nkb = nblk * (HBO_TILE / 16); a.h2 = h2; a.wmax_bits = d_wmax; a.kscale = kscale;
   a.colsq = colsq; a.ldc = ldc; a.nblk = nblk;
   if (counter) { a.work_counter = counter; hipMemsetAsync(counter, 0, sizeof(int), st); }
-  launch_post3(a, mpad / HBO_TILE, st);
+  return launch_post3(a, mpad / HBO_TILE, st);
 }
 
 
@@ -421,7 +421,7 @@ static void consume_chunk(const PostCall& pc, const PostPlan& p, const PostWs& w
   int* counter = (ch.counter >= 0 && w.counters) ? w.counters + ch.counter : nullptr;
   if (p.form != FORM_MFMA) {
     ProfScope ps(c, "post_gemm", 1, sa);
-    post3_product(k->w3, s.K3, t->nblk, ch.mpad, p.form == FORM_F16X2, k->d_wmax, p.kscale, reinterpret_cast<float*>(s.colsq), ch.ldq, counter, sa);
+    c->last_post_resident = post3_product(k->w3, s.K3, t->nblk, ch.mpad, p.form == FORM_F16X2, k->d_wmax, p.kscale, reinterpret_cast<float*>(s.colsq), ch.ldq, counter, sa);
   } else {
     ProfScope ps(c, "post_gemm", 1, sa);
     GemmArgs a = {}; a.tasks = k->d_desc; a.mode = GEMM_POST; a.B = s.K; a.ldb = ch.ldq; a.V = p.full_cov ? w.V : nullptr; a.colsq = s.colsq;
@@ -430,10 +430,12 @@ static void consume_chunk(const PostCall& pc, const PostPlan& p, const PostWs& w
       for (int i = 0; i < t->nblk; ++i) pairs += (i + p.kchunk) / p.kchunk;
       a.kchunk = p.kchunk; a.V = w.vpart; a.colsq = nullptr;
       launch_gemm(dtype, a, dim3(ch.mpad / HBO_TILE, pairs, 1), sa);
+      c->last_post_resident = 0;
       launch_post_colsq_split(dtype, w.vpart, t->npad, ch.ldq, ch.mpad, t->nblk, p.kchunk, s.colsq, sa);
     } else {
       if (counter) { a.work_counter = counter; hipMemsetAsync(counter, 0, sizeof(int), sa); a.persistent = 2 * p.n_cus; }
       launch_gemm(dtype, a, dim3(ch.mpad / HBO_TILE, t->nblk, 1), sa);
+      c->last_post_resident = a.work_counter && a.persistent > 0;   // (gemm.hip: gemm_plan keeps a one-task GEMM_POST with both resident)
     } }
   { ProfScope ps(c, "post_epilogue", 1, sa);
     PostArgs pa = {}; pa.Kxq = s.K; pa.ldq = ch.ldq; pa.npad = t->npad; pa.n = (int)t->n; pa.nblk = t->nblk; pa.alpha = t->svec; pa.colsq = s.colsq; pa.mupart = s.mupart;
@@ -468,6 +470,7 @@ static int posterior(hbo_ctx* c, const hbo_model* m, hbo_cache* k, const void* x
   const size_t es = esize(dtype);
   const PostCall pc = {c, m, k, ov ? ov->md : c->d_model, ov ? ov->mlp_w : c->d_mlp_w, ov ? ov->mlp_b : c->d_mlp_b, acq_id, param, add_noise, scale};
   PostPlan p = post_plan(c, m, M, k ? k->t->nblk : 0, full_cov != 0, ov ? &ov->lane : nullptr);
+  c->last_post_resident = 0;
   if (p.refuse) return fail(c, p.refuse, "posterior: full_cov limited to 65536 queries");
   PostWs w;
   rc = post_acquire(pc, M, ov, acq_out != nullptr, p, w);

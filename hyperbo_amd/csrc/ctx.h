@@ -112,6 +112,7 @@ struct hbo_ctx {
   int opt_post_serial = 0;     // hbo_tune("post_serial"): the streamed posterior's producer side (cross Gram) on the SAME stream as its products: isolated stage times
   int opt_spd_diag_bound = 0;  // hbo_tune("spd_diag_bound"), test hook: hbo_spd_solve reads max_i A_ii off its host matrix, so that it can take the f16x2 form
   int last_chol_form = 0;      // Fp32Form of the last run_potrf's trailing updates (hbo_get_option "chol_form")
+  int last_post_resident = 0;  // the last posterior product (V = W Kxq: GEMM_POST, or post3.hip's) ran as a resident grid drawing tiles from a counter (hbo_get_option "post_resident")
   int last_inv_forms = 0;      // since the last run_potrf: 1 / 2 a level of the inverse ran on bf16x3 / f16x2 (trtri_level3), 4 / 8 K^-1 = W^T W did (hbo_get_option "inv_forms")
   int opt_fault_shard = 0;     // hbo_tune("fault_shard"): ONE-SHOT fault injection for the tests of the sharded objective's failure paths
   bool comm_aborted = false;   // set by comm_abort: sharded calls fail with HBO_ERR_COMM until hbo_comm_init builds a new communicator

@@ -386,7 +386,7 @@ struct Split3Block { const float* in; int64_t ld, gstep; unsigned short* out; in
 void launch_split3_block(const Split3Block& a, int ngrp, bool transposed, hipStream_t st);
 void launch_split3_panel(const Syrk3Args& a, int row_tiles, int ntasks, hipStream_t st);
 void launch_syrk3(const Syrk3Args& a, int ntiles, int ntasks, hipStream_t st);
-void launch_post3(const Post3Args& a, int col_tiles, hipStream_t st);
+bool launch_post3(const Post3Args& a, int col_tiles, hipStream_t st);   // true: it ran as a resident grid
 
 struct AcqGradArgs {
   const void* Fq; const void* F; int fdim; int64_t n; int npad;   // kernel features: queries [M][fdim], training [n][fdim]

@@ -532,7 +532,7 @@ float post2h_scale_for(double bound) {
   return ldexpf(1.f, 14 - e);
 }
 template <bool H2>
-static void launch_post3_t(void (*kern)(Post3Args), Post3Args a, hipStream_t st) {
+static bool launch_post3_t(void (*kern)(Post3Args), Post3Args a, hipStream_t st) {
   constexpr int LDS = Pipe<H2>::LDS_BYTES;
   static unsigned long long seen = 0;
   if (hbo_first_use_on_device(seen))
@@ -541,15 +541,16 @@ static void launch_post3_t(void (*kern)(Post3Args), Post3Args a, hipStream_t st)
     int dev = 0, cus = 256;
     hipGetDevice(&dev); hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
     const int resident = 2 * cus;   // two workgroups per CU (amdgpu_waves_per_eu(2, 2))
-    if (a.col_tiles * a.nblk > 2 * resident) { hipLaunchKernelGGL(kern, dim3(resident, 1), dim3(256), LDS, st, a); return; }
+    if (a.col_tiles * a.nblk > 2 * resident) { hipLaunchKernelGGL(kern, dim3(resident, 1), dim3(256), LDS, st, a); return true; }
     a.work_counter = nullptr;
   }
   hipLaunchKernelGGL(kern, dim3(a.col_tiles, a.nblk), dim3(256), LDS, st, a);
+  return false;
 }
-void launch_post3(const Post3Args& a_in, int col_tiles, hipStream_t st) {
+// true: the launch was a resident grid drawing its tiles from a.work_counter
+bool launch_post3(const Post3Args& a_in, int col_tiles, hipStream_t st) {
   Post3Args a = a_in; a.col_tiles = col_tiles;
-  if (a.h2) launch_post3_t<true>(post2h_kernel, a, st);
-  else launch_post3_t<false>(post3_kernel, a, st);
+  return a.h2 ? launch_post3_t<true>(post2h_kernel, a, st) : launch_post3_t<false>(post3_kernel, a, st);
 }
 
 void launch_split3_panel(const Syrk3Args& a, int row_tiles, int ntasks, hipStream_t st) {

@@ -335,7 +335,10 @@ int hbo_set_option(hbo_ctx* ctx, const char* name, int64_t value);
  *                         observations, n > 128, an MLP basis, a linear_mlp mean, a Kumaraswamy kernel) keep the per-sample path.
  *                         The library only stores it: the Python layer reads it back and routes its calls.
  * hbo_get_option reads an option back (the same names; unknown names are an error), and the read-only eig_sweeps: the outer Jacobi
- * sweeps of the last hbo_sym_eig / hbo_nll_spectral call (largest over its batches). */
+ * sweeps of the last hbo_sym_eig / hbo_nll_spectral call (largest over its batches); and the read-only post_resident: 1 when the
+ * product V = L^-1 Kxq of the context's last hbo_predict / hbo_acq call (of its last chunk) ran as a resident grid drawing its tiles
+ * from a counter, 0 when it ran as a plain grid, was split along K, or the call had no cache or was refused.  The results do not
+ * depend on it; it is there for the tests to know which launch they checked (chol_form / inv_forms: hbo_tune.h). */
 int hbo_get_option(hbo_ctx* ctx, const char* name, int64_t* out);
 
 /* ---- symmetric eigensolver: the device form of the reference's SVD routines (objectives.py:157-176, linalg.py:113-126,

@@ -58,7 +58,8 @@
  *   chol_form              form of the trailing updates of the context's last factorisation: 0 fp32 MFMA (and all of fp64), 1 bf16x3,
  *                          2 f16x2 (the profile's stage names are the same for all three)
  *   inv_forms              what ran on the 16-bit matrix cores since that factorisation, as bits: 1 / 2 a level of the inverse on bf16x3 /
- *                          f16x2 (syrk3_kernel modes 1 and 2), 4 / 8 K^-1 = W^T W on bf16x3 / f16x2 (mode 3); 0: all on fp32 / fp64 MFMA */
+ *                          f16x2 (syrk3_kernel modes 1 and 2), 4 / 8 K^-1 = W^T W on bf16x3 / f16x2 (mode 3); 0: all on fp32 / fp64 MFMA
+ *   post_resident          (documented in hbo.h) 1: the last posterior product ran as a resident grid */
 #ifndef HBO_TUNE_H_
 #define HBO_TUNE_H_
 #include "hbo.h"
