@@ -36,6 +36,29 @@ def make_model(rng, mean_name, mlp_kernel, d, dtype=np.float64):
   return model
 
 
+def lengthscale(rng, fdim, ls):
+  """Raw length-scales.  ARD: fdim length-scales around 0.5 sqrt(fdim) (a Gram matrix that neither decays to the diagonal nor fills
+  with ones on inputs in [0, 1]^fdim or on tanh features), each its own; scalar: one length-scale (the n_ls == 1 sums)."""
+  return inv_softplus(0.5 * np.sqrt(fdim) * np.exp(rng.uniform(-0.4, 0.4, size=(fdim if ls == 'ard' else 1))))
+
+
+def mlp_model(rng, d, feats, kname, ls):
+  """Raw params.model of a kernel on the MLP basis d -> feats under a linear_mlp mean (signal variance 0.8, noise 0.1)."""
+  flast = feats[-1]
+  model = {'signal_variance': inv_softplus(0.8), 'noise_variance': inv_softplus(0.1),
+           'linear_mean': {'kernel': rng.normal(size=(flast, 1)) / np.sqrt(flast), 'bias': rng.normal(size=1)}, 'mlp_params': {}}
+  if kname == 'dot_product':
+    model['dot_prod_sigma'] = inv_softplus(0.5 * np.sqrt(flast))
+    model['dot_prod_bias'] = np.array(0.2)
+  else:
+    model['lengthscale'] = lengthscale(rng, flast, ls)
+  fin = d
+  for l, f in enumerate(feats):
+    model['mlp_params'][f'Dense_{l}'] = {'kernel': rng.normal(size=(fin, f)) * (2.0 / np.sqrt(fin)), 'bias': rng.normal(size=f) * 0.1}
+    fin = f
+  return model
+
+
 def flatten(tree):
   out = []
   def rec(t):

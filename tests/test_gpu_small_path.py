@@ -136,12 +136,6 @@ WIDTH_SIZES = [128, 90, 33, 2]
 WIDTHS = [15, 16, 17, 31, 32, 33, 64, 65, 256]   # 256: HBO_MAX_FEATURE_DIM
 
 
-def _lengthscale(rng, fdim, ls):
-  """ARD: fdim length-scales around 0.5 sqrt(fdim) (a Gram matrix that neither decays to the diagonal nor fills with ones on
-  inputs in [0, 1]^fdim or on tanh features), each its own; scalar: one length-scale (the n_ls == 1 sum of small.hip)."""
-  return helpers.inv_softplus(0.5 * np.sqrt(fdim) * np.exp(rng.uniform(-0.4, 0.4, size=(fdim if ls == 'ard' else 1))))
-
-
 @pytest.mark.parametrize('ls', ['ard', 'scalar'])
 @pytest.mark.parametrize('dtype', [np.float64, np.float32], ids=['fp64', 'fp32'])
 @pytest.mark.parametrize('kname', STATIONARY)
@@ -151,7 +145,7 @@ def test_input_width_per_leaf(gpu_ctx, d, kname, dtype, ls):
   compared with the oracle only: from 32 features the blocked path takes the matrix-core Gram, this path the direct form."""
   defs, kernel, mean, _, _ = _native()
   rng = np.random.default_rng([d, STATIONARY.index(kname), int(dtype == np.float32), int(ls == 'scalar')])
-  model = _cast({'lengthscale': _lengthscale(rng, d, ls), 'signal_variance': helpers.inv_softplus(0.8),
+  model = _cast({'lengthscale': helpers.lengthscale(rng, d, ls), 'signal_variance': helpers.inv_softplus(0.8),
                  'noise_variance': helpers.inv_softplus(0.1),
                  'linear_mean': {'kernel': rng.normal(size=(d, 1)) / np.sqrt(d), 'bias': rng.normal(size=1)}}, dtype)
   po, pn = o.GPParams(model=_cast(model, np.float64)), defs.GPParams(model=model)
@@ -159,22 +153,6 @@ def test_input_width_per_leaf(gpu_ctx, d, kname, dtype, ls):
   g, _ = _check_nll_and_grad(gpu_ctx, mean.linear, getattr(kernel, kname), pn, dsn, o.linear, getattr(o, kname), po, dso, dtype,
                              f'width d={d} {ls}', blocked=dtype == np.float64)
   assert g['lengthscale'].shape == ((d,) if ls == 'ard' else (1,))
-
-
-def _mlp_model(rng, d, feats, kname, ls):
-  flast = feats[-1]
-  model = {'signal_variance': helpers.inv_softplus(0.8), 'noise_variance': helpers.inv_softplus(0.1),
-           'linear_mean': {'kernel': rng.normal(size=(flast, 1)) / np.sqrt(flast), 'bias': rng.normal(size=1)}, 'mlp_params': {}}
-  if kname == 'dot_product':
-    model['dot_prod_sigma'] = helpers.inv_softplus(0.5 * np.sqrt(flast))
-    model['dot_prod_bias'] = np.array(0.2)
-  else:
-    model['lengthscale'] = _lengthscale(rng, flast, ls)
-  fin = d
-  for l, f in enumerate(feats):
-    model['mlp_params'][f'Dense_{l}'] = {'kernel': rng.normal(size=(fin, f)) * (2.0 / np.sqrt(fin)), 'bias': rng.normal(size=f) * 0.1}
-    fin = f
-  return model
 
 
 # (last layer, kernel, length-scale): the dot product at 33 features only -- it has no length-scale, its features' gradient is all
@@ -190,7 +168,7 @@ def test_mlp_last_layer_width_per_leaf(gpu_ctx, flast, kname, ls, dtype):
   defs, kernel, mean, _, _ = _native()
   rng = np.random.default_rng([flast, (STATIONARY + ['dot_product']).index(kname), int(dtype == np.float32), int(ls == 'scalar'), 7])
   d, feats = 5, (12, flast)
-  model = _cast(_mlp_model(rng, d, feats, kname, ls), dtype)
+  model = _cast(helpers.mlp_model(rng, d, feats, kname, ls), dtype)
   cfg = {'mlp_features': feats}
   po, pn = o.GPParams(model=_cast(model, np.float64), config=dict(cfg)), defs.GPParams(model=model, config=dict(cfg))
   dso, dsn = _batch(rng, WIDTH_SIZES, d, dtype)
@@ -206,7 +184,7 @@ def test_se_kumar_per_leaf_fp64(gpu_ctx, d):
   defs, kernel, mean, objectives, utils = _native()
   rng = np.random.default_rng([d, 17])
   model = helpers.make_model(rng, 'constant', False, d)
-  model['lengthscale'] = _lengthscale(rng, d, 'ard')
+  model['lengthscale'] = helpers.lengthscale(rng, d, 'ard')
   model['kumar_params'] = {'a': rng.uniform(-1.5, 1.5, size=d), 'b': rng.uniform(-1.5, 1.5, size=d)}
   dso = {}
   for n in (128, 100, 64, 17, 1):
