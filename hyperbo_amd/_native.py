@@ -96,6 +96,25 @@ class LbfgsEval(C.Structure):
 LBFGS_START, LBFGS_MAIN, LBFGS_LINE_SEARCH, LBFGS_IDLE = 0, 1, 2, 3
 (LBFGS_RUNNING, LBFGS_CONVERGED_AT_START, LBFGS_CONVERGED, LBFGS_NO_PROGRESS, LBFGS_INSTABILITY, LBFGS_STEPS_DONE) = range(6)
 
+class AcqOptOpts(C.Structure):
+  """hbo_acq_opt_opts: the options of the projected L-BFGS of hbo_acq_maximize."""
+  _fields_ = [('memory', C.c_int32), ('ls_steps', C.c_int32), ('max_iters', C.c_int32), ('c1', C.c_double), ('tau', C.c_double),
+              ('pgtol', C.c_double), ('ftol', C.c_double)]
+
+
+class AcqOptEval(C.Structure):
+  """hbo_acq_opt_eval: one record of the log of hbo_acq_maximize."""
+  _fields_ = [('kind', C.c_int32), ('iter', C.c_int32), ('alpha', C.c_double), ('value', C.c_double)]
+
+
+# the same record as a NumPy dtype ([evals, R] logs)
+ACQ_OPT_EVAL_DTYPE = np.dtype([('kind', np.int32), ('iter', np.int32), ('alpha', np.float64), ('value', np.float64)])
+
+ACQ_OPT_S_EVALS = 8   # csrc/acq_opt_ctl.h: the header word of a start's state that counts its evaluations
+# hbo_acq_opt_kind / hbo_acq_opt_status
+ACQ_OPT_START, ACQ_OPT_MAIN, ACQ_OPT_LINE_SEARCH, ACQ_OPT_IDLE = 0, 1, 2, 3
+(ACQ_OPT_RUNNING, ACQ_OPT_CONVERGED, ACQ_OPT_FTOL, ACQ_OPT_NO_PROGRESS, ACQ_OPT_NONFINITE_AT_START, ACQ_OPT_STEPS_DONE) = range(6)
+
 # hbo_train_warp / hbo_train_target
 TRAIN_WARP_IDENTITY, TRAIN_WARP_SOFTPLUS, TRAIN_WARP_SOFTPLUS_EPS, TRAIN_WARP_SQUAREPLUS = 0, 1, 2, 3
 (TRAIN_NONE, TRAIN_LENGTHSCALE, TRAIN_SIGNAL_VARIANCE, TRAIN_NOISE_VARIANCE, TRAIN_CONSTANT, TRAIN_DOT_PROD_SIGMA, TRAIN_DOT_PROD_BIAS,
@@ -129,6 +148,13 @@ SIGNATURES = {
                                _P, C.POINTER(C.c_double)]),
     'hbo_acq_grad_samples': (C.c_int, [_P, _P, C.c_int32, C.POINTER(_P), _P, C.c_int64, C.c_int, C.POINTER(C.c_double),
                                        C.POINTER(C.c_double), C.c_double, _P, C.POINTER(C.c_double)]),
+    'hbo_probe_acq_grad_samples64': (C.c_int, [_P, _P, C.c_int32, C.POINTER(_P), _P, C.c_int64, C.c_int, C.POINTER(C.c_double),
+                                               C.POINTER(C.c_double), C.c_double, _P, C.POINTER(C.c_double), C.POINTER(C.c_double)]),   # hbo_tune.h (test hook)
+    'hbo_acq_opt_state_doubles': (C.c_int64, [C.c_int32, C.c_int32]),
+    'hbo_acq_maximize': (C.c_int, [_P, _P, C.c_int32, C.POINTER(_P), _P, C.c_int32, _P, _P, C.c_int, C.POINTER(C.c_double),
+                                   C.POINTER(C.c_double), C.c_double, C.POINTER(AcqOptOpts), _P, C.c_int32, _P, _P, _P, _P]),
+    'hbo_probe_acq_opt_ctl': (C.c_int, [_P, C.c_int32, C.c_int, C.POINTER(AcqOptOpts), _P, _P, _P, _P, _P, C.c_int32, _P, _P,
+                                        C.POINTER(AcqOptEval), C.POINTER(C.c_int32)]),   # include/hbo_tune.h (test hook)
     'hbo_bo_simulated': (C.c_int, [_P, _P, C.POINTER(BoRun), C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_double), _P, _P,
                                    C.POINTER(C.c_int32)]),
     'hbo_predict': (C.c_int, [_P, C.POINTER(Model), _P, _P, C.c_int64, C.c_int, _P, _P]),

@@ -217,6 +217,50 @@ def _acq_fused_unmet(model, sub_dataset_key, n_samples=1, n_kept=None, enabled=N
   return None
 
 
+ACQ_OPT_DEFAULTS = dict(memory=10, ls_steps=20, max_iters=200, c1=1e-4, tau=0.5, pgtol=1e-5, ftol=2.2e-9)
+ACQ_OPT_SEGMENT = 48       # evaluations per hbo_acq_maximize call (profiles/acq_opt.md: how it was chosen)
+ACQ_OPT_MAX_EVALS = 4096   # evaluations a maximisation may spend in all
+
+
+def _acq_opt_unmet(model, sub_dataset_key, acfun_sub, n_samples=1, n_kept=None):
+  """The first condition that keeps a maximisation off the device loop (hbo_acq_maximize), as a message, or None: an acquisition
+  function outside the native registry, then `_acq_fused_unmet`'s conditions without the option check.  Host-side checks only."""
+  if acfun_sub not in _NATIVE_ID:
+    return f'the acquisition function {getattr(acfun_sub, "__name__", acfun_sub)!r} is not one of the native ones (EI, PI, UCB)'
+  return _acq_fused_unmet(model, sub_dataset_key, n_samples, n_kept, enabled=True)
+
+
+def _device_maximize(built, handles, noises, x0, lo, hi, acq_id, acfun_param, scale, opts, want_log):
+  """hbo_acq_maximize in segments of opts['segment'] evaluations until no start is RUNNING or opts['max_evals'] are spent.
+  x0 [R, D] in the model dtype; lo / hi [D] float64 or None.  Returns (x [R, D], values [R], status [R], evaluations [R], log or None)."""
+  s_count, (r_count, d) = len(built), x0.shape
+  ctx = handles[0].ctx
+  structs = (nat.Model * s_count)(*[b.struct for b in built])
+  caches = (nat.C.c_void_p * s_count)(*[h.handle for h in handles])
+  prm = (nat.C.c_double * s_count)(*([float(acfun_param)] * s_count))
+  nse = (nat.C.c_double * s_count)(*[float(v) for v in noises])
+  o = nat.AcqOptOpts(*[opts[k] for k in ('memory', 'ls_steps', 'max_iters', 'c1', 'tau', 'pgtol', 'ftol')])
+  ns = nat.lib().hbo_acq_opt_state_doubles(d, o.memory)
+  state = np.zeros((r_count, max(ns, 1)), dtype=np.float64)
+  x = np.zeros((r_count, d), dtype=np.float64)
+  val = np.full(r_count, np.nan)
+  status = np.zeros(r_count, dtype=np.int32)
+  logs, spent = [], 0
+  while spent < opts['max_evals']:
+    evals = int(min(opts['segment'], opts['max_evals'] - spent))
+    log = np.zeros((evals, r_count), dtype=nat.ACQ_OPT_EVAL_DTYPE) if want_log else None
+    ctx.check(nat.lib().hbo_acq_maximize(ctx.handle, structs, s_count, caches, nat.ptr(x0), r_count, nat.ptr(lo), nat.ptr(hi), int(acq_id),
+                                         prm, nse, float(scale), nat.C.byref(o), nat.ptr(state), evals, nat.ptr(x), nat.ptr(val),
+                                         nat.ptr(status), nat.ptr(log)))
+    spent += evals
+    if want_log:
+      logs.append(log)
+    if not np.any(status == nat.ACQ_OPT_RUNNING):
+      break
+  n_evals = state[:, nat.ACQ_OPT_S_EVALS].astype(np.int64)
+  return x, val, status, n_evals, (np.concatenate(logs) if want_log else None)
+
+
 def _fused_value_and_grad(built, handles, noises, xq, acq_id, acfun_param, scale):
   """((S, M, 1) values in the model dtype, (S, M, D) gradients in float64) of S models over their finished factors: one
   hbo_acq_grad_samples call -- one upload, one launch, one copy back."""
@@ -350,7 +394,60 @@ def acfun_wrapper(acfun_sub, acfun_callback_default):
                                      grad.ctypes.data_as(nat.C.POINTER(nat.C.c_double))))
     return out, grad
 
+  def maximize(*, model, sub_dataset_key, x_init, bounds=None, acfun_callback=acfun_callback_default, opts=None):
+    """Maximises the acquisition function over a box on the device (hbo_acq_maximize: projected L-BFGS, every start in one call, no
+    host round trip per evaluation).  x_init [D] or [R, D]: the starts; bounds: None ([0, 1]^D) or D (lo, hi) pairs; opts: overrides
+    of ACQ_OPT_DEFAULTS, plus 'segment' (evaluations per call), 'max_evals' and 'log' (keep the per-evaluation log).
+    Returns (x_best [D] float64, value_best, info): the start with the largest finite value wins, the lowest index among equals;
+    without any, x_init[0] and NaN.  info: per-start 'x', 'value', 'status', 'evals', and 'log' ([evaluations, R] records) on
+    request.  Works on the cached factors value_and_grad uses; a model the device loop does not cover raises
+    HboError(HBO_ERR_UNSUPPORTED) -- there is no fall-back."""
+    o = dict(ACQ_OPT_DEFAULTS, segment=ACQ_OPT_SEGMENT, max_evals=ACQ_OPT_MAX_EVALS, log=False)
+    o.update(opts or {})
+    x_init = np.atleast_2d(np.asarray(x_init, dtype=np.float64))
+    hgp = isinstance(model, gp.HGP)
+    samples = model.get_model_params_samples() if hgp else None
+    n_samples = len(samples) if hgp else 1
+    unmet = _acq_opt_unmet(model, sub_dataset_key, acfun_sub, n_samples)
+    if unmet is not None:
+      raise nat.HboError(nat.HBO_ERR_UNSUPPORTED, 'ac_func.maximize: ' + unmet)
+    acfun_param = acfun_callback(model, sub_dataset_key)
+    if hgp:
+      sd = model.dataset[sub_dataset_key]
+      dtype = _model.infer_dtype(sd.x, sd.y)
+      built, noises = _sample_models(model, samples, dtype)
+      handles = _hgp_sample_caches(model, sub_dataset_key, samples, dtype)
+      unmet = _acq_opt_unmet(model, sub_dataset_key, acfun_sub, n_samples, len(handles))
+      if unmet is not None:
+        raise nat.HboError(nat.HBO_ERR_UNSUPPORTED, 'ac_func.maximize: ' + unmet)
+      _, scale = model.predict_noise_and_scale(True, True)
+    else:
+      model.setup_predictor(sub_dataset_key)
+      handle = model.params.cache[sub_dataset_key].handle
+      dtype = handle.dtype
+      add_noise, scale = model.predict_noise_and_scale(True, True)
+      built = [_model.BuiltModel(model.mean_func, model.cov_func, model.params, model.warp_func, dtype, model.input_dim)]
+      handles, noises = [handle], [add_noise]
+    lo = hi = None
+    if bounds is not None:
+      b = np.asarray(bounds, dtype=np.float64).reshape(model.input_dim, 2)
+      lo, hi = np.ascontiguousarray(b[:, 0]), np.ascontiguousarray(b[:, 1])
+    x0 = np.ascontiguousarray(x_init, dtype=dtype)
+    x, val, status, n_evals, log = _device_maximize(built, handles, noises, x0, lo, hi, _NATIVE_ID[acfun_sub], acfun_param, scale, o,
+                                                    bool(o['log']))
+    if hgp:
+      model.update_model_params(samples[-1])   # as every HGP path here leaves it (gp.py:674-678)
+    info = {'x': x, 'value': val, 'status': status, 'evals': n_evals}
+    if o['log']:
+      info['log'] = log
+    finite = np.isfinite(val)
+    if not finite.any():
+      return x_init[0].copy(), float('nan'), info
+    best = int(np.argmax(np.where(finite, val, -np.inf)))
+    return x[best].copy(), float(val[best]), info
+
   acquisition_function.value_and_grad = value_and_grad
+  acquisition_function.maximize = maximize
   return acquisition_function
 
 

@@ -44,9 +44,16 @@ def retrain_model(model, sub_dataset_key, random_key=None, get_params_path=None,
 def bayesopt(key, model, sub_dataset_key, query_oracle, ac_func, iters, input_sampler):
   """bayesopt.py:75-133: continuous BO on [0,1]^D -- pick the best of `input_sampler`'s candidates, then
   L-BFGS-B on -ac_func from there (SciPy's, the one jaxopt.ScipyBoundedMinimize wraps) with the native
-  `ac_func.value_and_grad`, query the oracle, append."""
+  `ac_func.value_and_grad`, query the oracle, append.
+
+  With config['acq_opt_on_device'] set, the SciPy call is replaced by `ac_func.maximize` (hbo_acq_maximize: the optimiser itself on
+  the device) from the config['acq_opt_starts'] (default 1) best candidates -- ordered by acquisition value, the lower index first
+  among equals -- once the sub-dataset has observations; an iteration without any (the prior branch) takes the SciPy path.  There is
+  no fall-back: the iteration at which the sub-dataset has grown past 128 observations raises HboError(HBO_ERR_UNSUPPORTED)."""
   rng = _rng(key)
   input_dim = model.input_dim
+  cfg = model.params.config or {}
+  on_device = bool(cfg.get('acq_opt_on_device'))
   bounds = [(0.0, 1.0)] * input_dim
   for i in range(iters):
     start_time = time.time()
@@ -60,6 +67,9 @@ def bayesopt(key, model, sub_dataset_key, query_oracle, ac_func, iters, input_sa
     x_init = np.asarray(x_samples[select_idx], dtype=np.float64)
     if ac_func.__name__ in ('rand', 'random_search'):
       x_opt = x_init
+    elif on_device and model.has_observations(sub_dataset_key):
+      starts = np.argsort(-np.asarray(evals, dtype=np.float64).reshape(-1), kind='stable')[:max(1, int(cfg.get('acq_opt_starts', 1)))]
+      x_opt, _, _ = ac_func.maximize(model=model, sub_dataset_key=sub_dataset_key, x_init=x_samples[starts])
     else:
       def neg_acq(x):
         val, grad = ac_func.value_and_grad(model=model, sub_dataset_key=sub_dataset_key, x_queries=x[None, :])

@@ -25,7 +25,7 @@ __global__ __launch_bounds__(256) void acq_small_kernel(AcqSmallArgs a) {
   T* acq = static_cast<T*>(a.acq_out) + (int64_t)s * a.M + q;
   double* g = a.grad_out + ((int64_t)s * a.M + q) * D;
   if (sm.bad) {   // (uniform) the factor is not positive definite: NaN rows, as hbo_acq_grad
-    if (tid == 0) *acq = (T)NAN;
+    if (tid == 0) { *acq = (T)NAN; if (a.val64_out) a.val64_out[(int64_t)s * a.M + q] = NAN; }
     for (int d = tid; d < D; d += 256) g[d] = NAN;
     return;
   }
@@ -101,6 +101,7 @@ __global__ __launch_bounds__(256) void acq_small_kernel(AcqSmallArgs a) {
     else { const double uu = (mu - sm.param) / sd; val = sd * ei_over_sd(uu); amu = norm_cdf(uu); asd = norm_pdf(uu); }
     s_amu = amu; s_avar = asd / (2.0 * sd) * a.scale;
     *acq = (T)val;
+    if (a.val64_out) a.val64_out[(int64_t)s * a.M + q] = val;
   }
   __syncthreads();
   const double amu = s_amu, avar = s_avar;

@@ -333,6 +333,49 @@ struct hbo_cache {
   unsigned int* d_wmax = nullptr;    // device: bits of max |W|
 };
 
+// What hbo_acq_grad_samples and hbo_acq_maximize ask of their S (model, cache) pairs, before any device work: one model family without
+// input warp, MLP basis or linear_mlp mean, and finished caches of 1..128 observations that match their models.  *any_bad: a cache is
+// not positive definite.
+static int acq_samples_check(hbo_ctx* c, const std::string& fn, const hbo_model* models, int32_t S, hbo_cache* const* caches, bool* any_bad) {
+  const hbo_model* m0 = &models[0];
+  for (int s = 0; s < S; ++s) {
+    const hbo_model* m = &models[s];
+    // (before validate_model: a packed array element has no hbo_model_kumar tail to read)
+    if (m->input_warp != HBO_WARP_NONE)
+      return fail(c, HBO_ERR_UNSUPPORTED, fn + "input-warped (Kumaraswamy) models are not supported; evaluate the samples with hbo_acq_grad");
+    int rc = validate_model(c, m);
+    if (rc) return rc;
+    if (!same_model_family(m, m0)) return fail(c, HBO_ERR_ARG, fn + "the samples must share dtype, covariance, mean and input_dim");
+    if (m->kernel_uses_mlp) return fail(c, HBO_ERR_UNSUPPORTED, fn + "a kernel on an MLP basis is not supported; evaluate the samples with hbo_acq_grad");
+    if (m->mean_id == HBO_MEAN_LINEAR_MLP) return fail(c, HBO_ERR_UNSUPPORTED, fn + "a linear_mlp mean is not supported; evaluate the samples with hbo_acq_grad");
+    const hbo_cache* k = caches[s];
+    if (!k || !k->t || k->t->n <= 0) return fail(c, HBO_ERR_UNSUPPORTED, fn + "a sample without observations (the prior branch) is not supported; evaluate it with hbo_acq_grad");
+    if (k->t->n > HBO_TILE) return fail(c, HBO_ERR_UNSUPPORTED, fn + "a cache has n > 128; evaluate the samples with hbo_acq_grad");
+    if (k->dtype != m->dtype || k->D != m->input_dim) return fail(c, HBO_ERR_ARG, fn + "cache/model mismatch");
+    if (k->input_warp != m->input_warp) return fail(c, HBO_ERR_ARG, fn + "the cache was factorised with another input warp");
+    *any_bad = *any_bad || k->info != INT_MAX;
+  }
+  return HBO_OK;
+}
+
+// the records acq_small_kernel reads of those pairs (hbo_internal.h: AcqSmallSample) and their per-feature values, hv [S][2 D]
+static void acq_small_pack(AcqSmallSample* hs, double* hv, const hbo_model* models, int32_t S, hbo_cache* const* caches, const double* params,
+                           const double* add_noise) {
+  const int D = models[0].input_dim;
+  ModelDev md;
+  for (int s = 0; s < S; ++s) {
+    const hbo_cache* k = caches[s]; const TaskHost* t = k->t;
+    fill_model_dev(md, &models[s]);
+    AcqSmallSample& r = hs[s];
+    memset(&r, 0, sizeof r);
+    r.F = k->h_desc.F; r.W = t->W; r.alpha = t->svec; r.ld = t->ld; r.n = (int)t->n; r.bad = k->info != INT_MAX;
+    r.sv = md.sv; r.inv_sigma2 = 1.0 / (md.dot_sigma * md.dot_sigma); r.bias2 = md.dot_bias * md.dot_bias;
+    r.constant = md.constant; r.linear_bias = md.linear_bias; r.param = params[s]; r.add_noise = add_noise[s];
+    memcpy(hv + (size_t)s * 2 * D, md.inv_ls, sizeof(double) * D);
+    memcpy(hv + (size_t)s * 2 * D + D, md.lin_w, sizeof(double) * D);
+  }
+}
+
 static void fill_nan(void* p, size_t count, int dtype) {
   if (dtype == HBO_F64) for (size_t i = 0; i < count; ++i) ((double*)p)[i] = NAN;
   else for (size_t i = 0; i < count; ++i) ((float*)p)[i] = NAN;

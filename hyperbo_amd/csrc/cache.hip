@@ -758,9 +758,10 @@ extern "C" int hbo_acq_grad(hbo_ctx* c, const hbo_model* m, hbo_cache* k, const 
 //      a workgroup per (sample, query) pair), one copy back, one wait -- whatever S is.  Row s = hbo_acq_grad of sample s up to the order
 //      of summation.  The prior branch, MLP bases and input-warped models stay with hbo_acq_grad (HBO_ERR_UNSUPPORTED here, before any
 //      device work).
-extern "C" int hbo_acq_grad_samples(hbo_ctx* c, const hbo_model* models, int32_t S, hbo_cache* const* caches, const void* xq, int64_t M,
-                                    int acq_id, const double* params, const double* add_noise, double scale, void* acq_out,
-                                    double* grad_out) {
+//      val64_out (nullable, [S][M]): the values before they are rounded to the model dtype (include/hbo_tune.h:
+//      hbo_probe_acq_grad_samples64); without it the call is hbo_acq_grad_samples, to the byte of every buffer.
+static int acq_grad_samples(hbo_ctx* c, const hbo_model* models, int32_t S, hbo_cache* const* caches, const void* xq, int64_t M, int acq_id,
+                            const double* params, const double* add_noise, double scale, void* acq_out, double* grad_out, double* val64_out) {
   if (!models || !caches || !xq || !params || !add_noise || !acq_out || !grad_out) return fail(c, HBO_ERR_ARG, "hbo_acq_grad_samples: null argument");
   if (S <= 0 || S > 4096) return fail(c, HBO_ERR_ARG, "hbo_acq_grad_samples: 1 <= S <= 4096");
   if (acq_id < 0 || acq_id > HBO_ACQ_UCB) return fail(c, HBO_ERR_ARG, "hbo_acq_grad_samples: bad acq_id");
@@ -768,23 +769,7 @@ extern "C" int hbo_acq_grad_samples(hbo_ctx* c, const hbo_model* models, int32_t
   if (M < 0) return fail(c, HBO_ERR_ARG, "hbo_acq_grad_samples: M < 0");
   const hbo_model* m0 = &models[0];
   bool any_bad = false;
-  for (int s = 0; s < S; ++s) {
-    const hbo_model* m = &models[s];
-    // (before validate_model: a packed array element has no hbo_model_kumar tail to read)
-    if (m->input_warp != HBO_WARP_NONE)
-      return fail(c, HBO_ERR_UNSUPPORTED, "hbo_acq_grad_samples: input-warped (Kumaraswamy) models are not supported; evaluate the samples with hbo_acq_grad");
-    int rc = validate_model(c, m);
-    if (rc) return rc;
-    if (!same_model_family(m, m0)) return fail(c, HBO_ERR_ARG, "hbo_acq_grad_samples: the samples must share dtype, covariance, mean and input_dim");
-    if (m->kernel_uses_mlp) return fail(c, HBO_ERR_UNSUPPORTED, "hbo_acq_grad_samples: a kernel on an MLP basis is not supported; evaluate the samples with hbo_acq_grad");
-    if (m->mean_id == HBO_MEAN_LINEAR_MLP) return fail(c, HBO_ERR_UNSUPPORTED, "hbo_acq_grad_samples: a linear_mlp mean is not supported; evaluate the samples with hbo_acq_grad");
-    const hbo_cache* k = caches[s];
-    if (!k || !k->t || k->t->n <= 0) return fail(c, HBO_ERR_UNSUPPORTED, "hbo_acq_grad_samples: a sample without observations (the prior branch) is not supported; evaluate it with hbo_acq_grad");
-    if (k->t->n > HBO_TILE) return fail(c, HBO_ERR_UNSUPPORTED, "hbo_acq_grad_samples: a cache has n > 128; evaluate the samples with hbo_acq_grad");
-    if (k->dtype != m->dtype || k->D != m->input_dim) return fail(c, HBO_ERR_ARG, "hbo_acq_grad_samples: cache/model mismatch");
-    if (k->input_warp != m->input_warp) return fail(c, HBO_ERR_ARG, "hbo_acq_grad_samples: the cache was factorised with another input warp");
-    any_bad = any_bad || k->info != INT_MAX;
-  }
+  if (int rc = acq_samples_check(c, "hbo_acq_grad_samples: ", models, S, caches, &any_bad)) return rc;
   if (M == 0) return HBO_OK;
   HIPCHK(c, hipSetDevice(c->device));
   const int dtype = m0->dtype, D = m0->input_dim;
@@ -794,7 +779,8 @@ extern "C" int hbo_acq_grad_samples(hbo_ctx* c, const hbo_model* models, int32_t
   // one block up: [S records][S x 2 D doubles][M x D queries]; one block down: [S x M x D doubles][S x M values]
   const size_t smp_b = al(sizeof(AcqSmallSample) * S), vec_b = al(sizeof(double) * 2 * D * S), xq_b = (size_t)M * D * es;
   const size_t grad_b = al(sizeof(double) * (size_t)S * M * D), acq_b = (size_t)S * M * es;
-  const size_t in_b = smp_b + vec_b + xq_b, out_b = grad_b + acq_b;
+  const size_t v64_o = al(grad_b + acq_b), v64_b = val64_out ? sizeof(double) * (size_t)S * M : 0;
+  const size_t in_b = smp_b + vec_b + xq_b, out_b = val64_out ? v64_o + v64_b : grad_b + acq_b;
   char* d_in = static_cast<char*>(ws_get(c, WS_AF_IN, in_b));
   char* d_out = static_cast<char*>(ws_get(c, WS_AF_OUT, out_b));
   if (!d_in || !d_out) return HBO_ERR_HIP;
@@ -804,18 +790,7 @@ extern "C" int hbo_acq_grad_samples(hbo_ctx* c, const hbo_model* models, int32_t
   char* stage_out = stage + al(in_b);
   AcqSmallSample* hs = reinterpret_cast<AcqSmallSample*>(stage);
   double* hv = reinterpret_cast<double*>(stage + smp_b);
-  ModelDev md;
-  for (int s = 0; s < S; ++s) {
-    const hbo_cache* k = caches[s]; const TaskHost* t = k->t;
-    fill_model_dev(md, &models[s]);
-    AcqSmallSample& r = hs[s];
-    memset(&r, 0, sizeof r);
-    r.F = k->h_desc.F; r.W = t->W; r.alpha = t->svec; r.ld = t->ld; r.n = (int)t->n; r.bad = k->info != INT_MAX;
-    r.sv = md.sv; r.inv_sigma2 = 1.0 / (md.dot_sigma * md.dot_sigma); r.bias2 = md.dot_bias * md.dot_bias;
-    r.constant = md.constant; r.linear_bias = md.linear_bias; r.param = params[s]; r.add_noise = add_noise[s];
-    memcpy(hv + (size_t)s * 2 * D, md.inv_ls, sizeof(double) * D);
-    memcpy(hv + (size_t)s * 2 * D + D, md.lin_w, sizeof(double) * D);
-  }
+  acq_small_pack(hs, hv, models, S, caches, params, add_noise);
   memcpy(stage + smp_b + vec_b, xq, xq_b);
   HIPCHK(c, hipMemcpyAsync(d_in, stage, in_b, hipMemcpyHostToDevice, st));
   HIPCHK(c, hipEventRecord(c->ev_upload, st));
@@ -823,13 +798,27 @@ extern "C" int hbo_acq_grad_samples(hbo_ctx* c, const hbo_model* models, int32_t
   a.smp = reinterpret_cast<const AcqSmallSample*>(d_in); a.vec = reinterpret_cast<const double*>(d_in + smp_b); a.xq = d_in + smp_b + vec_b;
   a.D = D; a.M = M; a.kernel_id = m0->kernel_id; a.mean_id = m0->mean_id; a.acq_id = acq_id; a.scale = scale;
   a.grad_out = reinterpret_cast<double*>(d_out); a.acq_out = d_out + grad_b;
+  if (val64_out) a.val64_out = reinterpret_cast<double*>(d_out + v64_o);
   launch_acq_small(dtype, a, S, st);
   HIPCHK(c, hipMemcpyAsync(stage_out, d_out, out_b, hipMemcpyDeviceToHost, st));
   HIPCHK(c, hipStreamSynchronize(st));
   HIPCHK(c, hipGetLastError());
   memcpy(grad_out, stage_out, sizeof(double) * (size_t)S * M * D);
   memcpy(acq_out, stage_out + grad_b, acq_b);
+  if (val64_out) memcpy(val64_out, stage_out + v64_o, v64_b);
   return any_bad ? HBO_NOT_PD : HBO_OK;
+}
+extern "C" int hbo_acq_grad_samples(hbo_ctx* c, const hbo_model* models, int32_t S, hbo_cache* const* caches, const void* xq, int64_t M,
+                                    int acq_id, const double* params, const double* add_noise, double scale, void* acq_out,
+                                    double* grad_out) {
+  return acq_grad_samples(c, models, S, caches, xq, M, acq_id, params, add_noise, scale, acq_out, grad_out, nullptr);
+}
+// include/hbo_tune.h (TEST HOOK): hbo_acq_grad_samples with the fp64 values hbo_acq_maximize's control kernel reads
+extern "C" int hbo_probe_acq_grad_samples64(hbo_ctx* c, const hbo_model* models, int32_t S, hbo_cache* const* caches, const void* xq, int64_t M,
+                                            int acq_id, const double* params, const double* add_noise, double scale, void* acq_out,
+                                            double* grad_out, double* val64_out) {
+  if (!val64_out) return fail(c, HBO_ERR_ARG, "hbo_probe_acq_grad_samples64: val64_out is null");
+  return acq_grad_samples(c, models, S, caches, xq, M, acq_id, params, add_noise, scale, acq_out, grad_out, val64_out);
 }
 
 // ---- the simulated BO loop of R runs in one call (bayesopt.py:136-190; kernels and the recurrence: bo_loop.hip) ----

@@ -416,6 +416,7 @@ struct AcqSmallArgs {
   const void* xq; int D; int64_t M;                  // queries [M][D] (model dtype)
   int kernel_id, mean_id, acq_id; double scale;
   void* acq_out; double* grad_out;                   // [S][M] model dtype, [S][M][D]
+  double* val64_out;                                 // nullable [S][M]: the value before it is rounded to the model dtype (acq_opt.hip)
 };
 void launch_acq_small(int dtype, const AcqSmallArgs& a, int S, hipStream_t st);
 // ---- the simulated BO loop on the device (bo_loop.hip; host side: cache.hip: hbo_bo_simulated) ----

@@ -249,6 +249,51 @@ int hbo_acq_grad(hbo_ctx* ctx, const hbo_model* model, hbo_cache* cache, const v
 int hbo_acq_grad_samples(hbo_ctx* ctx, const hbo_model* models, int32_t S, hbo_cache* const* caches, const void* xq, int64_t M,
                          int acq_id, const double* params, const double* add_noise, double scale, void* acq_out, double* grad_out);
 
+/* ---- bayesopt()'s inner maximisation of the acquisition function on the device (hyperbo/bo_utils/bayesopt.py:116-125), R starts
+ *      in ONE call: a box-constrained projected L-BFGS that minimises f(x) = -(mean over the S samples of the acquisition) over
+ *      lo <= x <= hi (csrc/acq_opt_ctl.h; the algorithm: DESIGN.md section 6).  One upload, then `evals` rounds of two stream-ordered
+ *      launches -- hbo_acq_grad_samples' kernel on grid (R, S) over the starts' pending points, then one control workgroup per start,
+ *      which sums the S per-sample results in sample order (fp64), runs one step of the state machine and writes the next pending
+ *      point -- and one synchronisation and one copy back.  No atomics, every sum in a fixed order, no fused multiply-adds in the
+ *      control code: identical calls are bit-identical, a start does not depend on what shares the call, and a run gives the same
+ *      bits however it is cut into calls.
+ *      models, S, caches, acq_id, params, add_noise, scale: as hbo_acq_grad_samples (same checks, same refusals, same return codes).
+ *      x0 [R, input_dim] (model dtype): the starts.  lo, hi [input_dim] doubles (both null: 0 and 1); for an fp32 model they must be
+ *        fp32 numbers.  Every probe is clipped to the box component by component and rounded to the model dtype, so bounds are hit
+ *        exactly and x_out is representable in the model dtype.
+ *      opts: memory (10; at most 64), ls_steps (20), max_iters (200), c1 (1e-4), tau (0.5), pgtol (1e-5), ftol (2.2e-9) -- the defaults are
+ *        the caller's to fill in.  memory 1..64, ls_steps and max_iters >= 1, 0 < c1 < 1, 0 < tau < 1, pgtol and ftol >= 0.
+ *      state [R, hbo_acq_opt_state_doubles(input_dim, memory)], in / out: all zero = a fresh run from x0; otherwise the run goes on
+ *        where the call that left the state stopped (x0 is then not read).  A call that returns an error has not written it.
+ *      x_out [R, input_dim]: the iterate (the last accepted point).  val_out [R]: the acquisition value there (+mean, not f; NaN
+ *        before the first evaluation and after NONFINITE_AT_START).  status [R]: hbo_acq_opt_status.
+ *      log (nullable) [evals, R]: one record per round and start.  kind START (the first evaluation), LINE_SEARCH (a rejected probe),
+ *        MAIN (an accepted probe: main step `iter` is taken) or IDLE (the start had stopped: its evaluation ran on the old pending
+ *        point and was ignored; value 0); alpha: the probe's step; value: f at the point evaluated.
+ *      HBO_ERR_ARG (before any device work): those of hbo_acq_grad_samples, R outside 1..4096, evals outside 1..4096, bad opts,
+ *      lo > hi or not finite, an x0 outside the box or not finite, a state that is neither all zero nor one an earlier call left.
+ *      HBO_ERR_UNSUPPORTED (before any device work): those of hbo_acq_grad_samples, and a state (input_dim, opts.memory) beyond the
+ *      64 KB of LDS the control kernel stages it in (memory 10 fits every input_dim up to 256).
+ *      HBO_NOT_PD: a cache is not positive definite (every start then stops with NONFINITE_AT_START). */
+enum hbo_acq_opt_kind { HBO_ACQ_OPT_START = 0, HBO_ACQ_OPT_MAIN = 1, HBO_ACQ_OPT_LINE_SEARCH = 2, HBO_ACQ_OPT_IDLE = 3 };
+enum hbo_acq_opt_status {
+  HBO_ACQ_OPT_RUNNING = 0, HBO_ACQ_OPT_CONVERGED = 1, HBO_ACQ_OPT_FTOL = 2, HBO_ACQ_OPT_NO_PROGRESS = 3, HBO_ACQ_OPT_NONFINITE_AT_START = 4,
+  HBO_ACQ_OPT_STEPS_DONE = 5
+};
+typedef struct hbo_acq_opt_opts {
+  int32_t memory, ls_steps, max_iters;
+  double c1, tau, pgtol, ftol;
+} hbo_acq_opt_opts;
+typedef struct hbo_acq_opt_eval {
+  int32_t kind, iter;
+  double alpha, value;
+} hbo_acq_opt_eval;
+int64_t hbo_acq_opt_state_doubles(int32_t input_dim, int32_t memory);
+int hbo_acq_maximize(hbo_ctx* ctx, const hbo_model* models, int32_t S, hbo_cache* const* caches, const void* x0, int32_t R,
+                     const double* lo, const double* hi, int acq_id, const double* params, const double* add_noise, double scale,
+                     const hbo_acq_opt_opts* opts, double* state, int32_t evals, double* x_out, double* val_out, int32_t* status,
+                     hbo_acq_opt_eval* log);
+
 /* ---- the simulated BO loop over a pool of pre-evaluated candidates (hyperbo/bo_utils/bayesopt.py:136-190), every iteration of R
  *      independent runs in ONE call: all launches are queued up front and the results come back behind them: one synchronisation, at the end.
  *      Per iteration the host loop evaluates the acquisition function at the pool, takes np.argmax and appends the chosen (x, y); here

@@ -37,7 +37,8 @@
  *   poison        0/1      tests: an evaluation (objective / factor paths on the blocked pipeline) first fills what it is about to recompute --
  *                          the lower triangles of A and W, all of S, alpha, d f / d mu -- with NaN, so that a launch that skips work shows up
  *                          as NaN instead of hiding behind an earlier evaluation's identical numbers in the same pooled buffers; tests/conftest.py
- *                          turns it on for the whole GPU tier (default 0)
+ *                          turns it on for the whole GPU tier (default 0).  The per-evaluation scratch of hbo_acq_maximize (per-sample
+ *                          gradients and values of the pending points) and its device log come back filled as well
  *   fault_shard   0..2     ONE-SHOT fault injection into the next hbo_objective_sharded call of this context (tests of the failure
  *                          paths): 1 = the rank's local part counts as failed -> it joins the all-reduce with NaN in every slot;
  *                          2 = and it cannot produce that buffer either -> ncclCommAbort, the peers' all-reduce fails, later sharded
@@ -85,6 +86,21 @@ int hbo_probe_post_product(hbo_ctx* ctx, int form, const float* W, int64_t n, co
  * HBO_ERR_ARG (hbo_last_error(NULL)) on a bad argument. */
 int hbo_probe_lbfgs_ctl(double* state, int32_t P, const hbo_lbfgs_opts* opts, const double* x0, double value, const double* grad,
                         double* x_next, double* x_iter, hbo_lbfgs_eval* eval, int32_t* status);
+/* TEST HOOK: hbo_acq_grad_samples (same arguments, same launch, same results) that also returns val64_out [S, M]: the acquisition
+ * values before they are rounded to the model dtype -- what the control kernel of hbo_acq_maximize reads.  For an fp64 model
+ * val64_out equals acq_out to the bit. */
+int hbo_probe_acq_grad_samples64(hbo_ctx* ctx, const hbo_model* models, int32_t S, hbo_cache* const* caches, const void* xq, int64_t M,
+                                 int acq_id, const double* params, const double* add_noise, double scale, void* acq_out, double* grad_out,
+                                 double* val64_out);
+/* TEST HOOK: the control code of hbo_acq_maximize (csrc/acq_opt_ctl.h, the text its control kernel compiles) on the host, one thread,
+ * for one evaluation of one start; no context, no device.  D: input_dim; dtype: the model dtype the pending point is rounded to.
+ * lo, hi [D] (both null: 0 and 1).  vals [S] and grads [S, D]: the per-sample acquisition values (fp64) and gradients at the point the
+ * state wants evaluated: x0 [D] (doubles) for an all-zero state (x0 is then required), the x_next of the previous call otherwise.
+ * x_next [D]: the point to evaluate next; x_iter (nullable) [D]: the iterate; *eval: the log record; *status: hbo_acq_opt_status.
+ * HBO_ERR_ARG (hbo_last_error(NULL)) on a bad argument. */
+int hbo_probe_acq_opt_ctl(double* state, int32_t D, int dtype, const hbo_acq_opt_opts* opts, const double* lo, const double* hi,
+                          const double* x0, const double* vals, const double* grads, int32_t S, double* x_next, double* x_iter,
+                          hbo_acq_opt_eval* eval, int32_t* status);
 #ifdef __cplusplus
 }
 #endif
