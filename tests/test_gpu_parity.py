@@ -2455,10 +2455,13 @@ def test_fp32_posterior_on_bf16_matrix_cores_is_as_accurate_as_fp32_mfma(gpu_ctx
   """fp32 caches run the posterior product V = L^-1 Kxq on the bf16 MFMA from exact three-way splits of both operands
   (csrc/post3.hip; gp.py:295-305 is the reference's solve).  Claim under test: the result is fp32-accurate -- its error
   against the fp64 path is not larger than that of the fp32-MFMA product it replaces (same inputs, option off) -- for every
-  kernel of the registry, ragged sizes, several chunks; and the planes of W follow a row append of the cache."""
+  kernel of the registry, ragged sizes, several chunks; and the planes of W follow a row append of the cache: 1230 + 40 = 1270 rows
+  fit the 1280 of the ten blocks (ragged before and after), so hbo_cache_append runs -- the handle is asserted to be the same object
+  -- and the fp64 leg's posterior after it is held against the oracle, not only against itself."""
+  import types
   defs, _, acfun, gp, kernel, mean, _, utils = _native()
   rng = np.random.default_rng(77)
-  d, n, M = 6, 1300, 7000      # (enough candidates for the matrix-core product: below 2 x CUs tiles the split-K fp32 path takes over)
+  d, n, M = 6, 1270, 7000     # (enough candidates for the matrix-core product: below 2 x CUs tiles the split-K fp32 path takes over)
   isp = lambda v: np.log(np.expm1(np.asarray(v, dtype=np.float64)))
   model = {'lengthscale': isp(np.full(d, 0.8)), 'signal_variance': isp(1.2), 'noise_variance': isp(3e-2), 'constant': np.array(0.3),
            'dot_prod_sigma': isp(1.5), 'dot_prod_bias': np.array(0.4)}
@@ -2477,13 +2480,25 @@ def test_fp32_posterior_on_bf16_matrix_cores_is_as_accurate_as_fp32_mfma(gpu_ctx
       mu, var = g.predict(xq.astype(dt), 0)
       ei = acfun.expected_improvement(model=g, sub_dataset_key=0, x_queries=xq.astype(dt))
       # the cache grows by 40 rows (O(N^2) append): W changes, its bf16 planes must be rebuilt
+      h0 = g.params.cache[0].handle
       g.update_sub_dataset(defs.SubDataset(x[n - 40:].astype(dt), y[n - 40:].astype(dt)), 0, is_append=True)
       mu2, var2 = g.predict(xq.astype(dt), 0)
+      assert g.params.cache[0].handle is h0 and h0.n == n, (name, 'the 40 rows were not appended in place')
       out[name] = [np.asarray(a, np.float64).ravel() for a in (mu, var, ei, mu2, var2)]
   finally:
     gpu_ctx.set_option('post_bf16x3', 1)
     gpu_ctx.set_option('post_f16x2', 1)
     gpu_ctx.set_option('post_chunk', 8192)
+  # the fp64 leg after the append against the oracle's factorisation of all n points (the queries in chunks: the oracle's pairwise
+  # differences are an n x M x d array)
+  po = o.GPParams(model=model)
+  ko = getattr(o, kname)
+  cho, kio, _ = o.solve_gp_linear_system(o.constant, ko, po, x, y, WFO)
+  parts = [o.predict(o.constant, ko, po, x, y, xq[q:q + 1000], WFO, cache=types.SimpleNamespace(chol=cho, kinvy=kio)) for q in range(0, M, 1000)]
+  mu_o, var_o = o.gp_predict_postprocess(po, {0: o.SubDataset(x, y)}, np.vstack([p[0] for p in parts]), np.vstack([p[1] for p in parts]),
+                                         WFO, False, True, True)
+  e_mu, e_var = helpers.rel_err(out['f64'][3], mu_o.ravel()), helpers.rel_err(out['f64'][4], var_o.ravel())
+  assert e_mu < 1e-8 and e_var < 1e-8, (kname, 'fp64 after append against the oracle', e_mu, e_var)
   for j, what in enumerate(('mean', 'variance', 'EI', 'mean after append', 'variance after append')):
     ref = out['f64'][j]
     scale = max(np.abs(ref).max(), 1e-6)
