@@ -26,6 +26,26 @@ def random_search(model, x_queries, **unused_kwargs):
   return model.rng.uniform(size=(x_queries.shape[0], 1))
 
 
+def _paths_over_pool(model, sub_dataset_key, x_queries, num_samples, key, num_features):
+  if isinstance(model, gp.HGP):
+    raise ValueError('Thompson sampling is defined for a GP with one set of hyper-parameters, not for an HGP')
+  return model.sample_paths(np.asarray(x_queries), sub_dataset_key=sub_dataset_key, num_samples=num_samples, num_features=num_features,
+                            key=key)
+
+
+def thompson_sampling(model, sub_dataset_key, x_queries, key=None, num_features=1024, **unused_kwargs):
+  """[M, 1]: ONE posterior sample path over the candidates (GP.sample_paths); its argmax is a Thompson-sampling suggestion.  key: a
+  numpy Generator or an int seed, None takes model.rng.  Usable as `ac_func` of the host loops of bayesopt.py; it has neither
+  value_and_grad nor maximize, so bayesopt.bayesopt keeps the best candidate unrefined."""
+  return _paths_over_pool(model, sub_dataset_key, x_queries, 1, key, num_features)
+
+
+def thompson_batch(model, sub_dataset_key, x_queries, batch_size, key=None, num_features=1024):
+  """`batch_size` candidate indices, the argmax of one posterior path each (the lowest index among equals): q parallel suggestions
+  from a single device call."""
+  return np.argmax(_paths_over_pool(model, sub_dataset_key, x_queries, int(batch_size), key, num_features), axis=0)
+
+
 def _norm_pdf(x):
   return np.exp(-0.5 * x * x) / np.sqrt(2 * np.pi)
 

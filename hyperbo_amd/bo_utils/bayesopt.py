@@ -65,8 +65,8 @@ def bayesopt(key, model, sub_dataset_key, query_oracle, ac_func, iters, input_sa
       evals = ac_func(model=model, sub_dataset_key=sub_dataset_key, x_queries=x_samples)
       select_idx = int(np.argmax(evals))
     x_init = np.asarray(x_samples[select_idx], dtype=np.float64)
-    if ac_func.__name__ in ('rand', 'random_search'):
-      x_opt = x_init
+    if ac_func.__name__ in ('rand', 'random_search') or not (hasattr(ac_func, 'value_and_grad') or hasattr(ac_func, 'maximize')):
+      x_opt = x_init   # (neither a gradient nor a maximiser to refine with, e.g. thompson_sampling: the best candidate stays as it is)
     elif on_device and model.has_observations(sub_dataset_key):
       starts = np.argsort(-np.asarray(evals, dtype=np.float64).reshape(-1), kind='stable')[:max(1, int(cfg.get('acq_opt_starts', 1)))]
       x_opt, _, _ = ac_func.maximize(model=model, sub_dataset_key=sub_dataset_key, x_init=x_samples[starts])

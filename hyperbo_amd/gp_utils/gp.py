@@ -17,6 +17,7 @@ from hyperbo_amd.basics import definitions as defs
 from hyperbo_amd.basics import linalg
 from hyperbo_amd.basics import params_utils
 from hyperbo_amd.gp_utils import objectives as obj
+from hyperbo_amd.gp_utils import pathwise
 
 retrieve_params = params_utils.retrieve_params
 GPCache = defs.GPCache
@@ -638,6 +639,29 @@ class GP:
       cov = cov * cov.dtype.type(scale)
     return mu, cov
 
+  def sample_paths(self, queried_inputs, sub_dataset_key: Union[int, str] = 0, num_samples: int = 1, num_features: int = 1024,
+                   key=None, unbiased: bool = True) -> np.ndarray:
+    """[M, num_samples] joint draws of the latent function at queried_inputs from the posterior over the sub-dataset (the prior
+    without observations), one column per path, in the model dtype: pathwise sampling over `num_features` random features
+    (gp_utils/pathwise.py; hbo_sample_paths).  No counterpart in the reference, whose joint draw goes through predict(full_cov=True).
+    key: a numpy Generator or an int seed; None takes self.rng.  unbiased: the deviation from the posterior mean is scaled by
+    sqrt(T / (T - 1)) -- the mean comes as one more column of the same call -- so that the moments match predict(with_noise=False)."""
+    if key is None:
+      if self.rng is None:
+        raise ValueError('sample_paths needs a random key: pass key=, or set model.rng')
+      key = self.rng
+    handle = None
+    if self.has_observations(sub_dataset_key):
+      self.setup_predictor(sub_dataset_key)
+      handle = self.params.cache[sub_dataset_key].handle
+    _, scale = self.predict_noise_and_scale(False, unbiased)
+    out = pathwise.sample_paths(self.mean_func, self.cov_func, self.params, queried_inputs, self.warp_func, handle, self.input_dim,
+                                num_samples=num_samples, num_features=num_features, key=key, mean_column=scale != 1.0)
+    if scale != 1.0:
+      mean = out[:, -1:]
+      out = mean + (out[:, :-1] - mean) * out.dtype.type(np.sqrt(scale))
+    return out
+
   def predict_noise_and_scale(self, with_noise=True, unbiased=True):
     """The (noise_variance, T/(T-1)) post-processing constants of gp.py:607-619."""
     add_noise = 0.0
@@ -681,3 +705,7 @@ class HGP(GP):
       self.update_model_params(model_params)
       results.append(super().predict(queried_inputs, sub_dataset_key, full_cov, with_noise))
     return results
+
+  def sample_paths(self, *unused_args, **unused_kwargs):
+    raise ValueError('sample_paths is defined for a GP with one set of hyper-parameters; draw from each parameter sample of an HGP '
+                     'with a GP of its own')

@@ -201,6 +201,26 @@ int hbo_predict(hbo_ctx* ctx, const hbo_model* model, hbo_cache* cache, const vo
 int hbo_acq(hbo_ctx* ctx, const hbo_model* model, hbo_cache* cache, const void* xq, int64_t M,
             int acq_id, double param, double add_noise, double scale, void* out);
 
+/* ---- S posterior sample paths over one shared basis of F features (pathwise / Matheron sampling; no counterpart in the reference,
+ *      whose only joint draw is predict(full_cov=True): M^2 memory and an M^3 factorisation on top).  With phi(x) what the covariance
+ *      sees (the raw x, the last MLP layer, the Kumaraswamy-warped x; width fdim), m the mean function and Ktilde the matrix the cache
+ *      factorised, k(X,X) + (noise_variance + eps) I:
+ *        SE / Matern, A = sqrt(2 signal_variance / F):   p_s(x) = A sum_j w[j,s] cos(omega_j . phi(x) + phase_j)
+ *        dot product (F = fdim + 1, exact; omega, phase unused): p_s(x) = sum_d w[d,s] phi_d(x) / dot_prod_sigma + dot_prod_bias w[fdim,s]
+ *        v[:,s] = Ktilde^-1 (y - m(X) - p_s(X) - sqrt(noise_variance + eps) eps[:,s])
+ *        out[q,s] = m(x_q) + p_s(x_q) + sum_i k(x_q, X_i) v[i,s]          (cache == NULL, the prior branch: m(x_q) + p_s(x_q))
+ *      out is the latent, noise-free function; with w = 0 and eps = 0 it is hbo_predict's mean.  The caller draws omega [F,fdim]
+ *      (already divided by the lengthscale: the device never sees it for the prior term), phase [F], w [F,S] and eps [n,S] (NULL if and
+ *      only if cache is NULL), all in the model dtype (hyperbo_amd/gp_utils/pathwise.py holds the spectral recipe); out [M,S], model
+ *      dtype.  Cost: one O(n^2) solve per path, then O(M (F + n)) per path; every cosine and every cross-Gram entry is shared by the S
+ *      paths.  Queries stream in chunks of post_chunk; a row of out does not depend on the chunk size, a column not on the other columns
+ *      of the call, and identical calls are bit-identical (fp64 sums in a fixed order, no atomics).
+ *      HBO_ERR_ARG, before any device call and with out untouched: a null ctx or argument, S outside 1..1024, F outside 1..65536, a
+ *      dot-product model with F != fdim + 1, eps without a cache or a cache without eps, a cache/model mismatch.  A cache that is not
+ *      positive definite: out is NaN, HBO_NOT_PD (as hbo_predict). */
+int hbo_sample_paths(hbo_ctx* ctx, const hbo_model* model, hbo_cache* cache /* nullable */, const void* xq, int64_t M, int32_t S, int32_t F,
+                     const void* omega, const void* phase, const void* w, const void* eps, void* out);
+
 /* ---- S hyper-parameter samples of ONE model family as one batch: what acquisition functions do on an HGP
  *      (hyperbo/bo_utils/acfun.py:72-82 loops model.predict over model.params.samples, gp.py:666-682; the jax counterpart is a
  *      vmap over the draws).  models[s]: sample s (same dtype, covariance, mean and MLP architecture for all); x [n,D], y [n,m]
