@@ -142,20 +142,18 @@ extern "C" int hbo_acq_maximize(hbo_ctx* c, const hbo_model* models, int32_t S, 
   HIPCHK(c, hipSetDevice(c->device));
   const size_t es = esize(dtype);
   hipStream_t st = c->stream;
-  auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
   // one block up: [S records][S x 2 D doubles][lo, hi][R x D pending points][R states]; the log follows the states, and one copy brings
   // [states | log] back.  Scratch of the rounds: [S x R x D gradients][S x R values fp64][S x R values in the model dtype]
-  const size_t smp_b = al(sizeof(AcqSmallSample) * S), vec_b = al(sizeof(double) * 2 * D * S), box_b = al(sizeof(double) * 2 * D);
-  const size_t pend_b = al((size_t)R * D * es), state_b = al(sizeof(double) * (size_t)R * ns);
+  const size_t smp_b = align256(sizeof(AcqSmallSample) * S), vec_b = align256(sizeof(double) * 2 * D * S), box_b = align256(sizeof(double) * 2 * D);
+  const size_t pend_b = align256((size_t)R * D * es), state_b = align256(sizeof(double) * (size_t)R * ns);
   const size_t log_b = log ? sizeof(hbo_acq_opt_eval) * (size_t)evals * R : 0;
   const size_t o_state = smp_b + vec_b + box_b + pend_b, up_b = o_state + state_b, down_b = state_b + log_b;
-  const size_t grad_b = al(sizeof(double) * (size_t)S * R * D), val_b = al(sizeof(double) * (size_t)S * R), acq_b = (size_t)S * R * es;
+  const size_t grad_b = align256(sizeof(double) * (size_t)S * R * D), val_b = align256(sizeof(double) * (size_t)S * R), acq_b = (size_t)S * R * es;
   char* d_in = static_cast<char*>(ws_get(c, WS_AO_IN, up_b + log_b));
   char* d_out = static_cast<char*>(ws_get(c, WS_AO_OUT, grad_b + val_b + acq_b));
   if (!d_in || !d_out) return HBO_ERR_HIP;
-  HIPCHK(c, hipEventSynchronize(c->ev_upload));   // the pinned buffer may still feed an earlier upload
-  char* stage = static_cast<char*>(pinned_stage(c, up_b + log_b));
-  if (!stage) return fail(c, HBO_ERR_HIP, fn + "no pinned staging memory");
+  char* stage = static_cast<char*>(stage_begin(c, fn.c_str(), up_b + log_b));
+  if (!stage) return HBO_ERR_HIP;
   acq_small_pack(reinterpret_cast<AcqSmallSample*>(stage), reinterpret_cast<double*>(stage + smp_b), models, S, caches, params, add_noise);
   double* hbox = reinterpret_cast<double*>(stage + smp_b + vec_b);
   for (int i = 0; i < D; ++i) { hbox[i] = lo ? lo[i] : 0.0; hbox[D + i] = hi ? hi[i] : 1.0; }
@@ -179,8 +177,7 @@ extern "C" int hbo_acq_maximize(hbo_ctx* c, const hbo_model* models, int32_t S, 
       else reinterpret_cast<float*>(hpend)[(size_t)r * D + i] = (float)v.xt[i];
     }
   }
-  HIPCHK(c, hipMemcpyAsync(d_in, stage, up_b, hipMemcpyHostToDevice, st));
-  HIPCHK(c, hipEventRecord(c->ev_upload, st));
+  HIPCHK(c, stage_upload(c, d_in, stage, up_b, st));
 
   AcqSmallArgs a = {};
   a.smp = reinterpret_cast<const AcqSmallSample*>(d_in); a.vec = reinterpret_cast<const double*>(d_in + smp_b);

@@ -1,6 +1,6 @@
 // d acquisition / d x_query over the parameter samples of an HGP in ONE launch, for caches of n <= 128 observations (one 128-block):
 // what bayesopt()'s inner L-BFGS-B asks for dozens of times per BO iteration (bayesopt.py:116-125 over acfun.py:72-82).  The per-sample
-// path (cache.hip: hbo_acq_grad) is about eight latency-bound launches and a host round trip per sample; here one workgroup owns one
+// path (acq_grad.hip: hbo_acq_grad) is about eight latency-bound launches and a host round trip per sample; here one workgroup owns one
 // (sample, query) pair and does all of post.hip: acq_grad_kernel's maths itself, from the finished cache of that sample:
 //   k_i = k(x, X_i),  l = W k,  beta = W^T l,  mu = k.alpha + m(x),  var = k(x, x) - |l|^2,  coef_i = a_mu alpha_i - 2 a_var beta_i,
 //   SE / Matern: g_d = sum_i coef_i dk/du_i 2 (x_d - X_id) / ls_d^2;  dot: g = sum_i coef_i X_i / sigma^2 + a_var 2 x / sigma^2;

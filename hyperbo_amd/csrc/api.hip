@@ -279,23 +279,23 @@ extern "C" int hbo_dataset_create(hbo_ctx* c, int dtype, int input_dim, const hb
   // All inputs of all tasks travel in ONE block: laid out in a pinned staging buffer (x, the column sums of y, the
   // divergence rows), one host-to-device copy, the tasks point into the block.  (Three synchronous copies per task cost
   // ~1 ms for 24 small tasks -- what an Adam step of GP.train() pays when it re-samples its batch, gp.py:101-111.)
-  auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-  size_t total = 0;
+  struct TaskOff { size_t x, ysum, ydiv; };
+  std::vector<TaskOff> offs(std::max(n_tasks, 0));   // (n_tasks <= 0: an empty dataset)
+  BlockLayout lay;
   for (int k = 0; k < n_tasks; ++k) {
     const hbo_task& tk = tasks[k];
     if (tk.n <= 0) continue;  // objectives.py:184-185: empty sub-datasets are skipped
     if (tk.m <= 0 || !tk.x || !tk.y) { hbo_dataset_free(c, ds); return fail(c, HBO_ERR_ARG, "hbo_dataset_create: bad task"); }
-    total += al((size_t)tk.n * input_dim * es) + al((size_t)tk.n * es);
-    total += al((size_t)(tk.m + 1) * tk.n * es);
+    offs[k].x = lay.take((size_t)tk.n * input_dim * es); offs[k].ysum = lay.take((size_t)tk.n * es);
+    offs[k].ydiv = lay.take((size_t)(tk.m + 1) * tk.n * es);
   }
+  const size_t total = lay.off;
   unsigned char* stage = nullptr;
   if (total) {
-    HIPCHK(c, hipEventSynchronize(c->ev_upload));   // the pinned buffer may still feed an earlier upload
-    stage = static_cast<unsigned char*>(pinned_stage(c, total));
+    stage = static_cast<unsigned char*>(stage_begin(c, "hbo_dataset_create: ", total));
     hipError_t e = stage ? dev_alloc(c, &ds->d_inputs, total) : hipErrorOutOfMemory;
     if (e != hipSuccess) { hbo_dataset_free(c, ds); return fail(c, HBO_ERR_HIP, std::string("hbo_dataset_create: ") + hipGetErrorString(e)); }
   }
-  size_t off = 0;
   for (int k = 0; k < n_tasks; ++k) {
     const hbo_task& tk = tasks[k];
     if (tk.n <= 0) continue;
@@ -303,22 +303,21 @@ extern "C" int hbo_dataset_create(hbo_ctx* c, int dtype, int input_dim, const hb
     ds->tasks.push_back(t);
     t->owns_inputs = false;
     t->n = tk.n; t->m = tk.m; t->npad = round_up(tk.n, HBO_TILE); t->nblk = t->npad / HBO_TILE; t->ld = padded_ld(t->npad, dtype);
-    t->X = (char*)ds->d_inputs + off;
-    memcpy(stage + off, tk.x, (size_t)tk.n * input_dim * es);
-    off += al((size_t)tk.n * input_dim * es);
+    t->X = (char*)ds->d_inputs + offs[k].x;
+    memcpy(stage + offs[k].x, tk.x, (size_t)tk.n * input_dim * es);
     // ysum (sum over columns, in double then cast)
-    t->ysum = (char*)ds->d_inputs + off;
+    t->ysum = (char*)ds->d_inputs + offs[k].ysum;
+    unsigned char* ys = stage + offs[k].ysum;
     for (int64_t i = 0; i < tk.n; ++i) {
       double sum = 0;
       for (int a = 0; a < tk.m; ++a) sum += host_elem(tk.y, dtype, i * tk.m + a);
-      if (dtype == HBO_F64) ((double*)(stage + off))[i] = sum; else ((float*)(stage + off))[i] = (float)sum;
+      if (dtype == HBO_F64) ((double*)ys)[i] = sum; else ((float*)ys)[i] = (float)sum;
     }
-    off += al((size_t)tk.n * es);
     {
       // sample statistics of objectives.py:57-58: mu_data = mean over the m aligned columns, cov_data =
       // (1/m) sum_a yc_a yc_a^T (jnp.cov(bias=True)); kept as its m rank-1 factors.
-      t->ydiv = (char*)ds->d_inputs + off;
-      unsigned char* yd = stage + off;
+      t->ydiv = (char*)ds->d_inputs + offs[k].ydiv;
+      unsigned char* yd = stage + offs[k].ydiv;
       const double rs = 1.0 / sqrt((double)tk.m);
       for (int64_t i = 0; i < tk.n; ++i) {
         double mu0 = 0;
@@ -329,13 +328,11 @@ extern "C" int hbo_dataset_create(hbo_ctx* c, int dtype, int input_dim, const hb
           if (dtype == HBO_F64) ((double*)yd)[(size_t)a * tk.n + i] = v; else ((float*)yd)[(size_t)a * tk.n + i] = (float)v;
         }
       }
-      off += al((size_t)(tk.m + 1) * tk.n * es);
     }
     ds->max_nblk = std::max(ds->max_nblk, t->nblk);
   }
   if (total) {
-    hipError_t e = hipMemcpyAsync(ds->d_inputs, stage, total, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipEventRecord(c->ev_upload, c->stream);
+    hipError_t e = stage_upload(c, ds->d_inputs, stage, total, c->stream);
     if (e != hipSuccess) { hbo_dataset_free(c, ds); return fail(c, HBO_ERR_HIP, std::string("hbo_dataset_create: ") + hipGetErrorString(e)); }
   }
   ds->ntasks = (int)ds->tasks.size();
@@ -370,28 +367,31 @@ extern "C" int hbo_dataset_subsample(hbo_ctx* c, const hbo_dataset* src, const i
   HIPCHK(c, hipSetDevice(c->device));
   const int T = src->ntasks, dtype = src->dtype, D = src->D;
   const size_t es = esize(dtype);
-  auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-  size_t total = 0; int64_t nidx = 0, max_dst = 0;
+  struct TaskOff { size_t x, ysum, ydiv; };
+  std::vector<TaskOff> offs(T);
+  BlockLayout lay;
+  int64_t nidx = 0, max_dst = 0;
   for (int k = 0; k < T; ++k) {
     const TaskHost* t = src->tasks[k];
     const int64_t nd = counts[k] < 0 ? t->n : counts[k];
     if (nd <= 0 || nd > t->n) return fail(c, HBO_ERR_ARG, "hbo_dataset_subsample: counts[k] must be in 1..n_k (or negative: the whole task)");
     if (counts[k] >= 0) { if (!idx) return fail(c, HBO_ERR_ARG, "hbo_dataset_subsample: idx is null"); nidx += nd; }
-    total += al((size_t)nd * D * es) + al((size_t)nd * es) + (t->ydiv ? al((size_t)(t->m + 1) * nd * es) : 0);
+    offs[k].x = lay.take((size_t)nd * D * es); offs[k].ysum = lay.take((size_t)nd * es);
+    offs[k].ydiv = t->ydiv ? lay.take((size_t)(t->m + 1) * nd * es) : 0;
     max_dst = std::max(max_dst, nd);
   }
+  const size_t total = lay.off;
   hbo_dataset* ds = new hbo_dataset();
   ds->dtype = dtype; ds->D = D;
   if (T == 0) { *out = ds; return HBO_OK; }
   // descriptors + indices through the pinned staging buffer, one copy
-  const size_t desc_b = al(sizeof(GatherTask) * T), idx_b = al(sizeof(int32_t) * (size_t)std::max<int64_t>(nidx, 1));
-  HIPCHK(c, hipEventSynchronize(c->ev_upload));
-  unsigned char* stage = static_cast<unsigned char*>(pinned_stage(c, desc_b + idx_b));
+  const size_t desc_b = align256(sizeof(GatherTask) * T), idx_b = align256(sizeof(int32_t) * (size_t)std::max<int64_t>(nidx, 1));
+  unsigned char* stage = static_cast<unsigned char*>(stage_begin(c, "hbo_dataset_subsample: ", desc_b + idx_b));
   unsigned char* d_args = static_cast<unsigned char*>(ws_get(c, WS_GATHER, desc_b + idx_b));
   hipError_t e = (stage && d_args) ? dev_alloc(c, &ds->d_inputs, total) : hipErrorOutOfMemory;
   if (e != hipSuccess) { hbo_dataset_free(c, ds); return fail(c, HBO_ERR_HIP, std::string("hbo_dataset_subsample: ") + hipGetErrorString(e)); }
   GatherTask* g = reinterpret_cast<GatherTask*>(stage);
-  size_t off = 0; int64_t ioff = 0;
+  int64_t ioff = 0;
   for (int k = 0; k < T; ++k) {
     const TaskHost* s = src->tasks[k];
     const int64_t nd = counts[k] < 0 ? s->n : counts[k];
@@ -399,9 +399,8 @@ extern "C" int hbo_dataset_subsample(hbo_ctx* c, const hbo_dataset* src, const i
     ds->tasks.push_back(t);
     t->owns_inputs = false;
     t->n = nd; t->m = s->m; t->npad = round_up(nd, HBO_TILE); t->nblk = t->npad / HBO_TILE; t->ld = padded_ld(t->npad, dtype);
-    t->X = (char*)ds->d_inputs + off; off += al((size_t)nd * D * es);
-    t->ysum = (char*)ds->d_inputs + off; off += al((size_t)nd * es);
-    if (s->ydiv) { t->ydiv = (char*)ds->d_inputs + off; off += al((size_t)(s->m + 1) * nd * es); }
+    t->X = (char*)ds->d_inputs + offs[k].x; t->ysum = (char*)ds->d_inputs + offs[k].ysum;
+    if (s->ydiv) t->ydiv = (char*)ds->d_inputs + offs[k].ydiv;
     g[k] = GatherTask{s->X, s->ysum, s->ydiv, t->X, t->ysum, t->ydiv, s->n, nd, ioff, s->m, counts[k] >= 0 ? 1 : 0};
     if (counts[k] >= 0) {
       for (int64_t r = 0; r < nd; ++r) if (idx[ioff + r] < 0 || idx[ioff + r] >= s->n) { hbo_dataset_free(c, ds); return fail(c, HBO_ERR_ARG, "hbo_dataset_subsample: index out of range"); }
@@ -411,8 +410,7 @@ extern "C" int hbo_dataset_subsample(hbo_ctx* c, const hbo_dataset* src, const i
   }
   if (nidx) memcpy(stage + desc_b, idx, sizeof(int32_t) * (size_t)nidx);
   hipStream_t st = c->stream;
-  e = hipMemcpyAsync(d_args, stage, desc_b + idx_b, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) e = hipEventRecord(c->ev_upload, st);
+  e = stage_upload(c, d_args, stage, desc_b + idx_b, st);
   if (e == hipSuccess) {
     launch_gather_rows(dtype, reinterpret_cast<const GatherTask*>(d_args), reinterpret_cast<const int32_t*>(d_args + desc_b), T, max_dst, D, st);
     e = hipGetLastError();

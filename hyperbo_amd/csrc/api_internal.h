@@ -1,7 +1,9 @@
 // Host-side internals shared by the translation units of the C ABI (api.hip: context, options, datasets, dense entry points;
-// objective.hip: hbo_objective / hbo_objective_sharded; cache.hip: hbo_factor, row append, posterior, acquisition): model
-// validation and upload, the MLP feature pipeline and the query-side features of everything that reads a factor (query_features), the
-// per-task device buffers and the descriptors the kernels read, and the plan of a posterior call (post_plan: every decision, no HIP call).
+// objective.hip: hbo_objective / hbo_objective_sharded; cache.hip: hbo_factor, row append, posterior, acquisition; acq_grad.hip: its
+// gradient): model validation and upload, the set-up the batched entry points share (model_family_check, mlp_shape, models_pack,
+// stage_begin / stage_upload), the MLP feature pipeline and the query-side features of everything that reads a factor
+// (query_features), the per-task device buffers and the descriptors the kernels read, and the plan of a posterior call (post_plan:
+// every decision, no HIP call).
 #pragma once
 #include "ctx.h"
 
@@ -73,13 +75,42 @@ static int validate_model(hbo_ctx* c, const hbo_model* m) {
   return HBO_OK;
 }
 
-// S hyper-parameter samples of ONE model family (hbo_acq_samples, hbo_nll_samples): same dtype, covariance, mean, input_dim and
-// MLP architecture -- everything that shapes a launch; only the values differ
+// S hyper-parameter samples of ONE model family: same dtype, covariance, mean, input_dim and MLP architecture -- everything that
+// shapes a launch; only the values differ
 static bool same_model_family(const hbo_model* m, const hbo_model* m0) {
   bool same = m->dtype == m0->dtype && m->kernel_id == m0->kernel_id && m->mean_id == m0->mean_id && m->input_dim == m0->input_dim &&
               m->kernel_uses_mlp == m0->kernel_uses_mlp && m->n_lengthscale == m0->n_lengthscale && needs_mlp(m) == needs_mlp(m0);
   if (same && needs_mlp(m0)) { same = m->n_layers == m0->n_layers; for (int l = 0; same && l < m0->n_layers; ++l) same = m->features[l] == m0->features[l]; }
   return same;
+}
+// What every batched entry point asks of its S models, per sample in this order: no input warp (HBO_ERR_UNSUPPORTED; before
+// validate_model: a packed array element has no hbo_model_kumar tail to read), a valid model, the family of models[0] (HBO_ERR_ARG).
+// fn: "hbo_xyz: ", the head of every message; advice: what to call instead for a warped model.  Touches no device (c may be null).
+static int model_family_check(hbo_ctx* c, const std::string& fn, const hbo_model* models, int32_t S, const char* advice) {
+  for (int s = 0; s < S; ++s) {
+    const hbo_model* m = &models[s];
+    if (m->input_warp != HBO_WARP_NONE) return fail(c, HBO_ERR_UNSUPPORTED, fn + "input-warped (Kumaraswamy) models are not supported; " + advice);
+    if (int rc = validate_model(c, m)) return rc;
+    if (!same_model_family(m, &models[0])) return fail(c, HBO_ERR_ARG, fn + "the samples' models must share dtype, covariance, mean, input_dim and MLP architecture");
+  }
+  return HBO_OK;
+}
+
+// The MLP of a model layer by layer (L = 0 without one): inputs, outputs, bytes of the weights [fin][fout] and of the bias, and
+// `per_sample`, the bytes of one model's weights with every array at a 256-byte boundary (models_pack below)
+struct MlpShape { int L; int fin[HBO_MAX_MLP_LAYERS], fout[HBO_MAX_MLP_LAYERS]; size_t wb[HBO_MAX_MLP_LAYERS], bb[HBO_MAX_MLP_LAYERS]; size_t per_sample; };
+static MlpShape mlp_shape(const hbo_model* m) {
+  MlpShape s = {};
+  if (!needs_mlp(m)) return s;
+  s.L = m->n_layers;
+  int fin = m->input_dim;
+  for (int l = 0; l < s.L; ++l) {
+    s.fin[l] = fin; s.fout[l] = m->features[l];
+    s.wb[l] = (size_t)fin * m->features[l] * esize(m->dtype); s.bb[l] = (size_t)m->features[l] * esize(m->dtype);
+    s.per_sample += align256(s.wb[l]) + align256(s.bb[l]);
+    fin = m->features[l];
+  }
+  return s;
 }
 
 static double host_elem(const void* p, int dtype, int64_t i) {
@@ -93,6 +124,12 @@ static inline double chol_diag_bound_of(const hbo_model* m) {
   const double b = (double)m->signal_variance + (double)m->noise_variance + (double)m->eps;
   return (b > 0 && b < 1e30) ? b : 0.0;
 }
+// ... of a batch of S models factorised together: the largest bound; any unknown -> unknown
+static inline double chol_diag_bound_of(const hbo_model* models, int S) {
+  double all = chol_diag_bound_of(&models[0]);
+  for (int s = 1; s < S; ++s) { const double b = chol_diag_bound_of(&models[s]); all = (b > 0 && all > 0) ? std::max(all, b) : 0.0; }
+  return all;
+}
 struct CholBoundScope {   // valid from run_potrf to the last product of the inverse / K^-1 of the same matrices
   hbo_ctx* c;
   CholBoundScope(hbo_ctx* ctx, double b) : c(ctx) { c->run.chol_diag_bound = b; }
@@ -103,6 +140,57 @@ static void fill_model_dev(ModelDev& h, const hbo_model* m) {
   memset(&h, 0, sizeof h);
   model_dev_fill(h, m, 0, 1);
 }
+// S models of one family and their MLP weights as ONE block (hbo_acq_samples, hbo_bo_simulated):
+//   [ModelDev[S]] [sample 0: per layer the weights, then the bias, each at a 256-byte boundary] [sample 1: ...] ...
+// models_pack fills its host copy `h` (models_pack_bytes; the padding is the caller's to zero) and the tables w_dev / b_dev
+// [S][HBO_MAX_MLP_LAYERS] with the addresses the arrays have once the block sits at d_base on the device.
+static size_t models_pack_bytes(const MlpShape& sh, int S) { return align256(sizeof(ModelDev) * S) + sh.per_sample * S; }
+static void models_pack(char* h, char* d_base, const hbo_model* models, int S, const MlpShape& sh, void** w_dev, void** b_dev) {
+  ModelDev* hm = reinterpret_cast<ModelDev*>(h);
+  BlockLayout lay;
+  lay.take(sizeof(ModelDev) * S);
+  for (int s = 0; s < S; ++s) {
+    fill_model_dev(hm[s], &models[s]);
+    for (int l = 0; l < sh.L; ++l) {
+      const size_t o_w = lay.take(sh.wb[l]), o_b = lay.take(sh.bb[l]);
+      memcpy(h + o_w, models[s].mlp_kernel[l], sh.wb[l]); memcpy(h + o_b, models[s].mlp_bias[l], sh.bb[l]);
+      w_dev[(size_t)s * HBO_MAX_MLP_LAYERS + l] = d_base + o_w; b_dev[(size_t)s * HBO_MAX_MLP_LAYERS + l] = d_base + o_b;
+    }
+  }
+}
+
+// ---- the pinned stage ------------------------------------------------------------------------
+// Small uploads go through ONE pinned buffer per context, hp_stage (and the model through a pinned ModelDev of its own, h_model),
+// copied asynchronously; ev_upload marks the last such copy.  The protocol, whole:
+//   stage_begin(c, fn, bytes) -> fill -> stage_upload(c, dst, stage, bytes, st)
+// stage_begin waits until the previous upload has read the buffer, then returns it grown to `bytes` (null: c->err says why, behind fn = "hbo_xyz: ");
+// stage_upload queues the copy and records ev_upload behind it.  Two rules keep this free of races:
+//   * between the fill and stage_upload nothing may ask for a LARGER stage (stage_begin, pinned_stage): growing frees the buffer;
+//   * after stage_upload the buffer is not written again before the next stage_begin (stage_wait) has returned.
+// A call may also use the buffer as the target of a copy BACK on the stream of its uploads (pinned_stage alone: such a copy is
+// ordered behind them).
+static void* pinned_stage(hbo_ctx* c, size_t bytes) {
+  if (c->hp_stage_bytes < bytes) {
+    if (c->hp_stage) { hipDeviceSynchronize(); hipHostFree(c->hp_stage); c->hp_stage = nullptr; c->hp_stage_bytes = 0; }
+    const size_t want = std::max<size_t>(bytes * 2, 1 << 16);
+    if (hipHostMalloc(&c->hp_stage, want, hipHostMallocDefault) != hipSuccess) { c->hp_stage = nullptr; return nullptr; }
+    c->hp_stage_bytes = want;
+  }
+  return c->hp_stage;
+}
+static hipError_t stage_wait(hbo_ctx* c) { return hipEventSynchronize(c->ev_upload); }
+static void* stage_begin(hbo_ctx* c, const char* fn, size_t bytes) {
+  const hipError_t e = stage_wait(c);
+  if (e != hipSuccess) { fail(c, HBO_ERR_HIP, std::string(fn) + "waiting for the last staged upload failed: " + hipGetErrorString(e)); return nullptr; }
+  void* p = pinned_stage(c, bytes);
+  if (!p) fail(c, HBO_ERR_HIP, std::string(fn) + "no pinned staging memory");
+  return p;
+}
+static hipError_t stage_upload(hbo_ctx* c, void* dst, const void* src, size_t bytes, hipStream_t st) {
+  const hipError_t e = hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, st);
+  return e != hipSuccess ? e : hipEventRecord(c->ev_upload, st);
+}
+
 // hbo_objective's per-call work up to the copy back (objective.hip).  With `sh` set it reduces [nll, count, grad] on the device into
 // ShardOut::d_red with the scatter map it uploads (launch_shard_reduce) and returns without waiting: the sharded objective all-reduces
 // that buffer, hbo_train_adam (train.hip) queues its first Adam step behind it and reuses the map for the steps after it.
@@ -125,24 +213,20 @@ static int upload_model(hbo_ctx* c, const hbo_model* m) {
   int rc = validate_model(c, m);
   if (rc) return rc;
   // the pinned copy may still be read by the previous upload (calls that return without waiting for the stream)
-  HIPCHK(c, hipEventSynchronize(c->ev_upload));
+  HIPCHK(c, stage_wait(c));
   ModelDev& h = *c->h_model;
   fill_model_dev(h, m);
-  HIPCHK(c, hipMemcpyAsync(c->d_model, &h, sizeof h, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipEventRecord(c->ev_upload, c->stream));
-  if (needs_mlp(m)) {
-    int fin = m->input_dim;
-    for (int l = 0; l < m->n_layers; ++l) {
-      const size_t wb = (size_t)fin * m->features[l] * esize(m->dtype), bb = (size_t)m->features[l] * esize(m->dtype);
-      if (c->mlp_w_bytes[l] < wb) { if (c->d_mlp_w[l]) hipFree(c->d_mlp_w[l]); HIPCHK(c, hbo_malloc(c, &c->d_mlp_w[l], wb)); c->mlp_w_bytes[l] = wb; }
-      if (c->mlp_b_bytes[l] < bb) { if (c->d_mlp_b[l]) hipFree(c->d_mlp_b[l]); HIPCHK(c, hbo_malloc(c, &c->d_mlp_b[l], bb)); c->mlp_b_bytes[l] = bb; }
-      HIPCHK(c, hipMemcpyAsync(c->d_mlp_w[l], m->mlp_kernel[l], wb, hipMemcpyHostToDevice, c->stream));
-      HIPCHK(c, hipMemcpyAsync(c->d_mlp_b[l], m->mlp_bias[l], bb, hipMemcpyHostToDevice, c->stream));
-      fin = m->features[l];
-    }
+  HIPCHK(c, stage_upload(c, c->d_model, &h, sizeof h, c->stream));
+  const MlpShape sh = mlp_shape(m);
+  for (int l = 0; l < sh.L; ++l) {
+    const size_t wb = sh.wb[l], bb = sh.bb[l];
+    if (c->mlp_w_bytes[l] < wb) { if (c->d_mlp_w[l]) hipFree(c->d_mlp_w[l]); HIPCHK(c, hbo_malloc(c, &c->d_mlp_w[l], wb)); c->mlp_w_bytes[l] = wb; }
+    if (c->mlp_b_bytes[l] < bb) { if (c->d_mlp_b[l]) hipFree(c->d_mlp_b[l]); HIPCHK(c, hbo_malloc(c, &c->d_mlp_b[l], bb)); c->mlp_b_bytes[l] = bb; }
+    HIPCHK(c, hipMemcpyAsync(c->d_mlp_w[l], m->mlp_kernel[l], wb, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->d_mlp_b[l], m->mlp_bias[l], bb, hipMemcpyHostToDevice, c->stream));
   }
   // the MLP weights come from the caller's pageable memory: make sure the copies have consumed them
-  if (needs_mlp(m)) HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (sh.L) HIPCHK(c, hipStreamSynchronize(c->stream));
   return HBO_OK;
 }
 
@@ -198,16 +282,6 @@ struct FeatBuf {   // device activations of one input matrix
     return HBO_OK;
   }
 };
-
-static void* pinned_stage(hbo_ctx* c, size_t bytes) {
-  if (c->hp_stage_bytes < bytes) {
-    if (c->hp_stage) { hipDeviceSynchronize(); hipHostFree(c->hp_stage); c->hp_stage = nullptr; c->hp_stage_bytes = 0; }
-    const size_t want = std::max<size_t>(bytes * 2, 1 << 16);
-    if (hipHostMalloc(&c->hp_stage, want, hipHostMallocDefault) != hipSuccess) { c->hp_stage = nullptr; return nullptr; }
-    c->hp_stage_bytes = want;
-  }
-  return c->hp_stage;
-}
 
 // ---- datasets ----------------------------------------------------------------------------
 struct TaskHost {
@@ -333,19 +407,13 @@ struct hbo_cache {
   unsigned int* d_wmax = nullptr;    // device: bits of max |W|
 };
 
-// What hbo_acq_grad_samples and hbo_acq_maximize ask of their S (model, cache) pairs, before any device work: one model family without
-// input warp, MLP basis or linear_mlp mean, and finished caches of 1..128 observations that match their models.  *any_bad: a cache is
-// not positive definite.
+// What hbo_acq_grad_samples and hbo_acq_maximize ask of their S (model, cache) pairs, before any device work: one model family
+// (model_family_check) without MLP basis or linear_mlp mean, and finished caches of 1..128 observations that match their models.
+// *any_bad: a cache is not positive definite.
 static int acq_samples_check(hbo_ctx* c, const std::string& fn, const hbo_model* models, int32_t S, hbo_cache* const* caches, bool* any_bad) {
-  const hbo_model* m0 = &models[0];
+  if (int rc = model_family_check(c, fn, models, S, "evaluate the samples with hbo_acq_grad")) return rc;
   for (int s = 0; s < S; ++s) {
     const hbo_model* m = &models[s];
-    // (before validate_model: a packed array element has no hbo_model_kumar tail to read)
-    if (m->input_warp != HBO_WARP_NONE)
-      return fail(c, HBO_ERR_UNSUPPORTED, fn + "input-warped (Kumaraswamy) models are not supported; evaluate the samples with hbo_acq_grad");
-    int rc = validate_model(c, m);
-    if (rc) return rc;
-    if (!same_model_family(m, m0)) return fail(c, HBO_ERR_ARG, fn + "the samples must share dtype, covariance, mean and input_dim");
     if (m->kernel_uses_mlp) return fail(c, HBO_ERR_UNSUPPORTED, fn + "a kernel on an MLP basis is not supported; evaluate the samples with hbo_acq_grad");
     if (m->mean_id == HBO_MEAN_LINEAR_MLP) return fail(c, HBO_ERR_UNSUPPORTED, fn + "a linear_mlp mean is not supported; evaluate the samples with hbo_acq_grad");
     const hbo_cache* k = caches[s];

@@ -1,5 +1,6 @@
-// GPCache side of the C ABI: hbo_factor (hyperbo/basics/linalg.py:72-110 behind gp.py:540-560), the O(N^2) row append,
-// and everything that reads a cache -- hbo_predict (gp.py:242-305), hbo_acq (acfun.py:36-142), hbo_acq_grad / hbo_acq_grad_samples (bayesopt.py:116-125).
+// GPCache side of the C ABI: hbo_factor (hyperbo/basics/linalg.py:72-110 behind gp.py:540-560), the O(N^2) row append, the
+// posterior behind hbo_predict (gp.py:242-305) and hbo_acq (acfun.py:36-142), and hbo_acq_samples, the batch form of factor plus
+// posterior.  (The acquisition gradient over a cache: acq_grad.hip; the simulated BO loop: bo_loop.hip.)
 #include "api_internal.h"
 
 // ---- one cache builder and one factor pipeline (hbo_factor: one cache; hbo_acq_samples: S of them as one batch) --------------------
@@ -81,10 +82,7 @@ static int enqueue_factor(hbo_ctx* c, const FactorBatch& fb) {
   TrtriProgress trtri_pg;
   const bool early_trtri = use_early_trtri(c, S, nblk);
   c->trtri_host_task = S == 1 ? fb.ks[0]->h_desc : TaskDesc{};
-  // (the largest bound over the samples; any unknown -> unknown)
-  double bound_all = chol_diag_bound_of(&fb.models[0]);
-  for (int s = 1; s < S; ++s) { const double b = chol_diag_bound_of(&fb.models[s]); bound_all = (b > 0 && bound_all > 0) ? std::max(bound_all, b) : 0.0; }
-  CholBoundScope bound_scope(c, bound_all);
+  CholBoundScope bound_scope(c, chol_diag_bound_of(fb.models, S));
   { ProfScope ps(c, "potrf", 1); run_potrf(c, dtype, fb.d_batch, S, nblk, fb.d_infos, early_trtri ? &trtri_pg : nullptr); }
   if (fb.keep_rows) HIPCHK(c, keep_aug(true));
   { ProfScope ps(c, "trtri", 1); run_trtri(c, dtype, fb.d_batch, S, nblk, &trtri_pg); }
@@ -311,26 +309,25 @@ struct PostWs {
 static int post_acquire(const PostCall& pc, int64_t M, const PosteriorOverride* ov, bool want_acq, PostPlan& p, PostWs& w) {
   hbo_ctx* c = pc.c; const hbo_model* m = pc.m; hbo_cache* k = pc.k;
   const int wso = p.wso, nbuf = p.nbuf;
-  auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
   auto get = [&](int slot, size_t bytes) { return (char*)ws_get(c, slot + wso, bytes); };
   w.es = esize(p.dtype); w.row_b = (size_t)m->input_dim * w.es;
   const size_t es = w.es;
-  w.vec_b = al((size_t)p.mc_max * es);
+  w.vec_b = align256((size_t)p.mc_max * es);
   if (ov) w.xq = (char*)const_cast<void*>(ov->xq_dev);
   else if (!(w.xq = (char*)ws_get(c, WS_XQ, (size_t)M * w.row_b))) return HBO_ERR_HIP;
   if (!(w.mu0 = get(WS_MU0, w.vec_b * nbuf)) || !(w.kd = get(WS_KD, w.vec_b * nbuf))) return HBO_ERR_HIP;
   if (!(w.mu = get(WS_MU, (size_t)M * es)) || !(w.var = get(WS_VAR, (size_t)M * es))) return HBO_ERR_HIP;
   if (ov) w.acq = ov->acq_dev;
   else if (want_acq && !(w.acq = get(WS_ACQ, (size_t)M * es))) return HBO_ERR_HIP;
-  w.kwq_b = al((size_t)p.mc_max * w.row_b);   // Kumaraswamy: w(queries) per workspace
+  w.kwq_b = align256((size_t)p.mc_max * w.row_b);   // Kumaraswamy: w(queries) per workspace
   if (is_kumar(m) && !(w.kwq = get(WS_KW_Q, w.kwq_b * nbuf))) return HBO_ERR_HIP;
   if (needs_mlp(m)) for (int l = 0; l < m->n_layers; ++l) {
-    w.fq_b[l] = al((size_t)p.mc_max * m->features[l] * es);
+    w.fq_b[l] = align256((size_t)p.mc_max * m->features[l] * es);
     if (!(w.fq[l] = get(WS_FQ0 + l, w.fq_b[l] * nbuf))) return HBO_ERR_HIP;
   }
   TaskHost* t = k ? k->t : nullptr;
   if (k) {
-    w.K_b = al((size_t)t->npad * p.ldq_max * es); w.colsq_b = al((size_t)t->nblk * p.ldq_max * es);
+    w.K_b = align256((size_t)t->npad * p.ldq_max * es); w.colsq_b = align256((size_t)t->nblk * p.ldq_max * es);
     if (!(w.K = get(WS_K, w.K_b * nbuf)) || !(w.colsq = get(WS_COLSQ, w.colsq_b * nbuf)) || !(w.mupart = get(WS_MUPART, w.colsq_b * nbuf))) return HBO_ERR_HIP;
     if (p.full_cov && !(w.V = get(WS_V, (size_t)t->npad * p.ldq_max * es))) return HBO_ERR_HIP;
   }
@@ -361,7 +358,7 @@ static int post_acquire(const PostCall& pc, int64_t M, const PosteriorOverride* 
     }
   }
   if (p.form != FORM_MFMA) {
-    w.k3_b = al((size_t)p.mpad_max * t->npad * p.planes * sizeof(unsigned short));   // (mpad / 128) x nkb blocks of `planes` x 128 x 16
+    w.k3_b = align256((size_t)p.mpad_max * t->npad * p.planes * sizeof(unsigned short));   // (mpad / 128) x nkb blocks of `planes` x 128 x 16
     if (!(w.K3 = (unsigned short*)get(WS_K3, w.k3_b * nbuf))) { c->err.clear(); replan(POST_NO_SPLIT3); }
   }
   if (p.chunk(0).counter >= 0) w.counters = (int*)ws_get(c, WS_COUNTERS, sizeof(int) * HBO_N_COUNTERS);   // (the first chunk is the largest)
@@ -556,52 +553,32 @@ extern "C" int hbo_acq_samples(hbo_ctx* c, const hbo_model* models, int32_t S, c
   if (M <= 0) return HBO_OK;
   HIPCHK(c, hipSetDevice(c->device));
   const hbo_model* m0 = &models[0];
-  for (int s = 0; s < S; ++s) {
-    const hbo_model* m = &models[s];
-    // (before validate_model: a packed array element has no hbo_model_kumar tail to read)
-    if (m->input_warp != HBO_WARP_NONE)
-      return fail(c, HBO_ERR_UNSUPPORTED, "hbo_acq_samples: input-warped (Kumaraswamy) models are not supported; evaluate the samples with hbo_acq");
-    int rc = validate_model(c, m);
-    if (rc) return rc;
-    if (!same_model_family(m, m0)) return fail(c, HBO_ERR_ARG, "hbo_acq_samples: the samples must share dtype, covariance, mean and MLP architecture");
-  }
+  if (int rc = model_family_check(c, "hbo_acq_samples: ", models, S, "evaluate the samples with hbo_acq")) return rc;
   prof_begin(c);
   const int dtype = m0->dtype;
   const size_t es = esize(dtype);
   hipStream_t st = c->stream;
   const int D = m0->input_dim;
   const bool mlp = needs_mlp(m0);
-  const int L = mlp ? m0->n_layers : 0;
   std::vector<hbo_cache*> ks(S, nullptr);
   auto cleanup = [&]() { for (hbo_cache* k : ks) if (k) hbo_cache_free(c, k); };
-  // ---- the S models, their MLP weights, the queries: device copies that live for the whole call
-  ModelDev* d_models = static_cast<ModelDev*>(ws_get(c, WS_SMP_MODELS, sizeof(ModelDev) * S));
+  // ---- the S models with their MLP weights (one block, through the pinned stage) and the queries: device copies that live for the whole call
+  // (the stage keeps twice models_b of pinned host memory, pinned_stage, until a larger request replaces it: S ModelDevs, and S times the weights of the MLP where there is one)
+  const MlpShape sh = mlp_shape(m0);
+  const size_t models_b = models_pack_bytes(sh, S);
+  ModelDev* d_models = static_cast<ModelDev*>(ws_get(c, WS_SMP_MODELS, models_b));
   TaskDesc* d_batch = static_cast<TaskDesc*>(ws_get(c, WS_SMP_DESC, sizeof(TaskDesc) * S));
   int* d_infos = static_cast<int*>(ws_get(c, WS_SMP_INFO, sizeof(int) * S));
   char* d_acq = static_cast<char*>(ws_get(c, WS_SMP_ACQ, (size_t)S * M * es));
   char* d_xq = static_cast<char*>(ws_get(c, WS_SMP_XQ, (size_t)M * D * es));
   if (!d_models || !d_batch || !d_infos || !d_acq || !d_xq) return HBO_ERR_HIP;
-  std::vector<ModelDev> h_models(S);
-  for (int s = 0; s < S; ++s) fill_model_dev(h_models[s], &models[s]);
-  HIPCHK_OR(c, hipMemcpyAsync(d_models, h_models.data(), sizeof(ModelDev) * S, hipMemcpyHostToDevice, st), cleanup());
-  HIPCHK_OR(c, hipMemcpyAsync(d_xq, xq, (size_t)M * D * es, hipMemcpyHostToDevice, st), cleanup());
   std::vector<void*> w_dev((size_t)S * HBO_MAX_MLP_LAYERS, nullptr), b_dev((size_t)S * HBO_MAX_MLP_LAYERS, nullptr);
-  if (mlp) {
-    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    size_t per = 0; int fin = D;
-    for (int l = 0; l < L; ++l) { per += al((size_t)fin * m0->features[l] * es) + al((size_t)m0->features[l] * es); fin = m0->features[l]; }
-    char* blk = static_cast<char*>(ws_get(c, WS_SMP_MLP, per * S));
-    if (!blk) return HBO_ERR_HIP;
-    for (int s = 0; s < S; ++s) {
-      char* p = blk + per * s; fin = D;
-      for (int l = 0; l < L; ++l) {
-        const size_t wb = (size_t)fin * m0->features[l] * es, bb = (size_t)m0->features[l] * es;
-        w_dev[(size_t)s * HBO_MAX_MLP_LAYERS + l] = p; HIPCHK_OR(c, hipMemcpyAsync(p, models[s].mlp_kernel[l], wb, hipMemcpyHostToDevice, st), cleanup()); p += al(wb);
-        b_dev[(size_t)s * HBO_MAX_MLP_LAYERS + l] = p; HIPCHK_OR(c, hipMemcpyAsync(p, models[s].mlp_bias[l], bb, hipMemcpyHostToDevice, st), cleanup()); p += al(bb);
-        fin = m0->features[l];
-      }
-    }
-  }
+  char* h_models = static_cast<char*>(stage_begin(c, "hbo_acq_samples: ", models_b));
+  if (!h_models) return HBO_ERR_HIP;
+  memset(h_models, 0, models_b);
+  models_pack(h_models, reinterpret_cast<char*>(d_models), models, S, sh, w_dev.data(), b_dev.data());
+  HIPCHK_OR(c, stage_upload(c, d_models, h_models, models_b, st), cleanup());
+  HIPCHK_OR(c, hipMemcpyAsync(d_xq, xq, (size_t)M * D * es, hipMemcpyHostToDevice, st), cleanup());
   // ---- S caches over the same observations (each a complete hbo_cache: everything that reads one works on them)
   const std::vector<unsigned char> yt = transpose_y(y, n, mcols, es);
   std::vector<TaskDesc> h_batch(S);
@@ -650,340 +627,6 @@ extern "C" int hbo_acq_samples(hbo_ctx* c, const hbo_model* models, int32_t S, c
   for (int s = 0; s < S; ++s) if (h_infos[s] != INT_MAX) fill_nan((char*)out + (size_t)s * M * es, (size_t)M, dtype);
   cleanup();
   return any_bad ? HBO_NOT_PD : HBO_OK;
-}
-
-// ---- d acquisition / d x_query: what jaxopt's L-BFGS-B differentiates in bayesopt() (bayesopt.py:116-125) ----
-extern "C" int hbo_acq_grad(hbo_ctx* c, const hbo_model* m, hbo_cache* k, const void* xq, int64_t M, int acq_id,
-                            double param, double add_noise, double scale, void* acq_out, double* grad_out) {
-  if (!c || !xq || !acq_out || !grad_out || !m) return fail(c, HBO_ERR_ARG, "hbo_acq_grad: null argument");
-  if (acq_id < 0 || acq_id > HBO_ACQ_UCB) return fail(c, HBO_ERR_ARG, "hbo_acq_grad: bad acq_id");
-  if (M <= 0) return HBO_OK;
-  HIPCHK(c, hipSetDevice(c->device));
-  int rc = validate_model(c, m);
-  if (rc) return rc;
-  rc = upload_model(c, m);
-  if (rc) return rc;
-  const int dtype = m->dtype;
-  if (k && (k->dtype != dtype || k->D != m->input_dim)) return fail(c, HBO_ERR_ARG, "hbo_acq_grad: cache/model mismatch");
-  if (k && k->input_warp != m->input_warp) return fail(c, HBO_ERR_ARG, "hbo_acq_grad: the cache was factorised with another input warp");
-  const bool kumar = is_kumar(m);
-  const size_t es = esize(dtype);
-  hipStream_t st = c->stream;
-  const int D = m->input_dim, fdim = feature_dim(m);
-  const bool mlp = needs_mlp(m);
-  const int L = m->n_layers, flast = mlp ? m->features[L - 1] : 0;
-  TaskHost* t = (k && k->t->n > 0) ? k->t : nullptr;
-  const int64_t CH = 1024;   // queries per pass: three [CH][npad] panels of workspace
-  const int64_t mc_max = std::min<int64_t>(M, CH);
-  int maxf = D;
-  for (int l = 0; l < L; ++l) maxf = std::max(maxf, (int)m->features[l]);
-  size_t nparam = 1;
-  { int fin0 = D; for (int l = 0; l < L; ++l) { nparam = std::max(nparam, (size_t)(fin0 + 1) * m->features[l]); fin0 = m->features[l]; } }
-  void* d_xq = ws_get(c, WS_XQ, (size_t)mc_max * D * es);
-  void* d_mu0 = ws_get(c, WS_MU0, (size_t)mc_max * es);
-  void* d_kd = ws_get(c, WS_KD, (size_t)mc_max * es);
-  void* d_acq = ws_get(c, WS_ACQ, (size_t)mc_max * es);
-  double* d_gf = (double*)ws_get(c, WS_AG_GF, (size_t)mc_max * fdim * sizeof(double));
-  double* d_dmu = (double*)ws_get(c, WS_AG_DMU, (size_t)mc_max * sizeof(double));
-  double* d_gx = (double*)ws_get(c, WS_AG_GX, (size_t)mc_max * D * sizeof(double));
-  double* d_t0 = (double*)ws_get(c, WS_AG_T0, (size_t)mc_max * maxf * sizeof(double));
-  double* d_t1 = (double*)ws_get(c, WS_AG_T1, (size_t)mc_max * maxf * sizeof(double));
-  double* d_dw = (double*)ws_get(c, WS_AG_DW, nparam * sizeof(double));   // weight-gradient sink of the shared MLP backward
-  if (!d_xq || !d_mu0 || !d_kd || !d_acq || !d_gf || !d_dmu || !d_gx || !d_t0 || !d_t1 || !d_dw) return HBO_ERR_HIP;
-  void* d_kwq = kumar ? ws_get(c, WS_KW_Q, (size_t)mc_max * D * es) : nullptr;
-  if (kumar && !d_kwq) return HBO_ERR_HIP;
-  void *d_K = nullptr, *d_L = nullptr, *d_B = nullptr;
-  if (t) {
-    d_K = ws_get(c, WS_AG_K, (size_t)mc_max * t->npad * es); d_L = ws_get(c, WS_AG_L, (size_t)mc_max * t->npad * es);
-    d_B = ws_get(c, WS_AG_B, (size_t)mc_max * t->npad * es);
-    if (!d_K || !d_L || !d_B) return HBO_ERR_HIP;
-  }
-  void* fq_acts[HBO_MAX_MLP_LAYERS] = {nullptr};
-  if (mlp) for (int l = 0; l < L; ++l) { fq_acts[l] = ws_get(c, WS_FQ0 + l, (size_t)mc_max * m->features[l] * es); if (!fq_acts[l]) return HBO_ERR_HIP; }
-  const bool bad = k && k->info != INT_MAX;
-  for (int64_t q0 = 0; q0 < M; q0 += CH) {
-    const int64_t mc = std::min<int64_t>(CH, M - q0);
-    HIPCHK(c, hipMemcpyAsync(d_xq, (const char*)xq + (size_t)q0 * D * es, (size_t)mc * D * es, hipMemcpyHostToDevice, st));
-    const void* Fq = query_features(c, m, c->d_model, c->d_mlp_w, c->d_mlp_b, d_xq, mc, fq_acts, d_kwq, d_mu0, d_kd, st).Fq;
-    if (t) {
-      HIPCHK(c, hipMemsetAsync(d_K, 0, (size_t)mc * t->npad * es, st));
-      GramArgs g = {}; g.kernel_id = c->h_model->kernel_id; g.mfma_min_f = c->opt_gram_mfma; g.x1 = Fq; g.x2 = k->h_desc.F; g.out = d_K; g.n1 = mc; g.n2 = t->n; g.ldo = t->npad; g.fdim = fdim;
-      launch_gram(dtype, g, c->d_model, dim3((unsigned)((t->n + 127) / 128), (unsigned)((mc + 127) / 128), 1), st);
-      launch_tri_matvec(dtype, t->W, t->ld, t->npad, d_K, t->npad, (int)mc, 0, d_L, t->npad, st);
-      launch_tri_matvec(dtype, t->W, t->ld, t->npad, d_L, t->npad, (int)mc, 1, d_B, t->npad, st);
-    }
-    AcqGradArgs a = {};
-    a.Fq = Fq; a.F = t ? k->h_desc.F : nullptr; a.fdim = fdim; a.n = t ? t->n : 0; a.npad = t ? t->npad : 0;
-    a.Kq = d_K; a.L = d_L; a.B = d_B; a.alpha = t ? t->svec : nullptr; a.kdiag = d_kd; a.muq = d_mu0;
-    a.acq_id = acq_id; a.param = param; a.add_noise = add_noise; a.scale = scale;
-    a.acq_out = d_acq; a.gfeat = d_gf; a.dmu = d_dmu; a.M = mc;
-    launch_acq_grad(dtype, a, c->d_model, st);
-    // assemble d/dx: kernel part (direct or through the MLP) + mean part (mean.py:62-79)
-    double* gmlp = nullptr;   // gradient w.r.t. the MLP output
-    if (m->kernel_uses_mlp) {
-      gmlp = d_gf;
-      if (m->mean_id == HBO_MEAN_LINEAR_MLP) launch_acq_grad_mean(d_dmu, c->d_model, mc, flast, gmlp, 1, st);
-      HIPCHK(c, hipMemsetAsync(d_gx, 0, (size_t)mc * D * sizeof(double), st));
-      if (m->mean_id == HBO_MEAN_LINEAR) launch_acq_grad_mean(d_dmu, c->d_model, mc, D, d_gx, 1, st);
-    } else {
-      if (kumar) launch_kumar_chain_dx(dtype, d_xq, mc, D, c->d_model, d_gf, d_gx, st);   // d acq / d w(x) * dw/dx
-      else HIPCHK(c, hipMemcpyAsync(d_gx, d_gf, (size_t)mc * D * sizeof(double), hipMemcpyDeviceToDevice, st));
-      if (m->mean_id == HBO_MEAN_LINEAR) launch_acq_grad_mean(d_dmu, c->d_model, mc, D, d_gx, 1, st);
-      if (m->mean_id == HBO_MEAN_LINEAR_MLP) { gmlp = d_t0; launch_acq_grad_mean(d_dmu, c->d_model, mc, flast, gmlp, 0, st); }
-    }
-    if (gmlp) {
-      double* cur = gmlp; double* other = (gmlp == d_t0) ? d_t1 : d_t0;
-      for (int l = L - 1; l >= 0; --l) {
-        const int fin = l ? m->features[l - 1] : D;
-        const void* in = l ? fq_acts[l - 1] : d_xq;
-        launch_dense_bwd(dtype, in, fq_acts[l], c->d_mlp_w[l], cur, other, d_dw, d_dw + (size_t)fin * m->features[l], mc, fin, m->features[l], st);
-        cur = other; other = (cur == d_t0) ? d_t1 : d_t0;
-      }
-      launch_add_inplace(d_gx, cur, mc * D, st);
-    }
-    HIPCHK(c, hipMemcpyAsync((char*)acq_out + (size_t)q0 * es, d_acq, (size_t)mc * es, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipMemcpyAsync(grad_out + (size_t)q0 * D, d_gx, (size_t)mc * D * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipStreamSynchronize(st));
-  }
-  HIPCHK(c, hipGetLastError());
-  if (bad) {
-    fill_nan(acq_out, (size_t)M, dtype);
-    for (int64_t i = 0; i < M * D; ++i) grad_out[i] = NAN;
-    return HBO_NOT_PD;
-  }
-  return HBO_OK;
-}
-
-// ---- the same for S parameter samples of one model family over their FINISHED caches, n <= 128: one upload, one launch (acq_small.hip:
-//      a workgroup per (sample, query) pair), one copy back, one wait -- whatever S is.  Row s = hbo_acq_grad of sample s up to the order
-//      of summation.  The prior branch, MLP bases and input-warped models stay with hbo_acq_grad (HBO_ERR_UNSUPPORTED here, before any
-//      device work).
-//      val64_out (nullable, [S][M]): the values before they are rounded to the model dtype (include/hbo_tune.h:
-//      hbo_probe_acq_grad_samples64); without it the call is hbo_acq_grad_samples, to the byte of every buffer.
-static int acq_grad_samples(hbo_ctx* c, const hbo_model* models, int32_t S, hbo_cache* const* caches, const void* xq, int64_t M, int acq_id,
-                            const double* params, const double* add_noise, double scale, void* acq_out, double* grad_out, double* val64_out) {
-  if (!models || !caches || !xq || !params || !add_noise || !acq_out || !grad_out) return fail(c, HBO_ERR_ARG, "hbo_acq_grad_samples: null argument");
-  if (S <= 0 || S > 4096) return fail(c, HBO_ERR_ARG, "hbo_acq_grad_samples: 1 <= S <= 4096");
-  if (acq_id < 0 || acq_id > HBO_ACQ_UCB) return fail(c, HBO_ERR_ARG, "hbo_acq_grad_samples: bad acq_id");
-  if (!c) return fail(c, HBO_ERR_ARG, "hbo_acq_grad_samples: ctx is null");
-  if (M < 0) return fail(c, HBO_ERR_ARG, "hbo_acq_grad_samples: M < 0");
-  const hbo_model* m0 = &models[0];
-  bool any_bad = false;
-  if (int rc = acq_samples_check(c, "hbo_acq_grad_samples: ", models, S, caches, &any_bad)) return rc;
-  if (M == 0) return HBO_OK;
-  HIPCHK(c, hipSetDevice(c->device));
-  const int dtype = m0->dtype, D = m0->input_dim;
-  const size_t es = esize(dtype);
-  hipStream_t st = c->stream;
-  auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-  // one block up: [S records][S x 2 D doubles][M x D queries]; one block down: [S x M x D doubles][S x M values]
-  const size_t smp_b = al(sizeof(AcqSmallSample) * S), vec_b = al(sizeof(double) * 2 * D * S), xq_b = (size_t)M * D * es;
-  const size_t grad_b = al(sizeof(double) * (size_t)S * M * D), acq_b = (size_t)S * M * es;
-  const size_t v64_o = al(grad_b + acq_b), v64_b = val64_out ? sizeof(double) * (size_t)S * M : 0;
-  const size_t in_b = smp_b + vec_b + xq_b, out_b = val64_out ? v64_o + v64_b : grad_b + acq_b;
-  char* d_in = static_cast<char*>(ws_get(c, WS_AF_IN, in_b));
-  char* d_out = static_cast<char*>(ws_get(c, WS_AF_OUT, out_b));
-  if (!d_in || !d_out) return HBO_ERR_HIP;
-  HIPCHK(c, hipEventSynchronize(c->ev_upload));   // the pinned buffer may still feed an earlier upload
-  char* stage = static_cast<char*>(pinned_stage(c, al(in_b) + out_b));
-  if (!stage) return fail(c, HBO_ERR_HIP, "hbo_acq_grad_samples: no pinned staging memory");
-  char* stage_out = stage + al(in_b);
-  AcqSmallSample* hs = reinterpret_cast<AcqSmallSample*>(stage);
-  double* hv = reinterpret_cast<double*>(stage + smp_b);
-  acq_small_pack(hs, hv, models, S, caches, params, add_noise);
-  memcpy(stage + smp_b + vec_b, xq, xq_b);
-  HIPCHK(c, hipMemcpyAsync(d_in, stage, in_b, hipMemcpyHostToDevice, st));
-  HIPCHK(c, hipEventRecord(c->ev_upload, st));
-  AcqSmallArgs a = {};
-  a.smp = reinterpret_cast<const AcqSmallSample*>(d_in); a.vec = reinterpret_cast<const double*>(d_in + smp_b); a.xq = d_in + smp_b + vec_b;
-  a.D = D; a.M = M; a.kernel_id = m0->kernel_id; a.mean_id = m0->mean_id; a.acq_id = acq_id; a.scale = scale;
-  a.grad_out = reinterpret_cast<double*>(d_out); a.acq_out = d_out + grad_b;
-  if (val64_out) a.val64_out = reinterpret_cast<double*>(d_out + v64_o);
-  launch_acq_small(dtype, a, S, st);
-  HIPCHK(c, hipMemcpyAsync(stage_out, d_out, out_b, hipMemcpyDeviceToHost, st));
-  HIPCHK(c, hipStreamSynchronize(st));
-  HIPCHK(c, hipGetLastError());
-  memcpy(grad_out, stage_out, sizeof(double) * (size_t)S * M * D);
-  memcpy(acq_out, stage_out + grad_b, acq_b);
-  if (val64_out) memcpy(val64_out, stage_out + v64_o, v64_b);
-  return any_bad ? HBO_NOT_PD : HBO_OK;
-}
-extern "C" int hbo_acq_grad_samples(hbo_ctx* c, const hbo_model* models, int32_t S, hbo_cache* const* caches, const void* xq, int64_t M,
-                                    int acq_id, const double* params, const double* add_noise, double scale, void* acq_out,
-                                    double* grad_out) {
-  return acq_grad_samples(c, models, S, caches, xq, M, acq_id, params, add_noise, scale, acq_out, grad_out, nullptr);
-}
-// include/hbo_tune.h (TEST HOOK): hbo_acq_grad_samples with the fp64 values hbo_acq_maximize's control kernel reads
-extern "C" int hbo_probe_acq_grad_samples64(hbo_ctx* c, const hbo_model* models, int32_t S, hbo_cache* const* caches, const void* xq, int64_t M,
-                                            int acq_id, const double* params, const double* add_noise, double scale, void* acq_out,
-                                            double* grad_out, double* val64_out) {
-  if (!val64_out) return fail(c, HBO_ERR_ARG, "hbo_probe_acq_grad_samples64: val64_out is null");
-  return acq_grad_samples(c, models, S, caches, xq, M, acq_id, params, add_noise, scale, acq_out, grad_out, val64_out);
-}
-
-// ---- the simulated BO loop of R runs in one call (bayesopt.py:136-190; kernels and the recurrence: bo_loop.hip) ----
-// Set-up once per call through the device code every posterior uses (query_features: MLP forward, mean, prior diagonal -- per run, with
-// its own model and weights), then the n0 + iters steps of every run as two stream-ordered launches each, all queued before the one
-// synchronisation.  The small records go up through the pinned stage, the pools straight from the caller's arrays, and the results
-// come back straight into the caller's arrays: no host-side copy of a pool.
-extern "C" int hbo_bo_simulated(hbo_ctx* c, const hbo_model* models, const hbo_bo_run* runs, int32_t R, int32_t iters, int32_t* sel_out,
-                                double* acq_out, void* mu_out, void* var_out, int32_t* status) {
-  if (!models || !runs || !sel_out || !acq_out || !status) return fail(c, HBO_ERR_ARG, "hbo_bo_simulated: null argument");
-  if (R <= 0 || R > 4096) return fail(c, HBO_ERR_ARG, "hbo_bo_simulated: 1 <= R <= 4096");
-  if (iters <= 0 || iters > 65536) return fail(c, HBO_ERR_ARG, "hbo_bo_simulated: 1 <= iters <= 65536");
-  const hbo_model* m0 = &models[0];
-  for (int r = 0; r < R; ++r) {
-    const hbo_model* m = &models[r];
-    const hbo_bo_run& u = runs[r];
-    // (before validate_model: a packed array element has no hbo_model_kumar tail to read)
-    if (m->input_warp != HBO_WARP_NONE)
-      return fail(c, HBO_ERR_UNSUPPORTED, "hbo_bo_simulated: input-warped (Kumaraswamy) models are not supported; run the host loop");
-    if (int rc = validate_model(c, m)) return rc;
-    if (!same_model_family(m, m0)) return fail(c, HBO_ERR_ARG, "hbo_bo_simulated: the runs' models must share dtype, covariance, mean, input_dim and MLP architecture");
-    if (u.M <= 0) return fail(c, HBO_ERR_ARG, "hbo_bo_simulated: a run has an empty candidate pool (M <= 0)");
-    if (u.n0 < 0 || u.M + u.n0 >= ((int64_t)1 << 31)) return fail(c, HBO_ERR_ARG, "hbo_bo_simulated: need n0 >= 0 and M + n0 < 2^31");
-    if (!u.xc || !u.yc || (u.n0 > 0 && (!u.x0 || !u.y0))) return fail(c, HBO_ERR_ARG, "hbo_bo_simulated: a run's pool or observations are null");
-    if (u.acq_id < 0 || u.acq_id > HBO_ACQ_UCB) return fail(c, HBO_ERR_ARG, "hbo_bo_simulated: bad acq_id");
-    if (u.param_mode < 0 || u.param_mode > HBO_BO_PARAM_MAX_PLUS_STD) return fail(c, HBO_ERR_ARG, "hbo_bo_simulated: bad param_mode");
-  }
-  const int dtype = m0->dtype, D = m0->input_dim, fdim = feature_dim(m0);
-  const size_t es = esize(dtype);
-  const bool mlp = needs_mlp(m0);
-  const int L = mlp ? m0->n_layers : 0;
-  auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-  // ---- sizes: [in] what goes up, [feat] set-up results (model dtype), [v] the fp64 state, [out] what comes back + the arg-max partials
-  size_t mlp_per = 0;
-  { int fin = D; for (int l = 0; l < L; ++l) { mlp_per += al((size_t)fin * m0->features[l] * es) + al((size_t)m0->features[l] * es); fin = m0->features[l]; } }
-  // (the head of [in] -- run records, pivots, 1 / lengthscale, models, MLP weights -- is staged in pinned memory; the pools go up straight from the caller's)
-  const size_t head_b = al(sizeof(BoRunDev) * R) + al(sizeof(BoPivot) * R) + al(sizeof(double) * fdim * R) + al(sizeof(ModelDev) * R) + mlp_per * R;
-  size_t in_b = head_b;
-  size_t feat_b = 0, v_b = 0, part_b = 0;
-  int64_t sum_M = 0, max_ncol = 0, max_steps = 0;
-  for (int r = 0; r < R; ++r) {
-    const int64_t ncol = runs[r].M + runs[r].n0, steps = runs[r].n0 + iters;
-    in_b += al((size_t)ncol * D * es) + al((size_t)ncol * es);
-    feat_b += 2 * al((size_t)ncol * es);
-    for (int l = 0; l < L; ++l) feat_b += al((size_t)ncol * m0->features[l] * es);
-    v_b += al(sizeof(double) * (size_t)steps * ncol) + 2 * al(sizeof(double) * ncol) + al(sizeof(double) * steps);
-    const size_t nch = (size_t)((runs[r].M + 255) / 256);
-    part_b += al(sizeof(double) * nch) + al(sizeof(int32_t) * nch);
-    sum_M += runs[r].M; max_ncol = std::max(max_ncol, ncol); max_steps = std::max(max_steps, steps);
-  }
-  const size_t acq_b = al(sizeof(double) * (size_t)R * iters), sel_b = al(sizeof(int32_t) * (size_t)R * iters), st_b = al(sizeof(int32_t) * R);
-  const size_t post_b = al((size_t)sum_M * es);
-  const size_t down_b = acq_b + sel_b + st_b + 2 * post_b, out_b = down_b + part_b;
-  if (!c) return fail(c, HBO_ERR_ARG, "hbo_bo_simulated: ctx is null");
-  HIPCHK(c, hipSetDevice(c->device));
-  { size_t total = 0;
-    HIPCHK(c, hipDeviceTotalMem(&total, c->device));
-    if (v_b > total / 2) return fail(c, HBO_ERR_UNSUPPORTED, "hbo_bo_simulated: the runs' workspaces ((n0 + iters) x (M + n0) doubles each) exceed half of the device memory; split the batch"); }
-  hipStream_t st = c->stream;
-  char* d_in = static_cast<char*>(ws_get(c, WS_BO_IN, in_b));
-  char* d_feat = static_cast<char*>(ws_get(c, WS_BO_FEAT, feat_b));
-  char* d_v = static_cast<char*>(ws_get(c, WS_BO_V, v_b));
-  char* d_out = static_cast<char*>(ws_get(c, WS_BO_OUT, out_b));
-  if (!d_in || !d_feat || !d_v || !d_out) return HBO_ERR_HIP;
-  // ---- the head of the block that goes up, and the device addresses of everything else
-  HIPCHK(c, hipEventSynchronize(c->ev_upload));   // the pinned buffer may still feed an earlier upload
-  char* h_in = static_cast<char*>(pinned_stage(c, head_b));
-  if (!h_in) return fail(c, HBO_ERR_HIP, "hbo_bo_simulated: no pinned staging memory");
-  memset(h_in, 0, head_b);
-  size_t off = 0;
-  auto take = [&](size_t bytes) { const size_t o = off; off += al(bytes); return o; };
-  const size_t o_runs = take(sizeof(BoRunDev) * R), o_piv = take(sizeof(BoPivot) * R), o_ils = take(sizeof(double) * fdim * R), o_md = take(sizeof(ModelDev) * R);
-  BoRunDev* h_runs = reinterpret_cast<BoRunDev*>(h_in + o_runs);
-  BoPivot* h_piv = reinterpret_cast<BoPivot*>(h_in + o_piv);
-  double* h_ils = reinterpret_cast<double*>(h_in + o_ils);
-  ModelDev* h_md = reinterpret_cast<ModelDev*>(h_in + o_md);
-  size_t xoff = head_b;   // the pools behind the head
-  std::vector<void*> w_dev((size_t)R * HBO_MAX_MLP_LAYERS, nullptr), b_dev((size_t)R * HBO_MAX_MLP_LAYERS, nullptr), acts((size_t)R * HBO_MAX_MLP_LAYERS, nullptr);
-  std::vector<const void*> d_x(R);
-  size_t foff = 0, voff = 0, poff = down_b, moff = 0;
-  for (int r = 0; r < R; ++r) {
-    const hbo_bo_run& u = runs[r];
-    const int64_t ncol = u.M + u.n0, steps = u.n0 + iters;
-    BoRunDev& q = h_runs[r];
-    fill_model_dev(h_md[r], &models[r]);
-    const ModelDev& md = h_md[r];
-    memcpy(h_ils + (size_t)r * fdim, md.inv_ls, sizeof(double) * fdim);
-    q.inv_ls = reinterpret_cast<const double*>(d_in + o_ils) + (size_t)r * fdim;
-    // inputs and values: the pool, then the initial observations (uploaded below)
-    d_x[r] = d_in + xoff; xoff += al((size_t)ncol * D * es);
-    q.y = d_in + xoff; xoff += al((size_t)ncol * es);
-    { int fin = D;
-      for (int l = 0; l < L; ++l) {
-        const size_t wb = (size_t)fin * m0->features[l] * es, bb = (size_t)m0->features[l] * es;
-        const size_t o_w = take(wb), o_b = take(bb);
-        memcpy(h_in + o_w, models[r].mlp_kernel[l], wb); memcpy(h_in + o_b, models[r].mlp_bias[l], bb);
-        w_dev[(size_t)r * HBO_MAX_MLP_LAYERS + l] = d_in + o_w; b_dev[(size_t)r * HBO_MAX_MLP_LAYERS + l] = d_in + o_b;
-        acts[(size_t)r * HBO_MAX_MLP_LAYERS + l] = d_feat + foff; foff += al((size_t)ncol * m0->features[l] * es);
-        fin = m0->features[l];
-      } }
-    q.F = m0->kernel_uses_mlp ? acts[(size_t)r * HBO_MAX_MLP_LAYERS + L - 1] : d_x[r];   // what query_features hands the covariance
-    q.mu0 = d_feat + foff; foff += al((size_t)ncol * es);
-    q.kd = d_feat + foff; foff += al((size_t)ncol * es);
-    q.V = reinterpret_cast<double*>(d_v + voff); voff += al(sizeof(double) * (size_t)steps * ncol);
-    q.sumsq = reinterpret_cast<double*>(d_v + voff); voff += al(sizeof(double) * ncol);
-    q.mu = reinterpret_cast<double*>(d_v + voff); voff += al(sizeof(double) * ncol);
-    q.yobs = reinterpret_cast<double*>(d_v + voff); voff += al(sizeof(double) * steps);
-    q.piv = reinterpret_cast<BoPivot*>(d_in + o_piv) + r;
-    const size_t nch = (size_t)((u.M + 255) / 256);
-    q.part_val = reinterpret_cast<double*>(d_out + poff); poff += al(sizeof(double) * nch);
-    q.part_idx = reinterpret_cast<int32_t*>(d_out + poff); poff += al(sizeof(int32_t) * nch);
-    q.acq = reinterpret_cast<double*>(d_out) + (size_t)r * iters;
-    q.sel = reinterpret_cast<int32_t*>(d_out + acq_b) + (size_t)r * iters;
-    q.status = reinterpret_cast<int32_t*>(d_out + acq_b + sel_b) + r;
-    q.mu_out = mu_out ? d_out + acq_b + sel_b + st_b + moff * es : nullptr;
-    q.var_out = var_out ? d_out + acq_b + sel_b + st_b + post_b + moff * es : nullptr;
-    moff += (size_t)u.M;
-    q.M = u.M; q.ncol = ncol; q.n0 = (int)u.n0; q.steps = (int)steps;
-    q.fdim = fdim; q.kernel_id = m0->kernel_id; q.acq_id = u.acq_id; q.param_mode = u.param_mode;
-    q.param = u.param; q.add_noise = u.add_noise; q.scale0 = u.scale0; q.scale = u.scale;
-    q.sv = md.sv; q.inv_sigma2 = 1.0 / (md.dot_sigma * md.dot_sigma); q.bias2 = md.dot_bias * md.dot_bias; q.noise_eps = md.noise + md.eps;
-    h_piv[r].p = 0; h_piv[r].l = NAN; h_piv[r].z = NAN; h_piv[r].ymax = NAN;
-    h_piv[r].param = u.param_mode == HBO_BO_PARAM_CONST ? u.param : 0.0;   // over an empty y (acfun.py:145-148, 160-166)
-  }
-  // (from the first queued copy on, an error waits for the stream before it returns: the copies read and write the caller's memory)
-  auto bail = [&]() { hipStreamSynchronize(st); };
-  HIPCHK_OR(c, hipMemcpyAsync(d_in, h_in, head_b, hipMemcpyHostToDevice, st), bail());
-  HIPCHK_OR(c, hipEventRecord(c->ev_upload, st), bail());
-  for (int r = 0; r < R; ++r) {
-    const hbo_bo_run& u = runs[r];
-    char* dx = static_cast<char*>(const_cast<void*>(d_x[r]));
-    char* dy = static_cast<char*>(const_cast<void*>(h_runs[r].y));
-    HIPCHK_OR(c, hipMemcpyAsync(dx, u.xc, (size_t)u.M * D * es, hipMemcpyHostToDevice, st), bail());
-    HIPCHK_OR(c, hipMemcpyAsync(dy, u.yc, (size_t)u.M * es, hipMemcpyHostToDevice, st), bail());
-    if (u.n0 > 0) {
-      HIPCHK_OR(c, hipMemcpyAsync(dx + (size_t)u.M * D * es, u.x0, (size_t)u.n0 * D * es, hipMemcpyHostToDevice, st), bail());
-      HIPCHK_OR(c, hipMemcpyAsync(dy + (size_t)u.M * es, u.y0, (size_t)u.n0 * es, hipMemcpyHostToDevice, st), bail());
-    }
-  }
-  HIPCHK_OR(c, hipMemsetAsync(d_out + acq_b + sel_b, 0, st_b, st), bail());
-  // ---- set-up: features of all columns, the mean and the prior diagonal at them, per run under its own model
-  const ModelDev* d_md = reinterpret_cast<const ModelDev*>(d_in + o_md);
-  for (int r = 0; r < R; ++r) {
-    const int64_t ncol = runs[r].M + runs[r].n0;
-    const BoRunDev& q = h_runs[r];
-    query_features(c, &models[r], d_md + r, mlp ? &w_dev[(size_t)r * HBO_MAX_MLP_LAYERS] : nullptr, mlp ? &b_dev[(size_t)r * HBO_MAX_MLP_LAYERS] : nullptr,
-                   d_x[r], ncol, &acts[(size_t)r * HBO_MAX_MLP_LAYERS], nullptr, const_cast<void*>(q.mu0), const_cast<void*>(q.kd), st);
-  }
-  // ---- the steps, all queued: row l (the prior at l = 0, the final posterior at l = steps), then the selection / forced pivot of row l
-  const BoRunDev* d_runs = reinterpret_cast<const BoRunDev*>(d_in + o_runs);
-  for (int l = 0; l <= (int)max_steps; ++l) {
-    launch_bo_row(dtype, d_runs, R, max_ncol, l, st);
-    if (l < (int)max_steps) launch_bo_select(dtype, d_runs, R, l, st);
-  }
-  // ---- the results straight into the caller's arrays (the device block holds them in the caller's layout), one wait
-  HIPCHK_OR(c, hipMemcpyAsync(acq_out, d_out, sizeof(double) * (size_t)R * iters, hipMemcpyDeviceToHost, st), bail());
-  HIPCHK_OR(c, hipMemcpyAsync(sel_out, d_out + acq_b, sizeof(int32_t) * (size_t)R * iters, hipMemcpyDeviceToHost, st), bail());
-  HIPCHK_OR(c, hipMemcpyAsync(status, d_out + acq_b + sel_b, sizeof(int32_t) * R, hipMemcpyDeviceToHost, st), bail());
-  if (mu_out) HIPCHK_OR(c, hipMemcpyAsync(mu_out, d_out + acq_b + sel_b + st_b, (size_t)sum_M * es, hipMemcpyDeviceToHost, st), bail());
-  if (var_out) HIPCHK_OR(c, hipMemcpyAsync(var_out, d_out + acq_b + sel_b + st_b + post_b, (size_t)sum_M * es, hipMemcpyDeviceToHost, st), bail());
-  HIPCHK(c, hipStreamSynchronize(st));
-  HIPCHK(c, hipGetLastError());
-  for (int r = 0; r < R; ++r) if (status[r] < 0) return fail(c, HBO_ERR_HIP, "hbo_bo_simulated: a selection left the candidate pool (internal error)");
-  for (int r = 0; r < R; ++r) if (status[r] != HBO_OK) return HBO_NOT_PD;
-  return HBO_OK;
 }
 
 // Test hook (include/hbo_tune.h): the fp32 split-operand posterior product on caller-chosen operands -- W and Kxq go up padded as a

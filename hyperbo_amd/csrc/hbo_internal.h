@@ -419,7 +419,7 @@ struct AcqSmallArgs {
   double* val64_out;                                 // nullable [S][M]: the value before it is rounded to the model dtype (acq_opt.hip)
 };
 void launch_acq_small(int dtype, const AcqSmallArgs& a, int S, hipStream_t st);
-// ---- the simulated BO loop on the device (bo_loop.hip; host side: cache.hip: hbo_bo_simulated) ----
+// ---- the simulated BO loop on the device (bo_loop.hip: kernels and hbo_bo_simulated) ----
 // The pivot of the next row of a run: written by bo_select_kernel, read by the bo_row_kernel behind it.  Before the first selection
 // only `param` is read (set by the host: the acquisition parameter over an empty y).
 struct BoPivot {

@@ -144,10 +144,9 @@ int objective_local(hbo_ctx* c, const hbo_model* m_in, hbo_dataset* ds, int obje
   }
   if (!lds_only && !ds->d_svec && T > 1) {
     // first evaluation of this dataset: every task's alpha vector from ONE zeroed block
-    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
     const size_t es = esize(ds->dtype);
     size_t tot = 0;
-    for (TaskHost* t : ds->tasks) tot += al((size_t)t->npad * es * (obj == OBJ_NLL ? 1 : t->m + 1));
+    for (TaskHost* t : ds->tasks) tot += align256((size_t)t->npad * es * (obj == OBJ_NLL ? 1 : t->m + 1));
     bool fresh = true;
     for (TaskHost* t : ds->tasks) if (t->svec) fresh = false;
     if (fresh && dev_alloc(c, &ds->d_svec, tot) == hipSuccess) {
@@ -156,7 +155,7 @@ int objective_local(hbo_ctx* c, const hbo_model* m_in, hbo_dataset* ds, int obje
       for (TaskHost* t : ds->tasks) {
         const int cols = obj == OBJ_NLL ? 1 : t->m + 1;
         t->svec = (char*)ds->d_svec + off; t->svec_cols = cols; t->svec_shared = true;
-        off += al((size_t)t->npad * es * cols);
+        off += align256((size_t)t->npad * es * cols);
       }
     } else { (void)hipGetLastError(); ds->d_svec = nullptr; }
   }
@@ -218,13 +217,13 @@ int objective_local(hbo_ctx* c, const hbo_model* m_in, hbo_dataset* ds, int obje
   }
   ds->d_nll = ds->d_pack; ds->d_gradout = ds->d_pack + T; ds->d_info = reinterpret_cast<int*>(ds->d_pack + T + (size_t)T * out_stride);
   // small transfers go through one pinned buffer: descriptors up (only when they changed), results down in one copy
+  // (fetched at its final size here, and not waited for: a call whose descriptors stand only uses it as the target of the copy back)
   unsigned char* stage = static_cast<unsigned char*>(pinned_stage(c, std::max(sizeof(TaskDesc) * T, pack_bytes)));
   if (!stage) return fail(c, HBO_ERR_HIP, "hbo_objective: pinned staging buffer");
   if (ds->h_desc_dev.size() != (size_t)T || memcmp(ds->h_desc_dev.data(), ds->h_desc.data(), sizeof(TaskDesc) * T) != 0) {
-    HIPCHK(c, hipEventSynchronize(c->ev_upload));
+    HIPCHK(c, stage_wait(c));   // the upload before this one may still read the buffer
     memcpy(stage, ds->h_desc.data(), sizeof(TaskDesc) * T);
-    HIPCHK(c, hipMemcpyAsync(ds->d_desc, stage, sizeof(TaskDesc) * T, hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipEventRecord(c->ev_upload, st));   // the pinned buffer is written again further down (sharded: the scatter map)
+    HIPCHK(c, stage_upload(c, ds->d_desc, stage, sizeof(TaskDesc) * T, st));   // the pinned buffer is written again further down (sharded: the scatter map)
     ds->h_desc_dev = ds->h_desc;
   }
   // (a batch that takes the single-workgroup evaluation sets its info words itself: one launch less on a 60 us path)
@@ -379,10 +378,10 @@ int objective_local(hbo_ctx* c, const hbo_model* m_in, hbo_dataset* ds, int obje
     int* d_map = static_cast<int*>(ws_get(c, WS_SHARD_MAP, sizeof(int) * hmap.size()));
     double* d_red = static_cast<double*>(ws_get(c, WS_SHARD_RED, sizeof(double) * red_count));
     if (!d_map || !d_red) return HBO_ERR_HIP;
-    HIPCHK(c, hipEventSynchronize(c->ev_upload));
+    stage = static_cast<unsigned char*>(stage_begin(c, "hbo_objective: ", sizeof(int) * hmap.size()));
+    if (!stage) return HBO_ERR_HIP;
     memcpy(stage, hmap.data(), sizeof(int) * hmap.size());
-    HIPCHK(c, hipMemcpyAsync(d_map, stage, sizeof(int) * hmap.size(), hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipEventRecord(c->ev_upload, st));
+    HIPCHK(c, stage_upload(c, d_map, stage, sizeof(int) * hmap.size(), st));
     launch_shard_reduce(ds->d_nll, want_grad ? ds->d_gradout : nullptr, ds->d_info, T, out_stride, d_map, ds->d_mlpgrad, d_map + out_stride, nseg,
                         d_red, red_count, st);
     hipEvent_t ev1 = pool_event_timed(c, 1);
@@ -486,7 +485,7 @@ static int objective_impl(hbo_ctx* c, const hbo_model* m_in, hbo_dataset* ds, in
   HIPCHK(c, hipEventRecord(ev2, st));
   double* stage = static_cast<double*>(pinned_stage(c, sizeof(double) * red_count));
   if (!stage) return fail(c, HBO_ERR_HIP, "hbo_objective_sharded: pinned staging buffer");
-  HIPCHK(c, hipEventSynchronize(c->ev_upload));
+  HIPCHK(c, stage_wait(c));
   HIPCHK(c, hipMemcpyAsync(stage, so.d_red, sizeof(double) * red_count, hipMemcpyDeviceToHost, st));
   HIPCHK(c, hipStreamSynchronize(st));
   HIPCHK(c, hipGetLastError());

@@ -13,6 +13,13 @@ static inline int round_up(int64_t n, int q) { return (int)(((n + q - 1) / q) * 
 // leading dimension: padded extent + 128 bytes, so that rows do not sit at a power-of-two stride
 // (a 64 KiB row stride maps every row of a k-contiguous tile onto the same L2/HBM channel)
 static inline int64_t padded_ld(int64_t extent, int dtype) { return extent + 128 / (int64_t)esize(dtype); }
+// Blocks that travel or live as one allocation hold their parts at 256-byte boundaries.  BlockLayout hands out the offsets: one pass
+// over the parts gives every offset and, in `off`, the size -- the same pass, not a second copy of its expressions, places the pointers.
+static inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
+struct BlockLayout {
+  size_t off = 0;
+  size_t take(size_t bytes) { const size_t o = off; off += align256(bytes); return o; }
+};
 
 // Every device allocation of the library: out of memory with buffers parked in the pool (dev_free below) -> release them and
 // retry once.  (A training loop with changing batch shapes parks gigabytes; a posterior workspace must not fail beside them.)
@@ -32,7 +39,7 @@ static inline hipError_t hbo_malloc(hbo_ctx* c, void** out, size_t bytes) {
 #define HBO_H2_WORDS (3 * HBO_H2_LEVELS + 4)   // per level of the inverse: max |W11|, |S21|, |W22|; the last word: max |W| for K^-1 = W^T W
 enum WsSlot { WS_XQ = 1, WS_MU0, WS_KD, WS_MU, WS_VAR, WS_ACQ, WS_K, WS_COLSQ, WS_V, WS_KQQ, WS_COV,
               WS_AP_KX, WS_AP_L, WS_AP_W, WS_AP_MU, WS_AP_KD, WS_AP_Y, WS_VPART, WS_GATHER, WS_COUNTERS, WS_MUPART,
-              WS_AG_K, WS_AG_L, WS_AG_B, WS_AG_GF, WS_AG_DMU, WS_AG_GX, WS_AG_T0, WS_AG_T1, WS_AG_DW, WS_SHARD_RED, WS_SHARD_MAP, WS_SYRK3_A, WS_SYRK3_B, WS_TRTRI3_X, WS_TRTRI3_Y, WS_LAUUM3, WS_SMP_MODELS, WS_SMP_DESC, WS_SMP_INFO, WS_SMP_ACQ, WS_SMP_MLP, WS_SMP_XQ, WS_EXTRA_Z, WS_SMALL_W, WS_H2_AUG, WS_H2_SCALES, WS_FQ0 /* + layer */,
+              WS_AG_K, WS_AG_L, WS_AG_B, WS_AG_GF, WS_AG_DMU, WS_AG_GX, WS_AG_T0, WS_AG_T1, WS_AG_DW, WS_SHARD_RED, WS_SHARD_MAP, WS_SYRK3_A, WS_SYRK3_B, WS_TRTRI3_X, WS_TRTRI3_Y, WS_LAUUM3, WS_SMP_MODELS, WS_SMP_DESC, WS_SMP_INFO, WS_SMP_ACQ, WS_SMP_XQ, WS_EXTRA_Z, WS_SMALL_W, WS_H2_AUG, WS_H2_SCALES, WS_FQ0 /* + layer */,
               WS_FQ_LAST = WS_FQ0 + HBO_MAX_MLP_LAYERS - 1, WS_K3, WS_KW_Q, WS_KU_PART,
               WS_NS_MODELS, WS_NS_MODELS_X, WS_NS_DESC, WS_NS_PACK, WS_NS_MLP_W, WS_NS_MLPT, WS_NS_ACTS, WS_NS_MAT, WS_TRAIN, WS_AF_IN, WS_AF_OUT,
               WS_BO_IN, WS_BO_FEAT, WS_BO_V, WS_BO_OUT, WS_AO_IN, WS_AO_OUT,

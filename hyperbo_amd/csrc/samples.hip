@@ -24,23 +24,14 @@ __global__ void expand_models_kernel(const ModelDev* __restrict__ src, ModelDev*
   uint64_t* d = reinterpret_cast<uint64_t*>(dst + blockIdx.x);
   for (int i = threadIdx.x; i < NW; i += blockDim.x) d[i] = s[i];
 }
-inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 }  // namespace
 
 extern "C" int hbo_nll_samples(hbo_ctx* c, const hbo_model* models, int32_t S, hbo_dataset* ds, double* nll_sum,
                                double* nll_per_task) {
   if (!c || !models || !ds || !nll_sum) return fail(c, HBO_ERR_ARG, "hbo_nll_samples: null argument");
   if (S <= 0 || S > 4096) return fail(c, HBO_ERR_ARG, "hbo_nll_samples: 1 <= S <= 4096");
-  // (before validate_model: a packed array element has no hbo_model_kumar tail to read)
-  for (int s = 0; s < S; ++s)
-    if (models[s].input_warp != HBO_WARP_NONE)
-      return fail(c, HBO_ERR_UNSUPPORTED, "hbo_nll_samples: input-warped (Kumaraswamy) models are not supported; evaluate them with hbo_nll");
+  if (int rc = model_family_check(c, "hbo_nll_samples: ", models, S, "evaluate them with hbo_nll")) return rc;
   const hbo_model* m0 = &models[0];
-  for (int s = 0; s < S; ++s) {
-    int rc = validate_model(c, &models[s]);
-    if (rc) return rc;
-    if (!same_model_family(&models[s], m0)) return fail(c, HBO_ERR_ARG, "hbo_nll_samples: the samples must share dtype, covariance, mean and MLP architecture");
-  }
   const int T = ds->ntasks;
   if (T > 0 && (m0->dtype != ds->dtype || m0->input_dim != ds->D)) return fail(c, HBO_ERR_ARG, "hbo_nll_samples: model/dataset dtype or input_dim mismatch");
   for (int s = 0; s < S; ++s) nll_sum[s] = 0;
@@ -51,7 +42,8 @@ extern "C" int hbo_nll_samples(hbo_ctx* c, const hbo_model* models, int32_t S, h
   const size_t es = esize(dtype);
   hipStream_t st = c->stream;
   const bool mlp = needs_mlp(m0);
-  const int L = mlp ? m0->n_layers : 0;
+  const MlpShape sh = mlp_shape(m0);
+  const int L = sh.L;
   const int fdim = feature_dim(m0);
   const int max_nblk = ds->max_nblk, max_npad = max_nblk * HBO_TILE;
   int64_t max_n = 0;
@@ -64,27 +56,22 @@ extern "C" int hbo_nll_samples(hbo_ctx* c, const hbo_model* models, int32_t S, h
   std::vector<ModelDev> h_models(S);
   for (int s = 0; s < S; ++s) fill_model_dev(h_models[s], &models[s]);
   HIPCHK(c, hipMemcpyAsync(d_models, h_models.data(), sizeof(ModelDev) * S, hipMemcpyHostToDevice, st));
-  // layer l: [S][fin][fout] weights, then [S][fout] biases
-  std::vector<size_t> woff(L), boff(L), wbytes(L), bbytes(L);
+  // layer-major, as launch_mlp_forward_batch indexes them -- layer l: [S][fin][fout] weights, then [S][fout] biases
+  std::vector<size_t> woff(L), boff(L);
   std::vector<unsigned char> h_w;
   char* d_wblk = nullptr;
   if (mlp) {
-    size_t tot = 0; int fin = m0->input_dim;
-    for (int l = 0; l < L; ++l) {
-      wbytes[l] = (size_t)fin * m0->features[l] * es; bbytes[l] = (size_t)m0->features[l] * es;
-      woff[l] = tot; tot += align256(wbytes[l] * S);
-      boff[l] = tot; tot += align256(bbytes[l] * S);
-      fin = m0->features[l];
-    }
-    h_w.assign(tot, 0);
+    BlockLayout lay;
+    for (int l = 0; l < L; ++l) { woff[l] = lay.take(sh.wb[l] * S); boff[l] = lay.take(sh.bb[l] * S); }
+    h_w.assign(lay.off, 0);
     for (int s = 0; s < S; ++s)
       for (int l = 0; l < L; ++l) {
-        memcpy(h_w.data() + woff[l] + wbytes[l] * s, models[s].mlp_kernel[l], wbytes[l]);
-        memcpy(h_w.data() + boff[l] + bbytes[l] * s, models[s].mlp_bias[l], bbytes[l]);
+        memcpy(h_w.data() + woff[l] + sh.wb[l] * s, models[s].mlp_kernel[l], sh.wb[l]);
+        memcpy(h_w.data() + boff[l] + sh.bb[l] * s, models[s].mlp_bias[l], sh.bb[l]);
       }
-    d_wblk = static_cast<char*>(ws_get(c, WS_NS_MLP_W, tot));
+    d_wblk = static_cast<char*>(ws_get(c, WS_NS_MLP_W, lay.off));
     if (!d_wblk) return HBO_ERR_HIP;
-    HIPCHK(c, hipMemcpyAsync(d_wblk, h_w.data(), tot, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(d_wblk, h_w.data(), lay.off, hipMemcpyHostToDevice, st));
   }
   size_t act_pair = 0;   // bytes of one pair's activations, all layers
   if (mlp) for (int l = 0; l < L; ++l) act_pair += align256((size_t)std::max<int64_t>(max_n, 1) * m0->features[l] * es);
@@ -156,12 +143,9 @@ extern "C" int hbo_nll_samples(hbo_ctx* c, const hbo_model* models, int32_t S, h
     if (mlp) {
       HIPCHK(c, hipMemcpyAsync(d_mlpt, hm.data(), sizeof(MlpTaskDev) * P, hipMemcpyHostToDevice, st));
       ProfScope ps(c, "features", 1);
-      int fin = m0->input_dim;
-      for (int l = 0; l < L; ++l) {
-        launch_mlp_forward_batch(dtype, d_mlpt, P, max_n, l, d_wblk + woff[l] + wbytes[l] * s0, d_wblk + boff[l] + bbytes[l] * s0, fin,
-                                 m0->features[l], st, 1);
-        fin = m0->features[l];
-      }
+      for (int l = 0; l < L; ++l)
+        launch_mlp_forward_batch(dtype, d_mlpt, P, max_n, l, d_wblk + woff[l] + sh.wb[l] * s0, d_wblk + boff[l] + sh.bb[l] * s0, sh.fin[l],
+                                 sh.fout[l], st, 1);
     }
     if (fused) {
       ProfScope ps(c, "small_eval", 1);
@@ -177,9 +161,7 @@ extern "C" int hbo_nll_samples(hbo_ctx* c, const hbo_model* models, int32_t S, h
       { ProfScope ps(c, "gram", 1);
         GramArgs g = {}; g.kernel_id = m0->kernel_id; g.mfma_min_f = c->opt_gram_mfma; g.tasks = d_desc; g.fdim = fdim; g.symmetric = 1; g.padded = 1; g.model_stride = 1;
         launch_gram(dtype, g, d_mx, dim3(max_nblk, max_nblk, P), st); }
-      double bound_all = chol_diag_bound_of(&models[s0]);
-      for (int s = 1; s < sc; ++s) { const double b = chol_diag_bound_of(&models[s0 + s]); bound_all = (b > 0 && bound_all > 0) ? std::max(bound_all, b) : 0.0; }
-      CholBoundScope bound_scope(c, bound_all);
+      CholBoundScope bound_scope(c, chol_diag_bound_of(models + s0, sc));
       c->trtri_host_task = TaskDesc{};
       { ProfScope ps(c, "potrf", 1); run_potrf(c, dtype, d_desc, P, max_nblk, d_info); }
       { ProfScope ps(c, "nll_reduce", 1); launch_nll_reduce(dtype, d_desc, P, d_info, d_nll, st); }

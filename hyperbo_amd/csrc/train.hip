@@ -286,16 +286,15 @@ int train_check_regime(hbo_ctx* c, const std::string& fn, int dtype, int64_t max
   return HBO_OK;
 }
 
-// The head of both loops' upload: [leaves | goff | the starting model's arrays (model dtype)].  `take(bytes)` hands out offsets.
+// The head of both loops' upload: [leaves | goff | the starting model's arrays (model dtype)], the first parts of the block `lay` lays out
 struct TrainPack { size_t o_leaf, o_goff, o_ls, o_lin, o_ka, o_kb; int n_ls, fm; };
-template <class Take>
-TrainPack train_pack_layout(Take&& take, const hbo_model* m, int32_t P) {
+TrainPack train_pack_layout(BlockLayout& lay, const hbo_model* m, int32_t P) {
   TrainPack p;
   const size_t es = esize(m->dtype);
   p.n_ls = m->kernel_id == HBO_KERNEL_DOT ? 0 : m->n_lengthscale; p.fm = mean_feature_dim(m);
-  p.o_leaf = take(sizeof(hbo_train_leaf) * P); p.o_goff = take(sizeof(int) * P);
-  p.o_ls = take(es * std::max(p.n_ls, 1)); p.o_lin = take(es * std::max(p.fm, 1));
-  p.o_ka = take(es * m->input_dim); p.o_kb = take(es * m->input_dim);
+  p.o_leaf = lay.take(sizeof(hbo_train_leaf) * P); p.o_goff = lay.take(sizeof(int) * P);
+  p.o_ls = lay.take(es * std::max(p.n_ls, 1)); p.o_lin = lay.take(es * std::max(p.fm, 1));
+  p.o_ka = lay.take(es * m->input_dim); p.o_kb = lay.take(es * m->input_dim);
   return p;
 }
 void train_pack_fill(unsigned char* h, const TrainPack& p, const hbo_model* m, const hbo_train_leaf* leaves, const std::vector<int>& goff, int32_t P) {
@@ -319,7 +318,6 @@ void train_dev_set(TrainDev& t, hbo_ctx* c, const hbo_model* m, unsigned char* d
   for (int l = 0; l < HBO_MAX_MLP_LAYERS; ++l) { t.mlp_w[l] = c->d_mlp_w[l]; t.mlp_b[l] = c->d_mlp_b[l]; }
   t.md = c->d_model;
 }
-inline size_t train_align(size_t b) { return (b + 255) & ~(size_t)255; }
 
 int lbfgs_check_opts(hbo_ctx* c, const std::string& fn, const hbo_lbfgs_opts* o) {
   if (!o) return fail(c, HBO_ERR_ARG, fn + "opts is null");
@@ -433,17 +431,16 @@ extern "C" int hbo_train_adam(hbo_ctx* c, const hbo_model* m, hbo_dataset* ds, c
       gt.push_back(GatherTask{s->X, s->ysum, s->ydiv, t->X, t->ysum, t->ydiv, s->n, t->n, ioff[k], s->m, 1});
     }
   }
-  size_t off = 0;
-  auto take = [&](size_t b) { const size_t o = off; off += train_align(b); return o; };
-  const TrainPack pack = train_pack_layout(take, m, P);
-  const size_t o_b1 = take(sizeof(double) * steps), o_b2 = take(sizeof(double) * steps);
-  const size_t o_gt = take(sizeof(GatherTask) * std::max<size_t>(gt.size(), 1));
-  const size_t o_rows = take(sizeof(int32_t) * std::max<int64_t>(batch_counts ? nidx * steps : 0, 1));
-  const size_t o_x = take(sizeof(double) * P), o_m = take(sizeof(double) * P), o_v = take(sizeof(double) * P);
-  const size_t o_int = take(2 * sizeof(int)), o_loss = take(sizeof(double) * steps);
-  const size_t up_bytes = off;
-  const size_t o_trace = take(x_trace ? sizeof(double) * steps * (size_t)P : 0);
-  const size_t total = off;
+  BlockLayout blk;
+  const TrainPack pack = train_pack_layout(blk, m, P);
+  const size_t o_b1 = blk.take(sizeof(double) * steps), o_b2 = blk.take(sizeof(double) * steps);
+  const size_t o_gt = blk.take(sizeof(GatherTask) * std::max<size_t>(gt.size(), 1));
+  const size_t o_rows = blk.take(sizeof(int32_t) * std::max<int64_t>(batch_counts ? nidx * steps : 0, 1));
+  const size_t o_x = blk.take(sizeof(double) * P), o_m = blk.take(sizeof(double) * P), o_v = blk.take(sizeof(double) * P);
+  const size_t o_int = blk.take(2 * sizeof(int)), o_loss = blk.take(sizeof(double) * steps);
+  const size_t up_bytes = blk.off;
+  const size_t o_trace = blk.take(x_trace ? sizeof(double) * steps * (size_t)P : 0);
+  const size_t total = blk.off;
   std::vector<unsigned char> h(total, 0);
   auto cp = [&](size_t o, const void* src, size_t b) { if (b) memcpy(h.data() + o, src, b); };
   train_pack_fill(h.data(), pack, m, leaves, goff, P);
@@ -542,14 +539,13 @@ extern "C" int hbo_train_lbfgs(hbo_ctx* c, const hbo_model* m, hbo_dataset* ds, 
   if (!so.d_red || so.red_count != 2 + lay.total) return fail(c, HBO_ERR_HIP, fn + "no reduction buffer");
 
   // ---- one upload: [leaves | goff | initial arrays | state], then log and trace; the copy back takes [state .. trace]
-  size_t off = 0;
-  auto take = [&](size_t b) { const size_t o = off; off += train_align(b); return o; };
-  const TrainPack pack = train_pack_layout(take, m, P);
-  const size_t o_state = take(sizeof(double) * ns);
-  const size_t up_bytes = off;
-  const size_t o_log = take(sizeof(hbo_lbfgs_eval) * evals);
-  const size_t o_trace = take(x_trace ? sizeof(double) * evals * (size_t)P : 0);
-  const size_t total = off;
+  BlockLayout blk;
+  const TrainPack pack = train_pack_layout(blk, m, P);
+  const size_t o_state = blk.take(sizeof(double) * ns);
+  const size_t up_bytes = blk.off;
+  const size_t o_log = blk.take(sizeof(hbo_lbfgs_eval) * evals);
+  const size_t o_trace = blk.take(x_trace ? sizeof(double) * evals * (size_t)P : 0);
+  const size_t total = blk.off;
   std::vector<unsigned char> h(total, 0);
   train_pack_fill(h.data(), pack, m, leaves, goff, P);
   memcpy(h.data() + o_state, state, sizeof(double) * ns);

@@ -1,4 +1,4 @@
-"""CPU side of the shape tier of hbo_acq_grad (csrc/cache.hip: the per-cache gradient d acquisition / d x_query that bayesopt() hands to
+"""CPU side of the shape tier of hbo_acq_grad (csrc/acq_grad.hip: the per-cache gradient d acquisition / d x_query that bayesopt() hands to
 L-BFGS-B; csrc/post.hip: acq_grad_kernel, tri_matvec_kernel, tri_matmat_fwd_kernel / tri_matmat_trans_kernel; the MLP backward to the
 query; kumar_chain_dx_kernel).  Shared by tests/test_acq_grad_cases_host.py (this file judged on its own) and
 tests/test_gpu_acq_grad_shapes.py (the device against it):

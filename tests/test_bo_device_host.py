@@ -9,6 +9,7 @@ import pytest
 
 import bo_device_cases as cases
 import bo_loop_oracle as blo
+import family_check_cases as family
 import helpers
 from hyperbo_amd import _native as nat
 from hyperbo_amd.basics import definitions as defs
@@ -131,6 +132,18 @@ def test_argument_errors_come_before_any_device_call():
   err = lambda: (nat.lib().hbo_last_error(None) or b'').decode()
   check_refusals(None, err)
   assert bo_call(bo_args()) == nat.HBO_ERR_ARG and 'ctx is null' in err()
+
+
+@pytest.mark.parametrize('name', list(family.CASES))
+def test_mixed_batches_are_refused_in_the_shared_order(name):
+  """A pair of models the batched entry points' shared check refuses (family_check_cases.py), before the context is asked for."""
+  err = lambda: (nat.lib().hbo_last_error(None) or b'').decode()
+  a = bo_args(R=2)
+  a['models'], keep, code, word = family.pair(name)
+  assert bo_call(a) == code and word.format(fn='hbo_bo_simulated') in err(), (name, err())
+  sel, acq, status = a['_keep'][5:]
+  assert np.all(sel == 7) and np.all(acq == 7.0) and np.all(status == 7)   # no output was touched
+  del keep
 
 
 # ---- the Python layer ------------------------------------------------------------------------------------------------------

@@ -5,7 +5,7 @@ about a third of the cases, one standard deviation above it: acq_grad_cases.refe
 tests/acq_grad_cases.py and are judged on their own by tests/test_acq_grad_cases_host.py (conditions, mutants, the oracle against
 central differences); conditions 1 - 3 are asserted here again for every case.
 
-What the cases reach that nothing else in the suite does (csrc/post.hip, csrc/cache.hip: hbo_acq_grad):
+What the cases reach that nothing else in the suite does (csrc/post.hip, csrc/acq_grad.hip: hbo_acq_grad):
   A  acq_grad_kernel's thread layout FD = next_pow2(features), G = 256 / FD groups: FD 1 .. 256, G 256 .. 1, the `d += 256` fill of s_fq
   B  the MLP backward to the query: last layers up to 256, a hidden layer wider than both ends, four layers, the gmlp = d_t0 branch
   C  M = 1 (tri_matvec_kernel) against M >= 2 (tri_matmat_*_kernel, partial groups of 8), both sides of the 1024-query pass
