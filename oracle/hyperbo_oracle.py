@@ -693,12 +693,16 @@ def multivariate_normal_divergence(mean_func, cov_func, params, dataset, warp_fu
   return 0. if num == 0 else total / num
 
 
-def _divergence_sub_dataset_value_and_grad(kind, mean_func, cov_func, params, vx, vy, warp_func):
+def _divergence_sub_dataset_value_and_grad(kind, mean_func, cov_func, params, vx, vy, warp_func, return_terms=False, adjoint=None, mean_vx=None):
   """Value and d/d(raw params.model) of one aligned sub-dataset's partial KL ('ekl') or Euclidean ('euc')
   divergence.  Implemented by re-using the NLL machinery's chain rule with
      ekl:  f = tr(K1^-1 C0) + d^T K1^-1 d + logdet K1,   df/dK1 = K1^-1 - K1^-1 (C0 + d d^T) K1^-1,  df/dmu1 = 2 K1^-1 d
      euc:  f = |d| + |C0 - K1|_F,                          df/dK1 = (K1 - C0)/|C0-K1|_F,               df/dmu1 = d/|d|
-  (d = mu1 - mu0, K1 = K + noise I, no jitter: objectives.py:63-65)."""
+  (d = mu1 - mu0, K1 = K + noise I, no jitter: objectives.py:63-65).
+  return_terms: also the terms the value is the sum of -- ekl: 'tr', 'mahalanobis', 'logdet'; euc: 'dnorm', 'fnorm'.
+  adjoint: a callable (kind, k1, c0, d, kinv or None) -> (df/dK1, df/dmu1) in place of the two above: the tests chain WRONG
+  derivations through the same backward pass (tests/divergence_cases.py: MUTANTS).
+  mean_vx: the inputs of a 'linear' mean where they are not the kernel's (a kernel on warped inputs, tests/kumar_oracle.py)."""
   model = params.model
   vx = np.asarray(vx, dtype=np.float64); vy = np.asarray(vy, dtype=np.float64)
   n, m = vy.shape
@@ -722,13 +726,16 @@ def _divergence_sub_dataset_value_and_grad(kind, mean_func, cov_func, params, vx
   if use_mlp_k or mean_name == 'linear_mlp':
     acts = _mlp_forward_cache(model['mlp_params'], vx)
   feat = acts[-1] if use_mlp_k else vx
+  mvx = vx if mean_vx is None else np.asarray(mean_vx, dtype=np.float64)
+  if mean_vx is not None and acts is not None:
+    raise NotImplementedError('mean_vx with an MLP basis')
   if mean_name == 'zero':
     mu1 = np.zeros(n)
   elif mean_name == 'constant':
     mu1 = np.full(n, float(np.squeeze(warped('constant'))))
   else:
     lm = model['linear_mean']
-    inp = vx if mean_name == 'linear' else acts[-1]
+    inp = mvx if mean_name == 'linear' else acts[-1]
     mu1 = (inp @ np.asarray(lm['kernel'], dtype=np.float64) + np.asarray(lm['bias'], dtype=np.float64))[:, 0]
   noise = float(np.squeeze(warped('noise_variance')))
   if base == 'dot_product':
@@ -752,14 +759,19 @@ def _divergence_sub_dataset_value_and_grad(kind, mean_func, cov_func, params, vx
   if kind == 'ekl':
     chol = spla.cholesky(k1, lower=True)
     kinv = spla.cho_solve((chol, True), np.eye(n))
+    terms = {'tr': float(np.sum(kinv * c0)), 'mahalanobis': float(d @ kinv @ d), 'logdet': float(2 * np.sum(np.log(np.diag(chol))))}
     value = float(np.sum(kinv * c0) + d @ kinv @ d + 2 * np.sum(np.log(np.diag(chol))))
     gmat = kinv - kinv @ (c0 + np.outer(d, d)) @ kinv
     dmu = 2 * kinv @ d
   else:
+    kinv = None
     nd = np.sqrt(np.sum(d * d)); fn = np.sqrt(np.sum((c0 - k1)**2))
+    terms = {'dnorm': float(nd), 'fnorm': float(fn)}
     value = float(nd + fn)
     gmat = (k1 - c0) / fn if fn > 0 else np.zeros_like(k1)
     dmu = d / nd if nd > 0 else np.zeros_like(d)
+  if adjoint is not None:
+    gmat, dmu = adjoint(kind, k1, c0, d, kinv)
   dmu = dmu[:, None]
   grads = _tree_zeros_like(model)
   grads['noise_variance'] = chain('noise_variance', np.trace(gmat)).reshape(np.shape(model['noise_variance']))
@@ -780,7 +792,7 @@ def _divergence_sub_dataset_value_and_grad(kind, mean_func, cov_func, params, vx
   if mean_name == 'constant':
     grads['constant'] = chain('constant', np.sum(dmu)).reshape(np.shape(model['constant']))
   elif mean_name in ('linear', 'linear_mlp'):
-    inp = vx if mean_name == 'linear' else acts[-1]
+    inp = mvx if mean_name == 'linear' else acts[-1]
     lm = model['linear_mean']
     grads['linear_mean'] = {'kernel': (inp.T @ dmu).reshape(np.shape(lm['kernel'])),
                             'bias': np.sum(dmu, axis=0).reshape(np.shape(lm['bias']))}
@@ -788,6 +800,8 @@ def _divergence_sub_dataset_value_and_grad(kind, mean_func, cov_func, params, vx
       dfeat = dfeat + dmu @ np.asarray(lm['kernel'], dtype=np.float64).T
   if acts is not None and (use_mlp_k or mean_name == 'linear_mlp'):
     grads['mlp_params'] = _mlp_backward(model['mlp_params'], acts, dfeat)
+  if return_terms:
+    return value, grads, terms
   return value, grads
 
 

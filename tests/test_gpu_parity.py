@@ -1295,6 +1295,12 @@ def test_cached_cholesky_path_of_inverse_spdmatrix_vector_product(gpu_ctx, n, m)
 
 
 # ---- divergence objectives (objectives.py:29-106): EKL / Euclid on the device vs the oracle ------------------
+# These tests compare the MEAN over the tasks.  Per task, relative to each task's own terms, across the column edge m + 1 = 128 and
+# the row edge n = 128, every family on the nvec path, mixed batches, fp32 and the zero-norm guards: tests/test_gpu_divergence.py
+# (cases, reference, bounds and mutants: tests/divergence_cases.py, judged on the CPU by tests/test_divergence_cases_host.py).
+FP32_DIVERGENCE_TOL = 2e-4   # value (of max(|mean|, 1)) and per leaf; measured 1.3e-5 / 5.5e-6 at worst (profiles/divergence_errors.md); was 2e-3
+
+
 def _aligned_datasets(rng, d):
   dso = {'a': o.SubDataset(*helpers.synthetic_task(rng, 150, d, m=6), aligned=1),
          'b': o.SubDataset(*helpers.synthetic_task(rng, 20, d, m=10), aligned='x'),
@@ -1357,7 +1363,7 @@ def test_divergence_with_more_than_127_aligned_columns(gpu_ctx, kind, kname, mlp
   vo, go = o.divergence_value_and_grad(kind, getattr(o, mname), ko, po, dso, WFO)
   fn = objectives.ekl if kind == 'ekl' else objectives.euc
   vn, gn = fn.value_and_grad(getattr(mean, mname), kn, pn, dsn, utils.DEFAULT_WARP_FUNC)
-  vtol, gtol = (1e-10 * (50 if kind == 'ekl' else 1), FP64_GRAD_TOL) if dtype == np.float64 else (2e-3, 2e-3)
+  vtol, gtol = (1e-10 * (50 if kind == 'ekl' else 1), FP64_GRAD_TOL) if dtype == np.float64 else (FP32_DIVERGENCE_TOL, FP32_DIVERGENCE_TOL)
   assert abs(vn - vo) <= vtol * max(abs(vo), 1.0), (vn, vo)
   fo, fng = helpers.flatten(go), helpers.flatten(gn)
   helpers.assert_grad_close(gn, go, gtol, label=kind)
@@ -1499,9 +1505,9 @@ def test_divergence_fp32_and_no_aligned_data(gpu_ctx):
   for kind, fn in (('ekl', objectives.ekl), ('euc', objectives.euc)):
     vo, go = o.divergence_value_and_grad(kind, o.constant, o.matern52, po, dso, WFO)
     vn, gn = fn.value_and_grad(mean.constant, kernel.matern52, pn, dsn, utils.DEFAULT_WARP_FUNC)
-    assert abs(vn - vo) <= 2e-3 * max(abs(vo), 1.0)
+    assert abs(vn - vo) <= FP32_DIVERGENCE_TOL * max(abs(vo), 1.0)
     fo, fng = helpers.flatten(go), helpers.flatten(gn)
-    helpers.assert_grad_close(gn, go, 2e-3, label=kind)
+    helpers.assert_grad_close(gn, go, FP32_DIVERGENCE_TOL, label=kind)
   only_iid = {'iid': defs.SubDataset(*helpers.synthetic_task(rng, 10, d))}
   p64 = defs.GPParams(model=model, config={})
   assert objectives.ekl(mean.constant, kernel.matern52, p64, only_iid, utils.DEFAULT_WARP_FUNC) == 0.
