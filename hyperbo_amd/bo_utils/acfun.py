@@ -118,6 +118,33 @@ def _sample_models(model, samples, dtype):
   return cached[1], cached[2]
 
 
+def _sample_args(built, handles, noises, acfun_param):
+  """The per-sample ctypes arrays of the batched calls: (models, caches or None without handles, acquisition parameters, noises)."""
+  s = len(built)
+  structs = (nat.Model * s)(*[b.struct for b in built])
+  caches = None if handles is None else (nat.C.c_void_p * s)(*[h.handle for h in handles])
+  prm = (nat.C.c_double * s)(*([float(acfun_param)] * s))
+  nse = (nat.C.c_double * s)(*[float(v) for v in noises])
+  return structs, caches, prm, nse
+
+
+def _single_model(model, sub_dataset_key, x_queries=None):
+  """The set-up of the single-model calls: (factor handle or None without observations, x_queries in the model dtype, BuiltModel,
+  noise, scale); the last three are None for an empty set of queries.  Fused device path: posterior (gp.py:562-620 incl. +noise
+  and T/(T-1)) + acquisition epilogue."""
+  handle = None
+  if model.has_observations(sub_dataset_key):
+    model.setup_predictor(sub_dataset_key)
+    handle = model.params.cache[sub_dataset_key].handle
+  dtype = handle.dtype if handle is not None else _model.infer_dtype(x_queries)
+  xq = None if x_queries is None else np.ascontiguousarray(x_queries, dtype=dtype)
+  if xq is not None and xq.shape[0] == 0:
+    return handle, xq, None, None, None
+  add_noise, scale = model.predict_noise_and_scale(True, True)
+  bm = _model.BuiltModel(model.mean_func, model.cov_func, model.params, model.warp_func, dtype, model.input_dim)
+  return handle, xq, bm, add_noise, scale
+
+
 def _samples_per_call(n, dtype, n_samples):
   """How many samples hbo_acq_samples may factorise at once: every sample holds a complete cache (Gram -> L, L^-1 and the
   K^-1 scratch, 3 matrices of npad x ld) -- at most HALF of the device's memory, and the entry point's own limit of 4096."""
@@ -153,9 +180,7 @@ def hgp_sample_values(model, sub_dataset_key, x_queries, acq_id, acfun_param):
   s0 = 0
   while s0 < s_count:
     sc = min(chunk, s_count - s0)
-    structs = (nat.Model * sc)(*[b.struct for b in built[s0:s0 + sc]])
-    prm = (nat.C.c_double * sc)(*([float(acfun_param)] * sc))
-    nse = (nat.C.c_double * sc)(*noises[s0:s0 + sc])
+    structs, _, prm, nse = _sample_args(built[s0:s0 + sc], None, noises[s0:s0 + sc], acfun_param)
     part = out[s0:s0 + sc]
     rc = nat.lib().hbo_acq_samples(ctx.handle, structs, sc, nat.ptr(x), x.shape[0], nat.ptr(y), y.shape[1], nat.ptr(xq), xq.shape[0],
                                    int(acq_id), prm, nse, float(scale), part.ctypes.data_as(nat.C.c_void_p))
@@ -255,10 +280,7 @@ def _device_maximize(built, handles, noises, x0, lo, hi, acq_id, acfun_param, sc
   x0 [R, D] in the model dtype; lo / hi [D] float64 or None.  Returns (x [R, D], values [R], status [R], evaluations [R], log or None)."""
   s_count, (r_count, d) = len(built), x0.shape
   ctx = handles[0].ctx
-  structs = (nat.Model * s_count)(*[b.struct for b in built])
-  caches = (nat.C.c_void_p * s_count)(*[h.handle for h in handles])
-  prm = (nat.C.c_double * s_count)(*([float(acfun_param)] * s_count))
-  nse = (nat.C.c_double * s_count)(*[float(v) for v in noises])
+  structs, caches, prm, nse = _sample_args(built, handles, noises, acfun_param)
   o = nat.AcqOptOpts(*[opts[k] for k in ('memory', 'ls_steps', 'max_iters', 'c1', 'tau', 'pgtol', 'ftol')])
   ns = nat.lib().hbo_acq_opt_state_doubles(d, o.memory)
   state = np.zeros((r_count, max(ns, 1)), dtype=np.float64)
@@ -286,10 +308,7 @@ def _fused_value_and_grad(built, handles, noises, xq, acq_id, acfun_param, scale
   hbo_acq_grad_samples call -- one upload, one launch, one copy back."""
   s_count, (nq, d) = len(built), xq.shape
   ctx = handles[0].ctx
-  structs = (nat.Model * s_count)(*[b.struct for b in built])
-  caches = (nat.C.c_void_p * s_count)(*[h.handle for h in handles])
-  prm = (nat.C.c_double * s_count)(*([float(acfun_param)] * s_count))
-  nse = (nat.C.c_double * s_count)(*[float(v) for v in noises])
+  structs, caches, prm, nse = _sample_args(built, handles, noises, acfun_param)
   out = np.empty((s_count, nq, 1), dtype=xq.dtype)
   g = np.empty((s_count, nq, d), dtype=np.float64)
   ctx.check(nat.lib().hbo_acq_grad_samples(ctx.handle, structs, s_count, caches, nat.ptr(xq), nq, int(acq_id), prm, nse, float(scale),
@@ -365,19 +384,10 @@ def acfun_wrapper(acfun_sub, acfun_callback_default):
       ac_vals = [acfun_sub(mu, np.sqrt(var), acfun_param) for mu, var in predicts]
       return np.mean(ac_vals, axis=0)
     acfun_param = acfun_callback(model, sub_dataset_key)
-    # fused device path: posterior (gp.py:562-620 incl. +noise and T/(T-1)) + acquisition epilogue
-    handle = None
-    if model.has_observations(sub_dataset_key):
-      model.setup_predictor(sub_dataset_key)
-      handle = model.params.cache[sub_dataset_key].handle
-    dtype = handle.dtype if handle is not None else _model.infer_dtype(x_queries)
-    xq = np.ascontiguousarray(x_queries, dtype=dtype)
-    out = np.empty((xq.shape[0], 1), dtype=dtype)
-    if xq.shape[0] == 0:
+    handle, xq, bm, add_noise, scale = _single_model(model, sub_dataset_key, x_queries)
+    out = np.empty((xq.shape[0], 1), dtype=xq.dtype)
+    if bm is None:
       return out
-    add_noise, scale = model.predict_noise_and_scale(True, True)
-    bm = _model.BuiltModel(model.mean_func, model.cov_func, model.params, model.warp_func, dtype,
-                           model.input_dim)
     ctx = handle.ctx if handle is not None else nat.default_context()
     ctx.check(nat.lib().hbo_acq(ctx.handle, bm.ref(), handle.handle if handle is not None else None,
                                 nat.ptr(xq), xq.shape[0], _NATIVE_ID[acfun_sub], float(acfun_param),
@@ -391,19 +401,11 @@ def acfun_wrapper(acfun_sub, acfun_callback_default):
     acfun_param = acfun_callback(model, sub_dataset_key)
     if isinstance(model, gp.HGP):
       return _hgp_value_and_grad(model, sub_dataset_key, x_queries, _NATIVE_ID[acfun_sub], acfun_param)
-    handle = None
-    if model.has_observations(sub_dataset_key):
-      model.setup_predictor(sub_dataset_key)
-      handle = model.params.cache[sub_dataset_key].handle
-    dtype = handle.dtype if handle is not None else _model.infer_dtype(x_queries)
-    xq = np.ascontiguousarray(x_queries, dtype=dtype)
-    out = np.empty((xq.shape[0], 1), dtype=dtype)
+    handle, xq, bm, add_noise, scale = _single_model(model, sub_dataset_key, x_queries)
+    out = np.empty((xq.shape[0], 1), dtype=xq.dtype)
     grad = np.zeros((xq.shape[0], model.input_dim), dtype=np.float64)
-    if xq.shape[0] == 0:
+    if bm is None:
       return out, grad
-    add_noise, scale = model.predict_noise_and_scale(True, True)
-    bm = _model.BuiltModel(model.mean_func, model.cov_func, model.params, model.warp_func, dtype,
-                           model.input_dim)
     if _acq_fused_unmet(model, sub_dataset_key) is None:   # option 'acq_fused': the one-launch path with S = 1
       outs, gs = _fused_value_and_grad([bm], [handle], [add_noise], xq, _NATIVE_ID[acfun_sub], acfun_param, scale)
       return outs[0], gs[0]
@@ -442,12 +444,9 @@ def acfun_wrapper(acfun_sub, acfun_callback_default):
         raise nat.HboError(nat.HBO_ERR_UNSUPPORTED, 'ac_func.maximize: ' + unmet)
       _, scale = model.predict_noise_and_scale(True, True)
     else:
-      model.setup_predictor(sub_dataset_key)
-      handle = model.params.cache[sub_dataset_key].handle
+      handle, _, bm, add_noise, scale = _single_model(model, sub_dataset_key)   # (_acq_opt_unmet: it has observations)
       dtype = handle.dtype
-      add_noise, scale = model.predict_noise_and_scale(True, True)
-      built = [_model.BuiltModel(model.mean_func, model.cov_func, model.params, model.warp_func, dtype, model.input_dim)]
-      handles, noises = [handle], [add_noise]
+      built, handles, noises = [bm], [handle], [add_noise]
     lo = hi = None
     if bounds is not None:
       b = np.asarray(bounds, dtype=np.float64).reshape(model.input_dim, 2)

@@ -86,7 +86,7 @@ extern "C" int hbo_ctx_destroy(hbo_ctx* c) {
   delete c;
   return HBO_OK;
 }
-// The eight options of the boundary (include/hbo.h).
+// The options of the boundary (include/hbo.h): eight that can be set, four more that can only be read.
 extern "C" int hbo_set_option(hbo_ctx* c, const char* name, int64_t value) {
   if (!c || !name) return HBO_ERR_ARG;
   if (!strcmp(name, "potrf_group")) { if (value < 0 || value > 16) return fail(c, HBO_ERR_ARG, "potrf_group in 0..16 (0: auto)"); c->opt_group = (int)value; return HBO_OK; }

@@ -271,18 +271,64 @@ int train_check_leaves(hbo_ctx* c, const std::string& fn, const hbo_model* m, co
   }
   return HBO_OK;
 }
-// the dataset against the model (after the caller has found it non-null)
-int train_check_dataset(hbo_ctx* c, const std::string& fn, const hbo_model* m, const hbo_dataset* ds) {
+// The argument checks of both training entry points, in the order both report them: model and P; own(), the caller's other arguments
+// that need neither the dataset nor the context; the leaf map; the dataset against the model; sizes(), which may lower the task sizes
+// s.nd to those of the caller's batch; then the context and the fused regime: every task of the batch in one 128-block, small_fused
+// on, enough LDS.
+struct TrainSetup { hbo_grad_layout lay; std::vector<int> goff; std::vector<int64_t> nd; int T = 0; int64_t max_n = 0; };
+template <class Own, class Sizes>
+int train_prologue(hbo_ctx* c, const std::string& fn, const hbo_model* m, int32_t P, const hbo_train_leaf* leaves, const hbo_dataset* ds,
+                   Own own, Sizes sizes, TrainSetup& s) {
+  if (!m) return fail(c, HBO_ERR_ARG, fn + "model is null");
+  if (P <= 0) return fail(c, HBO_ERR_ARG, fn + "P must be positive");
+  if (int rc = own()) return rc;
+  if (int rc = train_check_leaves(c, fn, m, leaves, P, s.lay, s.goff)) return rc;
+  if (!ds) return fail(c, HBO_ERR_ARG, fn + "dataset is null");
   if (ds->ntasks <= 0) return fail(c, HBO_ERR_ARG, fn + "the dataset has no tasks");
   if (m->dtype != ds->dtype || m->input_dim != ds->D) return fail(c, HBO_ERR_ARG, fn + "model/dataset dtype or input_dim mismatch");
+  s.T = ds->ntasks;
+  s.nd.resize(s.T);
+  for (int k = 0; k < s.T; ++k) s.nd[k] = ds->tasks[k]->n;
+  if (int rc = sizes()) return rc;
+  for (int k = 0; k < s.T; ++k) s.max_n = std::max(s.max_n, s.nd[k]);
+  if (!c) return fail(c, HBO_ERR_ARG, fn + "context is null");
+  if (s.max_n > HBO_TILE) return fail(c, HBO_ERR_UNSUPPORTED, fn + "a task of the batch has more than 128 points (only the fused regime runs on the device)");
+  if (!c->opt_small_fused) return fail(c, HBO_ERR_UNSUPPORTED, fn + "small_fused is off (only the fused regime runs on the device)");
+  if (small_eval_lds(ds->dtype) > c->lds_per_block) return fail(c, HBO_ERR_UNSUPPORTED, fn + "the device cannot give the single-workgroup evaluation its LDS");
   return HBO_OK;
 }
-// the context, then the fused regime: every task of the batch in one 128-block, small_fused on, enough LDS
-int train_check_regime(hbo_ctx* c, const std::string& fn, int dtype, int64_t max_n) {
-  if (!c) return fail(c, HBO_ERR_ARG, fn + "context is null");
-  if (max_n > HBO_TILE) return fail(c, HBO_ERR_UNSUPPORTED, fn + "a task of the batch has more than 128 points (only the fused regime runs on the device)");
-  if (!c->opt_small_fused) return fail(c, HBO_ERR_UNSUPPORTED, fn + "small_fused is off (only the fused regime runs on the device)");
-  if (small_eval_lds(dtype) > c->lds_per_block) return fail(c, HBO_ERR_UNSUPPORTED, fn + "the device cannot give the single-workgroup evaluation its LDS");
+
+// The evaluations of one resident batch, queued on the context's stream.  first() is everything hbo_objective does, up to the
+// device-side reduction: objective_local reduces [nll_sum, T, grad] on the device, without waiting, only for a caller that hands it a
+// ShardReq (the sharded objective's door), so it gets one whose count nobody reads, and host results that stay zero.  What it leaves in
+// ShardOut -- the reduction buffer the step kernels read, the scatter map, the stride -- serves every later evaluation: again() is the
+// three launches alone, no host-side set-up.
+struct TrainEval {
+  hbo_ctx* c; const hbo_model* m; int T; int64_t max_n; int grad_total;
+  ShardOut so;
+  int first(const std::string& fn, hbo_dataset* batch) {
+    std::vector<double> grad0(std::max(grad_total, 1));
+    double nll0 = 0, count0 = 0;
+    const ShardReq sh{&count0, nullptr};
+    if (int rc = objective_local(c, m, batch, HBO_OBJ_NLL, &nll0, nullptr, grad0.data(), &sh, &so)) return rc;
+    if (!so.d_red || so.red_count != 2 + grad_total) return fail(c, HBO_ERR_HIP, fn + "no reduction buffer");
+    return HBO_OK;
+  }
+  int again(hbo_dataset* batch) {
+    enqueue_fused_forward(c, m, batch, max_n, so.out_stride, true);
+    if (int rc = enqueue_backward(c, m, batch, max_n, OBJ_NLL, true)) return rc;
+    launch_shard_reduce(batch->d_nll, batch->d_gradout, batch->d_info, T, so.out_stride, so.d_map, batch->d_mlpgrad,
+                        so.d_map + so.out_stride, so.nseg, so.d_red, so.red_count, c->stream);
+    return HBO_OK;
+  }
+};
+// The end of both calls: the launches' error, ONE copy back of the block's bytes [first, total) to the same offsets of its host copy, one wait
+int train_finish(hbo_ctx* c, unsigned char* host, const unsigned char* dev, size_t first, size_t total) {
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipMemcpyAsync(host + first, dev + first, total - first, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipGetLastError());
+  prof_collect(c);
   return HBO_OK;
 }
 
@@ -354,34 +400,27 @@ extern "C" int hbo_train_adam(hbo_ctx* c, const hbo_model* m, hbo_dataset* ds, c
                               int32_t steps, double lr, double b1, double b2, double adam_eps,
                               const int64_t* batch_counts, const int32_t* batch_rows,
                               double* losses, double* x_trace, int32_t* steps_done) {
-  // ---- arguments: everything that does not need the context or the dataset first, then the dataset, then the context
   const std::string fn = "hbo_train_adam: ";
-  if (!m) return fail(c, HBO_ERR_ARG, fn + "model is null");
-  if (P <= 0) return fail(c, HBO_ERR_ARG, fn + "P must be positive");
-  if (steps <= 0) return fail(c, HBO_ERR_ARG, fn + "steps must be positive");
-  if (!leaves || !x || !adam_m || !adam_v || !bias1 || !bias2 || !losses || !steps_done)
-    return fail(c, HBO_ERR_ARG, fn + "null array argument (leaves, x, adam_m, adam_v, bias1, bias2, losses, steps_done)");
-  if (!batch_counts != !batch_rows) return fail(c, HBO_ERR_ARG, fn + "batch_counts and batch_rows are both given or both null");
-  if (!(lr == lr) || !(b1 == b1) || !(b2 == b2) || !(adam_eps == adam_eps))
-    return fail(c, HBO_ERR_ARG, fn + "lr, b1, b2 and adam_eps must be numbers");
-  hbo_grad_layout lay;
-  std::vector<int> goff;
-  if (int rc = train_check_leaves(c, fn, m, leaves, P, lay, goff)) return rc;
-  if (!ds) return fail(c, HBO_ERR_ARG, fn + "dataset is null");
-  if (int rc = train_check_dataset(c, fn, m, ds)) return rc;
-  const int T = ds->ntasks, D = ds->D, dtype = ds->dtype;
-  // the batch: its task sizes (the same every step), the rows a step consumes, and the order hbo_dataset_subsample keeps its tasks in
-  std::vector<int64_t> nd(T);
+  TrainSetup ts;
   int64_t nidx = 0;
-  for (int k = 0; k < T; ++k) {
-    const int64_t n = ds->tasks[k]->n;
-    nd[k] = n;
-    if (!batch_counts) continue;
-    const int64_t ck = batch_counts[k];
-    if (ck == 0 || ck > n) return fail(c, HBO_ERR_ARG, fn + "batch_counts[k] must be in 1..n_k (or negative: the whole task)");
-    if (ck > 0) { nd[k] = ck; nidx += ck; }
-  }
-  if (batch_counts) {
+  auto own = [&]() -> int {
+    if (steps <= 0) return fail(c, HBO_ERR_ARG, fn + "steps must be positive");
+    if (!leaves || !x || !adam_m || !adam_v || !bias1 || !bias2 || !losses || !steps_done)
+      return fail(c, HBO_ERR_ARG, fn + "null array argument (leaves, x, adam_m, adam_v, bias1, bias2, losses, steps_done)");
+    if (!batch_counts != !batch_rows) return fail(c, HBO_ERR_ARG, fn + "batch_counts and batch_rows are both given or both null");
+    if (!(lr == lr) || !(b1 == b1) || !(b2 == b2) || !(adam_eps == adam_eps))
+      return fail(c, HBO_ERR_ARG, fn + "lr, b1, b2 and adam_eps must be numbers");
+    return HBO_OK;
+  };
+  // the batch: its task sizes (the same every step) and the rows a step consumes
+  auto sizes = [&]() -> int {
+    if (!batch_counts) return HBO_OK;
+    const int T = ts.T;
+    for (int k = 0; k < T; ++k) {
+      const int64_t ck = batch_counts[k];
+      if (ck == 0 || ck > ts.nd[k]) return fail(c, HBO_ERR_ARG, fn + "batch_counts[k] must be in 1..n_k (or negative: the whole task)");
+      if (ck > 0) { ts.nd[k] = ck; nidx += ck; }
+    }
     for (int s = 1; s < steps; ++s)
       for (int k = 0; k < T; ++k)
         if ((batch_counts[(size_t)s * T + k] < 0) != (batch_counts[k] < 0) || (batch_counts[k] >= 0 && batch_counts[(size_t)s * T + k] != batch_counts[k]))
@@ -394,10 +433,11 @@ extern "C" int hbo_train_adam(hbo_ctx* c, const hbo_model* m, hbo_dataset* ds, c
           if (batch_rows[off] < 0 || batch_rows[off] >= ds->tasks[k]->n) return fail(c, HBO_ERR_ARG, fn + "batch_rows: index out of range");
       }
     }
-  }
-  int64_t max_n = 0;
-  for (int k = 0; k < T; ++k) max_n = std::max(max_n, nd[k]);
-  if (int rc = train_check_regime(c, fn, dtype, max_n)) return rc;
+    return HBO_OK;
+  };
+  if (int rc = train_prologue(c, fn, m, P, leaves, ds, own, sizes, ts)) return rc;
+  const int T = ts.T, D = ds->D, dtype = ds->dtype;
+  const int64_t max_n = ts.max_n;
 
   // ---- step 0: the batch, then everything hbo_objective does, up to the device-side reduction
   HIPCHK(c, hipSetDevice(c->device));
@@ -408,18 +448,14 @@ extern "C" int hbo_train_adam(hbo_ctx* c, const hbo_model* m, hbo_dataset* ds, c
     hbo_ctx* c; hbo_dataset* b;
     ~BatchGuard() { if (b) { (void)hipStreamSynchronize(c->stream); hbo_dataset_free(c, b); } }
   } guard{c, batch_counts ? batch : nullptr};
-  std::vector<double> grad0(std::max(lay.total, 1));
-  double nll0 = 0, count0 = 0;
-  ShardReq sh{&count0, nullptr};
-  ShardOut so;
-  if (int rc = objective_local(c, m, batch, HBO_OBJ_NLL, &nll0, nullptr, grad0.data(), &sh, &so)) return rc;
-  if (!so.d_red || so.red_count != 2 + lay.total) return fail(c, HBO_ERR_HIP, fn + "no reduction buffer");
+  TrainEval ev{c, m, T, max_n, ts.lay.total};
+  if (int rc = ev.first(fn, batch)) return rc;
 
   // ---- one upload: [leaves | goff | initial arrays | bias1 | bias2 | gather table | rows | x | m | v | halt, steps_done | losses],
   //      then the trace; the copy back takes [x .. trace]
   std::vector<int> perm(T);
   std::iota(perm.begin(), perm.end(), 0);
-  std::stable_sort(perm.begin(), perm.end(), [&](int a, int b) { return nd[a] > nd[b]; });   // hbo_dataset_subsample's task order
+  std::stable_sort(perm.begin(), perm.end(), [&](int a, int b) { return ts.nd[a] > ts.nd[b]; });   // hbo_dataset_subsample's task order
   std::vector<GatherTask> gt;
   if (batch_counts) {
     std::vector<int64_t> ioff(T, 0);
@@ -443,7 +479,7 @@ extern "C" int hbo_train_adam(hbo_ctx* c, const hbo_model* m, hbo_dataset* ds, c
   const size_t total = blk.off;
   std::vector<unsigned char> h(total, 0);
   auto cp = [&](size_t o, const void* src, size_t b) { if (b) memcpy(h.data() + o, src, b); };
-  train_pack_fill(h.data(), pack, m, leaves, goff, P);
+  train_pack_fill(h.data(), pack, m, leaves, ts.goff, P);
   cp(o_b1, bias1, sizeof(double) * steps); cp(o_b2, bias2, sizeof(double) * steps);
   cp(o_gt, gt.data(), sizeof(GatherTask) * gt.size());
   if (batch_counts) cp(o_rows, batch_rows, sizeof(int32_t) * nidx * steps);
@@ -457,7 +493,7 @@ extern "C" int hbo_train_adam(hbo_ctx* c, const hbo_model* m, hbo_dataset* ds, c
 
   AdamStepArgs a;
   memset(&a, 0, sizeof a);
-  train_dev_set(a.t, c, m, d, pack, P, so.d_red);
+  train_dev_set(a.t, c, m, d, pack, P, ev.so.d_red);
   a.x = reinterpret_cast<double*>(d + o_x); a.am = reinterpret_cast<double*>(d + o_m); a.av = reinterpret_cast<double*>(d + o_v);
   a.bias1 = reinterpret_cast<const double*>(d + o_b1); a.bias2 = reinterpret_cast<const double*>(d + o_b2);
   a.lr = lr; a.b1 = b1; a.b2 = b2; a.eps = adam_eps;
@@ -469,19 +505,12 @@ extern "C" int hbo_train_adam(hbo_ctx* c, const hbo_model* m, hbo_dataset* ds, c
   for (int s = 0; s < steps; ++s) {
     if (s > 0) {
       if (!gt.empty()) launch_gather_rows(dtype, d_gt, d_rows + (size_t)s * nidx, (int)gt.size(), max_n, D, st);
-      enqueue_fused_forward(c, m, batch, max_n, so.out_stride, true);
-      if (int rc = enqueue_backward(c, m, batch, max_n, OBJ_NLL, true)) return rc;
-      launch_shard_reduce(batch->d_nll, batch->d_gradout, batch->d_info, T, so.out_stride, so.d_map, batch->d_mlpgrad, so.d_map + so.out_stride,
-                          so.nseg, so.d_red, so.red_count, st);
+      if (int rc = ev.again(batch)) return rc;
     }
     { ProfScope ps(c, "adam_step", 1);
       hipLaunchKernelGGL(adam_step_kernel, dim3(1), dim3(ADAM_THREADS), 0, st, a, s); }
   }
-  HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipMemcpyAsync(h.data() + o_x, d + o_x, total - o_x, hipMemcpyDeviceToHost, st));
-  HIPCHK(c, hipStreamSynchronize(st));
-  HIPCHK(c, hipGetLastError());
-  prof_collect(c);
+  if (int rc = train_finish(c, h.data(), d, o_x, total)) return rc;
   memcpy(x, h.data() + o_x, sizeof(double) * P); memcpy(adam_m, h.data() + o_m, sizeof(double) * P); memcpy(adam_v, h.data() + o_v, sizeof(double) * P);
   memcpy(losses, h.data() + o_loss, sizeof(double) * steps);
   if (x_trace) memcpy(x_trace, h.data() + o_trace, sizeof(double) * steps * (size_t)P);
@@ -497,25 +526,17 @@ extern "C" int64_t hbo_lbfgs_state_doubles(int32_t P, int32_t memory) {
 extern "C" int hbo_train_lbfgs(hbo_ctx* c, const hbo_model* m, hbo_dataset* ds, const hbo_train_leaf* leaves, int32_t P,
                                const hbo_lbfgs_opts* opts, double* x, double* state, int32_t evals, hbo_lbfgs_eval* log,
                                double* x_trace, double* x_next, int32_t* evals_done, int32_t* status) {
-  // ---- arguments, in hbo_train_adam's order: what needs neither the dataset nor the context, the dataset, the context
   const std::string fn = "hbo_train_lbfgs: ";
-  if (!m) return fail(c, HBO_ERR_ARG, fn + "model is null");
-  if (P <= 0) return fail(c, HBO_ERR_ARG, fn + "P must be positive");
-  if (evals <= 0) return fail(c, HBO_ERR_ARG, fn + "evals must be positive");
-  if (!leaves || !x || !state || !log || !evals_done || !status)
-    return fail(c, HBO_ERR_ARG, fn + "null array argument (leaves, x, state, log, evals_done, status)");
-  if (int rc = lbfgs_check_opts(c, fn, opts)) return rc;
+  TrainSetup ts;
   bool fresh = false;
-  if (int rc = lbfgs_check_state(c, fn, state, opts, &fresh)) return rc;
-  hbo_grad_layout lay;
-  std::vector<int> goff;
-  if (int rc = train_check_leaves(c, fn, m, leaves, P, lay, goff)) return rc;
-  if (!ds) return fail(c, HBO_ERR_ARG, fn + "dataset is null");
-  if (int rc = train_check_dataset(c, fn, m, ds)) return rc;
-  const int T = ds->ntasks, dtype = ds->dtype;
-  int64_t max_n = 0;
-  for (int k = 0; k < T; ++k) max_n = std::max<int64_t>(max_n, ds->tasks[k]->n);
-  if (int rc = train_check_regime(c, fn, dtype, max_n)) return rc;
+  auto own = [&]() -> int {
+    if (evals <= 0) return fail(c, HBO_ERR_ARG, fn + "evals must be positive");
+    if (!leaves || !x || !state || !log || !evals_done || !status)
+      return fail(c, HBO_ERR_ARG, fn + "null array argument (leaves, x, state, log, evals_done, status)");
+    if (int rc = lbfgs_check_opts(c, fn, opts)) return rc;
+    return lbfgs_check_state(c, fn, state, opts, &fresh);
+  };
+  if (int rc = train_prologue(c, fn, m, P, leaves, ds, own, [] { return (int)HBO_OK; }, ts)) return rc;
 
   const int64_t ns = hbo_lbfgs_state_size(P, opts->memory);
   hbo_lbfgs_view hv = hbo_lbfgs_view_of(state, P, opts->memory);
@@ -531,12 +552,8 @@ extern "C" int hbo_train_lbfgs(hbo_ctx* c, const hbo_model* m, hbo_dataset* ds, 
   // ---- the first evaluation: everything hbo_objective does, up to the device-side reduction
   HIPCHK(c, hipSetDevice(c->device));
   hipStream_t st = c->stream;
-  std::vector<double> grad0(std::max(lay.total, 1));
-  double nll0 = 0, count0 = 0;
-  ShardReq sh{&count0, nullptr};
-  ShardOut so;
-  if (int rc = objective_local(c, m, ds, HBO_OBJ_NLL, &nll0, nullptr, grad0.data(), &sh, &so)) return rc;
-  if (!so.d_red || so.red_count != 2 + lay.total) return fail(c, HBO_ERR_HIP, fn + "no reduction buffer");
+  TrainEval ev{c, m, ts.T, ts.max_n, ts.lay.total};
+  if (int rc = ev.first(fn, ds)) return rc;
 
   // ---- one upload: [leaves | goff | initial arrays | state], then log and trace; the copy back takes [state .. trace]
   BlockLayout blk;
@@ -547,7 +564,7 @@ extern "C" int hbo_train_lbfgs(hbo_ctx* c, const hbo_model* m, hbo_dataset* ds, 
   const size_t o_trace = blk.take(x_trace ? sizeof(double) * evals * (size_t)P : 0);
   const size_t total = blk.off;
   std::vector<unsigned char> h(total, 0);
-  train_pack_fill(h.data(), pack, m, leaves, goff, P);
+  train_pack_fill(h.data(), pack, m, leaves, ts.goff, P);
   memcpy(h.data() + o_state, state, sizeof(double) * ns);
   unsigned char* d = static_cast<unsigned char*>(ws_get(c, WS_TRAIN, total));
   if (!d) return HBO_ERR_HIP;
@@ -555,36 +572,25 @@ extern "C" int hbo_train_lbfgs(hbo_ctx* c, const hbo_model* m, hbo_dataset* ds, 
 
   LbfgsArgs a;
   memset(&a, 0, sizeof a);
-  train_dev_set(a.t, c, m, d, pack, P, so.d_red);
+  train_dev_set(a.t, c, m, d, pack, P, ev.so.d_red);
   a.o = lbfgs_ctl_opts(opts);
   a.state = reinterpret_cast<double*>(d + o_state);
   a.log = reinterpret_cast<hbo_lbfgs_eval_ctl*>(d + o_log);
   a.trace = x_trace ? reinterpret_cast<double*>(d + o_trace) : nullptr;
 
-  auto enqueue_eval = [&]() -> int {
-    enqueue_fused_forward(c, m, ds, max_n, so.out_stride, true);
-    if (int rc = enqueue_backward(c, m, ds, max_n, OBJ_NLL, true)) return rc;
-    launch_shard_reduce(ds->d_nll, ds->d_gradout, ds->d_info, T, so.out_stride, so.d_map, ds->d_mlpgrad, so.d_map + so.out_stride,
-                        so.nseg, so.d_red, so.red_count, st);
-    return HBO_OK;
-  };
   if (!fresh) {
     // A continued run: the pending point's model again with the device's warps (objective_local evaluated the caller's, whose host
     // warps may differ in the last bit), so that a run gives the same bits however it is cut into calls.
     { ProfScope ps(c, "lbfgs_ctl", 1);
       hipLaunchKernelGGL(lbfgs_model_kernel, dim3(1), dim3(ADAM_THREADS), 0, st, a); }
-    if (int rc = enqueue_eval()) return rc;
+    if (int rc = ev.again(ds)) return rc;
   }
   for (int s = 0; s < evals; ++s) {
-    if (s > 0) { if (int rc = enqueue_eval()) return rc; }
+    if (s > 0) { if (int rc = ev.again(ds)) return rc; }
     { ProfScope ps(c, "lbfgs_ctl", 1);
       hipLaunchKernelGGL(lbfgs_ctl_kernel, dim3(1), dim3(ADAM_THREADS), 0, st, a, s); }
   }
-  HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipMemcpyAsync(h.data() + o_state, d + o_state, total - o_state, hipMemcpyDeviceToHost, st));
-  HIPCHK(c, hipStreamSynchronize(st));
-  HIPCHK(c, hipGetLastError());
-  prof_collect(c);
+  if (int rc = train_finish(c, h.data(), d, o_state, total)) return rc;
   memcpy(state, h.data() + o_state, sizeof(double) * ns);
   memcpy(log, h.data() + o_log, sizeof(hbo_lbfgs_eval) * evals);
   if (x_trace) memcpy(x_trace, h.data() + o_trace, sizeof(double) * evals * (size_t)P);

@@ -8,6 +8,7 @@ import ctypes as C
 from typing import Any, Callable, Dict, List, Tuple, Union
 
 import concurrent.futures
+import contextlib
 
 import numpy as np
 
@@ -215,6 +216,37 @@ def _adam_on_device_unmet(mean_func, cov_func, params, dataset, warp_func, objec
   return None
 
 
+@contextlib.contextmanager
+def _device_loop(name, mean_func, cov_func, params, dataset, warp_func, objective):
+  """The frame of _infer_adam_on_device and _infer_lbfgs_on_device (name: the config key).  Refuses what _adam_on_device_unmet names
+  with ValueError('<name>: ...'), opens the DeviceDataset, closes it on the way out and clears params.cache once the body has run.
+  The body gets (full, built, check): built(model_tree, template, n) -> (BuiltModel, leaf map, P) of one segment, P checked against
+  the n parameters; check(rc): HBO_ERR_UNSUPPORTED -> ValueError with the library's message, any other error as ctx.check raises it."""
+  why = _adam_on_device_unmet(mean_func, cov_func, params, dataset, warp_func, objective)
+  if why is not None:
+    raise ValueError(f'{name}: {why}.')
+  full = obj.DeviceDataset(dataset)
+
+  def built(model_tree, template, n):
+    bm = _model.BuiltModel(mean_func, cov_func, GPParams(model=model_tree, config=params.config), warp_func, full.dtype, full.input_dim)
+    leaves, P = _model.train_leaf_map(bm, template)
+    if P != n:
+      raise ValueError(f'{name}: the leaf map has {P} entries for {n} parameters')
+    return bm, leaves, P
+
+  def check(rc):
+    if rc == nat.HBO_ERR_UNSUPPORTED:
+      raise ValueError(f'{name}: ' + (nat.lib().hbo_last_error(full.ctx.handle) or b'').decode())
+    full.ctx.check(rc, allow_not_pd=False)
+  try:
+    if full.num_tasks == 0:
+      raise ValueError(f'{name}: the dataset has no task the NLL includes.')
+    yield full, built, check
+  finally:
+    full.close()
+  params.cache = {}
+
+
 def _infer_adam_on_device(mean_func, cov_func, params, dataset, warp_func, objective, rng, callback):
   """infer_parameters(method='adam') with config['adam_on_device'] = True: the steps run in segments of up to ADAM_SEGMENT on the
   device (hbo_train_adam: evaluation, reduction and Adam update queued back to back, one synchronisation per segment).  Same batches
@@ -222,31 +254,21 @@ def _infer_adam_on_device(mean_func, cov_func, params, dataset, warp_func, objec
   above; the callbacks of a segment are replayed after it.  Only the fused regime (every batch task n <= 128, NLL, no priors, warps of
   the closed set): anything else raises ValueError naming the first unmet condition."""
   from hyperbo_amd.basics import data_utils, lbfgs as lbfgs_lib
-  why = _adam_on_device_unmet(mean_func, cov_func, params, dataset, warp_func, objective)
-  if why is not None:
-    raise ValueError(f'adam_on_device: {why}.')
-  config = params.config
-  batch_size, max_steps = config['batch_size'], config['max_training_step']
-  opt = _Adam(config['learning_rate'])
-  x, unflatten = lbfgs_lib.tree_flatten(params.model)
-  vg = _value_and_grad_of(objective)
-  full = obj.DeviceDataset(dataset)
-  ctx = full.ctx
-  needs_resample = any(s.x.shape[0] >= batch_size for s in dataset.values())
-  index_iter = data_utils.sub_sample_index_iterator(rng, dataset, batch_size) if needs_resample else None
-  order = full.device_order_keys
-  am, av = np.zeros_like(x), np.zeros_like(x)
-  last_ix = None
-  step = 0
-  try:
-    if full.num_tasks == 0:
-      raise ValueError('adam_on_device: the dataset has no task the NLL includes.')
+  with _device_loop('adam_on_device', mean_func, cov_func, params, dataset, warp_func, objective) as (full, built, check):
+    config = params.config
+    batch_size, max_steps = config['batch_size'], config['max_training_step']
+    opt = _Adam(config['learning_rate'])
+    x, unflatten = lbfgs_lib.tree_flatten(params.model)
+    vg = _value_and_grad_of(objective)
+    needs_resample = any(s.x.shape[0] >= batch_size for s in dataset.values())
+    index_iter = data_utils.sub_sample_index_iterator(rng, dataset, batch_size) if needs_resample else None
+    order = full.device_order_keys
+    am, av = np.zeros_like(x), np.zeros_like(x)
+    last_ix = None
+    step = 0
     while step < max_steps:
       k = min(ADAM_SEGMENT, max_steps - step)
-      bm = _model.BuiltModel(mean_func, cov_func, GPParams(model=unflatten(x), config=config), warp_func, full.dtype, full.input_dim)
-      leaves, P = _model.train_leaf_map(bm, params.model)
-      if P != x.size:
-        raise ValueError(f'adam_on_device: the leaf map has {P} entries for {x.size} parameters')
+      bm, leaves, P = built(unflatten(x), params.model, x.size)
       counts = rows = None
       ixs = None
       if needs_resample:
@@ -260,12 +282,9 @@ def _infer_adam_on_device(mean_func, cov_func, params, dataset, warp_func, objec
       losses = np.empty(k, dtype=np.float64)
       trace = np.empty((k, x.size), dtype=np.float64)
       done = C.c_int32(0)
-      rc = nat.lib().hbo_train_adam(ctx.handle, bm.ref(), full._h, leaves, P, nat.ptr(x), nat.ptr(am), nat.ptr(av), nat.ptr(bias1),
-                                    nat.ptr(bias2), k, float(opt.lr), float(opt.b1), float(opt.b2), float(opt.eps),
-                                    nat.ptr(counts), nat.ptr(rows), nat.ptr(losses), nat.ptr(trace), C.byref(done))
-      if rc == nat.HBO_ERR_UNSUPPORTED:
-        raise ValueError('adam_on_device: ' + (nat.lib().hbo_last_error(ctx.handle) or b'').decode())
-      ctx.check(rc, allow_not_pd=False)
+      check(nat.lib().hbo_train_adam(full.ctx.handle, bm.ref(), full._h, leaves, P, nat.ptr(x), nat.ptr(am), nat.ptr(av), nat.ptr(bias1),
+                                     nat.ptr(bias2), k, float(opt.lr), float(opt.b1), float(opt.b2), float(opt.eps),
+                                     nat.ptr(counts), nat.ptr(rows), nat.ptr(losses), nat.ptr(trace), C.byref(done)))
       done = done.value
       for j in range(done):
         params.model = unflatten(trace[j])
@@ -289,9 +308,6 @@ def _infer_adam_on_device(mean_func, cov_func, params, dataset, warp_func, objec
         dev.close()
     if np.isfinite(final_loss):
       params.model = unflatten(x)
-  finally:
-    full.close()
-  params.cache = {}
   return params
 
 
@@ -307,55 +323,39 @@ def _infer_lbfgs_on_device(mean_func, cov_func, params, dataset, warp_func, obje
   'status' (hbo_lbfgs_status).
   The rules of adam_on_device apply: anything else raises ValueError naming the first unmet condition."""
   from hyperbo_amd.basics import data_utils, lbfgs as lbfgs_lib
-  why = _adam_on_device_unmet(mean_func, cov_func, params, dataset, warp_func, objective)
-  if why is not None:
-    raise ValueError(f'lbfgs_on_device: {why}.')
-  config = params.config
-  x, unflatten = lbfgs_lib.tree_flatten(params.model)
-  template = params.model
-  opts = nat.LbfgsOpts(memory=10, ls_steps=50, max_iters=int(config['max_training_step']), alpha=float(config.get('alpha', 1.0)),
-                       tol=1e-6, c1=1e-4, c2=0.9, grow=2.1, tau=0.5)   # lbfgs.lbfgs / backtracking_linesearch defaults
-  full = obj.DeviceDataset(dataset)
-  ctx = full.ctx
-  batch = None
-  try:
-    if full.num_tasks == 0:
-      raise ValueError('lbfgs_on_device: the dataset has no task the NLL includes.')
+  with _device_loop('lbfgs_on_device', mean_func, cov_func, params, dataset, warp_func, objective) as (full, built, check):
+    config = params.config
+    x, unflatten = lbfgs_lib.tree_flatten(params.model)
+    template = params.model
+    opts = nat.LbfgsOpts(memory=10, ls_steps=50, max_iters=int(config['max_training_step']), alpha=float(config.get('alpha', 1.0)),
+                         tol=1e-6, c1=1e-4, c2=0.9, grow=2.1, tau=0.5)   # lbfgs.lbfgs / backtracking_linesearch defaults
     batch = full.subsample(next(data_utils.sub_sample_index_iterator(rng, dataset, config['batch_size'])))   # gp.py:102-107
-    state = np.zeros(nat.lib().hbo_lbfgs_state_doubles(x.size, opts.memory), dtype=np.float64)
-    x_next = x.copy()
-    status = nat.LBFGS_RUNNING
-    log_all = []
-    while status == nat.LBFGS_RUNNING:
-      k = int(LBFGS_SEGMENT)
-      bm = _model.BuiltModel(mean_func, cov_func, GPParams(model=unflatten(x_next), config=config), warp_func, batch.dtype, batch.input_dim)
-      leaves, P = _model.train_leaf_map(bm, template)
-      if P != x.size:
-        raise ValueError(f'lbfgs_on_device: the leaf map has {P} entries for {x.size} parameters')
-      log = (nat.LbfgsEval * k)()
-      trace = np.empty((k, x.size), dtype=np.float64)
-      done, st = C.c_int32(0), C.c_int32(0)
-      rc = nat.lib().hbo_train_lbfgs(ctx.handle, bm.ref(), batch._h, leaves, P, C.byref(opts), nat.ptr(x), nat.ptr(state), k, log,
-                                     nat.ptr(trace), nat.ptr(x_next), C.byref(done), C.byref(st))
-      if rc == nat.HBO_ERR_UNSUPPORTED:
-        raise ValueError('lbfgs_on_device: ' + (nat.lib().hbo_last_error(ctx.handle) or b'').decode())
-      ctx.check(rc, allow_not_pd=False)
-      status = st.value
-      for j in range(done.value):
-        e = log[j]
-        log_all.append((e.kind, e.iter, e.alpha, e.value))
-        # lbfgs() calls back at the start and at every main step it does not leave as converged
-        recorded = e.kind == nat.LBFGS_START or (e.kind == nat.LBFGS_MAIN and not (status == nat.LBFGS_CONVERGED and j == done.value - 1))
-        if recorded and callback:
-          callback(step=e.iter, model_params=unflatten(trace[j]), loss=float(e.value))
-    params.model = unflatten(x)
-    if isinstance(config.get('lbfgs_eval_log'), dict):   # a dict the caller left in config: every evaluation, and how the run ended
-      config['lbfgs_eval_log'].update(evals=log_all, status=status)
-  finally:
-    if batch is not None:
+    try:
+      state = np.zeros(nat.lib().hbo_lbfgs_state_doubles(x.size, opts.memory), dtype=np.float64)
+      x_next = x.copy()
+      status = nat.LBFGS_RUNNING
+      log_all = []
+      while status == nat.LBFGS_RUNNING:
+        k = int(LBFGS_SEGMENT)
+        bm, leaves, P = built(unflatten(x_next), template, x.size)
+        log = (nat.LbfgsEval * k)()
+        trace = np.empty((k, x.size), dtype=np.float64)
+        done, st = C.c_int32(0), C.c_int32(0)
+        check(nat.lib().hbo_train_lbfgs(full.ctx.handle, bm.ref(), batch._h, leaves, P, C.byref(opts), nat.ptr(x), nat.ptr(state), k, log,
+                                        nat.ptr(trace), nat.ptr(x_next), C.byref(done), C.byref(st)))
+        status = st.value
+        for j in range(done.value):
+          e = log[j]
+          log_all.append((e.kind, e.iter, e.alpha, e.value))
+          # lbfgs() calls back at the start and at every main step it does not leave as converged
+          recorded = e.kind == nat.LBFGS_START or (e.kind == nat.LBFGS_MAIN and not (status == nat.LBFGS_CONVERGED and j == done.value - 1))
+          if recorded and callback:
+            callback(step=e.iter, model_params=unflatten(trace[j]), loss=float(e.value))
+      params.model = unflatten(x)
+      if isinstance(config.get('lbfgs_eval_log'), dict):   # a dict the caller left in config: every evaluation, and how the run ended
+        config['lbfgs_eval_log'].update(evals=log_all, status=status)
+    finally:
       batch.close()
-    full.close()
-  params.cache = {}
   return params
 
 

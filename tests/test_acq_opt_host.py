@@ -78,6 +78,18 @@ def test_hook_is_the_restatement_bit_for_bit(case):
     same_run(hook_run(case, r), ao.oracle_run(case, r))
 
 
+@pytest.mark.parametrize('memory', [1, 3])
+def test_hook_is_the_restatement_bit_for_bit_with_a_short_ring(memory):
+  """memory 1 (every pair overwrites the only slot) and 3 on box-matern32-ei: both starts take more than 8 main steps with a
+  component on a face of the box, so the ring wraps many times."""
+  case = ao.BY_NAME['box-matern32-ei']
+  inp, vg = ao.inputs(case), ao.oracle_value_and_grad(case)
+  for r in _starts(case):
+    got = run_hook(vg, inp.x0[r], inp.lo, inp.hi, memory=memory)
+    assert max(e[1] for e in got.log) >= 8 and np.any((got.x == inp.lo) | (got.x == inp.hi))
+    same_run(got, ao.minimise(vg, inp.x0[r], inp.lo, inp.hi, memory=memory))
+
+
 def test_hook_rounds_fp32_points_and_keeps_its_state_across_copies():
   case = ao.BY_NAME['box-matern32-ei']
   inp = ao.inputs(case)

@@ -227,6 +227,20 @@ def test_hook_is_the_host_driver_bit_for_bit_with_its_own_dots(monkeypatch, f, x
   assert np.array_equal(x_hook, x_host)
 
 
+@pytest.mark.parametrize('memory', [1, 3])
+def test_hook_is_the_host_driver_bit_for_bit_with_a_short_ring(monkeypatch, memory):
+  """memory 1 (every pair overwrites the only slot) and 3: the ring wraps from the second / fourth main step on (the P = 300 quadratic)."""
+  nat, defs, lbfgs, *_ = _mods()
+  f, x0, kw = quadratic, np.cos(np.arange(300.0)) + 1.5, dict(max_iters=25, tol=1e-30, memory=memory)
+  hook, x_hook, _ = run_hook(f, x0, **kw)
+  monkeypatch.setattr(lbfgs.np, 'vdot', fixed_order_dot)
+  host, x_host, _ = run_host(f, x0, monkeypatch, **kw)
+  monkeypatch.undo()
+  assert max(i for k, i, *_ in hook if k == nat.LBFGS_MAIN) >= 8
+  _same([(k, i, 0.0, x, v) for k, i, _, x, v in hook], [(k, i, 0.0, x, v) for k, i, _, x, v in host])
+  assert np.array_equal(x_hook, x_host)
+
+
 def test_hook_converged_at_start(monkeypatch):
   nat, *_ = _mods()
   hook, x, status, steps = compare(rosenbrock, np.array([1.0, 1.0]), monkeypatch)
