@@ -161,6 +161,10 @@ SIGNATURES = {
     'hbo_acq': (C.c_int, [_P, C.POINTER(Model), _P, _P, C.c_int64, C.c_int, C.c_double, C.c_double,
                           C.c_double, _P]),
     'hbo_sample_paths': (C.c_int, [_P, C.POINTER(Model), _P, _P, C.c_int64, C.c_int32, C.c_int32, _P, _P, _P, _P, _P]),
+    'hbo_sample_paths_grad': (C.c_int, [_P, C.POINTER(Model), _P, _P, C.c_int64, C.c_int32, C.c_int32, _P, _P, _P, _P, C.c_double, _P,
+                                        C.POINTER(C.c_double)]),
+    'hbo_paths_maximize': (C.c_int, [_P, C.POINTER(Model), _P, C.c_int32, C.c_int32, _P, _P, _P, _P, C.c_double, _P, C.c_int32, _P, _P,
+                                     C.POINTER(AcqOptOpts), _P, C.c_int32, _P, _P, _P, _P]),
     'hbo_acq_samples': (C.c_int, [_P, _P, C.c_int32, _P, C.c_int64, _P, C.c_int32, _P, C.c_int64, C.c_int, C.POINTER(C.c_double),
                                   C.POINTER(C.c_double), C.c_double, _P]),
     'hbo_nll_samples': (C.c_int, [_P, _P, C.c_int32, _P, C.POINTER(C.c_double), C.POINTER(C.c_double)]),

@@ -46,6 +46,55 @@ def thompson_batch(model, sub_dataset_key, x_queries, batch_size, key=None, num_
   return np.argmax(_paths_over_pool(model, sub_dataset_key, x_queries, int(batch_size), key, num_features), axis=0)
 
 
+def thompson_maximize(model, sub_dataset_key, x_candidates, batch_size=1, key=None, num_features=1024, starts=4, bounds=None, opts=None):
+  """[batch_size, D] float64: continuous Thompson sampling -- the maximisers over the box of `batch_size` posterior sample paths,
+  q suggestions from q paths x `starts` starts in one device call.  One draw of `batch_size` paths (GP.draw_paths) is scored at the
+  candidates; per path the `starts` best candidates (stable order, the lower index first among equals) start a projected L-BFGS on
+  the path itself (PathDraws.maximize: hbo_paths_maximize); per path the refined point with the largest value is returned, the lower
+  start index among equals (a path without a finite value keeps its best candidate).  key: a numpy Generator or an int seed, None
+  takes model.rng; bounds: None ([0, 1]^D) or D (lo, hi) pairs; opts: as PathDraws.maximize."""
+  if isinstance(model, gp.HGP):
+    raise ValueError('Thompson sampling is defined for a GP with one set of hyper-parameters, not for an HGP')
+  xc = np.asarray(x_candidates)
+  if xc.ndim != 2 or xc.shape[0] < 1:
+    raise ValueError(f'x_candidates must be [M, D] with M >= 1, got {xc.shape}')
+  q, r = int(batch_size), min(int(starts), xc.shape[0])
+  if q < 1 or r < 1:
+    raise ValueError('batch_size and starts must be at least 1')
+  draws = model.draw_paths(sub_dataset_key, num_samples=q, num_features=num_features, key=key)
+  scores = np.asarray(draws.values(xc), dtype=np.float64)                      # [M, q]
+  order = np.argsort(-scores, axis=0, kind='stable')[:r]                       # [r, q]
+  x0 = np.asarray(xc, dtype=np.float64)[order.T]                               # [q, r, D]
+  x, val, _ = draws.maximize(x0, bounds=bounds, opts=opts)
+  out = x0[:, 0, :].copy()
+  for s in range(q):
+    finite = np.isfinite(val[s])
+    if finite.any():
+      out[s] = x[s, int(np.argmax(np.where(finite, val[s], -np.inf)))]
+  return out
+
+
+class ThompsonContinuous:
+  """Thompson sampling for the continuous loop bayesopt.bayesopt: called, it scores candidates with a fresh posterior path (as
+  thompson_sampling does); `suggest` refines the best candidates on that path's own gradient (thompson_maximize) -- the loop takes
+  its next point from there, the prior branch included."""
+  __name__ = 'thompson_continuous'
+
+  def __init__(self, num_features=1024, starts=4, opts=None):
+    self.num_features, self.starts, self.opts = num_features, starts, opts
+
+  def __call__(self, model, sub_dataset_key, x_queries, key=None, **unused_kwargs):
+    return thompson_sampling(model, sub_dataset_key, x_queries, key=key, num_features=self.num_features)
+
+  def suggest(self, *, model, sub_dataset_key, x_candidates, key=None, batch_size=1, bounds=None):
+    """[batch_size, D]: thompson_maximize from the candidates."""
+    return thompson_maximize(model, sub_dataset_key, x_candidates, batch_size=batch_size, key=key, num_features=self.num_features,
+                             starts=self.starts, bounds=bounds, opts=self.opts)
+
+
+thompson_continuous = ThompsonContinuous()
+
+
 def _norm_pdf(x):
   return np.exp(-0.5 * x * x) / np.sqrt(2 * np.pi)
 

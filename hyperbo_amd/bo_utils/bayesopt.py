@@ -49,7 +49,10 @@ def bayesopt(key, model, sub_dataset_key, query_oracle, ac_func, iters, input_sa
   With config['acq_opt_on_device'] set, the SciPy call is replaced by `ac_func.maximize` (hbo_acq_maximize: the optimiser itself on
   the device) from the config['acq_opt_starts'] (default 1) best candidates -- ordered by acquisition value, the lower index first
   among equals -- once the sub-dataset has observations; an iteration without any (the prior branch) takes the SciPy path.  There is
-  no fall-back: the iteration at which the sub-dataset has grown past 128 observations raises HboError(HBO_ERR_UNSUPPORTED)."""
+  no fall-back: the iteration at which the sub-dataset has grown past 128 observations raises HboError(HBO_ERR_UNSUPPORTED).
+
+  An `ac_func` with a `suggest` attribute (acfun.thompson_continuous) proposes the point itself: x_opt is
+  `ac_func.suggest(model=, sub_dataset_key=, x_candidates=, key=)[0]` over the iteration's candidates and this loop's Generator."""
   rng = _rng(key)
   input_dim = model.input_dim
   cfg = model.params.config or {}
@@ -59,13 +62,20 @@ def bayesopt(key, model, sub_dataset_key, query_oracle, ac_func, iters, input_sa
     start_time = time.time()
     retrain_model(model, sub_dataset_key=sub_dataset_key, random_key=rng)
     x_samples = np.asarray(input_sampler(rng, input_dim))
-    if ac_func.__name__ in ('rand', 'random_search'):
+    suggest = getattr(ac_func, 'suggest', None)
+    if suggest is not None:
+      select_idx = 0   # (the strategy scores the candidates itself)
+    elif ac_func.__name__ in ('rand', 'random_search'):
       select_idx = int(rng.integers(x_samples.shape[0]))
     else:
       evals = ac_func(model=model, sub_dataset_key=sub_dataset_key, x_queries=x_samples)
       select_idx = int(np.argmax(evals))
     x_init = np.asarray(x_samples[select_idx], dtype=np.float64)
-    if ac_func.__name__ in ('rand', 'random_search') or not (hasattr(ac_func, 'value_and_grad') or hasattr(ac_func, 'maximize')):
+    if suggest is not None:
+      # a strategy that proposes points itself (acfun.thompson_continuous: the maximiser of a posterior sample path, refined on the
+      # device from the best candidates), with or without observations
+      x_opt = np.asarray(suggest(model=model, sub_dataset_key=sub_dataset_key, x_candidates=x_samples, key=rng)[0], dtype=np.float64)
+    elif ac_func.__name__ in ('rand', 'random_search') or not (hasattr(ac_func, 'value_and_grad') or hasattr(ac_func, 'maximize')):
       x_opt = x_init   # (neither a gradient nor a maximiser to refine with, e.g. thompson_sampling: the best candidate stays as it is)
     elif on_device and model.has_observations(sub_dataset_key):
       starts = np.argsort(-np.asarray(evals, dtype=np.float64).reshape(-1), kind='stable')[:max(1, int(cfg.get('acq_opt_starts', 1)))]

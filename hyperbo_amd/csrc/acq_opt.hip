@@ -4,31 +4,11 @@
 // runs one step of the state machine of acq_opt_ctl.h and writes the next pending point -- and one synchronisation and one copy back.
 // A start reads and writes only its own state, its own row of the pending points and its own columns of the per-sample results.
 // Also here: the host hook hbo_probe_acq_opt_ctl, the same control text on one thread.
-#include "api_internal.h"
-#define HBO_LBFGS_FN static __host__ __device__ inline
-#include "acq_opt_ctl.h"
+#include "acq_opt_host.h"
 #include "../../include/hbo_tune.h"
-
-static_assert(sizeof(hbo_acq_opt_opts) == sizeof(hbo_acq_opt_opts_ctl) && sizeof(hbo_acq_opt_eval) == sizeof(hbo_acq_opt_eval_ctl), "acq_opt_ctl.h restates hbo.h");
-static_assert(HBO_ACQ_OPT_START == HBO_ACQ_OPT_CTL_START && HBO_ACQ_OPT_MAIN == HBO_ACQ_OPT_CTL_MAIN && HBO_ACQ_OPT_LINE_SEARCH == HBO_ACQ_OPT_CTL_LINE_SEARCH &&
-              HBO_ACQ_OPT_IDLE == HBO_ACQ_OPT_CTL_IDLE && HBO_ACQ_OPT_RUNNING == HBO_ACQ_OPT_CTL_RUNNING && HBO_ACQ_OPT_CONVERGED == HBO_ACQ_OPT_CTL_CONVERGED &&
-              HBO_ACQ_OPT_FTOL == HBO_ACQ_OPT_CTL_FTOL && HBO_ACQ_OPT_NO_PROGRESS == HBO_ACQ_OPT_CTL_NO_PROGRESS &&
-              HBO_ACQ_OPT_NONFINITE_AT_START == HBO_ACQ_OPT_CTL_NONFINITE_AT_START && HBO_ACQ_OPT_STEPS_DONE == HBO_ACQ_OPT_CTL_STEPS_DONE,
-              "acq_opt_ctl.h restates hbo.h");
 
 namespace {
 enum { ACQ_OPT_THREADS = 256 };
-
-struct AcqOptArgs {
-  hbo_acq_opt_opts_ctl o;
-  double* state; int64_t ns;        // [R][ns]
-  const double* lo; const double* hi;   // [D] each
-  void* pending;                    // [R][D] model dtype: the queries of the next acq_small_kernel launch
-  const double* vals;               // [S][R] fp64 acquisition values of the pending points
-  const double* grads;              // [S][R][D]
-  hbo_acq_opt_eval_ctl* log;        // nullable [evals][R]
-  int D, R, S;
-};
 
 // One evaluation of one start: the step of acq_opt_ctl.h, the log record, the next pending point in the model dtype (the state's copy
 // already holds that rounded value).  The start's state is staged in LDS for the step -- its dot products are chains of dependent
@@ -53,7 +33,9 @@ __global__ __launch_bounds__(ACQ_OPT_THREADS) void acq_opt_ctl_kernel(AcqOptArgs
   T* p = static_cast<T*>(a.pending) + r * D;
   for (int i = tid; i < D; i += nthr) p[i] = (T)v.xt[i];
 }
-enum { ACQ_OPT_LDS_MAX = 65536 };
+}  // namespace
+
+// ---- shared with path_opt.hip (acq_opt_host.h) ----
 size_t acq_opt_lds_bytes(int64_t ns) { return sizeof(double) * (size_t)(ns + HBO_LBFGS_PARTIALS); }
 
 int acq_opt_check_opts(hbo_ctx* c, const std::string& fn, const hbo_acq_opt_opts* o) {
@@ -102,7 +84,10 @@ bool acq_opt_in_box(const double* x, const double* lo, const double* hi, int D) 
   }
   return true;
 }
-}  // namespace
+void launch_acq_opt_ctl(int dtype, const AcqOptArgs& a, int slot, hipStream_t st) {
+  if (dtype == HBO_F64) hipLaunchKernelGGL((acq_opt_ctl_kernel<double>), dim3(a.R), dim3(ACQ_OPT_THREADS), acq_opt_lds_bytes(a.ns), st, a, slot);
+  else hipLaunchKernelGGL((acq_opt_ctl_kernel<float>), dim3(a.R), dim3(ACQ_OPT_THREADS), acq_opt_lds_bytes(a.ns), st, a, slot);
+}
 
 extern "C" int64_t hbo_acq_opt_state_doubles(int32_t D, int32_t memory) {
   if (D <= 0 || memory < 1) return 0;
@@ -196,8 +181,7 @@ extern "C" int hbo_acq_maximize(hbo_ctx* c, const hbo_model* models, int32_t S, 
   if (c->opt_poison && log_b) HIPCHK(c, hipMemsetAsync(d_in + up_b, 0xFF, log_b, st));
   for (int e = 0; e < evals; ++e) {
     launch_acq_small(dtype, a, S, st);
-    if (dtype == HBO_F64) hipLaunchKernelGGL((acq_opt_ctl_kernel<double>), dim3(R), dim3(ACQ_OPT_THREADS), acq_opt_lds_bytes(ns), st, k, e);
-    else hipLaunchKernelGGL((acq_opt_ctl_kernel<float>), dim3(R), dim3(ACQ_OPT_THREADS), acq_opt_lds_bytes(ns), st, k, e);
+    launch_acq_opt_ctl(dtype, k, e, st);
   }
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipMemcpyAsync(stage + o_state, d_in + o_state, down_b, hipMemcpyDeviceToHost, st));

@@ -444,6 +444,19 @@ static void acq_small_pack(AcqSmallSample* hs, double* hv, const hbo_model* mode
   }
 }
 
+// ---- sample paths (paths.hip), shared with the path maximiser (path_opt.hip) ------------------
+// path_check: what both ask of (model, cache, S, F, eps) before any device call.  path_solve: the draws on the device and the weights
+// v of the update term over the cache's observations, with `scale` on the amplitude and the noise draw.
+struct PathSolve {
+  const void* om; const void* ph; const void* w;   // the draws on the device, model dtype (om / ph empty for the dot product)
+  double* sums;                                    // [rows][S] prior sums: scratch of the prior kernel
+  double* v; int64_t vld;                          // [S][vld] weights (null without a cache)
+  double A;                                        // the amplitude sqrt(2 signal_variance / F) (1 for the dot product), without `scale`
+};
+int path_check(hbo_ctx* c, const std::string& fn, const hbo_model* m, const hbo_cache* k, int32_t S, int32_t F, bool has_eps);
+int path_solve(hbo_ctx* c, const hbo_model* m, hbo_cache* k, int32_t S, int32_t F, const void* omega, const void* phase, const void* w,
+               const void* eps, double scale, int64_t sum_rows, PathSolve* ps);
+
 static void fill_nan(void* p, size_t count, int dtype) {
   if (dtype == HBO_F64) for (size_t i = 0; i < count; ++i) ((double*)p)[i] = NAN;
   else for (size_t i = 0; i < count; ++i) ((float*)p)[i] = NAN;

@@ -277,11 +277,8 @@ void launch_path_solve_t(const void* W, int64_t ldw, int n, const double* r, dou
 }
 }  // namespace
 
-extern "C" int hbo_sample_paths(hbo_ctx* c, const hbo_model* m, hbo_cache* k, const void* xq, int64_t M, int32_t S, int32_t F,
-                                const void* omega, const void* phase, const void* w, const void* eps, void* out) {
-  const std::string fn = "hbo_sample_paths: ";
-  // ---- every argument check, before any device call ----
-  if (!m || !xq || !omega || !phase || !w || !out) return fail(c, HBO_ERR_ARG, fn + "null argument");
+// What hbo_sample_paths and the entry points of path_opt.hip ask of (model, cache, S, F, eps), before any device call (c may be null)
+int path_check(hbo_ctx* c, const std::string& fn, const hbo_model* m, const hbo_cache* k, int32_t S, int32_t F, bool has_eps) {
   if (S < 1 || S > 1024) return fail(c, HBO_ERR_ARG, fn + "need 1 <= S <= 1024");
   if (F < 1 || F > 65536) return fail(c, HBO_ERR_ARG, fn + "need 1 <= F <= 65536");
   int rc = validate_model(c, m);
@@ -289,10 +286,74 @@ extern "C" int hbo_sample_paths(hbo_ctx* c, const hbo_model* m, hbo_cache* k, co
   const int dtype = m->dtype, D = m->input_dim, fdim = feature_dim(m);
   const bool is_dot = m->kernel_id == HBO_KERNEL_DOT;
   if (is_dot && F != fdim + 1) return fail(c, HBO_ERR_ARG, fn + "a dot-product model takes F = feature dim + 1 (its basis is exact)");
-  if ((k != nullptr) != (eps != nullptr)) return fail(c, HBO_ERR_ARG, fn + "eps goes with a cache: both or neither");
+  if ((k != nullptr) != has_eps) return fail(c, HBO_ERR_ARG, fn + "eps goes with a cache: both or neither");
   if (k && (k->dtype != dtype || k->D != D)) return fail(c, HBO_ERR_ARG, fn + "cache/model mismatch");
   if (k && k->input_warp != m->input_warp) return fail(c, HBO_ERR_ARG, fn + "the cache was factorised with another input warp");
   if (k && (!k->t || k->t->n <= 0)) return fail(c, HBO_ERR_ARG, fn + "the cache holds no observations");
+  return HBO_OK;
+}
+
+// The draws on the device and the weights of the update term, v[:,s] = Ktilde^-1 (y - m(X) - scale p_s(X) - scale sqrt(noise + eps) eps[:,s]):
+// the prior paths at the cached observations, the right-hand sides, the two triangular products.  `scale` multiplies the amplitude
+// and the noise scale (1 for hbo_sample_paths; the unbiased deviation scale of path_opt.hip).  sum_rows: rows the caller wants of the
+// [rows][S] prior sums (at least n are taken).  A cache that is not positive definite (or none) is left alone: v stays unset.
+int path_solve(hbo_ctx* c, const hbo_model* m, hbo_cache* k, int32_t S, int32_t F, const void* omega, const void* phase, const void* w,
+               const void* eps, double scale, int64_t sum_rows, PathSolve* ps) {
+  const int dtype = m->dtype, fdim = feature_dim(m);
+  const bool is_dot = m->kernel_id == HBO_KERNEL_DOT;
+  const size_t es = esize(dtype);
+  hipStream_t st = c->stream;
+  TaskHost* t = k ? k->t : nullptr;
+  const int n = t ? (int)t->n : 0;
+  ps->A = is_dot ? 1.0 : sqrt(2.0 * (double)m->signal_variance / (double)F);
+  const double sn = sqrt((double)m->noise_variance + (double)m->eps);
+  // the draws (omega / phase stay empty for the dot product)
+  const size_t om_b = is_dot ? 0 : (size_t)F * fdim * es, ph_b = is_dot ? 0 : (size_t)F * es, w_b = (size_t)F * S * es;
+  char* d_draw = (char*)ws_get(c, WS_PATH_DRAWS, om_b + ph_b + w_b + (size_t)n * S * es + 64);
+  double* d_sums = (double*)ws_get(c, WS_PATH_SUMS, (size_t)std::max<int64_t>(std::max<int64_t>(sum_rows, n), 1) * S * sizeof(double));
+  if (!d_draw || !d_sums) return HBO_ERR_HIP;
+  char* d_om = d_draw; char* d_ph = d_om + om_b; char* d_w = d_ph + ph_b; char* d_eps = d_w + w_b;
+  double *d_r = nullptr, *d_z = nullptr, *d_v = nullptr;
+  if (t) {
+    d_r = (double*)ws_get(c, WS_PATH_R, (size_t)S * t->npad * sizeof(double));
+    d_z = (double*)ws_get(c, WS_PATH_Z, (size_t)S * t->npad * sizeof(double));
+    d_v = (double*)ws_get(c, WS_PATH_V, (size_t)S * t->npad * sizeof(double));
+    if (!d_r || !d_z || !d_v) return HBO_ERR_HIP;
+  }
+  if (om_b) HIPCHK(c, hipMemcpyAsync(d_om, omega, om_b, hipMemcpyHostToDevice, st));
+  if (ph_b) HIPCHK(c, hipMemcpyAsync(d_ph, phase, ph_b, hipMemcpyHostToDevice, st));
+  HIPCHK(c, hipMemcpyAsync(d_w, w, w_b, hipMemcpyHostToDevice, st));
+  if (t) HIPCHK(c, hipMemcpyAsync(d_eps, eps, (size_t)n * S * es, hipMemcpyHostToDevice, st));
+  ps->om = d_om; ps->ph = d_ph; ps->w = d_w; ps->sums = d_sums; ps->v = d_v; ps->vld = t ? t->npad : 0;
+  if (!t || k->info != INT_MAX) return HBO_OK;
+  PathPriorArgs pa = {};
+  pa.fdim = fdim; pa.omega = d_om; pa.phase = d_ph; pa.w = d_w; pa.F = F; pa.S = S; pa.is_dot = is_dot; pa.sums = d_sums;
+  // the prior paths at the observations (their features are the cache's), the right-hand sides, v = W^T (W r)
+  { ProfScope pp(c, "path_prior", 1);
+    pa.feat = k->h_desc.F; pa.rows = n;
+    launch_path_prior(dtype, pa, c->d_model, st); }
+  ProfScope pp(c, "path_solve", 1);
+  const unsigned gb = (unsigned)(((int64_t)n * S + 255) / 256);
+  const double A = ps->A * scale, sns = sn * scale;
+  if (dtype == HBO_F64) {
+    hipLaunchKernelGGL((path_rhs_kernel<double>), dim3(gb), dim3(256), 0, st, (const double*)k->resid, d_sums, (const double*)d_eps, A, sns, n, S, (int64_t)t->npad, d_r);
+    launch_path_solve_t<double>(t->W, t->ld, n, d_r, d_z, d_v, t->npad, S, st);
+  } else {
+    hipLaunchKernelGGL((path_rhs_kernel<float>), dim3(gb), dim3(256), 0, st, (const float*)k->resid, d_sums, (const float*)d_eps, A, sns, n, S, (int64_t)t->npad, d_r);
+    launch_path_solve_t<float>(t->W, t->ld, n, d_r, d_z, d_v, t->npad, S, st);
+  }
+  return HBO_OK;
+}
+
+extern "C" int hbo_sample_paths(hbo_ctx* c, const hbo_model* m, hbo_cache* k, const void* xq, int64_t M, int32_t S, int32_t F,
+                                const void* omega, const void* phase, const void* w, const void* eps, void* out) {
+  const std::string fn = "hbo_sample_paths: ";
+  // ---- every argument check, before any device call ----
+  if (!m || !xq || !omega || !phase || !w || !out) return fail(c, HBO_ERR_ARG, fn + "null argument");
+  int rc = path_check(c, fn, m, k, S, F, eps != nullptr);
+  if (rc) return rc;
+  const int dtype = m->dtype, D = m->input_dim, fdim = feature_dim(m);
+  const bool is_dot = m->kernel_id == HBO_KERNEL_DOT;
   if (!c) return fail(c, HBO_ERR_ARG, fn + "ctx is null");
   if (M <= 0) return HBO_OK;
   HIPCHK(c, hipSetDevice(c->device));
@@ -303,57 +364,33 @@ extern "C" int hbo_sample_paths(hbo_ctx* c, const hbo_model* m, hbo_cache* k, co
   hipStream_t st = c->stream;
   TaskHost* t = k ? k->t : nullptr;
   const int n = t ? (int)t->n : 0;
-  const double A = is_dot ? 1.0 : sqrt(2.0 * (double)m->signal_variance / (double)F);
-  const double sn = sqrt((double)m->noise_variance + (double)m->eps);
   // queries stream in chunks of post_chunk, as hbo_predict's do
   const int64_t CH = std::max<int64_t>(c->opt_post_chunk, HBO_TILE), mc_max = std::min<int64_t>(M, CH);
   const int mpad_max = round_up(mc_max, HBO_TILE);
   const int64_t ldq_max = padded_ld(mpad_max, dtype);
-  // the draws (omega / phase stay empty for the dot product)
-  const size_t om_b = is_dot ? 0 : (size_t)F * fdim * es, ph_b = is_dot ? 0 : (size_t)F * es, w_b = (size_t)F * S * es;
-  char* d_draw = (char*)ws_get(c, WS_PATH_DRAWS, om_b + ph_b + w_b + (size_t)n * S * es + 64);
   void* d_xq = ws_get(c, WS_XQ, (size_t)M * D * es);
   void* d_mu0 = ws_get(c, WS_MU0, (size_t)mc_max * es);
   void* d_kd = ws_get(c, WS_KD, (size_t)mc_max * es);
-  double* d_sums = (double*)ws_get(c, WS_PATH_SUMS, (size_t)std::max<int64_t>(mc_max, n) * S * sizeof(double));
   void* d_out = ws_get(c, WS_PATH_OUT, (size_t)mc_max * S * es);
-  if (!d_draw || !d_xq || !d_mu0 || !d_kd || !d_sums || !d_out) return HBO_ERR_HIP;
-  char* d_om = d_draw; char* d_ph = d_om + om_b; char* d_w = d_ph + ph_b; char* d_eps = d_w + w_b;
+  if (!d_xq || !d_mu0 || !d_kd || !d_out) return HBO_ERR_HIP;
   void* d_kwq = is_kumar(m) ? ws_get(c, WS_KW_Q, (size_t)mc_max * D * es) : nullptr;
   if (is_kumar(m) && !d_kwq) return HBO_ERR_HIP;
   void* fq_acts[HBO_MAX_MLP_LAYERS] = {nullptr};
   if (needs_mlp(m)) for (int l = 0; l < m->n_layers; ++l) { fq_acts[l] = ws_get(c, WS_FQ0 + l, (size_t)mc_max * m->features[l] * es); if (!fq_acts[l]) return HBO_ERR_HIP; }
-  void* d_K = nullptr; double *d_r = nullptr, *d_z = nullptr, *d_v = nullptr;
+  void* d_K = nullptr;
   if (t) {
     d_K = ws_get(c, WS_K, (size_t)t->npad * ldq_max * es);
-    d_r = (double*)ws_get(c, WS_PATH_R, (size_t)S * t->npad * sizeof(double));
-    d_z = (double*)ws_get(c, WS_PATH_Z, (size_t)S * t->npad * sizeof(double));
-    d_v = (double*)ws_get(c, WS_PATH_V, (size_t)S * t->npad * sizeof(double));
-    if (!d_K || !d_r || !d_z || !d_v) return HBO_ERR_HIP;
+    if (!d_K) return HBO_ERR_HIP;
   }
-  if (om_b) HIPCHK(c, hipMemcpyAsync(d_om, omega, om_b, hipMemcpyHostToDevice, st));
-  if (ph_b) HIPCHK(c, hipMemcpyAsync(d_ph, phase, ph_b, hipMemcpyHostToDevice, st));
-  HIPCHK(c, hipMemcpyAsync(d_w, w, w_b, hipMemcpyHostToDevice, st));
-  if (t) HIPCHK(c, hipMemcpyAsync(d_eps, eps, (size_t)n * S * es, hipMemcpyHostToDevice, st));
   HIPCHK(c, hipMemcpyAsync(d_xq, xq, (size_t)M * D * es, hipMemcpyHostToDevice, st));
+  PathSolve sol = {};
+  rc = path_solve(c, m, k, S, F, omega, phase, w, eps, 1.0, mc_max, &sol);
+  if (rc) return rc;
+  double* d_sums = sol.sums; double* d_v = sol.v;
+  const double A = sol.A;
   PathPriorArgs pa = {};
-  pa.fdim = fdim; pa.omega = d_om; pa.phase = d_ph; pa.w = d_w; pa.F = F; pa.S = S; pa.is_dot = is_dot; pa.sums = d_sums;
+  pa.fdim = fdim; pa.omega = sol.om; pa.phase = sol.ph; pa.w = sol.w; pa.F = F; pa.S = S; pa.is_dot = is_dot; pa.sums = d_sums;
   const bool bad = k && k->info != INT_MAX;
-  if (t && !bad) {
-    // the prior paths at the observations (their features are the cache's), the right-hand sides, v = W^T (W r)
-    { ProfScope ps(c, "path_prior", 1);
-      pa.feat = k->h_desc.F; pa.rows = n;
-      launch_path_prior(dtype, pa, c->d_model, st); }
-    ProfScope ps(c, "path_solve", 1);
-    const unsigned gb = (unsigned)(((int64_t)n * S + 255) / 256);
-    if (dtype == HBO_F64) {
-      hipLaunchKernelGGL((path_rhs_kernel<double>), dim3(gb), dim3(256), 0, st, (const double*)k->resid, d_sums, (const double*)d_eps, A, sn, n, S, (int64_t)t->npad, d_r);
-      launch_path_solve_t<double>(t->W, t->ld, n, d_r, d_z, d_v, t->npad, S, st);
-    } else {
-      hipLaunchKernelGGL((path_rhs_kernel<float>), dim3(gb), dim3(256), 0, st, (const float*)k->resid, d_sums, (const float*)d_eps, A, sn, n, S, (int64_t)t->npad, d_r);
-      launch_path_solve_t<float>(t->W, t->ld, n, d_r, d_z, d_v, t->npad, S, st);
-    }
-  }
   for (int64_t q0 = 0; q0 < M && !bad; q0 += CH) {
     const int64_t mc = std::min<int64_t>(CH, M - q0);
     const int mpad = round_up(mc, HBO_TILE);

@@ -662,6 +662,35 @@ class GP:
       out = mean + (out[:, :-1] - mean) * out.dtype.type(np.sqrt(scale))
     return out
 
+  def draw_paths(self, sub_dataset_key: Union[int, str] = 0, num_samples: int = 1, num_features: int = 1024, key=None,
+                 unbiased: bool = True) -> pathwise.PathDraws:
+    """`num_samples` posterior sample paths over the sub-dataset (the prior without observations) as functions of x: a
+    pathwise.PathDraws, whose values / value_and_grad / maximize evaluate, differentiate and maximise them on the device at any
+    point of the box (hbo_sample_paths_grad, hbo_paths_maximize).  The draws are those sample_paths makes from the same key, in the
+    same order.  unbiased: the deviation from the posterior mean is scaled by sqrt(T / (T - 1)), as sample_paths does.  The draws
+    belong to the observations of this moment: after an update of the sub-dataset they raise ValueError."""
+    if isinstance(self, HGP):
+      raise ValueError('sample paths are defined for a GP with one set of hyper-parameters, not for an HGP')
+    if key is None:
+      if self.rng is None:
+        raise ValueError('draw_paths needs a random key: pass key=, or set model.rng')
+      key = self.rng
+    handle = None
+    if self.has_observations(sub_dataset_key):
+      self.setup_predictor(sub_dataset_key)
+      handle = self.params.cache[sub_dataset_key].handle
+    _, scale = self.predict_noise_and_scale(False, unbiased)
+    # (the prior branch has no observations to take the dtype from: that of the hyper-parameters)
+    leaves, stack = [], [self.params.model]
+    while stack:
+      t = stack.pop()
+      if isinstance(t, dict):
+        stack.extend(t.values())
+      else:
+        leaves.append(t)
+    return pathwise.PathDraws(self.mean_func, self.cov_func, self.params, self.warp_func, handle, self.input_dim,
+                              _model.infer_dtype(*leaves), num_samples, num_features, key, dev_scale=float(np.sqrt(scale)))
+
   def predict_noise_and_scale(self, with_noise=True, unbiased=True):
     """The (noise_variance, T/(T-1)) post-processing constants of gp.py:607-619."""
     add_noise = 0.0

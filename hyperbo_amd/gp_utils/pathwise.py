@@ -100,3 +100,127 @@ def sample_paths(mean_func, cov_func, params, x_query, warp_func=None, handle=No
   ctx.check(nat.lib().hbo_sample_paths(ctx.handle, bm.ref(), handle.handle if handle is not None else None, nat.ptr(xq), xq.shape[0], s_all,
                                        w.shape[0], nat.ptr(omega), nat.ptr(phase), nat.ptr(w), nat.ptr(eps), nat.ptr(out)))
   return out
+
+
+PATH_OPT_SEGMENT = 64       # evaluations per hbo_paths_maximize call (profiles/path_maximize.md)
+PATH_OPT_MAX_EVALS = 512    # evaluations a (path, start) pair may spend in all
+MAX_PAIRS = 4096            # hbo_paths_maximize: paths x starts
+
+
+class PathDraws:
+  """S posterior sample paths as FUNCTIONS of x: the draws of `draw` (made once, in the contract order), the cache they condition on
+  and the deviation scale, evaluated on the device at any later point -- values, gradients (hbo_sample_paths_grad) and maxima over a
+  box (hbo_paths_maximize; csrc/path_opt.hip).  Made by GP.draw_paths.  The draws are tied to the observations they were made
+  over: once the cache has grown (or was replaced), every method raises ValueError."""
+
+  def __init__(self, mean_func, cov_func, params, warp_func, handle, input_dim, dtype, num_samples, num_features, key, dev_scale=1.0):
+    rng = as_generator(key)
+    s, f = int(num_samples), int(num_features)
+    if s < 1 or s > MAX_SAMPLES:
+      raise ValueError(f'num_samples must lie in 1..{MAX_SAMPLES}, got {num_samples}')
+    if f < 1 or f > MAX_FEATURES:
+      raise ValueError(f'num_features must lie in 1..{MAX_FEATURES}, got {num_features}')
+    if not (np.isfinite(dev_scale) and dev_scale > 0):
+      raise ValueError(f'dev_scale must be a finite number > 0, got {dev_scale!r}')
+    self.dtype = np.dtype(handle.dtype if handle is not None else dtype)
+    self.bm = _model.BuiltModel(mean_func, cov_func, params, warp_func, self.dtype, input_dim)
+    self.input_dim = int(input_dim)
+    self.handle = handle
+    self.n = handle.n if handle is not None else 0
+    self._cache = handle.handle.value if handle is not None else None
+    self.dev_scale = float(dev_scale)
+    ls = warped_lengthscale(params, warp_func) if self.bm.kernel_id != nat.KERNEL_DOT else None
+    cast = lambda a: None if a is None else np.ascontiguousarray(a, dtype=self.dtype)
+    self.omega, self.phase, self.w, self.eps = [cast(a) for a in draw(rng, self.bm.kernel_id, self.bm.feat_dim, ls, f, s, self.n)]
+    self.num_samples = s
+
+  def _check(self):
+    if self.handle is not None and (self.handle.n != self.n or self.handle.handle.value != self._cache or not self._cache):
+      raise ValueError(f'these paths were drawn over {self.n} observations; the cache has changed since (it now holds '
+                       f'{self.handle.n}): draw again')
+
+  def _ctx(self):
+    return self.handle.ctx if self.handle is not None else nat.default_context()
+
+  def _queries(self, xq):
+    xq = np.ascontiguousarray(np.asarray(xq), dtype=self.dtype)
+    if xq.ndim != 2 or xq.shape[1] != self.input_dim:
+      raise ValueError(f'x must be [M, {self.input_dim}], got {xq.shape}')
+    return xq
+
+  def _device_value_and_grad(self, xq):
+    ctx = self._ctx()
+    out = np.empty((xq.shape[0], self.num_samples), dtype=self.dtype)
+    grad = np.empty((xq.shape[0], self.num_samples, self.input_dim), dtype=np.float64)
+    if xq.shape[0]:
+      ctx.check(nat.lib().hbo_sample_paths_grad(ctx.handle, self.bm.ref(), self.handle.handle if self.handle is not None else None,
+                                                nat.ptr(xq), xq.shape[0], self.num_samples, self.w.shape[0], nat.ptr(self.omega),
+                                                nat.ptr(self.phase), nat.ptr(self.w), nat.ptr(self.eps), self.dev_scale, nat.ptr(out),
+                                                grad.ctypes.data_as(nat.C.POINTER(nat.C.c_double))))
+    return out, grad
+
+  def _device_maximize(self, x0, lo, hi, o, state, evals, x, val, status, log):
+    ctx = self._ctx()
+    ctx.check(nat.lib().hbo_paths_maximize(ctx.handle, self.bm.ref(), self.handle.handle if self.handle is not None else None,
+                                           self.num_samples, self.w.shape[0], nat.ptr(self.omega), nat.ptr(self.phase), nat.ptr(self.w),
+                                           nat.ptr(self.eps), self.dev_scale, nat.ptr(x0), x0.shape[1], nat.ptr(lo), nat.ptr(hi),
+                                           nat.C.byref(o), nat.ptr(state), int(evals), nat.ptr(x), nat.ptr(val), nat.ptr(status),
+                                           nat.ptr(log)))
+
+  def value_and_grad(self, xq):
+    """([M, S] values in the model dtype, [M, S, D] gradients in float64) of the S paths at the rows of xq."""
+    self._check()
+    return self._device_value_and_grad(self._queries(xq))
+
+  def values(self, xq):
+    """[M, S] values of the S paths at the rows of xq, in the model dtype."""
+    return self.value_and_grad(xq)[0]
+
+  def maximize(self, x_init, bounds=None, opts=None, evals=None):
+    """Maximises every path over a box on the device (hbo_paths_maximize: the projected L-BFGS of hbo_acq_maximize, all paths and
+    starts in one call, no host round trip per evaluation).  x_init [S, R, D]: R starts per path ([R, D]: the same starts for
+    every path).  bounds: None ([0, 1]^D) or D (lo, hi) pairs.  opts: overrides of acfun.ACQ_OPT_DEFAULTS, plus 'segment'
+    (evaluations per call) and 'log' (keep the per-evaluation log).  evals: the evaluations a pair may spend in all
+    (PATH_OPT_MAX_EVALS), in segments, until no pair is RUNNING.
+    Returns (x [S, R, D] float64, values [S, R], info): info holds 'status' and 'evals' per pair, and 'log' on request."""
+    from hyperbo_amd.bo_utils import acfun
+    self._check()
+    o = dict(acfun.ACQ_OPT_DEFAULTS, segment=PATH_OPT_SEGMENT, log=False)
+    o.update(opts or {})
+    budget = PATH_OPT_MAX_EVALS if evals is None else int(evals)
+    if budget < 1 or int(o['segment']) < 1:
+      raise ValueError('evals and opts["segment"] must be at least 1')
+    s, d = self.num_samples, self.input_dim
+    x0 = np.asarray(x_init, dtype=np.float64)
+    if x0.ndim == 2:
+      x0 = np.broadcast_to(x0[None], (s,) + x0.shape)
+    if x0.ndim != 3 or x0.shape[0] != s or x0.shape[2] != d or x0.shape[1] < 1:
+      raise ValueError(f'x_init must be [{s}, R, {d}] or [R, {d}], got {np.shape(x_init)}')
+    r = x0.shape[1]
+    if s * r > MAX_PAIRS:
+      raise ValueError(f'{s} paths x {r} starts exceed {MAX_PAIRS} pairs')
+    x0 = np.ascontiguousarray(x0, dtype=self.dtype)
+    lo = hi = None
+    if bounds is not None:
+      b = np.asarray(bounds, dtype=np.float64).reshape(d, 2)
+      lo, hi = np.ascontiguousarray(b[:, 0]), np.ascontiguousarray(b[:, 1])
+    co = nat.AcqOptOpts(*[o[k] for k in ('memory', 'ls_steps', 'max_iters', 'c1', 'tau', 'pgtol', 'ftol')])
+    ns = nat.lib().hbo_acq_opt_state_doubles(d, co.memory)
+    state = np.zeros((s * r, max(ns, 1)), dtype=np.float64)
+    x = np.zeros((s, r, d), dtype=np.float64)
+    val = np.full((s, r), np.nan)
+    status = np.zeros((s, r), dtype=np.int32)
+    logs, spent = [], 0
+    while spent < budget:
+      seg = int(min(o['segment'], budget - spent))
+      log = np.zeros((seg, s * r), dtype=nat.ACQ_OPT_EVAL_DTYPE) if o['log'] else None
+      self._device_maximize(x0, lo, hi, co, state, seg, x, val, status, log)
+      spent += seg
+      if o['log']:
+        logs.append(log)
+      if not np.any(status == nat.ACQ_OPT_RUNNING):
+        break
+    info = {'status': status, 'evals': state[:, nat.ACQ_OPT_S_EVALS].astype(np.int64).reshape(s, r)}
+    if o['log']:
+      info['log'] = np.concatenate(logs)
+    return x, val, info

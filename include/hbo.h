@@ -221,6 +221,25 @@ int hbo_acq(hbo_ctx* ctx, const hbo_model* model, hbo_cache* cache, const void* 
 int hbo_sample_paths(hbo_ctx* ctx, const hbo_model* model, hbo_cache* cache /* nullable */, const void* xq, int64_t M, int32_t S, int32_t F,
                      const void* omega, const void* phase, const void* w, const void* eps, void* out);
 
+/* ---- value and d/dx of those paths at single points (csrc/path_opt.hip).  With c = dev_scale, the factor the deviation of a path
+ *      from the posterior mean is scaled by (GP.sample_paths' unbiased sqrt(T / (T - 1)); 1 gives hbo_sample_paths' paths):
+ *        f_s(x) = m(x) + c p_s(x) + sum_i k(x, X_i) u[i,s],   u[:,s] = Ktilde^-1 (y - m(X) - c p_s(X) - c sqrt(noise_variance + eps) eps[:,s])
+ *        SE / Matern:  df_s/dx_d = -c A sum_j w[j,s] sin(omega_j . x + phase_j) omega_jd + sum_i u[i,s] dk/du_i 2 (x_d - X_id) / ls_d^2
+ *                      (a Matern pair at zero distance contributes 0, as hbo_acq_grad)
+ *        dot product:  df_s/dx_d = c w[d,s] / dot_prod_sigma + sum_i u[i,s] X_id / dot_prod_sigma^2;   a linear mean adds its weight d.
+ *      u comes from the solve of hbo_sample_paths; after it a point costs O(F D + n D) per path and needs no factor: no limit on n, and
+ *      the prior branch (cache == NULL) is served.  The features are the raw x.  xq [M, input_dim], the draws and eps as
+ *      hbo_sample_paths; out [M,S] (model dtype), grad_out [M,S,input_dim] doubles.  One workgroup per (query, path) pair; sine and
+ *      cosine in the model dtype, every sum in fp64 in an order fixed by (n, F, input_dim) alone, no atomics: an entry does not depend
+ *      on the queries and paths that share the call (bit for bit), and identical calls are bit-identical.
+ *      HBO_ERR_ARG, before any device call and with the outputs untouched: those of hbo_sample_paths, and a dev_scale that is not
+ *      finite or not > 0.  HBO_ERR_UNSUPPORTED (before any device work; these stay with hbo_sample_paths): kernel_uses_mlp, a
+ *      linear_mlp mean, an input-warped (Kumaraswamy) model.  A cache that is not positive definite: out and grad_out are NaN,
+ *      HBO_NOT_PD.  M == 0 returns HBO_OK. */
+int hbo_sample_paths_grad(hbo_ctx* ctx, const hbo_model* model, hbo_cache* cache /* nullable */, const void* xq, int64_t M, int32_t S,
+                          int32_t F, const void* omega, const void* phase, const void* w, const void* eps, double dev_scale, void* out,
+                          double* grad_out);
+
 /* ---- S hyper-parameter samples of ONE model family as one batch: what acquisition functions do on an HGP
  *      (hyperbo/bo_utils/acfun.py:72-82 loops model.predict over model.params.samples, gp.py:666-682; the jax counterpart is a
  *      vmap over the draws).  models[s]: sample s (same dtype, covariance, mean and MLP architecture for all); x [n,D], y [n,m]
@@ -313,6 +332,28 @@ int hbo_acq_maximize(hbo_ctx* ctx, const hbo_model* models, int32_t S, hbo_cache
                      const double* lo, const double* hi, int acq_id, const double* params, const double* add_noise, double scale,
                      const hbo_acq_opt_opts* opts, double* state, int32_t evals, double* x_out, double* val_out, int32_t* status,
                      hbo_acq_opt_eval* log);
+
+/* ---- the maximisation of S posterior sample paths over a box, R starts each, in ONE call: continuous Thompson sampling -- q
+ *      suggestions from q paths (no counterpart in the reference).  The optimiser is that of hbo_acq_maximize, run on
+ *      f(x) = -f_s(x) for each of the S * R (path, start) pairs: one upload and one solve for u (hbo_sample_paths_grad), then `evals`
+ *      rounds of two stream-ordered launches -- the kernel of hbo_sample_paths_grad over the S * R pending points, each under its own
+ *      path, then hbo_acq_maximize's control kernel with one workgroup per pair -- and one synchronisation and one copy back.
+ *      model, cache, S, F, omega, phase, w, eps, dev_scale: as hbo_sample_paths_grad.  x0 [S, R, input_dim] (model dtype): the
+ *      starts of path s.  lo, hi, opts, evals, log: as hbo_acq_maximize, with S * R in the place of its R everywhere: state
+ *      [S * R, hbo_acq_opt_state_doubles(input_dim, memory)], x_out [S, R, input_dim], val_out [S, R] (the path's value at x_out),
+ *      status [S, R], log [evals, S * R].  All zero = a fresh run, otherwise the run goes on; a run gives the same bits however it is
+ *      cut into calls; a pair does not depend on what shares the call; bounds are hit exactly; an fp32 model takes fp32 numbers for
+ *      the box; the evaluation of a pending point is, to the bit, hbo_sample_paths_grad's at that point
+ *      (the optimiser sees the value as that call returns it: a number of the model dtype).
+ *      HBO_ERR_ARG (before any device work, nothing written): those of hbo_sample_paths_grad, R < 1, S * R > 4096, evals outside
+ *      1..4096, bad opts, lo > hi or not finite, an x0 outside the box or not finite, a state that is neither all zero nor one an
+ *      earlier call left.  HBO_ERR_UNSUPPORTED (before any device work): those of hbo_sample_paths_grad, and a state beyond the 64 KB
+ *      of LDS of the control kernel.  HBO_NOT_PD: the cache is not positive definite (val_out is NaN and every pair stops with
+ *      NONFINITE_AT_START). */
+int hbo_paths_maximize(hbo_ctx* ctx, const hbo_model* model, hbo_cache* cache /* nullable */, int32_t S, int32_t F, const void* omega,
+                       const void* phase, const void* w, const void* eps, double dev_scale, const void* x0, int32_t R, const double* lo,
+                       const double* hi, const hbo_acq_opt_opts* opts, double* state, int32_t evals, double* x_out, double* val_out,
+                       int32_t* status, hbo_acq_opt_eval* log);
 
 /* ---- the simulated BO loop over a pool of pre-evaluated candidates (hyperbo/bo_utils/bayesopt.py:136-190), every iteration of R
  *      independent runs in ONE call: all launches are queued up front and the results come back behind them: one synchronisation, at the end.
