@@ -110,10 +110,12 @@ def grad_leaf_errors(got, ref):
   return out
 
 
-def assert_grad_close(got, ref, tol, floor_rel=1e-3, label=''):
+def assert_grad_close(got, ref, tol, floor_rel=1e-3, label='', leaf_scales=None):
   """PER-LEAF gradient check: every leaf L must satisfy max|got_L - ref_L| <= tol * max(||ref_L||_inf, floor_rel * max|ref|).
   (A bound relative to the largest entry of the FLATTENED tree lets a wrong leaf that is 1e4 x smaller than the lengthscale
   gradient pass; the floor keeps leaves that are zero by cancellation testable: their error scales with the un-cancelled terms.)
+  leaf_scales: path -> the scale of a leaf's un-cancelled terms, from the reference (tests/mlp_cases.py); the floor of such a leaf is
+  min(floor_rel * max|ref|, that scale) -- a leaf whose terms themselves are smaller than the floor is held to its terms.
   The failure message names the worst leaf; with HBO_GRAD_LOG=<file> every call appends its worst ratio (tolerance audits)."""
   errs = grad_leaf_errors(got, ref)
   gmax = max((n for _, _, n in errs), default=0.0)
@@ -121,7 +123,10 @@ def assert_grad_close(got, ref, tol, floor_rel=1e-3, label=''):
   for path, err, norm in errs:
     if not np.isfinite(err):
       raise AssertionError(f'{label}: leaf {path} is not finite')
-    bound = tol * max(norm, floor_rel * gmax, 1e-300)
+    floor = floor_rel * gmax
+    if leaf_scales is not None and path in leaf_scales:
+      floor = min(floor, leaf_scales[path])
+    bound = tol * max(norm, floor, 1e-300)
     if err / bound > worst[0]:
       worst = (err / bound, path, err, norm)
   import os
