@@ -67,7 +67,7 @@ struct hbo_ctx {
   int opt_lauum_persist = 1;   // one large matrix: K^-1 = W^T W as a resident grid drawing its tiles from a counter (0: plain grid; 1: two workgroups
                                // on all but 16 CUs; n > 1: on all but n CUs)
   int opt_trtri_free = 48;   // CUs the inverse products that co-run with the panel chain leave free (0: one tile per workgroup)
-  int opt_poison = 0;          // tests: every evaluation first fills what it is about to recompute with NaN (gram.hip: poison_kernel)
+  int opt_poison = 0;          // tests: every evaluation first fills what it is about to recompute with NaN (taskvec.hip: poison_kernel)
   // ---- posterior options ----
   int opt_post_chunk = 8192;   // posterior / acquisition: candidates per pass (the cross-Gram workspace is npad x this, whatever M)
   int opt_post_f16x2 = 1;      // fp32 posterior product of the stationary covariances: two-way fp16 split, three MFMAs per product (post3.hip: post2h_kernel) instead of bf16x3's six

@@ -4,7 +4,7 @@
 //
 // Reference restated: jax.value_and_grad of hyperbo/gp_utils/objectives.py:109-210 (gp.py:134), with the VJP of
 // basics/linalg.py:129-171 and the zero-distance rule of linalg.py:173-197.
-#include "kernfun.h"
+#include "pair_tile.h"
 
 namespace {
 // ---------------------------------------------------------------------------------------
@@ -49,6 +49,7 @@ __global__ __launch_bounds__(256) void grad_contract_kernel(const TaskDesc* task
   for (int a = 0; a < GRA; ++a)
 #pragma unroll
     for (int b = 0; b < 8; ++b) acc[a][b] = (T)0;
+  // (its own copy of pt_accumulate: through the helper <float, true, SE> takes 130 VGPRs for 128, three waves per SIMD for four)
   for (int d0 = 0; d0 < fdim; d0 += DC) {
     __syncthreads();
     stage_x<T, GRA>(sA, F, n, fdim, r0, d0, md->inv_ls, !is_dot, tid);
@@ -60,7 +61,7 @@ __global__ __launch_bounds__(256) void grad_contract_kernel(const TaskDesc* task
 #pragma unroll
       for (int a = 0; a < GRA; ++a) av[a] = sA[dd * SXS + ty + 16 * a];
 #pragma unroll
-      for (int q = 0; q < 8; ++q) bv[q] = sB[dd * SXS + 16 * VEC * (q / VEC) + VEC * tx + (q % VEC)];
+      for (int q = 0; q < 8; ++q) bv[q] = sB[dd * SXS + pt_col<T>(tx, q)];
 #pragma unroll
       for (int a = 0; a < GRA; ++a)
 #pragma unroll
@@ -74,10 +75,9 @@ __global__ __launch_bounds__(256) void grad_contract_kernel(const TaskDesc* task
   //  180-232 VGPRs and from three to two waves per SIMD, and it is bound by latency, not by instruction count -- 0.255 ms at cfg 2
   //  against 0.28-0.29 with one or both; profiles/r04_elementwise.md)
   const ExpLit ec;
-  const T sv = (T)md->sv;
-  const T inv_sigma2 = (T)(1.0 / (md->dot_sigma * md->dot_sigma));
-  const T bias2 = (T)(md->dot_bias * md->dot_bias);
-  const T lh = (T)t.coef_lh, cc = (T)t.coef_c, noise = (T)md->noise;
+  const PairCoef<T> pc = pair_coef<T>(md);
+  const T sv = pc.sv, inv_sigma2 = pc.inv_sigma2, bias2 = pc.bias2, noise = pc.noise;
+  const T lh = (T)t.coef_lh, cc = (T)t.coef_c;
   const T wt = (ti == tj) ? (T)1 : (T)2;   // off-diagonal tiles stand for their mirror image too
   double a_gk = 0, a_tr = 0, a_g = 0, a_fro = 0;
   // gw[a][q] = weight * G_ij * dk/du  (re-uses acc storage)
@@ -89,7 +89,7 @@ __global__ __launch_bounds__(256) void grad_contract_kernel(const TaskDesc* task
   if (nvec > 0) {
 #pragma unroll
     for (int qb = 0; qb < 8 / VEC; ++qb) {
-      const vec_t v = gld(reinterpret_cast<const vec_t*>(sv_ + c0 + 16 * VEC * qb + VEC * tx));
+      const vec_t v = gld(reinterpret_cast<const vec_t*>(sv_ + c0 + pt_col<T>(tx, qb * VEC)));
 #pragma unroll
       for (int e = 0; e < VEC; ++e) sj[qb * VEC + e] = v[e];
     }
@@ -106,7 +106,7 @@ __global__ __launch_bounds__(256) void grad_contract_kernel(const TaskDesc* task
       const T sib = gld(vb + row);
 #pragma unroll
       for (int qb = 0; qb < 8 / VEC; ++qb) {
-        const vec_t v = gld(reinterpret_cast<const vec_t*>(vb + c0 + 16 * VEC * qb + VEC * tx));
+        const vec_t v = gld(reinterpret_cast<const vec_t*>(vb + c0 + pt_col<T>(tx, qb * VEC)));
 #pragma unroll
         for (int e = 0; e < VEC; ++e) outer[qb * VEC + e] += sib * v[e];
       }
@@ -114,14 +114,14 @@ __global__ __launch_bounds__(256) void grad_contract_kernel(const TaskDesc* task
     if (!euc) {
 #pragma unroll
       for (int qb = 0; qb < 8 / VEC; ++qb) {
-        const vec_t v = gld(reinterpret_cast<const vec_t*>(S + row * t.ld + c0 + 16 * VEC * qb + VEC * tx));
+        const vec_t v = gld(reinterpret_cast<const vec_t*>(S + row * t.ld + c0 + pt_col<T>(tx, qb * VEC)));
 #pragma unroll
         for (int e = 0; e < VEC; ++e) kinv_row[qb * VEC + e] = v[e];
       }
     }
 #pragma unroll
     for (int q = 0; q < 8; ++q) {
-      const int64_t col = c0 + 16 * VEC * (q / VEC) + VEC * tx + (q % VEC);
+      const int64_t col = c0 + pt_col<T>(tx, q);
       T gw = (T)0;
       if (row < n && col < n) {
         const T u = acc[a][q];
@@ -153,17 +153,10 @@ __global__ __launch_bounds__(256) void grad_contract_kernel(const TaskDesc* task
   if (is_dot) return;
   // second pass over the features: sum gw * ds_d^2
   for (int d0 = 0; d0 < fdim; d0 += DC) {
-    __syncthreads();
-    stage_x<T, GRA>(sA, F, n, fdim, r0, d0, md->inv_ls, true, tid);
-    stage_x<T>(sB, F, n, fdim, c0, d0, md->inv_ls, true, tid);
-    __syncthreads();
-    const int dlim = (fdim - d0) < DC ? (fdim - d0) : DC;
+    const int dlim = pt_stage<T, GRA, false>(sA, sB, F, n, F, n, fdim, r0, c0, d0, md->inv_ls, tid);
     for (int dd = 0; dd < dlim; ++dd) {
       T av[GRA], bv[8];
-#pragma unroll
-      for (int a = 0; a < GRA; ++a) av[a] = sA[dd * SXS + ty + 16 * a];
-#pragma unroll
-      for (int q = 0; q < 8; ++q) bv[q] = sB[dd * SXS + 16 * VEC * (q / VEC) + VEC * tx + (q % VEC)];
+      pt_read<T, GRA>(sA, sB, dd, tx, ty, av, bv);
       T s = (T)0;
 #pragma unroll
       for (int a = 0; a < GRA; ++a)
@@ -192,16 +185,12 @@ __global__ __launch_bounds__(256) void grad_feat_kernel(const TaskDesc* tasks, c
   const TaskDesc& t = tasks[blockIdx.z];
   const int ti = blockIdx.x, tj = blockIdx.y;
   if (ti >= t.nblk || tj > ti) return;
-  constexpr int VEC = 16 / sizeof(T);
-  constexpr int kid = KID;
-  constexpr bool is_dot = (kid == HBO_KERNEL_DOT);
+  constexpr bool is_dot = (KID == HBO_KERNEL_DOT);
   const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
   const int64_t r0 = (int64_t)ti * HBO_TILE, c0 = (int64_t)tj * HBO_TILE;
   const T* F = static_cast<const T*>(t.F);
-  const T* S = static_cast<const T*>(t.S);
   int64_t vstride; int nvec;
   const T* sv_ = outer_vecs<T>(t, obj, vstride, nvec);
-  const bool euc = (obj == OBJ_EUC);
   double* dF = static_cast<double*>(t.dF);
   const int64_t n = t.n;
 
@@ -210,67 +199,17 @@ __global__ __launch_bounds__(256) void grad_feat_kernel(const TaskDesc* tasks, c
   for (int a = 0; a < 8; ++a)
 #pragma unroll
     for (int b = 0; b < 8; ++b) acc[a][b] = (T)0;
-  for (int d0 = 0; d0 < fdim; d0 += DC) {
-    __syncthreads();
-    stage_x<T>(sA, F, n, fdim, r0, d0, md->inv_ls, !is_dot, tid);
-    stage_x<T>(sB, F, n, fdim, c0, d0, md->inv_ls, !is_dot, tid);
-    __syncthreads();
-    const int dlim = (fdim - d0) < DC ? (fdim - d0) : DC;
-    for (int dd = 0; dd < dlim; ++dd) {
-      T av[8], bv[8];
-#pragma unroll
-      for (int a = 0; a < 8; ++a) av[a] = sA[dd * SXS + ty + 16 * a];
-#pragma unroll
-      for (int q = 0; q < 8; ++q) bv[q] = sB[dd * SXS + 16 * VEC * (q / VEC) + VEC * tx + (q % VEC)];
-#pragma unroll
-      for (int a = 0; a < 8; ++a)
-#pragma unroll
-        for (int q = 0; q < 8; ++q) {
-          if (is_dot) acc[a][q] += av[a] * bv[q];
-          else { const T df = av[a] - bv[q]; acc[a][q] += df * df; }
-        }
-    }
-  }
-  const ExpLit ec;
-  const T sv = (T)md->sv;
-  const T inv_sigma2 = (T)(1.0 / (md->dot_sigma * md->dot_sigma));
-  const T bias2 = (T)(md->dot_bias * md->dot_bias);
-  const T lh = (T)t.coef_lh, cc = (T)t.coef_c, noise = (T)md->noise;
-  // g[a][q] = G_ij * dk/du (SE/Matern) or G_ij (dot);  G as in grad_contract_kernel
-#pragma unroll
-  for (int a = 0; a < 8; ++a) {
-    const int64_t row = r0 + ty + 16 * a;
-#pragma unroll
-    for (int q = 0; q < 8; ++q) {
-      const int64_t col = c0 + 16 * VEC * (q / VEC) + VEC * tx + (q % VEC);
-      T g = (T)0;
-      if (row < n && col < n) {
-        const T u = acc[a][q];
-        const T k = kfun(kid, u, sv, inv_sigma2, bias2, ec);
-        T outer = (T)0;
-        for (int b = 0; b < nvec; ++b) outer += sv_[(int64_t)b * vstride + row] * sv_[(int64_t)b * vstride + col];
-        const T G = euc ? (k + (row == col ? noise : (T)0) - outer) : (lh * S[row * t.ld + col] - cc * outer);
-        if (is_dot) g = G;
-        else g = G * dk_du(kid, u, k, sv, ec);
-      }
-      acc[a][q] = g;
-    }
-  }
+  pt_accumulate<T, 8, is_dot>(acc, sA, sB, F, n, F, n, fdim, r0, c0, md->inv_ls, tid);
+  // acc -> g[a][q] = G_ij * dk/du (SE/Matern) or G_ij (dot);  G as in grad_contract_kernel
+  pt_g_dkdu<T, KID>(acc, t, md, obj == OBJ_EUC, sv_, vstride, nvec, r0, c0, tx, ty);
   const bool offdiag = (ti != tj);
   for (int d0 = 0; d0 < fdim; d0 += DC) {
-    __syncthreads();
-    stage_x<T>(sA, F, n, fdim, r0, d0, md->inv_ls, !is_dot, tid);
-    stage_x<T>(sB, F, n, fdim, c0, d0, md->inv_ls, !is_dot, tid);
-    __syncthreads();
-    const int dlim = (fdim - d0) < DC ? (fdim - d0) : DC;
+    const int dlim = pt_stage<T, 8, is_dot>(sA, sB, F, n, F, n, fdim, r0, c0, d0, md->inv_ls, tid);
     for (int dd = 0; dd < dlim; ++dd) {
       const int d = d0 + dd;
       const double cd = is_dot ? 2.0 / (md->dot_sigma * md->dot_sigma) : 4.0 * md->inv_ls[d];
       T av[8], bv[8];
-#pragma unroll
-      for (int a = 0; a < 8; ++a) av[a] = sA[dd * SXS + ty + 16 * a];
-#pragma unroll
-      for (int q = 0; q < 8; ++q) bv[q] = sB[dd * SXS + 16 * VEC * (q / VEC) + VEC * tx + (q % VEC)];
+      pt_read<T, 8>(sA, sB, dd, tx, ty, av, bv);
       double rs[8], cs[8];
 #pragma unroll
       for (int q = 0; q < 8; ++q) cs[q] = 0;
@@ -298,7 +237,7 @@ __global__ __launch_bounds__(256) void grad_feat_kernel(const TaskDesc* tasks, c
         for (int q = 0; q < 8; ++q) {
           double s = cs[q];
           s += __shfl_xor(s, 16); s += __shfl_xor(s, 32);
-          const int64_t col = c0 + 16 * VEC * (q / VEC) + VEC * tx + (q % VEC);
+          const int64_t col = c0 + pt_col<T>(tx, q);
           if ((tid & 63) < 16 && col < n) atomicAdd(&dF[col * fdim + d], cd * s);
         }
       }
@@ -527,33 +466,23 @@ __global__ __launch_bounds__(256) void grad_finalize_kernel(const TaskDesc* task
 
 }  // namespace
 int grad_nacc(int kernel_id, int fdim) { return (kernel_id == HBO_KERNEL_DOT ? 3 : 2 + fdim) + 1; }
-namespace {
-template <typename T, bool MULTI>
-void launch_grad_contract_t(dim3 grid, hipStream_t st, int kernel_id, const TaskDesc* tasks, const ModelDev* md, int fdim,
-                            int nacc, int obj, double* partials, int64_t stride_task) {
-  switch (kernel_id) {
-    case HBO_KERNEL_SE: hipLaunchKernelGGL((grad_contract_kernel<T, MULTI, HBO_KERNEL_SE>), grid, dim3(256), 0, st, tasks, md, fdim, nacc, obj, partials, stride_task); break;
-    case HBO_KERNEL_MATERN32: hipLaunchKernelGGL((grad_contract_kernel<T, MULTI, HBO_KERNEL_MATERN32>), grid, dim3(256), 0, st, tasks, md, fdim, nacc, obj, partials, stride_task); break;
-    case HBO_KERNEL_MATERN52: hipLaunchKernelGGL((grad_contract_kernel<T, MULTI, HBO_KERNEL_MATERN52>), grid, dim3(256), 0, st, tasks, md, fdim, nacc, obj, partials, stride_task); break;
-    default: hipLaunchKernelGGL((grad_contract_kernel<T, MULTI, HBO_KERNEL_DOT>), grid, dim3(256), 0, st, tasks, md, fdim, nacc, obj, partials, stride_task); break;
-  }
-}
-}  // namespace
 void launch_grad_contract(int dtype, const TaskDesc* tasks, int ntasks, int max_nblk, const ModelDev* md,
                           int kernel_id, int fdim, int obj, double* partials, int64_t stride_task, hipStream_t st) {
   dim3 grid(2 * max_nblk, max_nblk, ntasks);   // 64-row half tiles: two partial slots per 128x128 tile
   const int nacc = grad_nacc(kernel_id, fdim);
-  if (obj == OBJ_NLL) {
-    if (dtype == HBO_F64) launch_grad_contract_t<double, false>(grid, st, kernel_id, tasks, md, fdim, nacc, obj, partials, stride_task);
-    else launch_grad_contract_t<float, false>(grid, st, kernel_id, tasks, md, fdim, nacc, obj, partials, stride_task);
-  } else {
-    if (dtype == HBO_F64) launch_grad_contract_t<double, true>(grid, st, kernel_id, tasks, md, fdim, nacc, obj, partials, stride_task);
-    else launch_grad_contract_t<float, true>(grid, st, kernel_id, tasks, md, fdim, nacc, obj, partials, stride_task);
-  }
+  dispatch_dtype(dtype, [&](auto tag) {
+    dispatch_kid(kernel_id, [&](auto kid) {
+      typedef typename decltype(tag)::type T;
+      constexpr int K = decltype(kid)::value;
+      if (obj == OBJ_NLL) hipLaunchKernelGGL((grad_contract_kernel<T, false, K>), grid, dim3(256), 0, st, tasks, md, fdim, nacc, obj, partials, stride_task);
+      else hipLaunchKernelGGL((grad_contract_kernel<T, true, K>), grid, dim3(256), 0, st, tasks, md, fdim, nacc, obj, partials, stride_task);
+    });
+  });
 }
 void launch_dmu(int dtype, const TaskDesc* tasks, int ntasks, int obj, hipStream_t st) {
-  if (dtype == HBO_F64) hipLaunchKernelGGL((dmu_kernel<double>), dim3(ntasks), dim3(256), 0, st, tasks, obj);
-  else hipLaunchKernelGGL((dmu_kernel<float>), dim3(ntasks), dim3(256), 0, st, tasks, obj);
+  dispatch_dtype(dtype, [&](auto tag) {
+    hipLaunchKernelGGL((dmu_kernel<typename decltype(tag)::type>), dim3(ntasks), dim3(256), 0, st, tasks, obj);
+  });
 }
 void launch_grad_finalize(int dtype, const TaskDesc* tasks, int ntasks, const ModelDev* md, int kernel_id,
                           int fdim, int obj, const double* partials, int64_t stride_task, double* out,
@@ -564,35 +493,29 @@ void launch_grad_finalize(int dtype, const TaskDesc* tasks, int ntasks, const Mo
     hipLaunchKernelGGL(grad_prereduce_kernel, dim3(GRAD_PRE, ntasks), dim3(256), 0, st, tasks, nacc, partials, stride_task, pre);
     partials = pre; stride_task = (int64_t)GRAD_PRE * nacc; pre_rows = GRAD_PRE;
   }
-  if (dtype == HBO_F64) hipLaunchKernelGGL((grad_finalize_kernel<double>), dim3(ntasks), dim3(256), 0, st, tasks, md, fdim, nacc, obj, partials, stride_task, out, out_stride, value_out, pre_rows);
-  else hipLaunchKernelGGL((grad_finalize_kernel<float>), dim3(ntasks), dim3(256), 0, st, tasks, md, fdim, nacc, obj, partials, stride_task, out, out_stride, value_out, pre_rows);
+  dispatch_dtype(dtype, [&](auto tag) {
+    hipLaunchKernelGGL((grad_finalize_kernel<typename decltype(tag)::type>), dim3(ntasks), dim3(256), 0, st, tasks, md, fdim, nacc, obj, partials, stride_task, out, out_stride, value_out, pre_rows);
+  });
 }
 void launch_scale_dF(const TaskDesc* tasks, int ntasks, int64_t max_n, int fdim, hipStream_t st) {
   dim3 grid((unsigned)((max_n * fdim + 255) / 256), 1, ntasks);
   hipLaunchKernelGGL(scale_dF_kernel, grid, dim3(256), 0, st, tasks, fdim);
 }
-namespace {
-template <typename T>
-void launch_grad_feat_t(dim3 grid, hipStream_t st, int kernel_id, const TaskDesc* tasks, const ModelDev* md, int fdim, int obj) {
-  switch (kernel_id) {
-    case HBO_KERNEL_SE: hipLaunchKernelGGL((grad_feat_kernel<T, HBO_KERNEL_SE>), grid, dim3(256), 0, st, tasks, md, fdim, obj); break;
-    case HBO_KERNEL_MATERN32: hipLaunchKernelGGL((grad_feat_kernel<T, HBO_KERNEL_MATERN32>), grid, dim3(256), 0, st, tasks, md, fdim, obj); break;
-    case HBO_KERNEL_MATERN52: hipLaunchKernelGGL((grad_feat_kernel<T, HBO_KERNEL_MATERN52>), grid, dim3(256), 0, st, tasks, md, fdim, obj); break;
-    default: hipLaunchKernelGGL((grad_feat_kernel<T, HBO_KERNEL_DOT>), grid, dim3(256), 0, st, tasks, md, fdim, obj); break;
-  }
-}
-}  // namespace
 void launch_grad_feat(int dtype, const TaskDesc* tasks, int ntasks, int max_nblk, const ModelDev* md, int kernel_id,
                       int fdim, int obj, hipStream_t st) {
   dim3 grid(max_nblk, max_nblk, ntasks);
-  if (dtype == HBO_F64) launch_grad_feat_t<double>(grid, st, kernel_id, tasks, md, fdim, obj);
-  else launch_grad_feat_t<float>(grid, st, kernel_id, tasks, md, fdim, obj);
+  dispatch_dtype(dtype, [&](auto tag) {
+    dispatch_kid(kernel_id, [&](auto kid) {
+      hipLaunchKernelGGL((grad_feat_kernel<typename decltype(tag)::type, decltype(kid)::value>), grid, dim3(256), 0, st, tasks, md, fdim, obj);
+    });
+  });
 }
 void launch_grad_feat_mean(int dtype, const TaskDesc* tasks, int ntasks, int64_t max_n, const ModelDev* md,
                            int fdim, hipStream_t st) {
   dim3 grid((unsigned)((max_n * fdim + 255) / 256), 1, ntasks);
-  if (dtype == HBO_F64) hipLaunchKernelGGL((grad_feat_mean_kernel<double>), grid, dim3(256), 0, st, tasks, md, fdim);
-  else hipLaunchKernelGGL((grad_feat_mean_kernel<float>), grid, dim3(256), 0, st, tasks, md, fdim);
+  dispatch_dtype(dtype, [&](auto tag) {
+    hipLaunchKernelGGL((grad_feat_mean_kernel<typename decltype(tag)::type>), grid, dim3(256), 0, st, tasks, md, fdim);
+  });
 }
 // one layer of the MLP backward pass for one task; dout (n x fout, double) is turned into dz in place
 void launch_dense_bwd(int dtype, const void* in, const void* out, const void* w, double* dout, double* din,
@@ -602,15 +525,12 @@ void launch_dense_bwd(int dtype, const void* in, const void* out, const void* w,
   const int rpb = 256;
   dim3 gw(fin + 1, (unsigned)((n + rpb - 1) / rpb));
   const int thr = fout < 64 ? 64 : (fout > 256 ? 256 : ((fout + 63) / 64) * 64);
-  if (dtype == HBO_F64) {
-    hipLaunchKernelGGL((dense_bwd_dz_kernel<double>), dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, st, dout, (const double*)out, cnt);
-    hipLaunchKernelGGL((dense_bwd_w_kernel<double>), gw, dim3(thr), 0, st, (const double*)in, dout, n, fin, fout, dW, db, rpb);
-    if (din) hipLaunchKernelGGL((dense_bwd_in_kernel<double>), dim3((unsigned)((n * fin + 255) / 256)), dim3(256), 0, st, dout, (const double*)w, n, fin, fout, din);
-  } else {
-    hipLaunchKernelGGL((dense_bwd_dz_kernel<float>), dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, st, dout, (const float*)out, cnt);
-    hipLaunchKernelGGL((dense_bwd_w_kernel<float>), gw, dim3(thr), 0, st, (const float*)in, dout, n, fin, fout, dW, db, rpb);
-    if (din) hipLaunchKernelGGL((dense_bwd_in_kernel<float>), dim3((unsigned)((n * fin + 255) / 256)), dim3(256), 0, st, dout, (const float*)w, n, fin, fout, din);
-  }
+  dispatch_dtype(dtype, [&](auto tag) {
+    typedef typename decltype(tag)::type T;
+    hipLaunchKernelGGL((dense_bwd_dz_kernel<T>), dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, st, dout, (const T*)out, cnt);
+    hipLaunchKernelGGL((dense_bwd_w_kernel<T>), gw, dim3(thr), 0, st, (const T*)in, dout, n, fin, fout, dW, db, rpb);
+    if (din) hipLaunchKernelGGL((dense_bwd_in_kernel<T>), dim3((unsigned)((n * fin + 255) / 256)), dim3(256), 0, st, dout, (const T*)w, n, fin, fout, din);
+  });
 }
 // [sum of the tasks' values, task count, gradient sum in the caller's layout] of one rank's shard, on the device (what the host loop of
 // hbo_objective does after the copy back: same order of summation).  One workgroup: the vector has a few dozen entries (plus the

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 #include "../../include/hbo.h"
 
 // Pointers fetched from descriptor structs are generic ("flat") to the compiler; flat loads count on
@@ -202,6 +203,22 @@ __device__ __forceinline__ void tl_end(unsigned long long* tl) {
   if (tl && threadIdx.x == 0) atomicMax(tl + 1, (unsigned long long)wall_clock64());
 #endif
 }
+// Host side: the run-time covariance id / dtype of a launch as a compile-time value of a generic lambda's argument, f(kid) with
+// decltype(kid)::value the id (anything but the three stationary ones: dot_product), f(tag) with decltype(tag)::type double or float
+template <typename F>
+inline void dispatch_kid(int kernel_id, F&& f) {
+  switch (kernel_id) {
+    case HBO_KERNEL_SE: f(std::integral_constant<int, HBO_KERNEL_SE>()); break;
+    case HBO_KERNEL_MATERN32: f(std::integral_constant<int, HBO_KERNEL_MATERN32>()); break;
+    case HBO_KERNEL_MATERN52: f(std::integral_constant<int, HBO_KERNEL_MATERN52>()); break;
+    default: f(std::integral_constant<int, HBO_KERNEL_DOT>()); break;
+  }
+}
+template <typename T> struct DtypeTag { typedef T type; };
+template <typename F>
+inline void dispatch_dtype(int dtype, F&& f) {
+  if (dtype == HBO_F64) f(DtypeTag<double>()); else f(DtypeTag<float>());
+}
 #endif
 
 // hipFuncSetAttribute is per device: a launcher sets its kernels' dynamic-LDS limit the first time it runs on EACH device of the
@@ -243,6 +260,7 @@ struct GramArgs {
 void launch_gram(int dtype, const GramArgs& a, const ModelDev* model, dim3 grid, hipStream_t st);
 void launch_kdiag(int dtype, const void* f, int64_t n, int fdim, const ModelDev* model, void* out,
                   hipStream_t st);
+// ---- around the Gram of a task (taskvec.hip) ------------------------------------------------------
 void launch_dense_tanh(int dtype, const void* in, const void* w, const void* b, void* out, int64_t n,
                        int fin, int fout, hipStream_t st);
 void launch_mean(int dtype, const void* fm, int64_t n, int fmean, const ModelDev* model, void* mu,
@@ -255,6 +273,15 @@ void launch_nll_reduce(int dtype, const TaskDesc* tasks, int ntasks, const int* 
 // xover / oover (single task only): explicit input vector [npad] / output vector [npad]
 void launch_wt_z(int dtype, const TaskDesc* tasks, int ntasks, int max_nblk, int aug_row, int out_col,
                  int out_ld, hipStream_t st, const void* xover = nullptr, void* oover = nullptr);
+void launch_extract_lower(int dtype, const void* A, int64_t ld, int64_t n, void* out, hipStream_t st);
+void launch_symmetrize_from_lower(int dtype, const void* S, int64_t ld, int64_t n, void* out, hipStream_t st);
+void launch_fill_spd(int dtype, const void* a_dense, int64_t n, void* A, int64_t ld, int npad, hipStream_t st);
+void launch_set_aug(int dtype, const void* b, int64_t n, int m, void* A, int64_t ld, int npad, hipStream_t st);
+// divergence objectives beyond 127 aligned columns: dst[b][j] = j < n ? src[b][j] : 0 for `count` rows of n -> npad elements, and
+// value[0] += coef * sum_b sum_j z[b][j]^2
+void launch_expand_rows(int dtype, const void* src, int64_t n, int npad, void* dst, int count, hipStream_t st);
+void launch_add_sumsq(int dtype, const void* z, int npad, int count, double coef, double* value, hipStream_t st);
+// ---- gradient kernels (grad.hip) ------------------------------------------------------------------
 int grad_nacc(int kernel_id, int fdim);   // accumulators per tile (incl. the Frobenius slot)
 void launch_grad_contract(int dtype, const TaskDesc* tasks, int ntasks, int max_nblk, const ModelDev* md,
                           int kernel_id, int fdim, int obj, double* partials, int64_t stride_task, hipStream_t st);
@@ -445,13 +472,6 @@ struct BoRunDev {
 };
 void launch_bo_row(int dtype, const BoRunDev* runs, int R, int64_t max_ncol, int step, hipStream_t st);
 void launch_bo_select(int dtype, const BoRunDev* runs, int R, int step, hipStream_t st);
-void launch_extract_lower(int dtype, const void* A, int64_t ld, int64_t n, void* out, hipStream_t st);
-void launch_symmetrize_from_lower(int dtype, const void* S, int64_t ld, int64_t n, void* out, hipStream_t st);
-void launch_fill_spd(int dtype, const void* a_dense, int64_t n, void* A, int64_t ld, int npad, hipStream_t st);
-void launch_set_aug(int dtype, const void* b, int64_t n, int m, void* A, int64_t ld, int npad, hipStream_t st);
-// divergence objectives beyond 127 aligned columns: dst[b][j] = j < n ? src[b][j] : 0 for `count` rows of n -> npad elements, and
-// value[0] += coef * sum_b sum_j z[b][j]^2
-void launch_expand_rows(int dtype, const void* src, int64_t n, int npad, void* dst, int count, hipStream_t st);
-void launch_add_sumsq(int dtype, const void* z, int npad, int count, double coef, double* value, hipStream_t st);
+// y = W x (trans=0, rows) or W^T x (trans=1) for lower-triangular W (npad x ld), x: [m][npad]  (post.hip)
 void launch_tri_matvec(int dtype, const void* W, int64_t ld, int npad, const void* x, int64_t xld, int m,
                        int trans, void* out, int64_t old, hipStream_t st);

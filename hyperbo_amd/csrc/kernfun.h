@@ -1,4 +1,4 @@
-// Device helpers shared by the elementwise / reduction kernels of the GP hot path (gram.hip, grad.hip, post.hip): the pair
+// Device helpers shared by the elementwise / reduction kernels of the GP hot path (gram.hip, taskvec.hip, grad.hip, post.hip): the pair
 // kernels of hyperbo/gp_utils/kernel.py:63-145 and their derivatives, LDS staging of feature blocks, the means of
 // hyperbo/gp_utils/mean.py:30-79, block reductions, the normal pdf / cdf of the acquisition functions (acfun.py:96-142).
 #pragma once
@@ -124,8 +124,6 @@ __device__ __forceinline__ void stage_x(T* s, const T* __restrict__ x, int64_t n
   }
 }
 
-// tile = 64 rows x 128 columns per 256-thread workgroup, 4x8 register micro-tile per thread
-// (an 8x8 micro-tile needs 256 VGPRs in fp64 -> 1 wave/SIMD and exposed exp/store latency).
 template <typename T>
 __device__ __forceinline__ T mean_at(const ModelDev* md, const T* fm, int fmean, int64_t i) {
   switch (md->mean_id) {

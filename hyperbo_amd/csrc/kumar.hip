@@ -6,7 +6,7 @@
 //             but without materialising d f / d w: every tile writes 2 D partial sums, one ordered finalisation sums tiles and tasks
 //             (no float atomics: two identical calls give bit-identical gradients, as the rest of the objective)
 //   query     hbo_acq_grad: d acq / d x = d acq / d w * dw/dx
-#include "kernfun.h"
+#include "pair_tile.h"
 
 namespace {
 constexpr int KC = 8;   // features per LDS chunk of the contraction (six [KC][128] blocks: fp64 fits the 64 KB of static LDS)
@@ -69,7 +69,7 @@ __global__ void kumar_forward_kernel(const TaskDesc* __restrict__ tasks, const T
   }
 }
 
-// one lower tile (ti, tj) of one task: the G_ij * dk/du of grad_feat_kernel (identical arithmetic), then per feature d
+// one lower tile (ti, tj) of one task: the G_ij * dk/du of grad_feat_kernel (the same pt_g_dkdu of pair_tile.h), then per feature d
 //   SE / Matern: c_d sum_ij g_ij (fs_i - fs_j)_d (h_i - [off-diagonal] h_j)_d,   c_d = 4 / ls_d
 //   dot:         c_d sum_ij G_ij (f_j h_i + [off-diagonal] f_i h_j)_d,          c_d = 2 / sigma^2
 // -- what grad_feat_kernel adds to dF for this tile, multiplied by h = dw/da (dw/db) and summed over its rows.  Wave shuffles, then
@@ -84,16 +84,12 @@ __global__ __launch_bounds__(256) void kumar_contract_kernel(const TaskDesc* tas
   const TaskDesc& t = tasks[blockIdx.z];
   const int ti = blockIdx.x, tj = blockIdx.y;
   if (ti >= t.nblk || tj > ti) return;
-  constexpr int VEC = 16 / sizeof(T);
-  constexpr int kid = KID;
-  constexpr bool is_dot = (kid == HBO_KERNEL_DOT);
+  constexpr bool is_dot = (KID == HBO_KERNEL_DOT);
   const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
   const int64_t r0 = (int64_t)ti * HBO_TILE, c0 = (int64_t)tj * HBO_TILE;
   const T* F = static_cast<const T*>(t.F);
-  const T* S = static_cast<const T*>(t.S);
   int64_t vstride; int nvec;
   const T* sv_ = outer_vecs<T>(t, obj, vstride, nvec);
-  const bool euc = (obj == OBJ_EUC);
   const int64_t n = t.n;
   T* sA = reinterpret_cast<T*>(lds);
   T* sB = sA + DC * SXS;
@@ -103,53 +99,8 @@ __global__ __launch_bounds__(256) void kumar_contract_kernel(const TaskDesc* tas
   for (int a = 0; a < 8; ++a)
 #pragma unroll
     for (int b = 0; b < 8; ++b) acc[a][b] = (T)0;
-  for (int d0 = 0; d0 < fdim; d0 += DC) {
-    __syncthreads();
-    stage_x<T>(sA, F, n, fdim, r0, d0, md->inv_ls, !is_dot, tid);
-    stage_x<T>(sB, F, n, fdim, c0, d0, md->inv_ls, !is_dot, tid);
-    __syncthreads();
-    const int dlim = (fdim - d0) < DC ? (fdim - d0) : DC;
-    for (int dd = 0; dd < dlim; ++dd) {
-      T av[8], bv[8];
-#pragma unroll
-      for (int a = 0; a < 8; ++a) av[a] = sA[dd * SXS + ty + 16 * a];
-#pragma unroll
-      for (int q = 0; q < 8; ++q) bv[q] = sB[dd * SXS + 16 * VEC * (q / VEC) + VEC * tx + (q % VEC)];
-#pragma unroll
-      for (int a = 0; a < 8; ++a)
-#pragma unroll
-        for (int q = 0; q < 8; ++q) {
-          if (is_dot) acc[a][q] += av[a] * bv[q];
-          else { const T df = av[a] - bv[q]; acc[a][q] += df * df; }
-        }
-    }
-  }
-  {
-    const ExpLit ec;
-    const T sv = (T)md->sv;
-    const T inv_sigma2 = (T)(1.0 / (md->dot_sigma * md->dot_sigma));
-    const T bias2 = (T)(md->dot_bias * md->dot_bias);
-    const T lh = (T)t.coef_lh, cc = (T)t.coef_c, noise = (T)md->noise;
-#pragma unroll
-    for (int a = 0; a < 8; ++a) {
-      const int64_t row = r0 + ty + 16 * a;
-#pragma unroll
-      for (int q = 0; q < 8; ++q) {
-        const int64_t col = c0 + 16 * VEC * (q / VEC) + VEC * tx + (q % VEC);
-        T g = (T)0;
-        if (row < n && col < n) {
-          const T u = acc[a][q];
-          const T k = kfun(kid, u, sv, inv_sigma2, bias2, ec);
-          T outer = (T)0;
-          for (int b = 0; b < nvec; ++b) outer += sv_[(int64_t)b * vstride + row] * sv_[(int64_t)b * vstride + col];
-          const T G = euc ? (k + (row == col ? noise : (T)0) - outer) : (lh * S[row * t.ld + col] - cc * outer);
-          if (is_dot) g = G;
-          else g = G * dk_du(kid, u, k, sv, ec);
-        }
-        acc[a][q] = g;
-      }
-    }
-  }
+  pt_accumulate<T, 8, is_dot>(acc, sA, sB, F, n, F, n, fdim, r0, c0, md->inv_ls, tid);
+  pt_g_dkdu<T, KID>(acc, t, md, obj == OBJ_EUC, sv_, vstride, nvec, r0, c0, tx, ty);
   const bool offdiag = (ti != tj);
   // phase 2 staging: scaled features and dw/da, dw/db of the tile's rows (A) and columns (B), KC features at a time
   T* fA = reinterpret_cast<T*>(lds);
@@ -184,7 +135,7 @@ __global__ __launch_bounds__(256) void kumar_contract_kernel(const TaskDesc* tas
         const double haa = hA[dd * SXS + ra], hab = hA[(KC + dd) * SXS + ra];
 #pragma unroll
         for (int q = 0; q < 8; ++q) {
-          const int cb = 16 * VEC * (q / VEC) + VEC * tx + (q % VEC);
+          const int cb = pt_col<T>(tx, q);
           const T bv = fB[dd * SXS + cb];
           const double hba = offdiag ? hB[dd * SXS + cb] : 0.0, hbb = offdiag ? hB[(KC + dd) * SXS + cb] : 0.0;
           if (is_dot) {
@@ -252,35 +203,29 @@ void launch_kumar_forward(int dtype, const TaskDesc* tasks, int ntasks, int64_t 
   const int64_t rows = tasks ? max_n : n;
   if (rows <= 0 || D <= 0 || (tasks && ntasks <= 0)) return;
   const dim3 grid((unsigned)((rows * D + 255) / 256), tasks ? (unsigned)ntasks : 1u);
-  if (dtype == HBO_F64) hipLaunchKernelGGL(kumar_forward_kernel<double>, grid, dim3(256), 0, st, tasks, (const double*)x, (double*)w, h, n, D, md);
-  else hipLaunchKernelGGL(kumar_forward_kernel<float>, grid, dim3(256), 0, st, tasks, (const float*)x, (float*)w, h, n, D, md);
+  dispatch_dtype(dtype, [&](auto tag) {
+    typedef typename decltype(tag)::type T;
+    hipLaunchKernelGGL(kumar_forward_kernel<T>, grid, dim3(256), 0, st, tasks, (const T*)x, (T*)w, h, n, D, md);
+  });
 }
-
-namespace {
-template <typename T>
-void launch_kumar_contract_t(dim3 grid, hipStream_t st, int kernel_id, const TaskDesc* tasks, const ModelDev* md, int D, int obj, int max_nblk,
-                             double* partials) {
-  switch (kernel_id) {
-    case HBO_KERNEL_SE: hipLaunchKernelGGL((kumar_contract_kernel<T, HBO_KERNEL_SE>), grid, dim3(256), 0, st, tasks, md, D, obj, max_nblk, partials); break;
-    case HBO_KERNEL_MATERN32: hipLaunchKernelGGL((kumar_contract_kernel<T, HBO_KERNEL_MATERN32>), grid, dim3(256), 0, st, tasks, md, D, obj, max_nblk, partials); break;
-    case HBO_KERNEL_MATERN52: hipLaunchKernelGGL((kumar_contract_kernel<T, HBO_KERNEL_MATERN52>), grid, dim3(256), 0, st, tasks, md, D, obj, max_nblk, partials); break;
-    default: hipLaunchKernelGGL((kumar_contract_kernel<T, HBO_KERNEL_DOT>), grid, dim3(256), 0, st, tasks, md, D, obj, max_nblk, partials); break;
-  }
-}
-}  // namespace
 
 void launch_kumar_grad(int dtype, const TaskDesc* tasks, int ntasks, int max_nblk, const ModelDev* md, int kernel_id, int D, int obj,
                        double* partials, double* out, hipStream_t st) {
   if (ntasks <= 0 || max_nblk <= 0) return;
   const dim3 grid(max_nblk, max_nblk, ntasks);
-  if (dtype == HBO_F64) launch_kumar_contract_t<double>(grid, st, kernel_id, tasks, md, D, obj, max_nblk, partials);
-  else launch_kumar_contract_t<float>(grid, st, kernel_id, tasks, md, D, obj, max_nblk, partials);
+  dispatch_dtype(dtype, [&](auto tag) {
+    dispatch_kid(kernel_id, [&](auto kid) {
+      hipLaunchKernelGGL((kumar_contract_kernel<typename decltype(tag)::type, decltype(kid)::value>), grid, dim3(256), 0, st, tasks, md, D, obj, max_nblk, partials);
+    });
+  });
   hipLaunchKernelGGL(kumar_finalize_kernel, dim3(2 * D), dim3(256), 0, st, tasks, ntasks, max_nblk, 2 * D, obj, partials, out);
 }
 
 void launch_kumar_chain_dx(int dtype, const void* xq, int64_t M, int D, const ModelDev* md, const double* gf, double* gx, hipStream_t st) {
   if (M <= 0) return;
   const dim3 grid((unsigned)((M * D + 255) / 256));
-  if (dtype == HBO_F64) hipLaunchKernelGGL(kumar_chain_dx_kernel<double>, grid, dim3(256), 0, st, (const double*)xq, M, D, md, gf, gx);
-  else hipLaunchKernelGGL(kumar_chain_dx_kernel<float>, grid, dim3(256), 0, st, (const float*)xq, M, D, md, gf, gx);
+  dispatch_dtype(dtype, [&](auto tag) {
+    typedef typename decltype(tag)::type T;
+    hipLaunchKernelGGL(kumar_chain_dx_kernel<T>, grid, dim3(256), 0, st, (const T*)xq, M, D, md, gf, gx);
+  });
 }

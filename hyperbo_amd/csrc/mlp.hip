@@ -1,6 +1,6 @@
 // The MLP basis of a batch of tasks in one launch per layer (hyperbo/gp_utils/basis_functions.py:24-36: flax Dense + tanh,
 // shared weights, applied to every sub-dataset's inputs) and its backward pass (what jax.value_and_grad of gp.py:134 does to it).
-// The per-task forms (gram.hip: dense_tanh_kernel, grad.hip: dense_bwd_*) cost 1 + 3 launches per task and layer: a pre-training
+// The per-task forms (taskvec.hip: dense_tanh_kernel, grad.hip: dense_bwd_*) cost 1 + 3 launches per task and layer: a pre-training
 // step over 24 sub-datasets of 100 points with a two-layer basis was 190 launches of ~5 us, 1.4 of its 1.6 ms.  Same arithmetic per
 // element, in the same order (the weight gradients are summed with fp64 atomics, as before).
 #include "hbo_internal.h"

@@ -465,12 +465,7 @@ void small_eval_t(const SmallArgs& a, int ntasks, int kernel_id, hipStream_t st)
   }
   const dim3 grid(ntasks), block(SMALL_THREADS);
   const int lds = small_lds_bytes<T>();
-  switch (kernel_id) {
-    case HBO_KERNEL_SE: hipLaunchKernelGGL((small_eval_kernel<T, HBO_KERNEL_SE>), grid, block, lds, st, a); break;
-    case HBO_KERNEL_MATERN32: hipLaunchKernelGGL((small_eval_kernel<T, HBO_KERNEL_MATERN32>), grid, block, lds, st, a); break;
-    case HBO_KERNEL_MATERN52: hipLaunchKernelGGL((small_eval_kernel<T, HBO_KERNEL_MATERN52>), grid, block, lds, st, a); break;
-    default: hipLaunchKernelGGL((small_eval_kernel<T, HBO_KERNEL_DOT>), grid, block, lds, st, a); break;
-  }
+  dispatch_kid(kernel_id, [&](auto kid) { hipLaunchKernelGGL((small_eval_kernel<T, decltype(kid)::value>), grid, block, lds, st, a); });
 }
 }  // namespace
 
