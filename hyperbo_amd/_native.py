@@ -182,6 +182,8 @@ SIGNATURES = {
     'hbo_tune': (C.c_int, [_P, C.c_char_p, C.c_int64]),   # include/hbo_tune.h: measurement hooks, not the boundary
     'hbo_mfma_peak_probe': (C.c_int, [_P, C.c_double, C.POINTER(C.c_double)]),   # include/hbo_tune.h
     'hbo_probe_post_product': (C.c_int, [_P, C.c_int, _P, C.c_int64, _P, C.c_int64, C.c_double, C.c_int, _P]),   # include/hbo_tune.h (test hook)
+    'hbo_probe_gram': (C.c_int, [_P, C.c_int, _P, C.c_int32, _P, C.POINTER(C.c_int64), C.c_int32, _P, C.c_int64, C.c_int, C.c_double, _P,
+                                 C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),   # include/hbo_tune.h (test hook)
     'hbo_comm_unique_id': (C.c_int, [_P]),
     'hbo_comm_init': (C.c_int, [_P, C.c_int, C.c_int, _P]),
     'hbo_comm_allreduce_sum': (C.c_int, [_P, C.POINTER(C.c_double), C.c_int32]),

@@ -667,3 +667,135 @@ extern "C" int hbo_probe_post_product(hbo_ctx* c, int form, const float* W, int6
   cleanup();
   return HBO_OK;
 }
+
+// Test hook (include/hbo_tune.h): launch_gram in the two forms hbo_gram never takes, on caller-chosen inputs, with every element of the
+// output buffer preset to a sentinel so that what the kernel leaves alone shows.  Form 1 is the launch of produce_chunk above (sizes from
+// post_plan), form 2 the launch of objective_local / enqueue_factor over a dataset built by hbo_dataset_create, its workspaces by
+// ensure_task_workspace and its descriptors by fill_desc.
+extern "C" int hbo_probe_gram(hbo_ctx* c, int form, const hbo_model* models, int32_t n_models, const void* x, const int64_t* ns, int32_t T,
+                              const void* x2, int64_t n2, int direct_form, double sentinel, void* out, int64_t out_cap, int64_t* rows_out,
+                              int64_t* ld_out) {
+  if (!c || !models || !x || !ns || !out || !rows_out || !ld_out) return fail(c, HBO_ERR_ARG, "hbo_probe_gram: null argument");
+  if (form != 1 && form != 2) return fail(c, HBO_ERR_ARG, "hbo_probe_gram: form is 1 (padded cross Gram) or 2 (batched task form)");
+  if (T <= 0 || T > 64) return fail(c, HBO_ERR_ARG, "hbo_probe_gram: 1 <= T <= 64");
+  if (form == 1 && (T != 1 || n_models != 1 || !x2 || n2 <= 0)) return fail(c, HBO_ERR_ARG, "hbo_probe_gram: form 1 takes one task, one model and x2 [n2 > 0, D]");
+  if (form == 2 && (x2 || n2 != 0 || direct_form != 0)) return fail(c, HBO_ERR_ARG, "hbo_probe_gram: form 2 takes neither x2 nor direct_form");
+  if (form == 2 && n_models != 1 && n_models != T) return fail(c, HBO_ERR_ARG, "hbo_probe_gram: form 2 takes one model or one per task");
+  if (direct_form != 0 && direct_form != 1) return fail(c, HBO_ERR_ARG, "hbo_probe_gram: direct_form is 0 or 1");
+  for (int k = 0; k < T; ++k) if (ns[k] <= 0 || ns[k] > 4096) return fail(c, HBO_ERR_ARG, "hbo_probe_gram: need 1 <= n <= 4096 for every task");
+  if (out_cap <= 0) return fail(c, HBO_ERR_ARG, "hbo_probe_gram: out_cap must be positive");
+  const hbo_model* m0 = &models[0];
+  for (int s = 0; s < n_models; ++s) {
+    const hbo_model* m = &models[s];
+    if (m->input_warp != HBO_WARP_NONE || needs_mlp(m)) return fail(c, HBO_ERR_ARG, "hbo_probe_gram: models with an MLP basis or an input warp are not taken");
+    if (validate_model(c, m)) return HBO_ERR_ARG;
+    if (!same_model_family(m, m0)) return fail(c, HBO_ERR_ARG, "hbo_probe_gram: the models must share dtype, covariance, mean and input_dim");
+  }
+  const int dtype = m0->dtype, D = m0->input_dim, fdim = feature_dim(m0);
+  const size_t es = esize(dtype);
+  PostPlan plan = {};
+  if (form == 1) {
+    plan = post_plan(c, m0, n2, round_up(ns[0], HBO_TILE) / HBO_TILE, false, nullptr);
+    if (plan.refuse || plan.nchunks != 1) return fail(c, HBO_ERR_ARG, "hbo_probe_gram: n2 must fit one posterior chunk (option post_chunk)");
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  hipStream_t st = c->stream;
+  auto fill = [&](std::vector<unsigned char>& h, size_t count) {
+    h.resize(count * es);
+    if (dtype == HBO_F64) for (size_t i = 0; i < count; ++i) ((double*)h.data())[i] = sentinel;
+    else for (size_t i = 0; i < count; ++i) ((float*)h.data())[i] = (float)sentinel;
+  };
+
+  if (form == 1) {
+    const int64_t n1 = ns[0];
+    const PostChunk ch = plan.chunk(0);
+    const int npad = round_up(n1, HBO_TILE), nblk = npad / HBO_TILE;
+    rows_out[0] = npad; ld_out[0] = ch.ldq;
+    const size_t count = (size_t)npad * ch.ldq;
+    if ((size_t)out_cap < count) return fail(c, HBO_ERR_ARG, "hbo_probe_gram: out_cap is smaller than the padded buffer");
+    int rc = upload_model(c, m0);
+    if (rc) return rc;
+    void *d1 = nullptr, *d2 = nullptr, *dk = nullptr;
+    auto cleanup = [&]() { for (void* p : {d1, d2, dk}) if (p) hipFree(p); };
+    std::vector<unsigned char> hs;
+    fill(hs, count);
+    HIPCHK_OR(c, hbo_malloc(c, &d1, (size_t)n1 * D * es), cleanup()); HIPCHK_OR(c, hbo_malloc(c, &d2, (size_t)n2 * D * es), cleanup());
+    HIPCHK_OR(c, hbo_malloc(c, &dk, count * es), cleanup());
+    HIPCHK_OR(c, hipMemcpyAsync(d1, x, (size_t)n1 * D * es, hipMemcpyHostToDevice, st), cleanup());
+    HIPCHK_OR(c, hipMemcpyAsync(d2, x2, (size_t)n2 * D * es, hipMemcpyHostToDevice, st), cleanup());
+    HIPCHK_OR(c, hipMemcpyAsync(dk, hs.data(), count * es, hipMemcpyHostToDevice, st), cleanup());
+    GramArgs g = {}; g.kernel_id = m0->kernel_id; g.mfma_min_f = c->opt_gram_mfma; g.x1 = d1; g.x2 = d2; g.out = dk; g.n1 = n1; g.n2 = ch.mc; g.ldo = ch.ldq;
+    g.n1pad = npad; g.n2pad = ch.mpad; g.fdim = fdim; g.symmetric = 0; g.padded = 1;
+    g.direct_form = direct_form;
+    launch_gram(dtype, g, c->d_model, dim3(ch.mpad / HBO_TILE, nblk, 1), st);
+    HIPCHK_OR(c, hipMemcpyAsync(out, dk, count * es, hipMemcpyDeviceToHost, st), cleanup());
+    HIPCHK_OR(c, hipStreamSynchronize(st), cleanup());
+    HIPCHK_OR(c, hipGetLastError(), cleanup());
+    cleanup();
+    return HBO_OK;
+  }
+
+  // form 2: the dataset of the T tasks (targets: zeros, one column), the workspaces and descriptors of an NLL evaluation
+  int64_t max_n = 0, rows = 0;
+  for (int k = 0; k < T; ++k) max_n = std::max(max_n, ns[k]);
+  const std::vector<unsigned char> y0((size_t)max_n * es, 0);
+  std::vector<hbo_task> tasks(T);
+  for (int k = 0; k < T; ++k) {
+    memset(&tasks[k], 0, sizeof(hbo_task));
+    tasks[k].x = (const char*)x + (size_t)rows * D * es; tasks[k].y = y0.data(); tasks[k].n = ns[k]; tasks[k].m = 1;
+    rows += ns[k];
+  }
+  hbo_dataset* ds = nullptr;
+  int rc = hbo_dataset_create(c, dtype, D, tasks.data(), T, &ds);
+  if (rc) return rc;
+  void* d_models = nullptr;
+  auto cleanup = [&]() { hipStreamSynchronize(st); hbo_dataset_free(c, ds); if (d_models) hipFree(d_models); };
+  // the dataset holds its tasks largest first; its inputs lie in the caller's order: order[z] = the caller's index of dataset task z
+  std::vector<TaskHost*> by_x(ds->tasks);
+  std::sort(by_x.begin(), by_x.end(), [](TaskHost* a, TaskHost* b) { return (const char*)a->X < (const char*)b->X; });
+  std::vector<int> order(T);
+  for (int z = 0; z < T; ++z) order[z] = (int)(std::find(by_x.begin(), by_x.end(), ds->tasks[z]) - by_x.begin());
+  size_t total = 0;
+  for (int k = 0; k < T; ++k) { rows_out[k] = by_x[k]->npad; ld_out[k] = by_x[k]->ld; total += (size_t)by_x[k]->npad * by_x[k]->ld; }
+  if ((size_t)out_cap < total) { cleanup(); return fail(c, HBO_ERR_ARG, "hbo_probe_gram: out_cap is smaller than the padded buffers"); }
+  const ModelDev* md = c->d_model;
+  int model_stride = 0;
+  std::vector<ModelDev> hm;
+  if (n_models == 1) {
+    rc = upload_model(c, m0);
+    if (rc) { cleanup(); return rc; }
+  } else {
+    hm.resize(T);
+    for (int z = 0; z < T; ++z) fill_model_dev(hm[z], &models[order[z]]);
+    HIPCHK_OR(c, hbo_malloc(c, &d_models, sizeof(ModelDev) * T), cleanup());
+    HIPCHK_OR(c, hipMemcpyAsync(d_models, hm.data(), sizeof(ModelDev) * T, hipMemcpyHostToDevice, st), cleanup());
+    md = static_cast<const ModelDev*>(d_models); model_stride = 1;
+  }
+  ds->h_desc.resize(T);
+  std::vector<std::vector<unsigned char>> hs(T);
+  for (int z = 0; z < T; ++z) {
+    TaskHost* t = ds->tasks[z];
+    rc = ensure_task_workspace(c, dtype, t, false, 1);
+    if (rc) { cleanup(); return rc; }
+    fill_desc(ds->h_desc[z], t, m0, dtype, OBJ_NLL);
+    const size_t count = (size_t)(t->npad + HBO_TILE) * t->ld;   // all of A, its augmented tile row too
+    fill(hs[z], count);
+    HIPCHK_OR(c, hipMemcpyAsync(t->A, hs[z].data(), count * es, hipMemcpyHostToDevice, st), cleanup());
+  }
+  HIPCHK_OR(c, dev_alloc(c, (void**)&ds->d_desc, sizeof(TaskDesc) * T), cleanup());
+  HIPCHK_OR(c, hipMemcpyAsync(ds->d_desc, ds->h_desc.data(), sizeof(TaskDesc) * T, hipMemcpyHostToDevice, st), cleanup());
+  const int max_nblk = ds->max_nblk;
+  GramArgs g = {}; g.kernel_id = m0->kernel_id; g.mfma_min_f = c->opt_gram_mfma; g.tasks = ds->d_desc; g.fdim = fdim; g.symmetric = 1; g.padded = 1;
+  g.model_stride = model_stride;
+  launch_gram(dtype, g, md, dim3(max_nblk, max_nblk, T), st);
+  size_t off = 0;
+  for (int k = 0; k < T; ++k) {
+    const size_t count = (size_t)by_x[k]->npad * by_x[k]->ld;
+    HIPCHK_OR(c, hipMemcpyAsync((char*)out + off * es, by_x[k]->A, count * es, hipMemcpyDeviceToHost, st), cleanup());
+    off += count;
+  }
+  HIPCHK_OR(c, hipStreamSynchronize(st), cleanup());
+  HIPCHK_OR(c, hipGetLastError(), cleanup());
+  cleanup();
+  return HBO_OK;
+}

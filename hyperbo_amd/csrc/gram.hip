@@ -175,6 +175,7 @@ __global__ __launch_bounds__(256) void gram_kernel(GramArgs g, const ModelDev* _
 // Well-scaled data stays on the matrix cores (cfg 3's 64 tanh features, length-scale 1, |a|^2 ~ 50: a tile falls back only if it holds a
 // pair with k > 0.006 sv, u < ~18 where the typical pair has u ~ 50).  The diagonal of a symmetric Gram gets u = 0 exactly; hbo_gram's
 // symmetric Gram (x1 == x2) computes the lower tiles only and stores each pair at (i, j) and (j, i): it equals its transpose exactly.
+// The diagonal tiles of the task form store their pairs the same way (tests/test_gpu_gram.py, group E).
 typedef __bf16 gm_bf16x8 __attribute__((ext_vector_type(8)));
 typedef float gm_f32x16 __attribute__((ext_vector_type(16)));
 typedef unsigned short gm_u16x8 __attribute__((ext_vector_type(8)));
@@ -249,6 +250,9 @@ __device__ __forceinline__ bool gm_finish(const GmTile& t, const gm_f32x16 (&acc
           }
           if (t.mirror) {   // (no padding: n1 == n2 == e1 == e2)
             if (gr < t.n1 && gcol <= gr) { gst(orow + cl + e, v); if (gcol != gr) gst(t.out + gcol * t.ldo + gr, v); }
+          } else if (t.symmetric && t.on_diag) {   // a diagonal tile of the task form: what lies above the diagonal is the mirror of what lies below it,
+            // to the bit, as gram_kernel leaves it (the six products of a pair are summed in another order at (j, i) than at (i, j))
+            if (gr < t.e1 && gcol <= gr) { gst(orow + cl + e, v); if (gcol != gr) gst(t.out + gcol * t.ldo + gr, v); }
           } else if (gr < t.e1 && gcol < t.e2) {
             gst(orow + cl + e, v);
           }

@@ -101,6 +101,23 @@ int hbo_probe_acq_grad_samples64(hbo_ctx* ctx, const hbo_model* models, int32_t 
 int hbo_probe_acq_opt_ctl(double* state, int32_t D, int dtype, const hbo_acq_opt_opts* opts, const double* lo, const double* hi,
                           const double* x0, const double* vals, const double* grads, int32_t S, double* x_next, double* x_iter,
                           hbo_acq_opt_eval* eval, int32_t* status);
+/* TEST HOOK (tests/test_gpu_gram.py): the Gram launch in the two forms hbo_gram does not take, on host arrays, with every element of
+ * the device output preset to `sentinel` (rounded to the model dtype) so that what the kernels do not write shows.  models [n_models]:
+ * no MLP basis, no linear_mlp mean, no input warp, one family.  x: the rows of the T tasks one after the other, [sum ns, input_dim];
+ * ns [T], 1 <= ns[k] <= 4096, T <= 64.  The WHOLE padded buffers come back in `out` (capacity out_cap elements), task after task in the
+ * caller's order, task k as rows_out[k] rows of ld_out[k] elements.
+ *   form 1  the posterior's padded cross Gram (cache.hip: produce_chunk): T = 1, n_models = 1, K(x, x2) with x2 [n2, input_dim];
+ *           symmetric = 0, padded = 1, extents rounded to 128 and the leading dimension of a posterior chunk, grid (n2pad / 128, nblk);
+ *           direct_form as the streamed posterior sets it (1: the fp32 VALU kernel whatever gram_mfma says).  n2 must fit one chunk.
+ *   form 2  the batched symmetric task form of the objectives and hbo_factor: a dataset of the T tasks, its workspaces and descriptors
+ *           from the set-up of an NLL evaluation, grid (max_nblk, max_nblk, T); n_models = 1: one model for the batch (model_stride 0),
+ *           n_models = T: models[k] for task k (model_stride 1).  x2 = NULL, n2 = 0, direct_form = 0.  A comes back without its
+ *           augmented tile row: rows_out[k] = npad.
+ * gram_mfma is the context's.  HBO_ERR_ARG (hbo_last_error) on a bad argument, before any device call except an out_cap that turns
+ * out too small; no product path calls this. */
+int hbo_probe_gram(hbo_ctx* ctx, int form, const hbo_model* models, int32_t n_models, const void* x, const int64_t* ns, int32_t T,
+                   const void* x2, int64_t n2, int direct_form, double sentinel, void* out, int64_t out_cap, int64_t* rows_out,
+                   int64_t* ld_out);
 #ifdef __cplusplus
 }
 #endif

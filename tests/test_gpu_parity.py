@@ -107,7 +107,7 @@ def test_gram_vs_oracle(gpu_ctx, kname, mlp, dtype, tol):
 def test_fp32_gram_on_the_matrix_cores_vs_oracle(gpu_ctx, kname, d):
   """fp32 Gram matrices of the stationary covariances with >= 32 features take gram_mfma_kernel (csrc/gram.hip, round 6):
   u = |a|^2 + |b|^2 - 2 a.b with the dot product from the exact three-way bf16 split on the matrix cores.  Symmetric and cross
-  Gram, sizes off the 128-tile grid, a feature count that is not a multiple of the 32-feature chunk, duplicated rows (u ~ 0, where
+  Gram, sizes off the 128-tile grid, a feature count that is not a multiple of the 16-feature chunk (GM_KC), duplicated rows (u ~ 0, where
   the expansion loses what the direct form keeps): against the fp64 oracle at the fp32 Gram's 2e-5, and against the direct-form
   kernel (hbo_tune gram_mfma = 0, on a context of its own) -- whose own error is recorded beside it."""
   defs, _, _, _, kernel, _, _, utils = _native()
