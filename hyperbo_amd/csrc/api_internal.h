@@ -2,8 +2,9 @@
 // objective.hip: hbo_objective / hbo_objective_sharded; cache.hip: hbo_factor, row append, posterior, acquisition; acq_grad.hip: its
 // gradient): model validation and upload, the set-up the batched entry points share (model_family_check, mlp_shape, models_pack,
 // stage_begin / stage_upload), the MLP feature pipeline and the query-side features of everything that reads a factor
-// (query_features), the per-task device buffers and the descriptors the kernels read, and the plan of a posterior call (post_plan:
-// every decision, no HIP call).
+// (query_features), the per-task device buffers and the descriptors the kernels read, the plans of a posterior call and of an
+// objective evaluation (post_plan, obj_plan: every decision, no HIP call), and the gradient scatter table of the objectives
+// (GradScatter).
 #pragma once
 #include "ctx.h"
 
@@ -207,6 +208,14 @@ void enqueue_fused_forward(hbo_ctx* c, const hbo_model* m, hbo_dataset* ds, int6
 int enqueue_backward(hbo_ctx* c, const hbo_model* m, hbo_dataset* ds, int64_t max_n, int obj, bool want_grad);
 void launch_shard_reduce(const double* nll, const double* grad, const int* info, int T, int out_stride, const int* map,
                          const double* mlp, const int* mlp_seg, int n_mlp_seg, double* out, int out_count, hipStream_t st);   // grad.hip
+// Task-sharded form (hbo_objective_sharded): the sums over this rank's tasks are formed on the device, all-reduced in place
+// over the context's RCCL communicator and copied to the host once.
+int comm_allreduce_device(hbo_ctx* c, double* d_buf, int count, hipStream_t st);   // comm.hip
+// The sharded form never leaves its peers alone in the collective: objective_local does everything up to (not including) the
+// all-reduce and hands back the device buffer [nll, count, grad]; whatever it returns, objective_impl then takes part in the ONE
+// all-reduce of the evaluation -- with NaN in every slot after a local failure (the peers see a NaN objective, not a hang) --
+// and only if not even that buffer can be had does it abort the communicator, so that the peers' collective fails too.
+int comm_abort(hbo_ctx* c);   // comm.hip
 
 // fills ctx->h_model, uploads it and the MLP weights
 static int upload_model(hbo_ctx* c, const hbo_model* m) {
@@ -540,4 +549,123 @@ static PostPlan post_plan(const hbo_ctx* c, const hbo_model* m, int64_t M, int n
   p.direct_form = p.nbuf == 2;
   p.own_counters = c->opt_lauum_persist && !ov_lane;
   return p;
+}
+
+// ---- objective plan ------------------------------------------------------------------------
+// Every decision of one hbo_objective evaluation (objective.hip: objective_local) that follows from the options, the model, the
+// dataset's shape (tasks, blocks, dtype, each task's n and m), the objective, want_grad and whether the call is sharded: no HIP call,
+// no allocation.  What needs the filled descriptors (the largest naug) is obj_setup's.  ds may be null or empty (a rank beyond the
+// task count): such a call only reads red_count.
+struct ObjPlan {
+  int obj, dtype, T, max_nblk, max_npad; bool want_grad, sharded;
+  bool euc, kumar, mlp, extras;
+  bool small_ok, fused_small, lds_only;
+  bool need_S;                 // the tasks' workspaces include S (K^-1, or the sweep's running matrix)
+  bool la, sweep, early_trtri; int qs;   // look-ahead; the one-sweep inverse and its row group; the recursive inverse started beside the chain
+  bool side_reduce;            // the small reductions on the idle panel stream
+  bool value_inverse;          // a value-only call that needs the inverse for its extra rows
+  bool contract;               // the gradient contraction runs (EUC: its value comes out of it too)
+  int64_t max_n; int fdim, nacc, out_stride; size_t pack_bytes;
+  int64_t stride_task; size_t partials_bytes;
+  int red_count;               // sharded: [nll, count, grad] of the whole job, reduced on the device
+};
+static ObjPlan obj_plan(const hbo_ctx* c, const hbo_model* m, const hbo_dataset* ds, const hbo_grad_layout& lay, int obj, bool want_grad, bool sharded) {
+  ObjPlan p = {};
+  p.obj = obj; p.want_grad = want_grad; p.sharded = sharded;
+  p.T = ds ? ds->ntasks : 0; p.dtype = ds ? ds->dtype : m->dtype; p.max_nblk = ds ? ds->max_nblk : 0; p.max_npad = p.max_nblk * HBO_TILE;
+  p.euc = obj == OBJ_EUC; p.kumar = is_kumar(m); p.mlp = needs_mlp(m);
+  p.red_count = 2 + (want_grad ? lay.total : 0);
+  // tasks with more than 127 aligned columns: their data rows do not ride in the augmented tile-row (TaskDesc::nvec)
+  if (obj != OBJ_NLL) for (int k = 0; k < p.T; ++k) if (ds->tasks[k]->m + 1 > HBO_TILE) p.extras = true;
+  for (int k = 0; k < p.T; ++k) p.max_n = std::max<int64_t>(p.max_n, ds->tasks[k]->n);
+  // (the single-workgroup evaluation needs 132 KB (fp64) / 68 KB (fp32) of LDS in one workgroup: a device that cannot give it -- any
+  //  ARCH other than gfx950 the Makefile is pointed at -- takes the blocked pipeline instead of failing at launch)
+  p.small_ok = c->opt_small_fused && ds && small_eval_lds(p.dtype) <= c->lds_per_block;
+  // every task fits one 128-block (the reference's training regime: sub-sampled tasks of 50-100 points): ONE launch, one workgroup
+  // per task does Gram -> factorisation -> inverse -> K^-1 -> contraction in LDS (small.hip) instead of the 13 launches of the blocked
+  // pipeline
+  // (a batch that takes the single-workgroup evaluation sets its info words itself: one launch less on a 60 us path)
+  p.fused_small = obj == OBJ_NLL && p.max_nblk == 1 && p.small_ok;
+  // A batch that takes the single-workgroup evaluation (small.hip) without an MLP keeps its matrices in
+  // LDS: no A / W / S / alpha buffers at all (a freshly sub-sampled batch per Adam step paid ~150 pool operations and two fills for
+  // buffers its one launch never reads); the leaf inverses that leaf_cholesky4 also stores go to one shared scratch block
+  p.lds_only = p.fused_small && !p.mlp && !(p.kumar && want_grad);
+  // (a batch with extra rows runs the inverse over ALL its tasks, value-only calls too: GEMM_TRTRI_A stores S21 of every task with
+  //  two or more blocks, so every task of such a batch needs S -- not only the ones with more than 127 aligned columns)
+  p.need_S = (want_grad || p.extras) && !p.euc;
+  p.la = use_lookahead(c, p.T, p.max_nblk);
+  // the inverse and K^-1 behind the panel chain, row group by row group (sched.hip:sweep_advance) -- or the block-recursive
+  // inverse started beside the chain and K^-1 = W^T W after it
+  p.sweep = want_grad && !p.euc && use_sweep(c, p.dtype, p.T, p.max_nblk);
+  p.qs = !p.sweep ? 0 : (c->opt_sweep_qs > 0 ? c->opt_sweep_qs : sweep_group(p.T, p.max_nblk));
+  p.early_trtri = !p.sweep && want_grad && use_early_trtri(c, p.T, p.max_nblk);
+  // the small reductions (log-determinant + quadratic form now, alpha = W^T z and d nll / d mu after the inverse) run on
+  // the idle panel stream beside the inverse and K^-1 = W^T W instead of between them (0.14 ms at cfg 2)
+  p.side_reduce = want_grad && obj == OBJ_NLL && p.la;
+  p.value_inverse = p.extras && !p.euc && !want_grad;   // value only: the inverse is needed for the extra rows all the same
+  p.contract = !p.fused_small && (want_grad || p.euc);   // EUC: the Frobenius norm of the value comes out of the contraction pass
+  p.fdim = feature_dim(m);
+  p.nacc = grad_nacc(m->kernel_id, p.fdim);
+  p.stride_task = (int64_t)(p.max_nblk * (p.max_nblk + 1)) * p.nacc;   // two half-tile slots per lower tile
+  p.partials_bytes = !p.contract ? 0 : sizeof(double) * (p.stride_task * p.T + (size_t)HBO_GRAD_PRE_ROWS * p.nacc * p.T);   // per-tile partials + their pre-reduction
+  // results of one evaluation, one device block = one copy back: [value T][gradient T x out_stride][info T (int)]
+  p.out_stride = (m->kernel_id == HBO_KERNEL_DOT ? 0 : m->n_lengthscale) + 6 + mean_feature_dim(m);
+  p.pack_bytes = sizeof(double) * p.T * (1 + (size_t)p.out_stride) + sizeof(int) * p.T;
+  return p;
+}
+
+// ---- gradient scatter table ------------------------------------------------------------------
+// Where an evaluation's gradient goes in the caller's layout (hbo_grad_layout): entry j of a task's gradient block (out_stride
+// entries: lengthscales, signal and noise variance, constant, dot-product sigma and bias, linear-mean weights and bias) is ADDED to
+// leaf map[j] (-1: the model has no such leaf); the leaves that come out already summed over the tasks -- the 2 D Kumaraswamy sums and
+// the MLP gradient, both in hbo_dataset::d_mlpgrad -- are ASSIGNED by segments (destination, source position, length).  Built once per
+// call; the sharded path uploads `w` as it stands ([out_stride ints][3 ints per segment]: what shard_reduce_kernel reads) and the host
+// finish walks the same words (grad_scatter_host).  Sized for the worst case a valid model has, so nothing here can overflow:
+// two Kumaraswamy segments beside a linear_mlp mean of HBO_MAX_MLP_LAYERS layers.
+enum { HBO_SCATTER_MAX_SEG = 2 + 2 * HBO_MAX_MLP_LAYERS, HBO_SCATTER_MAX_STRIDE = 2 * HBO_MAX_FEATURE_DIM + 6 };
+struct GradScatter {
+  int out_stride, nseg;
+  int w[HBO_SCATTER_MAX_STRIDE + 3 * HBO_SCATTER_MAX_SEG];
+  const int* seg() const { return w + out_stride; }
+  size_t bytes() const { return sizeof(int) * (out_stride + 3 * HBO_SCATTER_MAX_SEG); }
+};
+// kumar_a / kumar_b: hbo_grad_layout_kumar_of's offsets.  Without want_grad: every entry -1, no segment.
+static void grad_scatter_fill(GradScatter& g, const hbo_model* m, const hbo_grad_layout& lay, int32_t kumar_a, int32_t kumar_b, int out_stride, bool want_grad) {
+  g.out_stride = out_stride; g.nseg = 0;
+  for (int i = 0; i < out_stride + 3 * HBO_SCATTER_MAX_SEG; ++i) g.w[i] = -1;
+  if (!want_grad) return;
+  const int n_ls = m->kernel_id == HBO_KERNEL_DOT ? 0 : m->n_lengthscale;
+  const int fm = mean_feature_dim(m);
+  for (int d = 0; d < n_ls; ++d) g.w[d] = lay.lengthscale < 0 ? -1 : lay.lengthscale + d;
+  g.w[n_ls] = lay.signal_variance; g.w[n_ls + 1] = lay.noise_variance; g.w[n_ls + 2] = lay.constant;
+  g.w[n_ls + 3] = lay.dot_prod_sigma; g.w[n_ls + 4] = lay.dot_prod_bias;
+  for (int d = 0; d < fm; ++d) g.w[n_ls + 5 + d] = lay.linear_kernel < 0 ? -1 : lay.linear_kernel + d;
+  g.w[n_ls + 5 + fm] = lay.linear_bias;
+  auto segment = [&](int dst, int src, int len) { int* sg = g.w + out_stride + 3 * g.nseg++; sg[0] = dst; sg[1] = src; sg[2] = len; };
+  if (is_kumar(m)) {   // the 2 D Kumaraswamy leaves, already summed over the tasks
+    segment(kumar_a, 0, m->input_dim); segment(kumar_b, m->input_dim, m->input_dim);
+  }
+  if (needs_mlp(m)) {   // the MLP gradient, already summed over the tasks: per layer the weights, then the bias
+    int pos = 0, fin0 = m->input_dim;
+    for (int l = 0; l < m->n_layers; ++l) {
+      const int wn = fin0 * m->features[l], bn = m->features[l];
+      segment(lay.mlp_kernel[l], pos, wn); pos += wn;
+      segment(lay.mlp_bias[l], pos, bn); pos += bn;
+      fin0 = m->features[l];
+    }
+  }
+}
+// The host finish over the table: h_grad [T][out_stride] and h_info [T] as they come back from the device, h_seg the summed leaves
+// (may be null without segments).  Per-task entries are added, NaN for a task whose info word is set; segments are assigned, NaN
+// when any task failed (notpd).
+static void grad_scatter_host(const GradScatter& g, int T, const double* h_grad, const int* h_info, const double* h_seg, bool notpd, double* grad_sum) {
+  for (int k = 0; k < T; ++k) {
+    const double* o = h_grad + (size_t)k * g.out_stride;
+    const bool bad = h_info[k] != INT_MAX;
+    for (int j = 0; j < g.out_stride; ++j) if (g.w[j] >= 0) grad_sum[g.w[j]] += bad ? NAN : o[j];
+  }
+  for (int s = 0; s < g.nseg; ++s) {
+    const int* sg = g.seg() + 3 * s;
+    for (int i = 0; i < sg[2]; ++i) grad_sum[sg[0] + i] = notpd ? NAN : h_seg[sg[1] + i];
+  }
 }

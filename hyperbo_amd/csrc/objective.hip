@@ -1,6 +1,10 @@
 // The objectives of the C ABI: hbo_nll / hbo_objective (hyperbo/gp_utils/objectives.py:29-210 -- NLL, EKL, Euclid, value and
 // gradient in one pass: features -> Gram -> blocked Cholesky with the augmented rows -> inverse -> K^-1 -> contraction) and its
 // task-sharded form hbo_objective_sharded (device-side reduction + one in-place all-reduce).
+// On the host one evaluation (objective_local) reads top to bottom: checks -> obj_plan (api_internal.h: every decision, no HIP call)
+// -> obj_setup (workspaces, descriptors, the pinned stage) -> obj_steps over an ObjState (features, factor, reduce, inverse, extra
+// rows, contract) -> enqueue_backward -> obj_shard_reduce or obj_copy_back, both over ONE gradient scatter table (api_internal.h:
+// GradScatter).  objective_impl adds the sharded form's collective.
 #include "api_internal.h"
 #include <chrono>
 
@@ -8,16 +12,6 @@ extern "C" int hbo_nll(hbo_ctx* c, const hbo_model* m, hbo_dataset* ds, double* 
                        double* grad_sum) {
   return hbo_objective(c, m, ds, HBO_OBJ_NLL, nll_sum, nll_per_task, grad_sum);
 }
-
-// Task-sharded form (hbo_objective_sharded): the sums over this rank's tasks are formed on the device, all-reduced in place
-// over the context's RCCL communicator and copied to the host once.
-int comm_allreduce_device(hbo_ctx* c, double* d_buf, int count, hipStream_t st);   // comm.hip
-
-// The sharded form never leaves its peers alone in the collective: objective_local does everything up to (not including) the
-// all-reduce and hands back the device buffer [nll, count, grad]; whatever it returns, objective_impl then takes part in the ONE
-// all-reduce of the evaluation -- with NaN in every slot after a local failure (the peers see a NaN objective, not a hang) --
-// and only if not even that buffer can be had does it abort the communicator, so that the peers' collective fails too.
-int comm_abort(hbo_ctx* c);   // comm.hip
 
 // The launches of one evaluation that do not depend on the path taken (objective_local) or that hbo_train_adam (train.hip) queues once
 // per step without the host-side set-up: the batched MLP basis (one launch per layer), the Kumaraswamy forward (w(X) and dw/da, dw/db
@@ -80,63 +74,37 @@ int enqueue_backward(hbo_ctx* c, const hbo_model* m, hbo_dataset* ds, int64_t ma
   return HBO_OK;
 }
 
-int objective_local(hbo_ctx* c, const hbo_model* m_in, hbo_dataset* ds, int objective, double* nll_sum,
-                    double* nll_per_task, double* grad_sum, const ShardReq* sh, ShardOut* so) {
-  if (!c || !nll_sum || !m_in || (!ds && !sh)) return fail(c, HBO_ERR_ARG, "hbo_objective: null argument");
-  if (objective != HBO_OBJ_NLL && objective != HBO_OBJ_EKL && objective != HBO_OBJ_EUC) return fail(c, HBO_ERR_ARG, "hbo_objective: unknown objective id");
-  HIPCHK(c, hipSetDevice(c->device));
-  ModelCopy mcopy(m_in);   // (a Kumaraswamy model keeps its a, b)
-  if (objective != HBO_OBJ_NLL) mcopy.get()->eps = 0.0;   // objectives.py:63-65: cov_model = K + noise I, no jitter
-  const hbo_model* m = mcopy.get();
-  const bool kumar = is_kumar(m);
-  CholBoundScope bound_scope(c, 0.0);   // (set where the factorisation starts; cleared on every way out)
-  const int obj = objective;
-  const bool euc = obj == OBJ_EUC;
-  int rc = validate_model(c, m);
-  if (rc) return rc;
-  if (ds && ds->ntasks > 0 && (m->dtype != ds->dtype || m->input_dim != ds->D)) return fail(c, HBO_ERR_ARG, "hbo_objective: model/dataset dtype or input_dim mismatch");
-  hbo_grad_layout lay;
-  hbo_grad_layout_of(m, &lay);
-  const bool want_grad = grad_sum != nullptr;
-  *nll_sum = 0;
-  if (want_grad) for (int i = 0; i < lay.total; ++i) grad_sum[i] = 0;
-  const int T = ds ? ds->ntasks : 0;
-  hipStream_t st = c->stream;
-  // sharded: [nll, count, grad] of the whole job, reduced on the device
-  const int red_count = 2 + (want_grad ? lay.total : 0);
-  if (so) so->red_count = red_count;
-  if (T == 0) {
-    if (!sh) return HBO_OK;
-    // a rank beyond the task count: zeros into the collective
-    HIPCHK(c, hipSetDevice(c->device));
-    double* d_red = static_cast<double*>(ws_get(c, WS_SHARD_RED, sizeof(double) * red_count));
-    if (!d_red) return HBO_ERR_HIP;
-    hipEvent_t ev0 = pool_event_timed(c, 0), ev1 = pool_event_timed(c, 1);
-    HIPCHK(c, hipEventRecord(ev0, st));
-    HIPCHK(c, hipMemsetAsync(d_red, 0, sizeof(double) * red_count, st));
-    HIPCHK(c, hipEventRecord(ev1, st));
-    so->d_red = d_red; so->ev0 = ev0; so->ev1 = ev1;
-    return HBO_OK;
-  }
-  if (obj != OBJ_NLL) for (TaskHost* t : ds->tasks) if (!t->ydiv) return fail(c, HBO_ERR_ARG, "hbo_objective: the dataset carries no divergence rows");
-  // tasks with more than 127 aligned columns: their data rows do not ride in the augmented tile-row (TaskDesc::nvec)
-  bool extras = false;
-  if (obj != OBJ_NLL) for (TaskHost* t : ds->tasks) if (t->m + 1 > HBO_TILE) extras = true;
-  const int dtype = ds->dtype;
-  prof_begin(c);
-  const auto host_t0 = std::chrono::steady_clock::now();   // host time spent queueing this evaluation (stage "host_enqueue", level 1)
-  hipEvent_t ev_sh0 = nullptr;
-  if (sh) { ev_sh0 = pool_event_timed(c, 0); HIPCHK(c, hipEventRecord(ev_sh0, st)); }
-  rc = upload_model(c, m);
-  if (rc) return rc;
+namespace {
+// what set-up and the steps of one evaluation share: the call, its plan (api_internal.h: obj_plan), and the events in flight
+struct ObjState {
+  hbo_ctx* c; const hbo_model* m; hbo_dataset* ds; ObjPlan p;
+  unsigned char* stage = nullptr;   // the pinned buffer, at its final size (obj_setup)
+  int max_naug = 1;                 // augmented rows of the largest task: needs the filled descriptors
+  TrtriProgress trtri_pg; SweepState sweep_st;
+  hipStream_t side = nullptr;       // where the small reductions run: the panel stream, or the main one (step_reduce)
+  hipEvent_t ev_side = nullptr;     // behind d nll / d mu on the side stream, once the main stream has been told to wait for it
+};
 
-  // workspaces + descriptors.  A batch that takes the single-workgroup evaluation (small.hip) without an MLP keeps its matrices in
-  // LDS: no A / W / S / alpha buffers at all (a freshly sub-sampled batch per Adam step paid ~150 pool operations and two fills for
-  // buffers its one launch never reads); the leaf inverses that leaf_cholesky4 also stores go to one shared scratch block
-  // (the single-workgroup evaluation needs 132 KB (fp64) / 68 KB (fp32) of LDS in one workgroup: a device that cannot give it -- any
-  //  ARCH other than gfx950 the Makefile is pointed at -- takes the blocked pipeline instead of failing at launch)
-  const bool small_ok = c->opt_small_fused && ds && small_eval_lds(ds->dtype) <= c->lds_per_block;
-  const bool lds_only = obj == OBJ_NLL && ds->max_nblk == 1 && small_ok && !needs_mlp(m) && !(kumar && want_grad);
+// a rank beyond the task count: zeros into the collective
+int obj_empty_rank(hbo_ctx* c, int red_count, ShardOut* so) {
+  hipStream_t st = c->stream;
+  double* d_red = static_cast<double*>(ws_get(c, WS_SHARD_RED, sizeof(double) * red_count));
+  if (!d_red) return HBO_ERR_HIP;
+  hipEvent_t ev0 = pool_event_timed(c, 0), ev1 = pool_event_timed(c, 1);
+  HIPCHK(c, hipEventRecord(ev0, st));
+  HIPCHK(c, hipMemsetAsync(d_red, 0, sizeof(double) * red_count, st));
+  HIPCHK(c, hipEventRecord(ev1, st));
+  so->d_red = d_red; so->ev0 = ev0; so->ev1 = ev1;
+  return HBO_OK;
+}
+
+// workspaces + descriptors: everything the launches read, allocated and uploaded (what the plan's lds_only spares a batch is said there)
+int obj_setup(ObjState& s) {
+  hbo_ctx* c = s.c; const hbo_model* m = s.m; hbo_dataset* ds = s.ds; const ObjPlan& p = s.p;
+  const int T = p.T, dtype = p.dtype, obj = p.obj;
+  const bool lds_only = p.lds_only, want_grad = p.want_grad;
+  hipStream_t st = c->stream;
+  int rc;
   void* small_scratch = nullptr;
   if (lds_only) {
     small_scratch = ws_get(c, WS_SMALL_W, (size_t)HBO_TILE * padded_ld(HBO_TILE, ds->dtype) * esize(ds->dtype));
@@ -163,14 +131,12 @@ int objective_local(hbo_ctx* c, const hbo_model* m_in, hbo_dataset* ds, int obje
   for (int k = 0; k < T; ++k) {
     TaskHost* t = ds->tasks[k];
     if (!lds_only) {
-      // (a batch with extra rows runs the inverse over ALL its tasks, value-only calls too: GEMM_TRTRI_A stores S21 of every task with
-      //  two or more blocks, so every task of such a batch needs S -- not only the ones with more than 127 aligned columns)
-      rc = ensure_task_workspace(c, dtype, t, (want_grad || extras) && !euc, obj == OBJ_NLL ? 1 : t->m + 1);
+      rc = ensure_task_workspace(c, dtype, t, p.need_S, obj == OBJ_NLL ? 1 : t->m + 1);
       if (rc) return rc;
     }
-    if (needs_mlp(m)) { rc = t->feat.ensure(c, m, t->n); if (rc) return rc; }
-    if (kumar) { rc = ensure_kumar_buffers(c, m, t, t->n, want_grad); if (rc) return rc; }
-    if (needs_mlp(m) && want_grad) {
+    if (p.mlp) { rc = t->feat.ensure(c, m, t->n); if (rc) return rc; }
+    if (p.kumar) { rc = ensure_kumar_buffers(c, m, t, t->n, want_grad); if (rc) return rc; }
+    if (p.mlp && want_grad) {
       int maxf = m->input_dim;
       for (int l = 0; l < m->n_layers; ++l) maxf = std::max(maxf, (int)m->features[l]);
       const size_t need = (size_t)t->n * maxf;
@@ -186,9 +152,8 @@ int objective_local(hbo_ctx* c, const hbo_model* m_in, hbo_dataset* ds, int obje
     fill_desc(ds->h_desc[k], t, m, dtype, obj);
     if (lds_only && !ds->h_desc[k].W) ds->h_desc[k].W = small_scratch;   // (every task writes its leaf inverses there: never read)
   }
-  int64_t max_n = 0;
-  for (int k = 0; k < T; ++k) max_n = std::max<int64_t>(max_n, ds->tasks[k]->n);
-  if (needs_mlp(m)) {
+  for (int k = 0; k < T; ++k) s.max_naug = std::max(s.max_naug, ds->h_desc[k].naug);
+  if (p.mlp) {
     // per-task pointers of the batched MLP passes (mlp.hip); uploaded when an allocation moved
     std::vector<MlpTaskDev> hm(T);
     for (int k = 0; k < T; ++k) {
@@ -207,8 +172,8 @@ int objective_local(hbo_ctx* c, const hbo_model* m_in, hbo_dataset* ds, int obje
   // (per-dataset buffers come from the context's pool: a fresh batch per Adam step paid three hipMalloc + three synchronising
   //  hipFree for its descriptors, results and gradient partials)
   if (!ds->d_desc) HIPCHK(c, dev_alloc(c, (void**)&ds->d_desc, sizeof(TaskDesc) * T));
-  const int out_stride = (m->kernel_id == HBO_KERNEL_DOT ? 0 : m->n_lengthscale) + 6 + mean_feature_dim(m);
-  const size_t pack_bytes = sizeof(double) * T * (1 + (size_t)out_stride) + sizeof(int) * T;
+  const int out_stride = p.out_stride;
+  const size_t pack_bytes = p.pack_bytes;
   if (ds->pack_bytes < pack_bytes) {
     if (ds->d_pack) dev_free(c, ds->d_pack);
     ds->d_pack = nullptr; ds->pack_bytes = 0;
@@ -218,185 +183,167 @@ int objective_local(hbo_ctx* c, const hbo_model* m_in, hbo_dataset* ds, int obje
   ds->d_nll = ds->d_pack; ds->d_gradout = ds->d_pack + T; ds->d_info = reinterpret_cast<int*>(ds->d_pack + T + (size_t)T * out_stride);
   // small transfers go through one pinned buffer: descriptors up (only when they changed), results down in one copy
   // (fetched at its final size here, and not waited for: a call whose descriptors stand only uses it as the target of the copy back)
-  unsigned char* stage = static_cast<unsigned char*>(pinned_stage(c, std::max(sizeof(TaskDesc) * T, pack_bytes)));
-  if (!stage) return fail(c, HBO_ERR_HIP, "hbo_objective: pinned staging buffer");
+  s.stage = static_cast<unsigned char*>(pinned_stage(c, std::max(sizeof(TaskDesc) * T, pack_bytes)));
+  if (!s.stage) return fail(c, HBO_ERR_HIP, "hbo_objective: pinned staging buffer");
   if (ds->h_desc_dev.size() != (size_t)T || memcmp(ds->h_desc_dev.data(), ds->h_desc.data(), sizeof(TaskDesc) * T) != 0) {
     HIPCHK(c, stage_wait(c));   // the upload before this one may still read the buffer
-    memcpy(stage, ds->h_desc.data(), sizeof(TaskDesc) * T);
-    HIPCHK(c, stage_upload(c, ds->d_desc, stage, sizeof(TaskDesc) * T, st));   // the pinned buffer is written again further down (sharded: the scatter map)
+    memcpy(s.stage, ds->h_desc.data(), sizeof(TaskDesc) * T);
+    HIPCHK(c, stage_upload(c, ds->d_desc, s.stage, sizeof(TaskDesc) * T, st));   // the pinned buffer is written again later (sharded: the scatter table, obj_shard_reduce)
     ds->h_desc_dev = ds->h_desc;
   }
-  // (a batch that takes the single-workgroup evaluation sets its info words itself: one launch less on a 60 us path)
-  if (!(obj == OBJ_NLL && ds->max_nblk == 1 && small_ok)) HIPCHK(c, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(ds->d_info), INT_MAX, T, st));
+  if (!p.fused_small) HIPCHK(c, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(ds->d_info), INT_MAX, T, st));
+  return HBO_OK;
+}
 
-  const int max_nblk = ds->max_nblk, max_npad = max_nblk * HBO_TILE;
-  // every task fits one 128-block (the reference's training regime: sub-sampled tasks of 50-100 points): ONE launch, one workgroup
-  // per task does Gram -> factorisation -> inverse -> K^-1 -> contraction in LDS (small.hip) instead of the 13 launches below
-  const bool fused_small = obj == OBJ_NLL && max_nblk == 1 && small_ok;
-  auto mlp_forward = [&]() { enqueue_mlp_forward(c, m, ds, max_n); };
-  auto kumar_forward = [&]() { enqueue_kumar_forward(c, m, ds, max_n); };
-  if (fused_small) {
-    enqueue_fused_forward(c, m, ds, max_n, out_stride, want_grad);
-  } else {
-  if (c->opt_poison) launch_poison(dtype, ds->d_desc, T, max_npad, st);
+// ---- the steps of the blocked pipeline, in launch order (obj_steps) ---------------------------------------------------------
+// the MLP basis, the augmented rows, the Kumaraswamy forward
+void step_features(ObjState& s) {
+  hbo_ctx* c = s.c; hbo_dataset* ds = s.ds; const ObjPlan& p = s.p;
+  if (c->opt_poison) launch_poison(p.dtype, ds->d_desc, p.T, p.max_npad, c->stream);
   {
     ProfScope ps(c, "features", 1);
-    if (needs_mlp(m)) mlp_forward();
-    launch_aug_rows(dtype, ds->d_desc, T, max_npad, c->d_model, st);
+    if (p.mlp) enqueue_mlp_forward(c, s.m, ds, p.max_n);
+    launch_aug_rows(p.dtype, ds->d_desc, p.T, p.max_npad, c->d_model, c->stream);
   }
-  if (kumar) { ProfScope ps(c, "kumar_forward", 1); kumar_forward(); }
-  int max_naug = 1;
-  for (int k = 0; k < T; ++k) max_naug = std::max(max_naug, ds->h_desc[k].naug);
-  TrtriProgress trtri_pg;
-  SweepState sweep_st;
-  hipStream_t side = st; hipEvent_t ev_side = nullptr;
-  const bool la = use_lookahead(c, T, max_nblk);
-  // the inverse and K^-1 behind the panel chain, row group by row group (sched.hip:sweep_advance) -- or the block-recursive
-  // inverse started beside the chain and K^-1 = W^T W after it
-  const bool sweep = want_grad && !euc && use_sweep(c, dtype, T, max_nblk);
-  if (sweep) sweep_st.qs = c->opt_sweep_qs > 0 ? c->opt_sweep_qs : sweep_group(T, max_nblk);
-  const bool early_trtri = !sweep && want_grad && use_early_trtri(c, T, max_nblk);
-  if (!euc) {
-    {
-      ProfScope ps(c, "gram", 1);
-      GramArgs g = {}; g.kernel_id = c->h_model->kernel_id; g.mfma_min_f = c->opt_gram_mfma; g.tasks = ds->d_desc; g.fdim = feature_dim(m); g.symmetric = 1; g.padded = 1;
-      launch_gram(dtype, g, c->d_model, dim3(max_nblk, max_nblk, T), st);
-    }
-    {
-      c->trtri_host_task = TaskDesc{};
-      if (T == 1) c->trtri_host_task = ds->h_desc[0];
-      c->run.chol_diag_bound = chol_diag_bound_of(m);   // (cleared where the evaluation leaves: bound_scope)
-      ProfScope ps(c, "potrf", 1); run_potrf(c, dtype, ds->d_desc, T, max_nblk, ds->d_info, early_trtri ? &trtri_pg : nullptr, sweep ? &sweep_st : nullptr);
-    }
-    // the small reductions (log-determinant + quadratic form now, alpha = W^T z and d nll / d mu after the inverse) run on
-    // the idle panel stream beside the inverse and K^-1 = W^T W instead of between them (0.14 ms at cfg 2)
-    side = (want_grad && obj == OBJ_NLL && la) ? c->stream2 : st;
-    if (side != st) { hipEvent_t e = pool_event(c, 2); hipEventRecord(e, st); hipStreamWaitEvent(side, e, 0); }
-    { ProfScope ps(c, "nll_reduce", 1, side); launch_nll_reduce(dtype, ds->d_desc, T, ds->d_info, ds->d_nll, side); }
+  if (p.kumar) { ProfScope ps(c, "kumar_forward", 1); enqueue_kumar_forward(c, s.m, ds, p.max_n); }
+}
+// the Gram matrices and their blocked factorisation, with the inverse beside or behind the chain where the plan says so
+void step_factor(ObjState& s) {
+  hbo_ctx* c = s.c; hbo_dataset* ds = s.ds; const ObjPlan& p = s.p;
+  if (p.sweep) s.sweep_st.qs = p.qs;
+  {
+    ProfScope ps(c, "gram", 1);
+    GramArgs g = {}; g.kernel_id = c->h_model->kernel_id; g.mfma_min_f = c->opt_gram_mfma; g.tasks = ds->d_desc; g.fdim = p.fdim; g.symmetric = 1; g.padded = 1;
+    launch_gram(p.dtype, g, c->d_model, dim3(p.max_nblk, p.max_nblk, p.T), c->stream);
   }
+  c->trtri_host_task = TaskDesc{};
+  if (p.T == 1) c->trtri_host_task = ds->h_desc[0];
+  c->run.chol_diag_bound = chol_diag_bound_of(s.m);   // (cleared where the evaluation leaves: objective_local's bound_scope)
+  ProfScope ps(c, "potrf", 1);
+  run_potrf(c, p.dtype, ds->d_desc, p.T, p.max_nblk, ds->d_info, p.early_trtri ? &s.trtri_pg : nullptr, p.sweep ? &s.sweep_st : nullptr);
+}
+// the fork to the side stream (where the plan sends the small reductions there) and the first of them
+void step_reduce(ObjState& s) {
+  hbo_ctx* c = s.c; hbo_dataset* ds = s.ds; const ObjPlan& p = s.p;
+  hipStream_t st = c->stream;
+  s.side = p.side_reduce ? c->stream2 : st;
+  if (s.side != st) { hipEvent_t e = pool_event(c, 2); hipEventRecord(e, st); hipStreamWaitEvent(s.side, e, 0); }
+  ProfScope ps(c, "nll_reduce", 1, s.side);
+  launch_nll_reduce(p.dtype, ds->d_desc, p.T, ds->d_info, ds->d_nll, s.side);
+}
+// W = L^-1 and K^-1 in either form, alpha = W^T z and (side stream) d nll / d mu beside them
+void step_inverse(ObjState& s) {
+  hbo_ctx* c = s.c; hbo_dataset* ds = s.ds; const ObjPlan& p = s.p;
+  hipStream_t st = c->stream, side = s.side;
+  hipEvent_t w_done = side != st ? pool_event(c, 3) : nullptr;   // W is complete
+  if (p.sweep) {
+    // what the chain left: the last row group(s).  W is complete behind the last group's rows (event), K^-1 behind its update
+    ProfScope ps(c, "sweep_tail", 1);
+    sweep_advance(c, p.dtype, ds->d_desc, p.T, p.max_nblk, p.max_nblk, st, s.sweep_st, w_done);
+  } else {
+    { ProfScope ps(c, "trtri", 1);
+      run_trtri(c, p.dtype, ds->d_desc, p.T, p.max_nblk, &s.trtri_pg); }
+    if (w_done) hipEventRecord(w_done, st);
+  }
+  if (w_done) hipStreamWaitEvent(side, w_done, 0);
+  { ProfScope ps(c, "wt_z", 1, side);
+    for (int b = 0; b < s.max_naug; ++b) launch_wt_z(p.dtype, ds->d_desc, p.T, p.max_nblk, b, b, p.max_npad, side); }
+  if (side != st) {
+    launch_dmu(p.dtype, ds->d_desc, p.T, p.obj, side);
+    s.ev_side = pool_event(c, 4); hipEventRecord(s.ev_side, side);
+  }
+  // One sequence for both forms: record; [K^-1 = W^T W of the recursive form]; the main stream's wait.  The sweep has its K^-1
+  // already and queues nothing on the main stream between the record and the wait, so its wait follows the record at once.
+  if (!p.sweep) { ProfScope ps(c, "lauum", 1); run_lauum(c, p.dtype, ds->d_desc, p.T, p.max_nblk); }
+  if (s.ev_side) hipStreamWaitEvent(st, s.ev_side, 0);
+}
+// the data rows of tasks with more than 127 aligned columns, as outer-product vectors in svec columns 1..m (objectives.py:29-106
+// has no limit on m).  EUC: the rows themselves.  EKL: tr(K1^-1 C0) = sum_b |W row_b|^2 and alpha_b = W^T W row_b from the explicit
+// inverse (two triangular products over all m rows), the quadratic forms added to the task's value.  Main stream, W complete.
+int step_extra_rows(ObjState& s) {
+  hbo_ctx* c = s.c; hbo_dataset* ds = s.ds;
+  const int T = s.p.T, dtype = s.p.dtype; const bool euc = s.p.euc;
+  hipStream_t st = c->stream;
+  ProfScope ps(c, "extra_rows", 1);
+  // one scratch buffer for the largest of them, taken BEFORE the loop: growing it between two tasks would free memory that the
+  // first task's queued products still read
+  size_t zbytes = 0;
+  if (!euc) for (int k = 0; k < T; ++k) if (ds->h_desc[k].nvec) zbytes = std::max(zbytes, (size_t)ds->tasks[k]->m * ds->tasks[k]->npad * esize(dtype));
+  void* const zb = zbytes ? ws_get(c, WS_EXTRA_Z, zbytes) : nullptr;
+  if (zbytes && !zb) return HBO_ERR_HIP;
+  for (int k = 0; k < T; ++k) {
+    if (!ds->h_desc[k].nvec) continue;
+    TaskHost* t = ds->tasks[k];
+    const size_t es = esize(dtype);
+    char* cols = static_cast<char*>(t->svec) + (size_t)t->npad * es;   // column 1
+    launch_expand_rows(dtype, t->ydiv, t->n, t->npad, cols, t->m, st);
+    if (euc) continue;
+    launch_tri_matvec(dtype, t->W, t->ld, t->npad, cols, t->npad, t->m, 0, zb, t->npad, st);
+    launch_add_sumsq(dtype, zb, t->npad, t->m, ds->h_desc[k].coef_c, ds->d_nll + k, st);
+    launch_tri_matvec(dtype, t->W, t->ld, t->npad, zb, t->npad, t->m, 1, cols, t->npad, st);
+  }
+  return HBO_OK;
+}
+// d f / d mu (where the side stream has not done it), the per-tile contraction and its finalisation into the tasks' gradient blocks
+void step_contract(ObjState& s) {
+  hbo_ctx* c = s.c; const hbo_model* m = s.m; hbo_dataset* ds = s.ds; const ObjPlan& p = s.p;
+  hipStream_t st = c->stream;
+  ProfScope ps(c, "grad_contract", 1);
+  if (!s.ev_side) launch_dmu(p.dtype, ds->d_desc, p.T, p.obj, st);
+  launch_grad_contract(p.dtype, ds->d_desc, p.T, p.max_nblk, c->d_model, m->kernel_id, p.fdim, p.obj, ds->d_partials, p.stride_task, st);
+  launch_grad_finalize(p.dtype, ds->d_desc, p.T, c->d_model, m->kernel_id, p.fdim, p.obj, ds->d_partials, p.stride_task, ds->d_gradout, p.out_stride, p.euc ? ds->d_nll : nullptr, st,
+                       ds->d_partials + p.stride_task * p.T, p.max_nblk);
+}
+// the blocked pipeline: what a batch runs that does not take the single-workgroup evaluation
+int obj_steps(ObjState& s) {
+  hbo_ctx* c = s.c; hbo_dataset* ds = s.ds; const ObjPlan& p = s.p;
+  s.side = c->stream;
+  step_features(s);
+  if (!p.euc) { step_factor(s); step_reduce(s); }
+  if (p.value_inverse) {
+    { ProfScope ps(c, "trtri", 1); run_trtri(c, p.dtype, ds->d_desc, p.T, p.max_nblk, &s.trtri_pg); }
+    if (int rc = step_extra_rows(s)) return rc;
+  }
+  if (!p.contract) return HBO_OK;
+  if (ds->partials_bytes < p.partials_bytes) { if (ds->d_partials) dev_free(c, ds->d_partials); HIPCHK(c, dev_alloc(c, (void**)&ds->d_partials, p.partials_bytes)); ds->partials_bytes = p.partials_bytes; }
+  if (!p.euc) step_inverse(s);
+  if (p.extras) if (int rc = step_extra_rows(s)) return rc;
+  step_contract(s);
+  return HBO_OK;
+}
 
-  // the data rows of tasks with more than 127 aligned columns, as outer-product vectors in svec columns 1..m (objectives.py:29-106
-  // has no limit on m).  EUC: the rows themselves.  EKL: tr(K1^-1 C0) = sum_b |W row_b|^2 and alpha_b = W^T W row_b from the explicit
-  // inverse (two triangular products over all m rows), the quadratic forms added to the task's value.  Main stream, W complete.
-  auto extra_rows = [&]() -> int {
-    // one scratch buffer for the largest of them, taken BEFORE the loop: growing it between two tasks would free memory that the
-    // first task's queued products still read
-    size_t zbytes = 0;
-    if (!euc) for (int k = 0; k < T; ++k) if (ds->h_desc[k].nvec) zbytes = std::max(zbytes, (size_t)ds->tasks[k]->m * ds->tasks[k]->npad * esize(dtype));
-    void* const zb = zbytes ? ws_get(c, WS_EXTRA_Z, zbytes) : nullptr;
-    if (zbytes && !zb) return HBO_ERR_HIP;
-    for (int k = 0; k < T; ++k) {
-      if (!ds->h_desc[k].nvec) continue;
-      TaskHost* t = ds->tasks[k];
-      const size_t es = esize(dtype);
-      char* cols = static_cast<char*>(t->svec) + (size_t)t->npad * es;   // column 1
-      launch_expand_rows(dtype, t->ydiv, t->n, t->npad, cols, t->m, st);
-      if (euc) continue;
-      launch_tri_matvec(dtype, t->W, t->ld, t->npad, cols, t->npad, t->m, 0, zb, t->npad, st);
-      launch_add_sumsq(dtype, zb, t->npad, t->m, ds->h_desc[k].coef_c, ds->d_nll + k, st);
-      launch_tri_matvec(dtype, t->W, t->ld, t->npad, zb, t->npad, t->m, 1, cols, t->npad, st);
-    }
-    return HBO_OK;
-  };
-  if (extras && !euc && !want_grad) {   // value only: the inverse is needed for the extra rows all the same
-    { ProfScope ps(c, "trtri", 1); run_trtri(c, dtype, ds->d_desc, T, max_nblk, &trtri_pg); }
-    ProfScope ps(c, "extra_rows", 1);
-    rc = extra_rows(); if (rc) return rc;
-  }
-  const int fdim = feature_dim(m);
-  const int nacc = grad_nacc(m->kernel_id, fdim);
-  const int64_t stride_task = (int64_t)(max_nblk * (max_nblk + 1)) * nacc;   // two half-tile slots per lower tile
-  if (want_grad || euc) {   // EUC: the Frobenius norm of the value comes out of the contraction pass
-    const size_t pb = sizeof(double) * (stride_task * T + (size_t)HBO_GRAD_PRE_ROWS * nacc * T);   // per-tile partials + their pre-reduction
-    if (ds->partials_bytes < pb) { if (ds->d_partials) dev_free(c, ds->d_partials); HIPCHK(c, dev_alloc(c, (void**)&ds->d_partials, pb)); ds->partials_bytes = pb; }
-    if (!euc && sweep) {
-      // what the chain left: the last row group(s).  W is complete behind the last group's rows (event), K^-1 behind its update
-      hipEvent_t e = side != st ? pool_event(c, 3) : nullptr;
-      { ProfScope ps(c, "sweep_tail", 1);
-        sweep_advance(c, dtype, ds->d_desc, T, max_nblk, max_nblk, st, sweep_st, e); }
-      if (side != st) hipStreamWaitEvent(side, e, 0);
-      { ProfScope ps(c, "wt_z", 1, side);
-        for (int b = 0; b < max_naug; ++b) launch_wt_z(dtype, ds->d_desc, T, max_nblk, b, b, max_npad, side); }
-      if (side != st) {
-        launch_dmu(dtype, ds->d_desc, T, obj, side);
-        ev_side = pool_event(c, 4); hipEventRecord(ev_side, side);
-        hipStreamWaitEvent(st, ev_side, 0);
-      }
-    } else if (!euc) {
-      { ProfScope ps(c, "trtri", 1);
-        run_trtri(c, dtype, ds->d_desc, T, max_nblk, &trtri_pg); }
-      if (side != st) { hipEvent_t e = pool_event(c, 3); hipEventRecord(e, st); hipStreamWaitEvent(side, e, 0); }   // W is complete
-      { ProfScope ps(c, "wt_z", 1, side);
-        for (int b = 0; b < max_naug; ++b) launch_wt_z(dtype, ds->d_desc, T, max_nblk, b, b, max_npad, side); }
-      if (side != st) {
-        launch_dmu(dtype, ds->d_desc, T, obj, side);
-        ev_side = pool_event(c, 4); hipEventRecord(ev_side, side);
-      }
-      { ProfScope ps(c, "lauum", 1); run_lauum(c, dtype, ds->d_desc, T, max_nblk); }
-      if (ev_side) hipStreamWaitEvent(st, ev_side, 0);
-    }
-    if (extras) { ProfScope ps(c, "extra_rows", 1); rc = extra_rows(); if (rc) return rc; }
-    { ProfScope ps(c, "grad_contract", 1);
-      if (!ev_side) launch_dmu(dtype, ds->d_desc, T, obj, st);
-      launch_grad_contract(dtype, ds->d_desc, T, max_nblk, c->d_model, m->kernel_id, fdim, obj, ds->d_partials, stride_task, st);
-      launch_grad_finalize(dtype, ds->d_desc, T, c->d_model, m->kernel_id, fdim, obj, ds->d_partials, stride_task, ds->d_gradout, out_stride, euc ? ds->d_nll : nullptr, st,
-                           ds->d_partials + stride_task * T, max_nblk); }
-  }
-  }   // !fused_small
-  rc = enqueue_backward(c, m, ds, max_n, obj, want_grad);
-  if (rc) return rc;
-  if (sh) {
-    // [nll, count, grad] of this rank's tasks in the caller's gradient layout, on the device: entry j of a task's gradient block
-    // goes to map[j] (the scatter the host loop below does), the MLP gradient -- already summed over the tasks -- by segments
-    const int n_ls = m->kernel_id == HBO_KERNEL_DOT ? 0 : m->n_lengthscale;
-    const int fm = mean_feature_dim(m);
-    std::vector<int> hmap(out_stride + 3 * 2 * HBO_MAX_MLP_LAYERS, -1);
-    if (want_grad) {
-      for (int d = 0; d < n_ls; ++d) hmap[d] = lay.lengthscale < 0 ? -1 : lay.lengthscale + d;
-      hmap[n_ls] = lay.signal_variance; hmap[n_ls + 1] = lay.noise_variance; hmap[n_ls + 2] = lay.constant;
-      hmap[n_ls + 3] = lay.dot_prod_sigma; hmap[n_ls + 4] = lay.dot_prod_bias;
-      for (int d = 0; d < fm; ++d) hmap[n_ls + 5 + d] = lay.linear_kernel < 0 ? -1 : lay.linear_kernel + d;
-      hmap[n_ls + 5 + fm] = lay.linear_bias;
-    }
-    int nseg = 0;
-    if (want_grad && kumar) {   // the 2 D Kumaraswamy leaves, already summed over the tasks
-      int32_t ao = -1, bo = -1;
-      hbo_grad_layout_kumar_of(m, &ao, &bo);
-      int* sg = hmap.data() + out_stride;
-      sg[0] = ao; sg[1] = 0; sg[2] = m->input_dim; sg[3] = bo; sg[4] = m->input_dim; sg[5] = m->input_dim; nseg = 2;
-    }
-    if (want_grad && needs_mlp(m)) {
-      int pos = 0, fin0 = m->input_dim;
-      for (int l = 0; l < m->n_layers; ++l) {
-        const int wn = fin0 * m->features[l], bn = m->features[l];
-        int* sg = hmap.data() + out_stride + 3 * nseg;
-        sg[0] = lay.mlp_kernel[l]; sg[1] = pos; sg[2] = wn; ++nseg; pos += wn;
-        sg += 3; sg[0] = lay.mlp_bias[l]; sg[1] = pos; sg[2] = bn; ++nseg; pos += bn;
-        fin0 = m->features[l];
-      }
-    }
-    int* d_map = static_cast<int*>(ws_get(c, WS_SHARD_MAP, sizeof(int) * hmap.size()));
-    double* d_red = static_cast<double*>(ws_get(c, WS_SHARD_RED, sizeof(double) * red_count));
-    if (!d_map || !d_red) return HBO_ERR_HIP;
-    stage = static_cast<unsigned char*>(stage_begin(c, "hbo_objective: ", sizeof(int) * hmap.size()));
-    if (!stage) return HBO_ERR_HIP;
-    memcpy(stage, hmap.data(), sizeof(int) * hmap.size());
-    HIPCHK(c, stage_upload(c, d_map, stage, sizeof(int) * hmap.size(), st));
-    launch_shard_reduce(ds->d_nll, want_grad ? ds->d_gradout : nullptr, ds->d_info, T, out_stride, d_map, ds->d_mlpgrad, d_map + out_stride, nseg,
-                        d_red, red_count, st);
-    hipEvent_t ev1 = pool_event_timed(c, 1);
-    HIPCHK(c, hipEventRecord(ev1, st));
-    HIPCHK(c, hipGetLastError());
-    so->d_red = d_red; so->ev0 = ev_sh0; so->ev1 = ev1;
-    so->d_map = d_map; so->nseg = nseg; so->out_stride = out_stride;
-    return HBO_OK;
-  }
-  HIPCHK(c, hipMemcpyAsync(stage, ds->d_pack, pack_bytes, hipMemcpyDeviceToHost, st));
-  const double* h_nll = reinterpret_cast<const double*>(stage);
+// sharded: [nll, count, grad] of this rank's tasks in the caller's gradient layout, on the device, with the scatter table uploaded in
+// its device format (api_internal.h: GradScatter); returns without waiting
+int obj_shard_reduce(ObjState& s, const GradScatter& tab, hipEvent_t ev_sh0, ShardOut* so) {
+  hbo_ctx* c = s.c; hbo_dataset* ds = s.ds; const ObjPlan& p = s.p;
+  hipStream_t st = c->stream;
+  int* d_map = static_cast<int*>(ws_get(c, WS_SHARD_MAP, tab.bytes()));
+  double* d_red = static_cast<double*>(ws_get(c, WS_SHARD_RED, sizeof(double) * p.red_count));
+  if (!d_map || !d_red) return HBO_ERR_HIP;
+  s.stage = static_cast<unsigned char*>(stage_begin(c, "hbo_objective: ", tab.bytes()));
+  if (!s.stage) return HBO_ERR_HIP;
+  memcpy(s.stage, tab.w, tab.bytes());
+  HIPCHK(c, stage_upload(c, d_map, s.stage, tab.bytes(), st));
+  launch_shard_reduce(ds->d_nll, p.want_grad ? ds->d_gradout : nullptr, ds->d_info, p.T, p.out_stride, d_map, ds->d_mlpgrad, d_map + p.out_stride, tab.nseg,
+                      d_red, p.red_count, st);
+  hipEvent_t ev1 = pool_event_timed(c, 1);
+  HIPCHK(c, hipEventRecord(ev1, st));
+  HIPCHK(c, hipGetLastError());
+  so->d_red = d_red; so->ev0 = ev_sh0; so->ev1 = ev1;
+  so->d_map = d_map; so->nseg = tab.nseg; so->out_stride = p.out_stride;
+  return HBO_OK;
+}
+// not sharded: results down in one copy through the pinned buffer (and the summed leaves in one more), one wait, the host finish
+int obj_copy_back(ObjState& s, const GradScatter& tab, std::chrono::steady_clock::time_point host_t0, double* nll_sum, double* nll_per_task, double* grad_sum) {
+  hbo_ctx* c = s.c; hbo_dataset* ds = s.ds; const ObjPlan& p = s.p;
+  const int T = p.T;
+  hipStream_t st = c->stream;
+  HIPCHK(c, hipMemcpyAsync(s.stage, ds->d_pack, p.pack_bytes, hipMemcpyDeviceToHost, st));
+  const double* h_nll = reinterpret_cast<const double*>(s.stage);
   const double* h_grad = h_nll + T;
-  const int* h_info = reinterpret_cast<const int*>(h_grad + (size_t)T * out_stride);
+  const int* h_info = reinterpret_cast<const int*>(h_grad + (size_t)T * p.out_stride);
   std::vector<double> h_mlp;
-  if (want_grad && (needs_mlp(m) || kumar)) {
+  if (tab.nseg) {
     h_mlp.resize(ds->mlpgrad_elems);
     HIPCHK(c, hipMemcpyAsync(h_mlp.data(), ds->d_mlpgrad, sizeof(double) * ds->mlpgrad_elems, hipMemcpyDeviceToHost, st));
   }
@@ -410,42 +357,52 @@ int objective_local(hbo_ctx* c, const hbo_model* m_in, hbo_dataset* ds, int obje
   double total = 0;
   for (int k = 0; k < T; ++k) { total += h_nll[k]; if (h_info[k] != INT_MAX) notpd = true; if (nll_per_task) nll_per_task[k] = h_nll[k]; }
   *nll_sum = total;
-  if (want_grad) {
-    const int n_ls = m->kernel_id == HBO_KERNEL_DOT ? 0 : m->n_lengthscale;
-    const int fm = mean_feature_dim(m);
-    for (int k = 0; k < T; ++k) {
-      const double* o = h_grad + (size_t)k * out_stride;
-      const bool bad = h_info[k] != INT_MAX;
-      auto add = [&](int off, double v) { if (off >= 0) grad_sum[off] += bad ? NAN : v; };
-      for (int d = 0; d < n_ls; ++d) add(lay.lengthscale < 0 ? -1 : lay.lengthscale + d, o[d]);
-      add(lay.signal_variance, o[n_ls]);
-      add(lay.noise_variance, o[n_ls + 1]);
-      add(lay.constant, o[n_ls + 2]);
-      add(lay.dot_prod_sigma, o[n_ls + 3]);
-      add(lay.dot_prod_bias, o[n_ls + 4]);
-      for (int d = 0; d < fm; ++d) add(lay.linear_kernel + d, o[n_ls + 5 + d]);
-      add(lay.linear_bias, o[n_ls + 5 + fm]);
-    }
-    if (needs_mlp(m)) {
-      size_t pos = 0; int fin0 = m->input_dim;
-      for (int l = 0; l < m->n_layers; ++l) {
-        const size_t wn = (size_t)fin0 * m->features[l], bn = m->features[l];
-        for (size_t i = 0; i < wn; ++i) grad_sum[lay.mlp_kernel[l] + i] = notpd ? NAN : h_mlp[pos + i];
-        pos += wn;
-        for (size_t i = 0; i < bn; ++i) grad_sum[lay.mlp_bias[l] + i] = notpd ? NAN : h_mlp[pos + i];
-        pos += bn; fin0 = m->features[l];
-      }
-    }
-    if (kumar) {
-      int32_t ao = -1, bo = -1;
-      hbo_grad_layout_kumar_of(m, &ao, &bo);
-      for (int d = 0; d < m->input_dim; ++d) {
-        grad_sum[ao + d] = notpd ? NAN : h_mlp[d];
-        grad_sum[bo + d] = notpd ? NAN : h_mlp[m->input_dim + d];
-      }
-    }
-  }
+  if (p.want_grad) grad_scatter_host(tab, T, h_grad, h_info, h_mlp.data(), notpd, grad_sum);
   return notpd ? HBO_NOT_PD : HBO_OK;
+}
+}  // namespace
+
+int objective_local(hbo_ctx* c, const hbo_model* m_in, hbo_dataset* ds, int objective, double* nll_sum,
+                    double* nll_per_task, double* grad_sum, const ShardReq* sh, ShardOut* so) {
+  if (!c || !nll_sum || !m_in || (!ds && !sh)) return fail(c, HBO_ERR_ARG, "hbo_objective: null argument");
+  if (objective != HBO_OBJ_NLL && objective != HBO_OBJ_EKL && objective != HBO_OBJ_EUC) return fail(c, HBO_ERR_ARG, "hbo_objective: unknown objective id");
+  HIPCHK(c, hipSetDevice(c->device));
+  ModelCopy mcopy(m_in);   // (a Kumaraswamy model keeps its a, b)
+  if (objective != HBO_OBJ_NLL) mcopy.get()->eps = 0.0;   // objectives.py:63-65: cov_model = K + noise I, no jitter
+  const hbo_model* m = mcopy.get();
+  CholBoundScope bound_scope(c, 0.0);   // (set where the factorisation starts; cleared on every way out)
+  int rc = validate_model(c, m);
+  if (rc) return rc;
+  if (ds && ds->ntasks > 0 && (m->dtype != ds->dtype || m->input_dim != ds->D)) return fail(c, HBO_ERR_ARG, "hbo_objective: model/dataset dtype or input_dim mismatch");
+  hbo_grad_layout lay;
+  hbo_grad_layout_of(m, &lay);
+  const bool want_grad = grad_sum != nullptr;
+  *nll_sum = 0;
+  if (want_grad) for (int i = 0; i < lay.total; ++i) grad_sum[i] = 0;
+  ObjState s = {c, m, ds, obj_plan(c, m, ds, lay, objective, want_grad, sh != nullptr)};
+  const ObjPlan& p = s.p;
+  if (so) so->red_count = p.red_count;
+  if (p.T == 0) return sh ? obj_empty_rank(c, p.red_count, so) : HBO_OK;
+  if (p.obj != OBJ_NLL) for (TaskHost* t : ds->tasks) if (!t->ydiv) return fail(c, HBO_ERR_ARG, "hbo_objective: the dataset carries no divergence rows");
+  prof_begin(c);
+  const auto host_t0 = std::chrono::steady_clock::now();   // host time spent queueing this evaluation (stage "host_enqueue", level 1)
+  hipEvent_t ev_sh0 = nullptr;
+  if (sh) { ev_sh0 = pool_event_timed(c, 0); HIPCHK(c, hipEventRecord(ev_sh0, c->stream)); }
+  rc = upload_model(c, m);
+  if (rc) return rc;
+  rc = obj_setup(s);
+  if (rc) return rc;
+  if (p.fused_small) enqueue_fused_forward(c, m, ds, p.max_n, p.out_stride, want_grad);
+  else if ((rc = obj_steps(s))) return rc;
+  rc = enqueue_backward(c, m, ds, p.max_n, p.obj, want_grad);
+  if (rc) return rc;
+  // where the gradient goes in the caller's layout: ONE table for the device reduction and for the host finish
+  int32_t kumar_a = -1, kumar_b = -1;
+  if (p.kumar) hbo_grad_layout_kumar_of(m, &kumar_a, &kumar_b);
+  GradScatter tab;
+  grad_scatter_fill(tab, m, lay, kumar_a, kumar_b, p.out_stride, want_grad);
+  if (sh) return obj_shard_reduce(s, tab, ev_sh0, so);
+  return obj_copy_back(s, tab, host_t0, nll_sum, nll_per_task, grad_sum);
 }
 static int objective_impl(hbo_ctx* c, const hbo_model* m_in, hbo_dataset* ds, int objective, double* nll_sum,
                           double* nll_per_task, double* grad_sum, const ShardReq* sh) {
