@@ -605,17 +605,18 @@ extern "C" int hbo_spd_solve(hbo_ctx* c, int dtype, const void* a, int64_t n, co
   HIPCHK_OR(c, hipMemcpyAsync(d_desc, &h, sizeof h, hipMemcpyHostToDevice, st), cleanup());
   HIPCHK_OR(c, hipMemcpyAsync(d_info, &inf, sizeof(int), hipMemcpyHostToDevice, st), cleanup());
   HIPCHK_OR(c, hipStreamSynchronize(st), cleanup());
-  c->trtri_host_task = h;
   // hbo_tune "spd_diag_bound" (test hook): max_i A_ii off the caller's matrix -- what potrf_plan, trtri_level3 and run_lauum need to
   // take the f16x2 form, as hbo_factor does from the model's signal variance.  Default: 0 = unknown, the bf16x3 form
   double diag_bound = 0;
   if (c->opt_spd_diag_bound) for (int64_t i = 0; i < n; ++i) diag_bound = std::max(diag_bound, host_elem(a, dtype, i * n + i));
   CholBoundScope bound_scope(c, diag_bound);
-  { ProfScope ps(c, "potrf", 1); run_potrf(c, dtype, d_desc, 1, t->nblk, d_info); }
+  // (the inverse and K^-1 = W^T W behind the factorisation, nothing beside it)
+  InvRun inv = inv_run(c, dtype, d_desc, 1, t->nblk, &h, inv_out ? INV_W_KINV : (need_inv ? INV_W : INV_NONE), false);
+  { ProfScope ps(c, "potrf", 1); run_potrf(c, dtype, d_desc, 1, t->nblk, d_info, &inv); }
   if (need_inv) {
-    { ProfScope ps(c, "trtri", 1); run_trtri(c, dtype, d_desc, 1, t->nblk); }
+    { ProfScope ps(c, "trtri", 1); run_trtri(inv); }
     if (x_out && b) for (int col = 0; col < mcols; ++col) launch_wt_z(dtype, d_desc, 1, t->nblk, col, col, t->npad, st);
-    if (inv_out) { ProfScope ps(c, "lauum", 1); run_lauum(c, dtype, d_desc, 1, t->nblk); }
+    if (inv_out) { ProfScope ps(c, "lauum", 1); run_lauum(inv); }
   }
   HIPCHK_OR(c, hipMemcpyAsync(&inf, d_info, sizeof(int), hipMemcpyDeviceToHost, st), cleanup());
   HIPCHK_OR(c, hbo_malloc(c, &d_tmp, (size_t)n * n * es), cleanup());

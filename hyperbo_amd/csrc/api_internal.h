@@ -561,7 +561,7 @@ struct ObjPlan {
   bool euc, kumar, mlp, extras;
   bool small_ok, fused_small, lds_only;
   bool need_S;                 // the tasks' workspaces include S (K^-1, or the sweep's running matrix)
-  bool la, sweep, early_trtri; int qs;   // look-ahead; the one-sweep inverse and its row group; the recursive inverse started beside the chain
+  bool la; InvPlan inv;        // look-ahead; the route and placement of the inverse (sched.h: inv_plan)
   bool side_reduce;            // the small reductions on the idle panel stream
   bool value_inverse;          // a value-only call that needs the inverse for its extra rows
   bool contract;               // the gradient contraction runs (EUC: its value comes out of it too)
@@ -595,14 +595,12 @@ static ObjPlan obj_plan(const hbo_ctx* c, const hbo_model* m, const hbo_dataset*
   p.need_S = (want_grad || p.extras) && !p.euc;
   p.la = use_lookahead(c, p.T, p.max_nblk);
   // the inverse and K^-1 behind the panel chain, row group by row group (sched.hip:sweep_advance) -- or the block-recursive
-  // inverse started beside the chain and K^-1 = W^T W after it
-  p.sweep = want_grad && !p.euc && use_sweep(c, p.dtype, p.T, p.max_nblk);
-  p.qs = !p.sweep ? 0 : (c->opt_sweep_qs > 0 ? c->opt_sweep_qs : sweep_group(p.T, p.max_nblk));
-  p.early_trtri = !p.sweep && want_grad && use_early_trtri(c, p.T, p.max_nblk);
+  // inverse started beside the chain and K^-1 = W^T W after it (a gradient); or W alone behind the factorisation (a value with extra rows)
+  p.value_inverse = p.extras && !p.euc && !want_grad;   // value only: the inverse is needed for the extra rows all the same
+  p.inv = inv_plan(c, p.dtype, p.T, p.max_nblk, (want_grad && !p.euc) ? INV_W_KINV : ((want_grad || p.value_inverse) ? INV_W : INV_NONE), p.T == 1, want_grad);
   // the small reductions (log-determinant + quadratic form now, alpha = W^T z and d nll / d mu after the inverse) run on
   // the idle panel stream beside the inverse and K^-1 = W^T W instead of between them (0.14 ms at cfg 2)
   p.side_reduce = want_grad && obj == OBJ_NLL && p.la;
-  p.value_inverse = p.extras && !p.euc && !want_grad;   // value only: the inverse is needed for the extra rows all the same
   p.contract = !p.fused_small && (want_grad || p.euc);   // EUC: the Frobenius norm of the value comes out of the contraction pass
   p.fdim = feature_dim(m);
   p.nacc = grad_nacc(m->kernel_id, p.fdim);

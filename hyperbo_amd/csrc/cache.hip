@@ -79,13 +79,11 @@ static int enqueue_factor(hbo_ctx* c, const FactorBatch& fb) {
     g.model_stride = fb.model_stride;
     launch_gram(dtype, g, fb.d_models, dim3(nblk, nblk, S), st); }
   // the inverse W = L^-1 (kept for the posterior products) starts beside the panel chain, as in the objective path
-  TrtriProgress trtri_pg;
-  const bool early_trtri = use_early_trtri(c, S, nblk);
-  c->trtri_host_task = S == 1 ? fb.ks[0]->h_desc : TaskDesc{};
+  InvRun inv = inv_run(c, dtype, fb.d_batch, S, nblk, S == 1 ? &fb.ks[0]->h_desc : nullptr, INV_W);
   CholBoundScope bound_scope(c, chol_diag_bound_of(fb.models, S));
-  { ProfScope ps(c, "potrf", 1); run_potrf(c, dtype, fb.d_batch, S, nblk, fb.d_infos, early_trtri ? &trtri_pg : nullptr); }
+  { ProfScope ps(c, "potrf", 1); run_potrf(c, dtype, fb.d_batch, S, nblk, fb.d_infos, &inv); }
   if (fb.keep_rows) HIPCHK(c, keep_aug(true));
-  { ProfScope ps(c, "trtri", 1); run_trtri(c, dtype, fb.d_batch, S, nblk, &trtri_pg); }
+  { ProfScope ps(c, "trtri", 1); run_trtri(inv); }
   { ProfScope ps(c, "wt_z", 1);
     for (int a = 0; a < mcols; ++a) launch_wt_z(dtype, fb.d_batch, S, nblk, a, a, npad, st); }
   return HBO_OK;

@@ -23,10 +23,10 @@ struct hbo_ctx {
   hipStream_t stream3 = nullptr;   // the later block columns of F1 (run_potrf: split_f1), beside the next diagonal block's factorisation and solve
   hipStream_t stream4 = nullptr;   // early part of trtri, overlapped with the tail of potrf
   int* d_yield = nullptr;    // per-CU table (cu_token() -> panel-chain workgroups running there)
-  TaskDesc trtri_host_task = {};   // host copy of the single task's descriptor (pointers, ld) for the bf16-core launches of the inverse; valid when .A != null
-  // What one factorisation hands to the schedules that run beside and behind it (sched.hip).  The callers of run_potrf set
-  // chol_diag_bound before it and clear it when the evaluation leaves (CholBoundScope; objective.hip); everything else is set by
-  // run_potrf.
+  // What one factorisation hands to the schedules that run beside and behind it (sched.hip): launch-time facts, which those
+  // combine with their plan (sched.h: InvPlan) where a launch is made.  The callers of run_potrf set chol_diag_bound before it and
+  // clear it when the evaluation leaves (CholBoundScope; objective.hip); everything else is set by run_potrf.  (The host copy of a
+  // single task's descriptor is no part of this: it travels in the caller's InvRun.)
   struct Run {
     double chol_diag_bound = 0;        // max_i A_ii (signal variance + noise + jitter), 0: unknown.  Read by run_potrf and trtri_level3 (the
                                        // a-priori scale of the f16x2 products); valid until the last product of the inverse
@@ -45,7 +45,7 @@ struct hbo_ctx {
   int opt_group_inner = -1;  // two-level panel groups: column updates on the chain inside inner groups of this many panels (0: one level; -1: auto, see potrf_plan)
   int opt_cu_yield = 2;      // background GEMM workgroups pause while a panel-chain workgroup runs on their CU (single matrix,
                              // look-ahead): 1 = potf2 only, 2 = trsm and the chain's column updates too
-  int opt_small_nblk = -1;   // matrices up to this many 128-blocks use 64x64 GEMM tiles in trtri / lauum / the sweep (-1: auto, sched.hip: small_limit)
+  int opt_small_nblk = -1;   // matrices up to this many 128-blocks use 64x64 GEMM tiles in trtri / lauum / the sweep (-1: auto, sched.h: small_limit)
   int opt_persist_free = -1; // bulk trailing update runs as 2*(CUs - this) persistent workgroups (-1: auto, see potrf_plan)
   int opt_trtri_bf16x3 = 1;    // fp32, one matrix: the products of the block-recursive inverse on the bf16 cores from level trtri3_min_s on
   int opt_trtri3_min_s = 8;

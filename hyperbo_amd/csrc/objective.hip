@@ -80,7 +80,7 @@ struct ObjState {
   hbo_ctx* c; const hbo_model* m; hbo_dataset* ds; ObjPlan p;
   unsigned char* stage = nullptr;   // the pinned buffer, at its final size (obj_setup)
   int max_naug = 1;                 // augmented rows of the largest task: needs the filled descriptors
-  TrtriProgress trtri_pg; SweepState sweep_st;
+  InvRun inv = {};                  // the inverse side of this evaluation (step_factor)
   hipStream_t side = nullptr;       // where the small reductions run: the panel stream, or the main one (step_reduce)
   hipEvent_t ev_side = nullptr;     // behind d nll / d mu on the side stream, once the main stream has been told to wait for it
 };
@@ -210,17 +210,15 @@ void step_features(ObjState& s) {
 // the Gram matrices and their blocked factorisation, with the inverse beside or behind the chain where the plan says so
 void step_factor(ObjState& s) {
   hbo_ctx* c = s.c; hbo_dataset* ds = s.ds; const ObjPlan& p = s.p;
-  if (p.sweep) s.sweep_st.qs = p.qs;
   {
     ProfScope ps(c, "gram", 1);
     GramArgs g = {}; g.kernel_id = c->h_model->kernel_id; g.mfma_min_f = c->opt_gram_mfma; g.tasks = ds->d_desc; g.fdim = p.fdim; g.symmetric = 1; g.padded = 1;
     launch_gram(p.dtype, g, c->d_model, dim3(p.max_nblk, p.max_nblk, p.T), c->stream);
   }
-  c->trtri_host_task = TaskDesc{};
-  if (p.T == 1) c->trtri_host_task = ds->h_desc[0];
+  s.inv = {c, p.dtype, ds->d_desc, p.T, p.max_nblk, p.T == 1 ? &ds->h_desc[0] : nullptr, p.inv};
   c->run.chol_diag_bound = chol_diag_bound_of(s.m);   // (cleared where the evaluation leaves: objective_local's bound_scope)
   ProfScope ps(c, "potrf", 1);
-  run_potrf(c, p.dtype, ds->d_desc, p.T, p.max_nblk, ds->d_info, p.early_trtri ? &s.trtri_pg : nullptr, p.sweep ? &s.sweep_st : nullptr);
+  run_potrf(c, p.dtype, ds->d_desc, p.T, p.max_nblk, ds->d_info, &s.inv);
 }
 // the fork to the side stream (where the plan sends the small reductions there) and the first of them
 void step_reduce(ObjState& s) {
@@ -236,13 +234,12 @@ void step_inverse(ObjState& s) {
   hbo_ctx* c = s.c; hbo_dataset* ds = s.ds; const ObjPlan& p = s.p;
   hipStream_t st = c->stream, side = s.side;
   hipEvent_t w_done = side != st ? pool_event(c, 3) : nullptr;   // W is complete
-  if (p.sweep) {
+  if (p.inv.sweep) {
     // what the chain left: the last row group(s).  W is complete behind the last group's rows (event), K^-1 behind its update
     ProfScope ps(c, "sweep_tail", 1);
-    sweep_advance(c, p.dtype, ds->d_desc, p.T, p.max_nblk, p.max_nblk, st, s.sweep_st, w_done);
+    sweep_advance(s.inv, p.max_nblk, st, w_done);
   } else {
-    { ProfScope ps(c, "trtri", 1);
-      run_trtri(c, p.dtype, ds->d_desc, p.T, p.max_nblk, &s.trtri_pg); }
+    { ProfScope ps(c, "trtri", 1); run_trtri(s.inv); }
     if (w_done) hipEventRecord(w_done, st);
   }
   if (w_done) hipStreamWaitEvent(side, w_done, 0);
@@ -254,7 +251,7 @@ void step_inverse(ObjState& s) {
   }
   // One sequence for both forms: record; [K^-1 = W^T W of the recursive form]; the main stream's wait.  The sweep has its K^-1
   // already and queues nothing on the main stream between the record and the wait, so its wait follows the record at once.
-  if (!p.sweep) { ProfScope ps(c, "lauum", 1); run_lauum(c, p.dtype, ds->d_desc, p.T, p.max_nblk); }
+  if (!p.inv.sweep) { ProfScope ps(c, "lauum", 1); run_lauum(s.inv); }
   if (s.ev_side) hipStreamWaitEvent(st, s.ev_side, 0);
 }
 // the data rows of tasks with more than 127 aligned columns, as outer-product vectors in svec columns 1..m (objectives.py:29-106
@@ -301,7 +298,7 @@ int obj_steps(ObjState& s) {
   step_features(s);
   if (!p.euc) { step_factor(s); step_reduce(s); }
   if (p.value_inverse) {
-    { ProfScope ps(c, "trtri", 1); run_trtri(c, p.dtype, ds->d_desc, p.T, p.max_nblk, &s.trtri_pg); }
+    { ProfScope ps(c, "trtri", 1); run_trtri(s.inv); }
     if (int rc = step_extra_rows(s)) return rc;
   }
   if (!p.contract) return HBO_OK;

@@ -162,7 +162,6 @@ extern "C" int hbo_nll_samples(hbo_ctx* c, const hbo_model* models, int32_t S, h
         GramArgs g = {}; g.kernel_id = m0->kernel_id; g.mfma_min_f = c->opt_gram_mfma; g.tasks = d_desc; g.fdim = fdim; g.symmetric = 1; g.padded = 1; g.model_stride = 1;
         launch_gram(dtype, g, d_mx, dim3(max_nblk, max_nblk, P), st); }
       CholBoundScope bound_scope(c, chol_diag_bound_of(models + s0, sc));
-      c->trtri_host_task = TaskDesc{};
       { ProfScope ps(c, "potrf", 1); run_potrf(c, dtype, d_desc, P, max_nblk, d_info); }
       { ProfScope ps(c, "nll_reduce", 1); launch_nll_reduce(dtype, d_desc, P, d_info, d_nll, st); }
     }

@@ -15,17 +15,10 @@
 
 #include "../hyperbo_amd/csrc/api_internal.h"
 
-// ---- link seams: what the plan and the table call that lives in translation units with device code, as it is defined there ----
+// ---- link seams: what the plan and the table call that lives in translation units with device code, as it is defined there
+// (the schedules' policy -- use_sweep, sweep_group, small_limit -- is sched.h's own: inv_plan) ----
+static bool use_early_trtri(const hbo_ctx* c, int ntasks, int max_nblk) { return use_lookahead(c, ntasks, max_nblk) && c->opt_overlap_trtri && max_nblk >= 4; }   // (before: sched.h)
 thread_local std::string hbo_g_err;
-static int small_limit(const hbo_ctx* c, int dtype) { return c->opt_small_nblk >= 0 ? c->opt_small_nblk : (dtype == HBO_F64 ? 48 : 32); }   // sched.hip
-bool use_sweep(const hbo_ctx* c, int dtype, int ntasks, int max_nblk) {   // sched.hip
-  if (!c->opt_sweep || !use_lookahead(c, ntasks, max_nblk) || max_nblk < 8) return false;
-  if (c->opt_sweep >= 2) return true;
-  if (ntasks == 1) return dtype == HBO_F64 && max_nblk > 16 && max_nblk <= 48;
-  if (dtype == HBO_F32 && ntasks == 1 && max_nblk > small_limit(c, dtype) && (c->opt_trtri_bf16x3 || c->opt_lauum_bf16x3)) return false;
-  return true;
-}
-int sweep_group(int ntasks, int max_nblk) { return (ntasks == 1 && max_nblk > 28) ? 8 : 4; }   // sched.hip
 int small_eval_lds(int dtype) { return dtype == HBO_F64 ? 132 * 1024 : 68 * 1024; }   // small.hip (to the KB: the plan only compares it with lds_per_block)
 int grad_nacc(int kernel_id, int fdim) { return (kernel_id == HBO_KERNEL_DOT ? 3 : 2 + fdim) + 1; }   // grad.hip
 extern "C" int hbo_grad_layout_of(const hbo_model* m, hbo_grad_layout* out) {   // api.hip
@@ -139,8 +132,8 @@ void check_plan(const hbo_ctx* c, const hbo_model* m, const hbo_dataset* ds, int
   const int fdim = feature_dim(m);
   const int nacc = grad_nacc(m->kernel_id, fdim);
   const int64_t stride_task = (int64_t)(max_nblk * (max_nblk + 1)) * nacc;
-  differ("la", la, p.la, where); differ("sweep", sweep, p.sweep, where); differ("early_trtri", early_trtri, p.early_trtri, where);
-  if (sweep) differ("qs", qs, p.qs, where);
+  differ("la", la, p.la, where); differ("sweep", sweep, p.inv.sweep, where); differ("early_trtri", early_trtri, p.inv.early, where);
+  if (sweep) differ("qs", qs, p.inv.qs, where);
   differ("side stream", side, p.side_reduce, where); differ("value_inverse", value_inverse, p.value_inverse, where);
   differ("fdim", fdim, p.fdim, where); differ("nacc", nacc, p.nacc, where); differ("stride_task", stride_task, p.stride_task, where);
   differ("contract", want_grad || euc, p.contract, where);
