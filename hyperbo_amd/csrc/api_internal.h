@@ -1,6 +1,6 @@
-// Host-side internals shared by the translation units of the C ABI (api.hip: context, options, datasets, dense entry points;
-// objective.hip: hbo_objective / hbo_objective_sharded; cache.hip: hbo_factor, row append, posterior, acquisition; acq_grad.hip: its
-// gradient): model validation and upload, the set-up the batched entry points share (model_family_check, mlp_shape, models_pack,
+// Host-side internals shared by the translation units of the C ABI (api.hip: context, options, profile, gradient layout; dataset.hip:
+// datasets; dense.hip: the dense entry points on host arrays; probe.hip: the hooks of include/hbo_tune.h; objective.hip: hbo_objective /
+// hbo_objective_sharded; cache.hip: hbo_factor, cache export, row append, posterior, acquisition; acq_grad.hip: its gradient): model validation and upload, the set-up the batched entry points share (model_family_check, mlp_shape, models_pack,
 // stage_begin / stage_upload), the MLP feature pipeline and the query-side features of everything that reads a factor
 // (query_features), the per-task device buffers and the descriptors the kernels read, the plans of a posterior call and of an
 // objective evaluation (post_plan, obj_plan: every decision, no HIP call), and the gradient scatter table of the objectives
@@ -199,7 +199,7 @@ struct ShardReq { double* count; double* timing; };
 struct ShardOut { double* d_red = nullptr; hipEvent_t ev0 = nullptr, ev1 = nullptr; int red_count = 0; int* d_map = nullptr; int nseg = 0; int out_stride = 0; };
 int objective_local(hbo_ctx* c, const hbo_model* m_in, hbo_dataset* ds, int objective, double* nll_sum, double* nll_per_task,
                     double* grad_sum, const ShardReq* sh, ShardOut* so);
-// one row gather of hbo_dataset_subsample (api.hip): row r of task blockIdx.y of the destination = row idx[idx_off + r] (or r) of
+// one row gather of hbo_dataset_subsample (dataset.hip): row r of task blockIdx.y of the destination = row idx[idx_off + r] (or r) of
 // the source task; hbo_train_adam points the destinations at a batch that already exists and overwrites its rows in place
 struct GatherTask { const void* sx; const void* sys; const void* syd; void* dx; void* dys; void* dyd; int64_t n_src, n_dst, idx_off; int m, has_idx; };
 void launch_gather_rows(int dtype, const GatherTask* tasks, const int32_t* idx, int T, int64_t max_dst, int D, hipStream_t st);
@@ -305,6 +305,10 @@ struct TaskHost {
   void* KW = nullptr; size_t kw_bytes = 0;     // Kumaraswamy: w(X), the covariance's features
   double* KH = nullptr; size_t kh_bytes = 0;   // Kumaraswamy gradient: dw/da, dw/db (n x D doubles each)
 };
+// the shape of a task of n points and m target columns: padded to whole 128-blocks
+static void task_shape(TaskHost* t, int64_t n, int m, int dtype) {
+  t->n = n; t->m = m; t->npad = round_up(n, HBO_TILE); t->nblk = t->npad / HBO_TILE; t->ld = padded_ld(t->npad, dtype);
+}
 struct hbo_dataset {
   int dtype = 0, D = 0, ntasks = 0, max_nblk = 0;
   std::vector<TaskHost*> tasks;
@@ -470,6 +474,18 @@ static void fill_nan(void* p, size_t count, int dtype) {
   if (dtype == HBO_F64) for (size_t i = 0; i < count; ++i) ((double*)p)[i] = NAN;
   else for (size_t i = 0; i < count; ++i) ((float*)p)[i] = NAN;
 }
+// Host arrays are [n][m] (column a of row i at i * m + a); the device keeps them as m rows of npad (at a * npad + i).  Both directions
+// copy the n x m elements and nothing else: what `dst` holds beyond them (the rows' padding) stays as it was.
+static void cols_to_rows(void* dst, const void* src, int64_t n, int m, int64_t npad, size_t es) {
+  for (int64_t i = 0; i < n; ++i) for (int a = 0; a < m; ++a) memcpy((unsigned char*)dst + ((size_t)a * npad + i) * es, (const unsigned char*)src + ((size_t)i * m + a) * es, es);
+}
+static void rows_to_cols(void* dst, const void* src, int64_t n, int m, int64_t npad, size_t es) {
+  for (int64_t i = 0; i < n; ++i) for (int a = 0; a < m; ++a) memcpy((unsigned char*)dst + ((size_t)i * m + a) * es, (const unsigned char*)src + ((size_t)a * npad + i) * es, es);
+}
+// the three launches of the fp32 posterior product on the 16-bit matrix cores (cache.hip), which hbo_probe_post_product runs too
+void post3_split_w(const float* W, int64_t ld, int nblk, bool h2, unsigned short* w3, unsigned int* d_wmax, hipStream_t st);
+void post3_split_kxq(const float* K, int64_t ldq, int mpad, int npad, bool h2, float kscale, unsigned short* K3, hipStream_t st);
+bool post3_product(const unsigned short* w3, const unsigned short* K3, int nblk, int mpad, bool h2, const unsigned int* d_wmax, float kscale, float* colsq, int64_t ldc, int* counter, hipStream_t st);
 
 // ---- posterior plan ------------------------------------------------------------------------
 // Every decision of one posterior / acquisition call (cache.hip: posterior), from sizes and options alone: no HIP call, no allocation.

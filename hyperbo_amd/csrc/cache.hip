@@ -1,14 +1,13 @@
 // GPCache side of the C ABI: hbo_factor (hyperbo/basics/linalg.py:72-110 behind gp.py:540-560), the O(N^2) row append, the
-// posterior behind hbo_predict (gp.py:242-305) and hbo_acq (acfun.py:36-142), and hbo_acq_samples, the batch form of factor plus
-// posterior.  (The acquisition gradient over a cache: acq_grad.hip; the simulated BO loop: bo_loop.hip.)
+// posterior behind hbo_predict (gp.py:242-305) and hbo_acq (acfun.py:36-142), hbo_acq_samples, the batch form of factor plus
+// posterior, and hbo_cache_export / hbo_cache_free.  (The acquisition gradient over a cache: acq_grad.hip; the simulated BO loop: bo_loop.hip.)
 #include "api_internal.h"
 
 // ---- one cache builder and one factor pipeline (hbo_factor: one cache; hbo_acq_samples: S of them as one batch) --------------------
 // y (n x m, host) as y^T (m x n), so that aug row a = column a of y
 static std::vector<unsigned char> transpose_y(const void* y, int64_t n, int mcols, size_t es) {
   std::vector<unsigned char> yt((size_t)n * mcols * es);
-  for (int64_t i = 0; i < n; ++i)
-    for (int a = 0; a < mcols; ++a) memcpy(yt.data() + ((size_t)a * n + i) * es, (const unsigned char*)y + ((size_t)i * mcols + a) * es, es);
+  cols_to_rows(yt.data(), y, n, mcols, n, es);
   return yt;
 }
 // A cache over n observations and m target columns with everything a factorisation and its readers need allocated, and its descriptor
@@ -19,7 +18,7 @@ static int cache_alloc(hbo_ctx* c, const hbo_model* m, int64_t n, int mcols, hbo
   hbo_cache* k = new hbo_cache();
   k->dtype = dtype; k->D = m->input_dim; k->m = mcols; k->input_warp = m->input_warp;
   TaskHost* t = k->t = new TaskHost();
-  t->n = n; t->m = mcols; t->npad = round_up(n, HBO_TILE); t->nblk = t->npad / HBO_TILE; t->ld = padded_ld(t->npad, dtype);
+  task_shape(t, n, mcols, dtype);
   auto bail = [&](int code) { hbo_cache_free(c, k); return code; };
   HIPCHK_OR(c, dev_alloc(c, &t->X, (size_t)t->npad * m->input_dim * es), bail(0));   // capacity npad rows (row appends)
   HIPCHK_OR(c, dev_alloc(c, &t->ysum, (size_t)n * mcols * es), bail(0));
@@ -118,6 +117,45 @@ extern "C" int hbo_factor(hbo_ctx* c, const hbo_model* m, const void* x, int64_t
   prof_collect(c);
   *out = k;
   return k->info != INT_MAX ? HBO_NOT_PD : HBO_OK;
+}
+
+extern "C" int hbo_cache_free(hbo_ctx* c, hbo_cache* k) {
+  if (!k) return HBO_OK;
+  if (c) hipSetDevice(c->device);
+  free_task(c, k->t);
+  for (void* p : {(void*)k->d_desc, (void*)k->d_info, k->resid, k->zvec, (void*)k->w3, (void*)k->d_wmax}) if (p) hipFree(p);
+  delete k;
+  return HBO_OK;
+}
+
+extern "C" int hbo_cache_export(hbo_ctx* c, hbo_cache* k, void* chol_out, void* kinvy_out, void* ymu_out) {
+  if (!c || !k) return fail(c, HBO_ERR_ARG, "hbo_cache_export: null argument");
+  HIPCHK(c, hipSetDevice(c->device));
+  const size_t es = esize(k->dtype);
+  TaskHost* t = k->t;
+  const int64_t n = t->n;
+  const bool bad = k->info != INT_MAX;
+  if (chol_out) {
+    if (bad) fill_nan(chol_out, (size_t)n * n, k->dtype);
+    else {
+      DevBuf buf;
+      void* tmp = nullptr;
+      HIPCHK(c, buf.get(c, &tmp, (size_t)n * n * es));
+      launch_extract_lower(k->dtype, t->A, t->ld, n, tmp, c->stream);
+      HIPCHK(c, hipMemcpyAsync(chol_out, tmp, (size_t)n * n * es, hipMemcpyDeviceToHost, c->stream));
+      HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
+  }
+  std::vector<unsigned char> buf((size_t)k->m * t->npad * es);
+  auto export_cols = [&](const void* dev, void* outp, bool nanfill) -> int {
+    if (nanfill) { fill_nan(outp, (size_t)n * k->m, k->dtype); return HBO_OK; }
+    HIPCHK(c, hipMemcpy(buf.data(), dev, buf.size(), hipMemcpyDeviceToHost));
+    rows_to_cols(outp, buf.data(), n, k->m, t->npad, es);
+    return HBO_OK;
+  };
+  if (kinvy_out) { int rc = export_cols(t->svec, kinvy_out, bad); if (rc) return rc; }
+  if (ymu_out) { int rc = export_cols(k->resid, ymu_out, false); if (rc) return rc; }
+  return HBO_OK;
 }
 
 // O(N^2) row append (the reference re-factorises from scratch after every BO
@@ -235,24 +273,24 @@ extern "C" int hbo_cache_append(hbo_ctx* c, const hbo_model* m, hbo_cache* k, co
 }
 
 // ---- the three launches of the fp32 posterior product on the 16-bit matrix cores (post3.hip) -----------------------------------
-// Shared by the posterior below and by hbo_probe_post_product (include/hbo_tune.h), which feeds them caller-chosen operands.
+// Shared by the posterior below and by hbo_probe_post_product (probe.hip), which feeds them caller-chosen operands.
 // W [nblk * 128 rows, ld], lower triangular: its split copy w3 (blocks up to each row tile's diagonal block).  h2: two fp16 planes
 // by the scale that follows from max |W|, measured first into *d_wmax; else three bf16 planes
-static void post3_split_w(const float* W, int64_t ld, int nblk, bool h2, unsigned short* w3, unsigned int* d_wmax, hipStream_t st) {
+void post3_split_w(const float* W, int64_t ld, int nblk, bool h2, unsigned short* w3, unsigned int* d_wmax, hipStream_t st) {
   Split3Block sw = {}; sw.in = W; sw.ld = ld; sw.out = w3; sw.row_tiles = sw.last_rows = nblk;
   sw.nkb = nblk * (HBO_TILE / 16); sw.last_krows = nblk * HBO_TILE; sw.tri = 1;
   if (h2) { (void)hipMemsetAsync(d_wmax, 0, sizeof(unsigned int), st); sw.h2 = 1; sw.max_out = d_wmax; }   // max |W| first, then the split
   launch_split3_block(sw, 1, false, st);
 }
 // the cross Gram of one chunk, Kxq [npad, ldq] with mpad candidates (columns), transposed on the way: K3 rows = candidates
-static void post3_split_kxq(const float* K, int64_t ldq, int mpad, int npad, bool h2, float kscale, unsigned short* K3, hipStream_t st) {
+void post3_split_kxq(const float* K, int64_t ldq, int mpad, int npad, bool h2, float kscale, unsigned short* K3, hipStream_t st) {
   Split3Block sk = {}; sk.in = K; sk.ld = ldq; sk.out = K3; sk.row_tiles = sk.last_rows = mpad / HBO_TILE;
   sk.nkb = npad / 16; sk.last_krows = npad; sk.h2 = h2; sk.scale = kscale;
   launch_split3_block(sk, 1, true, st);
 }
 // colsq [nblk, ldc] = per row block of W the column sums of (W Kxq)^2.  counter (nullable): zeroed here and handed to launch_post3,
 // which turns a large product into a resident grid drawing its tiles from it (returns whether it did)
-static bool post3_product(const unsigned short* w3, const unsigned short* K3, int nblk, int mpad, bool h2, const unsigned int* d_wmax,
+bool post3_product(const unsigned short* w3, const unsigned short* K3, int nblk, int mpad, bool h2, const unsigned int* d_wmax,
                           float kscale, float* colsq, int64_t ldc, int* counter, hipStream_t st) {
   Post3Args a = {}; a.Wp = w3; a.Kp = K3; a.nkb = nblk * (HBO_TILE / 16); a.h2 = h2; a.wmax_bits = d_wmax; a.kscale = kscale;
   a.colsq = colsq; a.ldc = ldc; a.nblk = nblk;
@@ -627,173 +665,3 @@ extern "C" int hbo_acq_samples(hbo_ctx* c, const hbo_model* models, int32_t S, c
   return any_bad ? HBO_NOT_PD : HBO_OK;
 }
 
-// Test hook (include/hbo_tune.h): the fp32 split-operand posterior product on caller-chosen operands -- W and Kxq go up padded as a
-// cache holds them, the three launches of the posterior above run once over all M candidates, the per-row-block column sums of V^2
-// come back.  The split buffers are filled with 0xFF (NaN in bf16 and fp16) first: a block the product reads but no split wrote shows.
-extern "C" int hbo_probe_post_product(hbo_ctx* c, int form, const float* W, int64_t n, const float* Kxq, int64_t M, double k_bound,
-                                      int use_counter, float* colsq_out) {
-  if (!c || !W || !Kxq || !colsq_out) return fail(c, HBO_ERR_ARG, "hbo_probe_post_product: null argument");
-  if (form != 0 && form != 1) return fail(c, HBO_ERR_ARG, "hbo_probe_post_product: form is 0 (bf16x3) or 1 (f16x2)");
-  if (n <= 0 || n > 16384 || M <= 0 || M > (1 << 20)) return fail(c, HBO_ERR_ARG, "hbo_probe_post_product: need 1 <= n <= 16384 and 1 <= M <= 2^20");
-  if (use_counter != 0 && use_counter != 1) return fail(c, HBO_ERR_ARG, "hbo_probe_post_product: use_counter is 0 or 1");
-  if (form == 1 && (!(k_bound > 0) || !(k_bound < 1e30))) return fail(c, HBO_ERR_ARG, "hbo_probe_post_product: f16x2 needs a positive finite k_bound");
-  HIPCHK(c, hipSetDevice(c->device));
-  const bool h2 = form == 1;
-  const int planes = h2 ? 2 : 3;
-  const int npad = round_up(n, HBO_TILE), nblk = npad / HBO_TILE, mpad = round_up(M, HBO_TILE);
-  const int64_t ld = padded_ld(npad, HBO_F32), ldq = padded_ld(mpad, HBO_F32);
-  const float kscale = h2 ? post2h_scale_for(k_bound) : 1.f;
-  const size_t w_b = (size_t)npad * ld * sizeof(float), k_b = (size_t)npad * ldq * sizeof(float), c_b = (size_t)nblk * ldq * sizeof(float);
-  const size_t w3_b = (size_t)npad * npad * planes * sizeof(unsigned short), k3_b = (size_t)mpad * npad * planes * sizeof(unsigned short);
-  hipStream_t st = c->stream;
-  void *d_w = nullptr, *d_k = nullptr, *d_c = nullptr, *d_w3 = nullptr, *d_k3 = nullptr, *d_words = nullptr;
-  auto cleanup = [&]() { for (void* p : {d_w, d_k, d_c, d_w3, d_k3, d_words}) if (p) hipFree(p); };
-  HIPCHK_OR(c, hbo_malloc(c, &d_w, w_b), cleanup()); HIPCHK_OR(c, hbo_malloc(c, &d_k, k_b), cleanup()); HIPCHK_OR(c, hbo_malloc(c, &d_c, c_b), cleanup());
-  HIPCHK_OR(c, hbo_malloc(c, &d_w3, w3_b), cleanup()); HIPCHK_OR(c, hbo_malloc(c, &d_k3, k3_b), cleanup()); HIPCHK_OR(c, hbo_malloc(c, &d_words, 2 * sizeof(unsigned int)), cleanup());
-  HIPCHK_OR(c, hipMemsetAsync(d_w, 0, w_b, st), cleanup()); HIPCHK_OR(c, hipMemsetAsync(d_k, 0, k_b, st), cleanup()); HIPCHK_OR(c, hipMemsetAsync(d_c, 0, c_b, st), cleanup());
-  HIPCHK_OR(c, hipMemsetAsync(d_w3, 0xFF, w3_b, st), cleanup()); HIPCHK_OR(c, hipMemsetAsync(d_k3, 0xFF, k3_b, st), cleanup());
-  HIPCHK_OR(c, hipMemcpy2DAsync(d_w, (size_t)ld * sizeof(float), W, (size_t)n * sizeof(float), (size_t)n * sizeof(float), (size_t)n, hipMemcpyHostToDevice, st), cleanup());
-  HIPCHK_OR(c, hipMemcpy2DAsync(d_k, (size_t)ldq * sizeof(float), Kxq, (size_t)M * sizeof(float), (size_t)M * sizeof(float), (size_t)n, hipMemcpyHostToDevice, st), cleanup());
-  unsigned int* d_wmax = static_cast<unsigned int*>(d_words);
-  post3_split_w(static_cast<const float*>(d_w), ld, nblk, h2, static_cast<unsigned short*>(d_w3), d_wmax, st);
-  post3_split_kxq(static_cast<const float*>(d_k), ldq, mpad, npad, h2, kscale, static_cast<unsigned short*>(d_k3), st);
-  post3_product(static_cast<const unsigned short*>(d_w3), static_cast<const unsigned short*>(d_k3), nblk, mpad, h2, d_wmax, kscale,
-                static_cast<float*>(d_c), ldq, use_counter ? reinterpret_cast<int*>(d_wmax + 1) : nullptr, st);
-  HIPCHK_OR(c, hipMemcpy2DAsync(colsq_out, (size_t)M * sizeof(float), d_c, (size_t)ldq * sizeof(float), (size_t)M * sizeof(float), (size_t)nblk, hipMemcpyDeviceToHost, st), cleanup());
-  HIPCHK_OR(c, hipStreamSynchronize(st), cleanup());
-  HIPCHK_OR(c, hipGetLastError(), cleanup());
-  cleanup();
-  return HBO_OK;
-}
-
-// Test hook (include/hbo_tune.h): launch_gram in the two forms hbo_gram never takes, on caller-chosen inputs, with every element of the
-// output buffer preset to a sentinel so that what the kernel leaves alone shows.  Form 1 is the launch of produce_chunk above (sizes from
-// post_plan), form 2 the launch of objective_local / enqueue_factor over a dataset built by hbo_dataset_create, its workspaces by
-// ensure_task_workspace and its descriptors by fill_desc.
-extern "C" int hbo_probe_gram(hbo_ctx* c, int form, const hbo_model* models, int32_t n_models, const void* x, const int64_t* ns, int32_t T,
-                              const void* x2, int64_t n2, int direct_form, double sentinel, void* out, int64_t out_cap, int64_t* rows_out,
-                              int64_t* ld_out) {
-  if (!c || !models || !x || !ns || !out || !rows_out || !ld_out) return fail(c, HBO_ERR_ARG, "hbo_probe_gram: null argument");
-  if (form != 1 && form != 2) return fail(c, HBO_ERR_ARG, "hbo_probe_gram: form is 1 (padded cross Gram) or 2 (batched task form)");
-  if (T <= 0 || T > 64) return fail(c, HBO_ERR_ARG, "hbo_probe_gram: 1 <= T <= 64");
-  if (form == 1 && (T != 1 || n_models != 1 || !x2 || n2 <= 0)) return fail(c, HBO_ERR_ARG, "hbo_probe_gram: form 1 takes one task, one model and x2 [n2 > 0, D]");
-  if (form == 2 && (x2 || n2 != 0 || direct_form != 0)) return fail(c, HBO_ERR_ARG, "hbo_probe_gram: form 2 takes neither x2 nor direct_form");
-  if (form == 2 && n_models != 1 && n_models != T) return fail(c, HBO_ERR_ARG, "hbo_probe_gram: form 2 takes one model or one per task");
-  if (direct_form != 0 && direct_form != 1) return fail(c, HBO_ERR_ARG, "hbo_probe_gram: direct_form is 0 or 1");
-  for (int k = 0; k < T; ++k) if (ns[k] <= 0 || ns[k] > 4096) return fail(c, HBO_ERR_ARG, "hbo_probe_gram: need 1 <= n <= 4096 for every task");
-  if (out_cap <= 0) return fail(c, HBO_ERR_ARG, "hbo_probe_gram: out_cap must be positive");
-  const hbo_model* m0 = &models[0];
-  for (int s = 0; s < n_models; ++s) {
-    const hbo_model* m = &models[s];
-    if (m->input_warp != HBO_WARP_NONE || needs_mlp(m)) return fail(c, HBO_ERR_ARG, "hbo_probe_gram: models with an MLP basis or an input warp are not taken");
-    if (validate_model(c, m)) return HBO_ERR_ARG;
-    if (!same_model_family(m, m0)) return fail(c, HBO_ERR_ARG, "hbo_probe_gram: the models must share dtype, covariance, mean and input_dim");
-  }
-  const int dtype = m0->dtype, D = m0->input_dim, fdim = feature_dim(m0);
-  const size_t es = esize(dtype);
-  PostPlan plan = {};
-  if (form == 1) {
-    plan = post_plan(c, m0, n2, round_up(ns[0], HBO_TILE) / HBO_TILE, false, nullptr);
-    if (plan.refuse || plan.nchunks != 1) return fail(c, HBO_ERR_ARG, "hbo_probe_gram: n2 must fit one posterior chunk (option post_chunk)");
-  }
-  HIPCHK(c, hipSetDevice(c->device));
-  hipStream_t st = c->stream;
-  auto fill = [&](std::vector<unsigned char>& h, size_t count) {
-    h.resize(count * es);
-    if (dtype == HBO_F64) for (size_t i = 0; i < count; ++i) ((double*)h.data())[i] = sentinel;
-    else for (size_t i = 0; i < count; ++i) ((float*)h.data())[i] = (float)sentinel;
-  };
-
-  if (form == 1) {
-    const int64_t n1 = ns[0];
-    const PostChunk ch = plan.chunk(0);
-    const int npad = round_up(n1, HBO_TILE), nblk = npad / HBO_TILE;
-    rows_out[0] = npad; ld_out[0] = ch.ldq;
-    const size_t count = (size_t)npad * ch.ldq;
-    if ((size_t)out_cap < count) return fail(c, HBO_ERR_ARG, "hbo_probe_gram: out_cap is smaller than the padded buffer");
-    int rc = upload_model(c, m0);
-    if (rc) return rc;
-    void *d1 = nullptr, *d2 = nullptr, *dk = nullptr;
-    auto cleanup = [&]() { for (void* p : {d1, d2, dk}) if (p) hipFree(p); };
-    std::vector<unsigned char> hs;
-    fill(hs, count);
-    HIPCHK_OR(c, hbo_malloc(c, &d1, (size_t)n1 * D * es), cleanup()); HIPCHK_OR(c, hbo_malloc(c, &d2, (size_t)n2 * D * es), cleanup());
-    HIPCHK_OR(c, hbo_malloc(c, &dk, count * es), cleanup());
-    HIPCHK_OR(c, hipMemcpyAsync(d1, x, (size_t)n1 * D * es, hipMemcpyHostToDevice, st), cleanup());
-    HIPCHK_OR(c, hipMemcpyAsync(d2, x2, (size_t)n2 * D * es, hipMemcpyHostToDevice, st), cleanup());
-    HIPCHK_OR(c, hipMemcpyAsync(dk, hs.data(), count * es, hipMemcpyHostToDevice, st), cleanup());
-    GramArgs g = {}; g.kernel_id = m0->kernel_id; g.mfma_min_f = c->opt_gram_mfma; g.x1 = d1; g.x2 = d2; g.out = dk; g.n1 = n1; g.n2 = ch.mc; g.ldo = ch.ldq;
-    g.n1pad = npad; g.n2pad = ch.mpad; g.fdim = fdim; g.symmetric = 0; g.padded = 1;
-    g.direct_form = direct_form;
-    launch_gram(dtype, g, c->d_model, dim3(ch.mpad / HBO_TILE, nblk, 1), st);
-    HIPCHK_OR(c, hipMemcpyAsync(out, dk, count * es, hipMemcpyDeviceToHost, st), cleanup());
-    HIPCHK_OR(c, hipStreamSynchronize(st), cleanup());
-    HIPCHK_OR(c, hipGetLastError(), cleanup());
-    cleanup();
-    return HBO_OK;
-  }
-
-  // form 2: the dataset of the T tasks (targets: zeros, one column), the workspaces and descriptors of an NLL evaluation
-  int64_t max_n = 0, rows = 0;
-  for (int k = 0; k < T; ++k) max_n = std::max(max_n, ns[k]);
-  const std::vector<unsigned char> y0((size_t)max_n * es, 0);
-  std::vector<hbo_task> tasks(T);
-  for (int k = 0; k < T; ++k) {
-    memset(&tasks[k], 0, sizeof(hbo_task));
-    tasks[k].x = (const char*)x + (size_t)rows * D * es; tasks[k].y = y0.data(); tasks[k].n = ns[k]; tasks[k].m = 1;
-    rows += ns[k];
-  }
-  hbo_dataset* ds = nullptr;
-  int rc = hbo_dataset_create(c, dtype, D, tasks.data(), T, &ds);
-  if (rc) return rc;
-  void* d_models = nullptr;
-  auto cleanup = [&]() { hipStreamSynchronize(st); hbo_dataset_free(c, ds); if (d_models) hipFree(d_models); };
-  // the dataset holds its tasks largest first; its inputs lie in the caller's order: order[z] = the caller's index of dataset task z
-  std::vector<TaskHost*> by_x(ds->tasks);
-  std::sort(by_x.begin(), by_x.end(), [](TaskHost* a, TaskHost* b) { return (const char*)a->X < (const char*)b->X; });
-  std::vector<int> order(T);
-  for (int z = 0; z < T; ++z) order[z] = (int)(std::find(by_x.begin(), by_x.end(), ds->tasks[z]) - by_x.begin());
-  size_t total = 0;
-  for (int k = 0; k < T; ++k) { rows_out[k] = by_x[k]->npad; ld_out[k] = by_x[k]->ld; total += (size_t)by_x[k]->npad * by_x[k]->ld; }
-  if ((size_t)out_cap < total) { cleanup(); return fail(c, HBO_ERR_ARG, "hbo_probe_gram: out_cap is smaller than the padded buffers"); }
-  const ModelDev* md = c->d_model;
-  int model_stride = 0;
-  std::vector<ModelDev> hm;
-  if (n_models == 1) {
-    rc = upload_model(c, m0);
-    if (rc) { cleanup(); return rc; }
-  } else {
-    hm.resize(T);
-    for (int z = 0; z < T; ++z) fill_model_dev(hm[z], &models[order[z]]);
-    HIPCHK_OR(c, hbo_malloc(c, &d_models, sizeof(ModelDev) * T), cleanup());
-    HIPCHK_OR(c, hipMemcpyAsync(d_models, hm.data(), sizeof(ModelDev) * T, hipMemcpyHostToDevice, st), cleanup());
-    md = static_cast<const ModelDev*>(d_models); model_stride = 1;
-  }
-  ds->h_desc.resize(T);
-  std::vector<std::vector<unsigned char>> hs(T);
-  for (int z = 0; z < T; ++z) {
-    TaskHost* t = ds->tasks[z];
-    rc = ensure_task_workspace(c, dtype, t, false, 1);
-    if (rc) { cleanup(); return rc; }
-    fill_desc(ds->h_desc[z], t, m0, dtype, OBJ_NLL);
-    const size_t count = (size_t)(t->npad + HBO_TILE) * t->ld;   // all of A, its augmented tile row too
-    fill(hs[z], count);
-    HIPCHK_OR(c, hipMemcpyAsync(t->A, hs[z].data(), count * es, hipMemcpyHostToDevice, st), cleanup());
-  }
-  HIPCHK_OR(c, dev_alloc(c, (void**)&ds->d_desc, sizeof(TaskDesc) * T), cleanup());
-  HIPCHK_OR(c, hipMemcpyAsync(ds->d_desc, ds->h_desc.data(), sizeof(TaskDesc) * T, hipMemcpyHostToDevice, st), cleanup());
-  const int max_nblk = ds->max_nblk;
-  GramArgs g = {}; g.kernel_id = m0->kernel_id; g.mfma_min_f = c->opt_gram_mfma; g.tasks = ds->d_desc; g.fdim = fdim; g.symmetric = 1; g.padded = 1;
-  g.model_stride = model_stride;
-  launch_gram(dtype, g, md, dim3(max_nblk, max_nblk, T), st);
-  size_t off = 0;
-  for (int k = 0; k < T; ++k) {
-    const size_t count = (size_t)by_x[k]->npad * by_x[k]->ld;
-    HIPCHK_OR(c, hipMemcpyAsync((char*)out + off * es, by_x[k]->A, count * es, hipMemcpyDeviceToHost, st), cleanup());
-    off += count;
-  }
-  HIPCHK_OR(c, hipStreamSynchronize(st), cleanup());
-  HIPCHK_OR(c, hipGetLastError(), cleanup());
-  cleanup();
-  return HBO_OK;
-}

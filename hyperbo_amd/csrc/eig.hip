@@ -395,18 +395,6 @@ __global__ void spectral_rhs_kernel(const T* __restrict__ ysum, const T* __restr
   cv[i] = v;
 }
 
-struct DevBuf {   // device scratch of one call
-  std::vector<void*> ptrs;
-  ~DevBuf() { for (void* p : ptrs) hipFree(p); }
-  template <typename P> hipError_t get(hbo_ctx* c, P** out, size_t bytes) {
-    void* p = nullptr;
-    hipError_t e = hbo_malloc(c, &p, bytes);
-    if (e == hipSuccess) ptrs.push_back(p);
-    *out = static_cast<P*>(p);
-    return e;
-  }
-};
-
 inline unsigned blocks_of(int64_t n) { return (unsigned)((n + 255) / 256); }
 }  // namespace
 

@@ -1,0 +1,232 @@
+// What include/hbo_tune.h declares apart from hbo_tune itself (api.hip): the MFMA rate probe of bench.py and the test hooks that run
+// single launches of the posterior and the Gram on caller-chosen operands.  (hbo_probe_acq_grad_samples64 is a second door to
+// acq_grad.hip's acq_grad_samples and stays beside it; the control-text probes stay with their kernels in train.hip and acq_opt.hip.)
+#include "api_internal.h"
+
+// Sustained fp64 MFMA rate of THIS device, measured now (include/hbo_tune.h): every SIMD of every CU runs two waves of
+// back-to-back independent v_mfma_f64_16x16x4_f64 (4 accumulators per wave, no memory traffic) for ~`ms` milliseconds between two
+// HIP events.  What bench.py reports beside the 78.6 TFLOP/s datasheet figure: the denominator a kernel can actually reach at the
+// clock the chip holds under an fp64 MFMA load.  (Four accumulators per wave, the loop in assembly: see the kernel.)
+namespace {
+typedef double probe_d4 __attribute__((ext_vector_type(4)));
+__global__ __launch_bounds__(256) void mfma_probe_kernel(double* out, int iters) {
+  probe_d4 acc[4];
+  const double a = 1.0 + threadIdx.x * 1e-9, b = 1.0 - threadIdx.x * 1e-9;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) acc[i] = (probe_d4){0, 0, 0, 0};
+  // the whole loop is ONE assembly block: around a builtin (or a per-instruction asm) inside a C loop the register allocator parks
+  // the loop-carried accumulators in VGPRs and copies them to AGPRs and back every iteration (16 v_accvgpr moves per MFMA)
+  int n = iters;
+  asm volatile(
+      "1:\n"
+      "v_mfma_f64_16x16x4_f64 %0, %5, %6, %0\n"
+      "v_mfma_f64_16x16x4_f64 %1, %5, %6, %1\n"
+      "v_mfma_f64_16x16x4_f64 %2, %5, %6, %2\n"
+      "v_mfma_f64_16x16x4_f64 %3, %5, %6, %3\n"
+      "s_sub_u32 %4, %4, 1\n"
+      "s_cmp_lg_u32 %4, 0\n"
+      "s_cbranch_scc1 1b\n"
+      "s_nop 15\n"
+      : "+v"(acc[0]), "+v"(acc[1]), "+v"(acc[2]), "+v"(acc[3]), "+s"(n)
+      : "v"(a), "v"(b)
+      : "scc");
+  double sacc = 0;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) sacc += acc[i][0] + acc[i][1] + acc[i][2] + acc[i][3];
+  out[(size_t)blockIdx.x * blockDim.x + threadIdx.x] = sacc;
+}
+}  // namespace
+extern "C" int hbo_mfma_peak_probe(hbo_ctx* c, double ms, double* tflops_out) {
+  if (!c || !tflops_out || !(ms > 0) || ms > 1000) return fail(c, HBO_ERR_ARG, "hbo_mfma_peak_probe: bad argument");
+  HIPCHK(c, hipSetDevice(c->device));
+  const int blocks = 2 * c->n_cus;   // two 4-wave workgroups per CU: two waves per SIMD
+  double* d_out = static_cast<double*>(ws_get(c, WS_PROBE, sizeof(double) * 256 * blocks));
+  if (!d_out) return HBO_ERR_HIP;
+  hipEvent_t e0 = pool_event_timed(c, 0), e1 = pool_event_timed(c, 1);
+  double best = 0;
+  int iters = 8192;
+  for (int rep = 0; rep < 3; ++rep) {   // the first pass sizes the second and third to ~ms
+    HIPCHK(c, hipEventRecord(e0, c->stream));
+    hipLaunchKernelGGL(mfma_probe_kernel, dim3(blocks), dim3(256), 0, c->stream, d_out, iters);
+    HIPCHK(c, hipEventRecord(e1, c->stream));
+    HIPCHK(c, hipEventSynchronize(e1));
+    float el = 0;
+    HIPCHK(c, hipEventElapsedTime(&el, e0, e1));
+    const double flops = (double)blocks * 4 * (double)iters * 4 * 2048.0;   // waves x MFMAs x 16*16*4*2
+    if (rep > 0) best = std::max(best, flops / (el * 1e-3) / 1e12);
+    if (rep == 0) iters = (int)std::min(4.0e6, std::max(1024.0, iters * ms / std::max((double)el, 1e-3)));
+  }
+  HIPCHK(c, hipGetLastError());
+  *tflops_out = best;
+  return HBO_OK;
+}
+
+// Test hook (include/hbo_tune.h): the fp32 split-operand posterior product on caller-chosen operands -- W and Kxq go up padded as a
+// cache holds them, the three launches of the posterior (cache.hip: post3_*) run once over all M candidates, the per-row-block column sums of V^2
+// come back.  The split buffers are filled with 0xFF (NaN in bf16 and fp16) first: a block the product reads but no split wrote shows.
+extern "C" int hbo_probe_post_product(hbo_ctx* c, int form, const float* W, int64_t n, const float* Kxq, int64_t M, double k_bound,
+                                      int use_counter, float* colsq_out) {
+  if (!c || !W || !Kxq || !colsq_out) return fail(c, HBO_ERR_ARG, "hbo_probe_post_product: null argument");
+  if (form != 0 && form != 1) return fail(c, HBO_ERR_ARG, "hbo_probe_post_product: form is 0 (bf16x3) or 1 (f16x2)");
+  if (n <= 0 || n > 16384 || M <= 0 || M > (1 << 20)) return fail(c, HBO_ERR_ARG, "hbo_probe_post_product: need 1 <= n <= 16384 and 1 <= M <= 2^20");
+  if (use_counter != 0 && use_counter != 1) return fail(c, HBO_ERR_ARG, "hbo_probe_post_product: use_counter is 0 or 1");
+  if (form == 1 && (!(k_bound > 0) || !(k_bound < 1e30))) return fail(c, HBO_ERR_ARG, "hbo_probe_post_product: f16x2 needs a positive finite k_bound");
+  HIPCHK(c, hipSetDevice(c->device));
+  const bool h2 = form == 1;
+  const int planes = h2 ? 2 : 3;
+  const int npad = round_up(n, HBO_TILE), nblk = npad / HBO_TILE, mpad = round_up(M, HBO_TILE);
+  const int64_t ld = padded_ld(npad, HBO_F32), ldq = padded_ld(mpad, HBO_F32);
+  const float kscale = h2 ? post2h_scale_for(k_bound) : 1.f;
+  const size_t w_b = (size_t)npad * ld * sizeof(float), k_b = (size_t)npad * ldq * sizeof(float), c_b = (size_t)nblk * ldq * sizeof(float);
+  const size_t w3_b = (size_t)npad * npad * planes * sizeof(unsigned short), k3_b = (size_t)mpad * npad * planes * sizeof(unsigned short);
+  hipStream_t st = c->stream;
+  DevBuf buf;
+  void *d_w = nullptr, *d_k = nullptr, *d_c = nullptr, *d_w3 = nullptr, *d_k3 = nullptr, *d_words = nullptr;
+  HIPCHK(c, buf.get(c, &d_w, w_b)); HIPCHK(c, buf.get(c, &d_k, k_b)); HIPCHK(c, buf.get(c, &d_c, c_b));
+  HIPCHK(c, buf.get(c, &d_w3, w3_b)); HIPCHK(c, buf.get(c, &d_k3, k3_b)); HIPCHK(c, buf.get(c, &d_words, 2 * sizeof(unsigned int)));
+  HIPCHK(c, hipMemsetAsync(d_w, 0, w_b, st)); HIPCHK(c, hipMemsetAsync(d_k, 0, k_b, st)); HIPCHK(c, hipMemsetAsync(d_c, 0, c_b, st));
+  HIPCHK(c, hipMemsetAsync(d_w3, 0xFF, w3_b, st)); HIPCHK(c, hipMemsetAsync(d_k3, 0xFF, k3_b, st));
+  HIPCHK(c, hipMemcpy2DAsync(d_w, (size_t)ld * sizeof(float), W, (size_t)n * sizeof(float), (size_t)n * sizeof(float), (size_t)n, hipMemcpyHostToDevice, st));
+  HIPCHK(c, hipMemcpy2DAsync(d_k, (size_t)ldq * sizeof(float), Kxq, (size_t)M * sizeof(float), (size_t)M * sizeof(float), (size_t)n, hipMemcpyHostToDevice, st));
+  unsigned int* d_wmax = static_cast<unsigned int*>(d_words);
+  post3_split_w(static_cast<const float*>(d_w), ld, nblk, h2, static_cast<unsigned short*>(d_w3), d_wmax, st);
+  post3_split_kxq(static_cast<const float*>(d_k), ldq, mpad, npad, h2, kscale, static_cast<unsigned short*>(d_k3), st);
+  post3_product(static_cast<const unsigned short*>(d_w3), static_cast<const unsigned short*>(d_k3), nblk, mpad, h2, d_wmax, kscale,
+                static_cast<float*>(d_c), ldq, use_counter ? reinterpret_cast<int*>(d_wmax + 1) : nullptr, st);
+  HIPCHK(c, hipMemcpy2DAsync(colsq_out, (size_t)M * sizeof(float), d_c, (size_t)ldq * sizeof(float), (size_t)M * sizeof(float), (size_t)nblk, hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipStreamSynchronize(st));
+  HIPCHK(c, hipGetLastError());
+  return HBO_OK;
+}
+
+// Test hook (include/hbo_tune.h): launch_gram in the two forms hbo_gram never takes, on caller-chosen inputs, with every element of the
+// output buffer preset to a sentinel so that what the kernel leaves alone shows.  Form 1 is the launch of cache.hip's produce_chunk (sizes from
+// post_plan), form 2 the launch of objective_local / enqueue_factor over a dataset built by hbo_dataset_create, its workspaces by
+// ensure_task_workspace and its descriptors by fill_desc.
+extern "C" int hbo_probe_gram(hbo_ctx* c, int form, const hbo_model* models, int32_t n_models, const void* x, const int64_t* ns, int32_t T,
+                              const void* x2, int64_t n2, int direct_form, double sentinel, void* out, int64_t out_cap, int64_t* rows_out,
+                              int64_t* ld_out) {
+  if (!c || !models || !x || !ns || !out || !rows_out || !ld_out) return fail(c, HBO_ERR_ARG, "hbo_probe_gram: null argument");
+  if (form != 1 && form != 2) return fail(c, HBO_ERR_ARG, "hbo_probe_gram: form is 1 (padded cross Gram) or 2 (batched task form)");
+  if (T <= 0 || T > 64) return fail(c, HBO_ERR_ARG, "hbo_probe_gram: 1 <= T <= 64");
+  if (form == 1 && (T != 1 || n_models != 1 || !x2 || n2 <= 0)) return fail(c, HBO_ERR_ARG, "hbo_probe_gram: form 1 takes one task, one model and x2 [n2 > 0, D]");
+  if (form == 2 && (x2 || n2 != 0 || direct_form != 0)) return fail(c, HBO_ERR_ARG, "hbo_probe_gram: form 2 takes neither x2 nor direct_form");
+  if (form == 2 && n_models != 1 && n_models != T) return fail(c, HBO_ERR_ARG, "hbo_probe_gram: form 2 takes one model or one per task");
+  if (direct_form != 0 && direct_form != 1) return fail(c, HBO_ERR_ARG, "hbo_probe_gram: direct_form is 0 or 1");
+  for (int k = 0; k < T; ++k) if (ns[k] <= 0 || ns[k] > 4096) return fail(c, HBO_ERR_ARG, "hbo_probe_gram: need 1 <= n <= 4096 for every task");
+  if (out_cap <= 0) return fail(c, HBO_ERR_ARG, "hbo_probe_gram: out_cap must be positive");
+  const hbo_model* m0 = &models[0];
+  for (int s = 0; s < n_models; ++s) {
+    const hbo_model* m = &models[s];
+    if (m->input_warp != HBO_WARP_NONE || needs_mlp(m)) return fail(c, HBO_ERR_ARG, "hbo_probe_gram: models with an MLP basis or an input warp are not taken");
+    if (validate_model(c, m)) return HBO_ERR_ARG;
+    if (!same_model_family(m, m0)) return fail(c, HBO_ERR_ARG, "hbo_probe_gram: the models must share dtype, covariance, mean and input_dim");
+  }
+  const int dtype = m0->dtype, D = m0->input_dim, fdim = feature_dim(m0);
+  const size_t es = esize(dtype);
+  PostPlan plan = {};
+  if (form == 1) {
+    plan = post_plan(c, m0, n2, round_up(ns[0], HBO_TILE) / HBO_TILE, false, nullptr);
+    if (plan.refuse || plan.nchunks != 1) return fail(c, HBO_ERR_ARG, "hbo_probe_gram: n2 must fit one posterior chunk (option post_chunk)");
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  hipStream_t st = c->stream;
+  auto fill = [&](std::vector<unsigned char>& h, size_t count) {
+    h.resize(count * es);
+    if (dtype == HBO_F64) for (size_t i = 0; i < count; ++i) ((double*)h.data())[i] = sentinel;
+    else for (size_t i = 0; i < count; ++i) ((float*)h.data())[i] = (float)sentinel;
+  };
+
+  if (form == 1) {
+    const int64_t n1 = ns[0];
+    const PostChunk ch = plan.chunk(0);
+    const int npad = round_up(n1, HBO_TILE), nblk = npad / HBO_TILE;
+    rows_out[0] = npad; ld_out[0] = ch.ldq;
+    const size_t count = (size_t)npad * ch.ldq;
+    if ((size_t)out_cap < count) return fail(c, HBO_ERR_ARG, "hbo_probe_gram: out_cap is smaller than the padded buffer");
+    int rc = upload_model(c, m0);
+    if (rc) return rc;
+    DevBuf buf;
+    void *d1 = nullptr, *d2 = nullptr, *dk = nullptr;
+    std::vector<unsigned char> hs;
+    fill(hs, count);
+    HIPCHK(c, buf.get(c, &d1, (size_t)n1 * D * es)); HIPCHK(c, buf.get(c, &d2, (size_t)n2 * D * es));
+    HIPCHK(c, buf.get(c, &dk, count * es));
+    HIPCHK(c, hipMemcpyAsync(d1, x, (size_t)n1 * D * es, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(d2, x2, (size_t)n2 * D * es, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(dk, hs.data(), count * es, hipMemcpyHostToDevice, st));
+    GramArgs g = {}; g.kernel_id = m0->kernel_id; g.mfma_min_f = c->opt_gram_mfma; g.x1 = d1; g.x2 = d2; g.out = dk; g.n1 = n1; g.n2 = ch.mc; g.ldo = ch.ldq;
+    g.n1pad = npad; g.n2pad = ch.mpad; g.fdim = fdim; g.symmetric = 0; g.padded = 1;
+    g.direct_form = direct_form;
+    launch_gram(dtype, g, c->d_model, dim3(ch.mpad / HBO_TILE, nblk, 1), st);
+    HIPCHK(c, hipMemcpyAsync(out, dk, count * es, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    HIPCHK(c, hipGetLastError());
+    return HBO_OK;
+  }
+
+  // form 2: the dataset of the T tasks (targets: zeros, one column), the workspaces and descriptors of an NLL evaluation
+  int64_t max_n = 0, rows = 0;
+  for (int k = 0; k < T; ++k) max_n = std::max(max_n, ns[k]);
+  const std::vector<unsigned char> y0((size_t)max_n * es, 0);
+  std::vector<hbo_task> tasks(T);
+  for (int k = 0; k < T; ++k) {
+    memset(&tasks[k], 0, sizeof(hbo_task));
+    tasks[k].x = (const char*)x + (size_t)rows * D * es; tasks[k].y = y0.data(); tasks[k].n = ns[k]; tasks[k].m = 1;
+    rows += ns[k];
+  }
+  hbo_dataset* ds = nullptr;
+  int rc = hbo_dataset_create(c, dtype, D, tasks.data(), T, &ds);
+  if (rc) return rc;
+  DevBuf buf;
+  void* d_models = nullptr;
+  // (the dataset leaves when the call does, behind a wait: launches may still read its pooled buffers.  Before buf's memory is freed.)
+  struct DatasetGuard { hbo_ctx* c; hipStream_t st; hbo_dataset* ds; ~DatasetGuard() { hipStreamSynchronize(st); hbo_dataset_free(c, ds); } } guard = {c, st, ds};
+  // the dataset holds its tasks largest first; its inputs lie in the caller's order: order[z] = the caller's index of dataset task z
+  std::vector<TaskHost*> by_x(ds->tasks);
+  std::sort(by_x.begin(), by_x.end(), [](TaskHost* a, TaskHost* b) { return (const char*)a->X < (const char*)b->X; });
+  std::vector<int> order(T);
+  for (int z = 0; z < T; ++z) order[z] = (int)(std::find(by_x.begin(), by_x.end(), ds->tasks[z]) - by_x.begin());
+  size_t total = 0;
+  for (int k = 0; k < T; ++k) { rows_out[k] = by_x[k]->npad; ld_out[k] = by_x[k]->ld; total += (size_t)by_x[k]->npad * by_x[k]->ld; }
+  if ((size_t)out_cap < total) return fail(c, HBO_ERR_ARG, "hbo_probe_gram: out_cap is smaller than the padded buffers");
+  const ModelDev* md = c->d_model;
+  int model_stride = 0;
+  std::vector<ModelDev> hm;
+  if (n_models == 1) {
+    rc = upload_model(c, m0);
+    if (rc) return rc;
+  } else {
+    hm.resize(T);
+    for (int z = 0; z < T; ++z) fill_model_dev(hm[z], &models[order[z]]);
+    HIPCHK(c, buf.get(c, &d_models, sizeof(ModelDev) * T));
+    HIPCHK(c, hipMemcpyAsync(d_models, hm.data(), sizeof(ModelDev) * T, hipMemcpyHostToDevice, st));
+    md = static_cast<const ModelDev*>(d_models); model_stride = 1;
+  }
+  ds->h_desc.resize(T);
+  std::vector<std::vector<unsigned char>> hs(T);
+  for (int z = 0; z < T; ++z) {
+    TaskHost* t = ds->tasks[z];
+    rc = ensure_task_workspace(c, dtype, t, false, 1);
+    if (rc) return rc;
+    fill_desc(ds->h_desc[z], t, m0, dtype, OBJ_NLL);
+    const size_t count = (size_t)(t->npad + HBO_TILE) * t->ld;   // all of A, its augmented tile row too
+    fill(hs[z], count);
+    HIPCHK(c, hipMemcpyAsync(t->A, hs[z].data(), count * es, hipMemcpyHostToDevice, st));
+  }
+  HIPCHK(c, dev_alloc(c, (void**)&ds->d_desc, sizeof(TaskDesc) * T));
+  HIPCHK(c, hipMemcpyAsync(ds->d_desc, ds->h_desc.data(), sizeof(TaskDesc) * T, hipMemcpyHostToDevice, st));
+  const int max_nblk = ds->max_nblk;
+  GramArgs g = {}; g.kernel_id = m0->kernel_id; g.mfma_min_f = c->opt_gram_mfma; g.tasks = ds->d_desc; g.fdim = fdim; g.symmetric = 1; g.padded = 1;
+  g.model_stride = model_stride;
+  launch_gram(dtype, g, md, dim3(max_nblk, max_nblk, T), st);
+  size_t off = 0;
+  for (int k = 0; k < T; ++k) {
+    const size_t count = (size_t)by_x[k]->npad * by_x[k]->ld;
+    HIPCHK(c, hipMemcpyAsync((char*)out + off * es, by_x[k]->A, count * es, hipMemcpyDeviceToHost, st));
+    off += count;
+  }
+  HIPCHK(c, hipStreamSynchronize(st));
+  HIPCHK(c, hipGetLastError());
+  return HBO_OK;
+}

@@ -7,6 +7,7 @@
 #include <string.h>
 
 #include <string>
+#include <vector>
 
 static inline size_t esize(int dtype) { return dtype == HBO_F64 ? 8 : 4; }
 static inline int round_up(int64_t n, int q) { return (int)(((n + q - 1) / q) * q); }
@@ -33,6 +34,21 @@ static inline hipError_t hbo_malloc(hbo_ctx* c, void** out, size_t bytes) {
   }
   return e;
 }
+// Device memory that lives until the entry point that asked for it returns: get() allocates and records the pointer, the destructor
+// frees.  The one way to a call-lifetime temporary -- declared before anything whose destructor still uses the memory, so after the
+// call's last stream synchronise; never for pooled buffers (dev_alloc / dev_free below).
+struct DevBuf {
+  std::vector<void*> ptrs;
+  DevBuf() = default; DevBuf(const DevBuf&) = delete; DevBuf& operator=(const DevBuf&) = delete;   // (one owner per pointer)
+  ~DevBuf() { for (void* p : ptrs) hipFree(p); }
+  template <typename P> hipError_t get(hbo_ctx* c, P** out, size_t bytes) {
+    void* p = nullptr;
+    hipError_t e = hbo_malloc(c, &p, bytes);
+    if (e == hipSuccess) ptrs.push_back(p);
+    *out = static_cast<P*>(p);
+    return e;
+  }
+};
 
 // grow-only scratch buffer for `slot`; nullptr on allocation failure (ctx->err is set)
 #define HBO_H2_LEVELS 16
@@ -44,7 +60,7 @@ enum WsSlot { WS_XQ = 1, WS_MU0, WS_KD, WS_MU, WS_VAR, WS_ACQ, WS_K, WS_COLSQ, W
               WS_NS_MODELS, WS_NS_MODELS_X, WS_NS_DESC, WS_NS_PACK, WS_NS_MLP_W, WS_NS_MLPT, WS_NS_ACTS, WS_NS_MAT, WS_TRAIN, WS_AF_IN, WS_AF_OUT,
               WS_BO_IN, WS_BO_FEAT, WS_BO_V, WS_BO_OUT, WS_AO_IN, WS_AO_OUT,
               WS_PATH_DRAWS, WS_PATH_SUMS, WS_PATH_R, WS_PATH_Z, WS_PATH_V, WS_PATH_OUT,
-              WS_PO_IN, WS_PO_OUT, WS_SLOT_END };
+              WS_PO_IN, WS_PO_OUT, WS_PROBE /* hbo_mfma_peak_probe's sink */, WS_SLOT_END };
 // every slot is distinct by construction (auto-numbered; the per-layer range WS_FQ0.. is closed by WS_FQ_LAST before WS_K3), and the
 // posterior's per-lane offset (cache.hip: 4096 * lane) must clear the whole range
 static_assert(WS_FQ0 + HBO_MAX_MLP_LAYERS <= WS_K3 && WS_SLOT_END < 4096, "workspace slots overlap a lane offset");

@@ -455,7 +455,7 @@ extern "C" int hbo_train_adam(hbo_ctx* c, const hbo_model* m, hbo_dataset* ds, c
   //      then the trace; the copy back takes [x .. trace]
   std::vector<int> perm(T);
   std::iota(perm.begin(), perm.end(), 0);
-  std::stable_sort(perm.begin(), perm.end(), [&](int a, int b) { return ts.nd[a] > ts.nd[b]; });   // hbo_dataset_subsample's task order
+  std::stable_sort(perm.begin(), perm.end(), [&](int a, int b) { return ts.nd[a] > ts.nd[b]; });   // dataset_finish's task order (dataset.hip), as hbo_dataset_subsample leaves it
   std::vector<GatherTask> gt;
   if (batch_counts) {
     std::vector<int64_t> ioff(T, 0);

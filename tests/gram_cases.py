@@ -342,7 +342,7 @@ def padded_layout(case):
 
 
 def task_layout(n, np_dtype):
-  """(npad, ld) of a task's A (api.hip: hbo_dataset_create)."""
+  """(npad, ld) of a task's A (dataset.hip: hbo_dataset_create, through api_internal.h's task_shape)."""
   npad = round_up(n, TILE)
   return npad, padded_ld(npad, np_dtype)
 
