@@ -289,17 +289,30 @@ def _hgp_sample_caches(model, sub_dataset_key, samples, dtype):
 ACQ_FUSED_MAX_N = 128   # hbo_acq_grad_samples: one 128-block per cache
 
 
-def _acq_fused_unmet(model, sub_dataset_key, n_samples=1, n_kept=None, enabled=None):
+def _acq_blocked(model):
+  """True when model.params.config['acq_blocked'] asks for the entry points without the 128-observation limit
+  (hbo_acq_grad_samples_blocked, hbo_acq_maximize_blocked).  A model without params or config has not asked."""
+  cfg = getattr(getattr(model, 'params', None), 'config', None)
+  return bool(cfg.get('acq_blocked')) if isinstance(cfg, dict) else False
+
+
+def _blocked_max_n(model):
+  """The `max_n` of `_acq_fused_unmet` / `_acq_opt_unmet` for this model: None (no limit) with config['acq_blocked']."""
+  return None if _acq_blocked(model) else ACQ_FUSED_MAX_N
+
+
+def _acq_fused_unmet(model, sub_dataset_key, n_samples=1, n_kept=None, enabled=None, max_n=ACQ_FUSED_MAX_N):
   """The first condition that keeps a value_and_grad call from the one-launch path (hbo_acq_grad_samples, context option
   'acq_fused'), as a message, or None.  Host-side checks only.  n_kept: factor handles at hand for the n_samples parameter samples
-  (None: not known yet); enabled: the option's value (None: read from the default context)."""
+  (None: not known yet); enabled: the option's value (None: read from the default context); max_n: the largest sub-dataset (None:
+  no limit -- the caller goes to the _blocked entry points)."""
   if not (nat.acq_fused_enabled() if enabled is None else enabled):
     return "the context option 'acq_fused' is off"
   if not model.has_observations(sub_dataset_key):
     return 'the sub-dataset has no observations (the prior branch)'
   n = np.shape(model.dataset[sub_dataset_key].x)[0]
-  if n > ACQ_FUSED_MAX_N:
-    return f'the sub-dataset has {n} > {ACQ_FUSED_MAX_N} observations'
+  if max_n is not None and n > max_n:
+    return f'the sub-dataset has {n} > {max_n} observations'
   if getattr(model.cov_func, 'uses_mlp', False):
     return 'the kernel runs on an MLP basis'
   if getattr(model.mean_func, 'mean_id', None) == nat.MEAN_LINEAR_MLP:
@@ -316,17 +329,19 @@ ACQ_OPT_SEGMENT = 48       # evaluations per hbo_acq_maximize call (profiles/acq
 ACQ_OPT_MAX_EVALS = 4096   # evaluations a maximisation may spend in all
 
 
-def _acq_opt_unmet(model, sub_dataset_key, acfun_sub, n_samples=1, n_kept=None):
+def _acq_opt_unmet(model, sub_dataset_key, acfun_sub, n_samples=1, n_kept=None, max_n=ACQ_FUSED_MAX_N):
   """The first condition that keeps a maximisation off the device loop (hbo_acq_maximize), as a message, or None: an acquisition
   function outside the native registry, then `_acq_fused_unmet`'s conditions without the option check.  Host-side checks only."""
   if acfun_sub not in _NATIVE_ID:
     return f'the acquisition function {getattr(acfun_sub, "__name__", acfun_sub)!r} is not one of the native ones (EI, PI, UCB)'
-  return _acq_fused_unmet(model, sub_dataset_key, n_samples, n_kept, enabled=True)
+  return _acq_fused_unmet(model, sub_dataset_key, n_samples, n_kept, enabled=True, max_n=max_n)
 
 
-def _device_maximize(built, handles, noises, x0, lo, hi, acq_id, acfun_param, scale, opts, want_log):
-  """hbo_acq_maximize in segments of opts['segment'] evaluations until no start is RUNNING or opts['max_evals'] are spent.
+def _device_maximize(built, handles, noises, x0, lo, hi, acq_id, acfun_param, scale, opts, want_log, blocked=False):
+  """hbo_acq_maximize (blocked: hbo_acq_maximize_blocked, caches of any size) in segments of opts['segment'] evaluations until no start
+  is RUNNING or opts['max_evals'] are spent.
   x0 [R, D] in the model dtype; lo / hi [D] float64 or None.  Returns (x [R, D], values [R], status [R], evaluations [R], log or None)."""
+  entry = nat.lib().hbo_acq_maximize_blocked if blocked else nat.lib().hbo_acq_maximize
   s_count, (r_count, d) = len(built), x0.shape
   ctx = handles[0].ctx
   structs, caches, prm, nse = _sample_args(built, handles, noises, acfun_param)
@@ -340,9 +355,9 @@ def _device_maximize(built, handles, noises, x0, lo, hi, acq_id, acfun_param, sc
   while spent < opts['max_evals']:
     evals = int(min(opts['segment'], opts['max_evals'] - spent))
     log = np.zeros((evals, r_count), dtype=nat.ACQ_OPT_EVAL_DTYPE) if want_log else None
-    ctx.check(nat.lib().hbo_acq_maximize(ctx.handle, structs, s_count, caches, nat.ptr(x0), r_count, nat.ptr(lo), nat.ptr(hi), int(acq_id),
-                                         prm, nse, float(scale), nat.C.byref(o), nat.ptr(state), evals, nat.ptr(x), nat.ptr(val),
-                                         nat.ptr(status), nat.ptr(log)))
+    ctx.check(entry(ctx.handle, structs, s_count, caches, nat.ptr(x0), r_count, nat.ptr(lo), nat.ptr(hi), int(acq_id),
+                    prm, nse, float(scale), nat.C.byref(o), nat.ptr(state), evals, nat.ptr(x), nat.ptr(val),
+                    nat.ptr(status), nat.ptr(log)))
     spent += evals
     if want_log:
       logs.append(log)
@@ -352,16 +367,17 @@ def _device_maximize(built, handles, noises, x0, lo, hi, acq_id, acfun_param, sc
   return x, val, status, n_evals, (np.concatenate(logs) if want_log else None)
 
 
-def _fused_value_and_grad(built, handles, noises, xq, acq_id, acfun_param, scale):
+def _fused_value_and_grad(built, handles, noises, xq, acq_id, acfun_param, scale, blocked=False):
   """((S, M, 1) values in the model dtype, (S, M, D) gradients in float64) of S models over their finished factors: one
-  hbo_acq_grad_samples call -- one upload, one launch, one copy back."""
+  hbo_acq_grad_samples call -- one upload, one launch, one copy back (blocked: hbo_acq_grad_samples_blocked, caches of any size)."""
+  entry = nat.lib().hbo_acq_grad_samples_blocked if blocked else nat.lib().hbo_acq_grad_samples
   s_count, (nq, d) = len(built), xq.shape
   ctx = handles[0].ctx
   structs, caches, prm, nse = _sample_args(built, handles, noises, acfun_param)
   out = np.empty((s_count, nq, 1), dtype=xq.dtype)
   g = np.empty((s_count, nq, d), dtype=np.float64)
-  ctx.check(nat.lib().hbo_acq_grad_samples(ctx.handle, structs, s_count, caches, nat.ptr(xq), nq, int(acq_id), prm, nse, float(scale),
-                                           nat.ptr(out), g.ctypes.data_as(nat.C.POINTER(nat.C.c_double))))
+  ctx.check(entry(ctx.handle, structs, s_count, caches, nat.ptr(xq), nq, int(acq_id), prm, nse, float(scale),
+                  nat.ptr(out), g.ctypes.data_as(nat.C.POINTER(nat.C.c_double))))
   return out, g
 
 
@@ -386,9 +402,9 @@ def _hgp_value_and_grad(model, sub_dataset_key, x_queries, acq_id, acfun_param):
   built, noises = _sample_models(model, samples, dtype)
   handles = _hgp_sample_caches(model, sub_dataset_key, samples, dtype) if has_obs else []
   _, scale = model.predict_noise_and_scale(True, True)
-  if _acq_fused_unmet(model, sub_dataset_key, len(samples), len(handles)) is None:
-    # option 'acq_fused': every sample's pass in ONE launch over the kept factors; the mean as the loop below takes it
-    outs, gs = _fused_value_and_grad(built, handles, noises, xq, acq_id, acfun_param, scale)
+  if _acq_fused_unmet(model, sub_dataset_key, len(samples), len(handles), max_n=_blocked_max_n(model)) is None:
+    # option 'acq_fused': every sample's pass in ONE call over the kept factors; the mean as the loop below takes it
+    outs, gs = _fused_value_and_grad(built, handles, noises, xq, acq_id, acfun_param, scale, blocked=_acq_blocked(model))
     for out, g in zip(outs, gs):
       val += out
       grad += g
@@ -455,8 +471,9 @@ def acfun_wrapper(acfun_sub, acfun_callback_default):
     grad = np.zeros((xq.shape[0], model.input_dim), dtype=np.float64)
     if bm is None:
       return out, grad
-    if _acq_fused_unmet(model, sub_dataset_key) is None:   # option 'acq_fused': the one-launch path with S = 1
-      outs, gs = _fused_value_and_grad([bm], [handle], [add_noise], xq, _NATIVE_ID[acfun_sub], acfun_param, scale)
+    if _acq_fused_unmet(model, sub_dataset_key, max_n=_blocked_max_n(model)) is None:   # option 'acq_fused': the one-launch path with S = 1
+      outs, gs = _fused_value_and_grad([bm], [handle], [add_noise], xq, _NATIVE_ID[acfun_sub], acfun_param, scale,
+                                       blocked=_acq_blocked(model))
       return outs[0], gs[0]
     ctx = handle.ctx if handle is not None else nat.default_context()
     ctx.check(nat.lib().hbo_acq_grad(ctx.handle, bm.ref(), handle.handle if handle is not None else None,
@@ -472,14 +489,16 @@ def acfun_wrapper(acfun_sub, acfun_callback_default):
     Returns (x_best [D] float64, value_best, info): the start with the largest finite value wins, the lowest index among equals;
     without any, x_init[0] and NaN.  info: per-start 'x', 'value', 'status', 'evals', and 'log' ([evaluations, R] records) on
     request.  Works on the cached factors value_and_grad uses; a model the device loop does not cover raises
-    HboError(HBO_ERR_UNSUPPORTED) -- there is no fall-back."""
+    HboError(HBO_ERR_UNSUPPORTED) -- there is no fall-back.  More than 128 observations are such a model unless
+    model.params.config['acq_blocked'] is set: the calls then go to hbo_acq_maximize_blocked."""
     o = dict(ACQ_OPT_DEFAULTS, segment=ACQ_OPT_SEGMENT, max_evals=ACQ_OPT_MAX_EVALS, log=False)
     o.update(opts or {})
     x_init = np.atleast_2d(np.asarray(x_init, dtype=np.float64))
     hgp = isinstance(model, gp.HGP)
     samples = model.get_model_params_samples() if hgp else None
     n_samples = len(samples) if hgp else 1
-    unmet = _acq_opt_unmet(model, sub_dataset_key, acfun_sub, n_samples)
+    blocked, max_n = _acq_blocked(model), _blocked_max_n(model)
+    unmet = _acq_opt_unmet(model, sub_dataset_key, acfun_sub, n_samples, max_n=max_n)
     if unmet is not None:
       raise nat.HboError(nat.HBO_ERR_UNSUPPORTED, 'ac_func.maximize: ' + unmet)
     acfun_param = acfun_callback(model, sub_dataset_key)
@@ -488,7 +507,7 @@ def acfun_wrapper(acfun_sub, acfun_callback_default):
       dtype = _model.infer_dtype(sd.x, sd.y)
       built, noises = _sample_models(model, samples, dtype)
       handles = _hgp_sample_caches(model, sub_dataset_key, samples, dtype)
-      unmet = _acq_opt_unmet(model, sub_dataset_key, acfun_sub, n_samples, len(handles))
+      unmet = _acq_opt_unmet(model, sub_dataset_key, acfun_sub, n_samples, len(handles), max_n=max_n)
       if unmet is not None:
         raise nat.HboError(nat.HBO_ERR_UNSUPPORTED, 'ac_func.maximize: ' + unmet)
       _, scale = model.predict_noise_and_scale(True, True)
@@ -502,7 +521,7 @@ def acfun_wrapper(acfun_sub, acfun_callback_default):
       lo, hi = np.ascontiguousarray(b[:, 0]), np.ascontiguousarray(b[:, 1])
     x0 = np.ascontiguousarray(x_init, dtype=dtype)
     x, val, status, n_evals, log = _device_maximize(built, handles, noises, x0, lo, hi, _NATIVE_ID[acfun_sub], acfun_param, scale, o,
-                                                    bool(o['log']))
+                                                    bool(o['log']), blocked=blocked)
     if hgp:
       model.update_model_params(samples[-1])   # as every HGP path here leaves it (gp.py:674-678)
     info = {'x': x, 'value': val, 'status': status, 'evals': n_evals}

@@ -1,6 +1,7 @@
 // d acquisition / d x_query over a cache, what jaxopt's L-BFGS-B differentiates in bayesopt() (bayesopt.py:116-125): hbo_acq_grad for
 // one model and any cache (the launches: post.hip, trisolve.hip, mlp.hip, kumar.hip), and hbo_acq_grad_samples for S parameter samples
-// of one model family over finished caches of n <= 128 as one launch (acq_small.hip).  Host code only.
+// of one model family over finished caches: of n <= 128 as one launch (acq_small.hip), and hbo_acq_grad_samples_blocked for any n
+// (acq_blocked.hip: four launches per chunk of queries).  Host code only.
 #include "api_internal.h"
 
 extern "C" int hbo_acq_grad(hbo_ctx* c, const hbo_model* m, hbo_cache* k, const void* xq, int64_t M, int acq_id,
@@ -104,27 +105,43 @@ extern "C" int hbo_acq_grad(hbo_ctx* c, const hbo_model* m, hbo_cache* k, const 
   return HBO_OK;
 }
 
-// ---- the same for S parameter samples of one model family over their FINISHED caches, n <= 128: one upload, one launch (acq_small.hip:
-//      a workgroup per (sample, query) pair), one copy back, one wait -- whatever S is.  Row s = hbo_acq_grad of sample s up to the order
-//      of summation.  The prior branch, MLP bases and input-warped models stay with hbo_acq_grad (HBO_ERR_UNSUPPORTED here, before any
-//      device work).
+// ---- the same for S parameter samples of one model family over their FINISHED caches: one upload, the launches, one copy back, one
+//      wait -- whatever S is.  Row s = hbo_acq_grad of sample s up to the order of summation.  The prior branch, MLP bases and
+//      input-warped models stay with hbo_acq_grad (HBO_ERR_UNSUPPORTED here, before any device work).
+//      Every cache of n <= 128 (and no force_blocked): ONE launch (acq_small.hip: a workgroup per (sample, query) pair).  Otherwise every
+//      sample takes the four launches of acq_blocked.hip, the queries in chunks whose workspace ([S][chunk][ldv] doubles, three times)
+//      stays under ACQ_BLOCKED_WS_BYTES; a row's bits do not depend on the chunking.
 //      val64_out (nullable, [S][M]): the values before they are rounded to the model dtype (include/hbo_tune.h:
 //      hbo_probe_acq_grad_samples64); without it the call is hbo_acq_grad_samples, to the byte of every buffer.
-static int acq_grad_samples(hbo_ctx* c, const hbo_model* models, int32_t S, hbo_cache* const* caches, const void* xq, int64_t M, int acq_id,
-                            const double* params, const double* add_noise, double scale, void* acq_out, double* grad_out, double* val64_out) {
-  if (!models || !caches || !xq || !params || !add_noise || !acq_out || !grad_out) return fail(c, HBO_ERR_ARG, "hbo_acq_grad_samples: null argument");
-  if (S <= 0 || S > 4096) return fail(c, HBO_ERR_ARG, "hbo_acq_grad_samples: 1 <= S <= 4096");
-  if (acq_id < 0 || acq_id > HBO_ACQ_UCB) return fail(c, HBO_ERR_ARG, "hbo_acq_grad_samples: bad acq_id");
-  if (!c) return fail(c, HBO_ERR_ARG, "hbo_acq_grad_samples: ctx is null");
-  if (M < 0) return fail(c, HBO_ERR_ARG, "hbo_acq_grad_samples: M < 0");
+namespace {
+constexpr size_t ACQ_BLOCKED_WS_BYTES = (size_t)256 << 20;
+constexpr int64_t ACQ_BLOCKED_MAX_CHUNK = 65535;   // grid.y of the first launch
+struct AcqSamplesMode {
+  const char* fn;          // the entry point's name in messages
+  int max_n;               // the largest cache the entry point takes (acq_samples_check)
+  bool force_blocked;      // test hook: caches of n <= 128 through the blocked kernels too
+  int64_t chunk_queries;   // test hook: > 0 overrides the chunk size
+};
+}  // namespace
+static int acq_grad_samples(hbo_ctx* c, const AcqSamplesMode& mode, const hbo_model* models, int32_t S, hbo_cache* const* caches, const void* xq,
+                            int64_t M, int acq_id, const double* params, const double* add_noise, double scale, void* acq_out, double* grad_out,
+                            double* val64_out) {
+  const std::string fn = std::string(mode.fn) + ": ";
+  if (!models || !caches || !xq || !params || !add_noise || !acq_out || !grad_out) return fail(c, HBO_ERR_ARG, fn + "null argument");
+  if (S <= 0 || S > 4096) return fail(c, HBO_ERR_ARG, fn + "1 <= S <= 4096");
+  if (acq_id < 0 || acq_id > HBO_ACQ_UCB) return fail(c, HBO_ERR_ARG, fn + "bad acq_id");
+  if (!c) return fail(c, HBO_ERR_ARG, fn + "ctx is null");
+  if (M < 0) return fail(c, HBO_ERR_ARG, fn + "M < 0");
   const hbo_model* m0 = &models[0];
   bool any_bad = false;
-  if (int rc = acq_samples_check(c, "hbo_acq_grad_samples: ", models, S, caches, &any_bad)) return rc;
+  if (int rc = acq_samples_check(c, fn, models, S, caches, mode.max_n, &any_bad)) return rc;
   if (M == 0) return HBO_OK;
   HIPCHK(c, hipSetDevice(c->device));
   const int dtype = m0->dtype, D = m0->input_dim;
   const size_t es = esize(dtype);
   hipStream_t st = c->stream;
+  const int ldv = acq_blocked_ldv(S, caches);
+  const bool blocked = mode.force_blocked || ldv > HBO_TILE;
   // one block up: [S records][S x 2 D doubles][M x D queries]; one block down: [S x M x D doubles][S x M values]
   const size_t smp_b = align256(sizeof(AcqSmallSample) * S), vec_b = align256(sizeof(double) * 2 * D * S), xq_b = (size_t)M * D * es;
   const size_t grad_b = align256(sizeof(double) * (size_t)S * M * D), acq_b = (size_t)S * M * es;
@@ -133,7 +150,16 @@ static int acq_grad_samples(hbo_ctx* c, const hbo_model* models, int32_t S, hbo_
   char* d_in = static_cast<char*>(ws_get(c, WS_AF_IN, in_b));
   char* d_out = static_cast<char*>(ws_get(c, WS_AF_OUT, out_b));
   if (!d_in || !d_out) return HBO_ERR_HIP;
-  char* stage = static_cast<char*>(stage_begin(c, "hbo_acq_grad_samples: ", align256(in_b) + out_b));
+  int64_t chunk = 0;
+  double* d_work = nullptr;
+  if (blocked) {
+    const size_t per_query = sizeof(double) * 3 * (size_t)S * ldv;
+    chunk = mode.chunk_queries > 0 ? mode.chunk_queries : std::max<int64_t>(1, (int64_t)(ACQ_BLOCKED_WS_BYTES / per_query));
+    chunk = std::min(std::min(chunk, M), ACQ_BLOCKED_MAX_CHUNK);
+    d_work = static_cast<double*>(ws_get(c, WS_AB_WORK, per_query * (size_t)chunk));
+    if (!d_work) return HBO_ERR_HIP;
+  }
+  char* stage = static_cast<char*>(stage_begin(c, fn.c_str(), align256(in_b) + out_b));
   if (!stage) return HBO_ERR_HIP;
   char* stage_out = stage + align256(in_b);
   AcqSmallSample* hs = reinterpret_cast<AcqSmallSample*>(stage);
@@ -146,7 +172,18 @@ static int acq_grad_samples(hbo_ctx* c, const hbo_model* models, int32_t S, hbo_
   a.D = D; a.M = M; a.kernel_id = m0->kernel_id; a.mean_id = m0->mean_id; a.acq_id = acq_id; a.scale = scale;
   a.grad_out = reinterpret_cast<double*>(d_out); a.acq_out = d_out + grad_b;
   if (val64_out) a.val64_out = reinterpret_cast<double*>(d_out + v64_o);
-  launch_acq_small(dtype, a, S, st);
+  if (!blocked) launch_acq_small(dtype, a, S, st);
+  else {
+    AcqBlockedArgs b = {};
+    b.a = a; b.ldv = ldv;
+    const size_t plane = (size_t)S * chunk * ldv;
+    b.k = d_work; b.l = d_work + plane; b.beta = d_work + 2 * plane;
+    for (int64_t q0 = 0; q0 < M; q0 += chunk) {   // (stream order: a chunk's launches run after the ones before it have read the workspace)
+      b.q0 = q0; b.mc = std::min(chunk, M - q0);
+      launch_acq_blocked(dtype, b, S, st);
+    }
+  }
+  HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipMemcpyAsync(stage_out, d_out, out_b, hipMemcpyDeviceToHost, st));
   HIPCHK(c, hipStreamSynchronize(st));
   HIPCHK(c, hipGetLastError());
@@ -158,12 +195,30 @@ static int acq_grad_samples(hbo_ctx* c, const hbo_model* models, int32_t S, hbo_
 extern "C" int hbo_acq_grad_samples(hbo_ctx* c, const hbo_model* models, int32_t S, hbo_cache* const* caches, const void* xq, int64_t M,
                                     int acq_id, const double* params, const double* add_noise, double scale, void* acq_out,
                                     double* grad_out) {
-  return acq_grad_samples(c, models, S, caches, xq, M, acq_id, params, add_noise, scale, acq_out, grad_out, nullptr);
+  const AcqSamplesMode mode = {"hbo_acq_grad_samples", HBO_TILE, false, 0};
+  return acq_grad_samples(c, mode, models, S, caches, xq, M, acq_id, params, add_noise, scale, acq_out, grad_out, nullptr);
+}
+extern "C" int hbo_acq_grad_samples_blocked(hbo_ctx* c, const hbo_model* models, int32_t S, hbo_cache* const* caches, const void* xq,
+                                            int64_t M, int acq_id, const double* params, const double* add_noise, double scale,
+                                            void* acq_out, double* grad_out) {
+  const AcqSamplesMode mode = {"hbo_acq_grad_samples_blocked", INT_MAX, false, 0};
+  return acq_grad_samples(c, mode, models, S, caches, xq, M, acq_id, params, add_noise, scale, acq_out, grad_out, nullptr);
 }
 // include/hbo_tune.h (TEST HOOK): hbo_acq_grad_samples with the fp64 values hbo_acq_maximize's control kernel reads
 extern "C" int hbo_probe_acq_grad_samples64(hbo_ctx* c, const hbo_model* models, int32_t S, hbo_cache* const* caches, const void* xq, int64_t M,
                                             int acq_id, const double* params, const double* add_noise, double scale, void* acq_out,
                                             double* grad_out, double* val64_out) {
   if (!val64_out) return fail(c, HBO_ERR_ARG, "hbo_probe_acq_grad_samples64: val64_out is null");
-  return acq_grad_samples(c, models, S, caches, xq, M, acq_id, params, add_noise, scale, acq_out, grad_out, val64_out);
+  const AcqSamplesMode mode = {"hbo_acq_grad_samples", HBO_TILE, false, 0};
+  return acq_grad_samples(c, mode, models, S, caches, xq, M, acq_id, params, add_noise, scale, acq_out, grad_out, val64_out);
+}
+// include/hbo_tune.h (TEST HOOK): hbo_acq_grad_samples_blocked with those values, the blocked kernels on request and a chunk size
+extern "C" int hbo_probe_acq_grad_samples_blocked64(hbo_ctx* c, const hbo_model* models, int32_t S, hbo_cache* const* caches, const void* xq,
+                                                    int64_t M, int acq_id, const double* params, const double* add_noise, double scale,
+                                                    void* acq_out, double* grad_out, int32_t force_blocked, int64_t chunk_queries,
+                                                    double* val64_out) {
+  if (!val64_out) return fail(c, HBO_ERR_ARG, "hbo_probe_acq_grad_samples_blocked64: val64_out is null");
+  if (chunk_queries < 0) return fail(c, HBO_ERR_ARG, "hbo_probe_acq_grad_samples_blocked64: chunk_queries < 0");
+  const AcqSamplesMode mode = {"hbo_acq_grad_samples_blocked", INT_MAX, force_blocked != 0, chunk_queries};
+  return acq_grad_samples(c, mode, models, S, caches, xq, M, acq_id, params, add_noise, scale, acq_out, grad_out, val64_out);
 }

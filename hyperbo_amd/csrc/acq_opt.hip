@@ -1,6 +1,7 @@
 // hbo_acq_maximize: bayesopt()'s inner maximisation of the acquisition function (bayesopt.py:116-125) for R starts in one call.  One
 // upload, then per evaluation two stream-ordered launches with no host wait -- acq_small_kernel on grid (R, S) over the starts'
-// pending points (acq_small.hip), then acq_opt_ctl_kernel, one workgroup per start, which reduces the S per-sample results of its start,
+// pending points (acq_small.hip; hbo_acq_maximize_blocked over a cache of n > 128: the four launches of acq_blocked.hip in its
+// place), then acq_opt_ctl_kernel, one workgroup per start, which reduces the S per-sample results of its start,
 // runs one step of the state machine of acq_opt_ctl.h and writes the next pending point -- and one synchronisation and one copy back.
 // A start reads and writes only its own state, its own row of the pending points and its own columns of the per-sample results.
 // Also here: the host hook hbo_probe_acq_opt_ctl, the same control text on one thread.
@@ -94,11 +95,13 @@ extern "C" int64_t hbo_acq_opt_state_doubles(int32_t D, int32_t memory) {
   return hbo_acq_opt_state_size(D, memory);
 }
 
-extern "C" int hbo_acq_maximize(hbo_ctx* c, const hbo_model* models, int32_t S, hbo_cache* const* caches, const void* x0, int32_t R,
-                                const double* lo, const double* hi, int acq_id, const double* params, const double* add_noise, double scale,
-                                const hbo_acq_opt_opts* opts, double* state, int32_t evals, double* x_out, double* val_out, int32_t* status,
-                                hbo_acq_opt_eval* log) {
-  const std::string fn = "hbo_acq_maximize: ";
+// The body of hbo_acq_maximize and hbo_acq_maximize_blocked: they differ in the largest cache they take (max_n) and, with it, in the
+// evaluation step -- one launch of acq_small.hip when every cache has n <= 128, the four launches of acq_blocked.hip otherwise.
+static int acq_maximize(hbo_ctx* c, const char* name, int max_n, const hbo_model* models, int32_t S, hbo_cache* const* caches, const void* x0,
+                        int32_t R, const double* lo, const double* hi, int acq_id, const double* params, const double* add_noise, double scale,
+                        const hbo_acq_opt_opts* opts, double* state, int32_t evals, double* x_out, double* val_out, int32_t* status,
+                        hbo_acq_opt_eval* log) {
+  const std::string fn = std::string(name) + ": ";
   if (!models || !caches || !x0 || !params || !add_noise || !state || !x_out || !val_out || !status) return fail(c, HBO_ERR_ARG, fn + "null argument");
   if (S <= 0 || S > 4096) return fail(c, HBO_ERR_ARG, fn + "1 <= S <= 4096");
   if (acq_id < 0 || acq_id > HBO_ACQ_UCB) return fail(c, HBO_ERR_ARG, fn + "bad acq_id");
@@ -107,7 +110,7 @@ extern "C" int hbo_acq_maximize(hbo_ctx* c, const hbo_model* models, int32_t S, 
   if (evals <= 0 || evals > 4096) return fail(c, HBO_ERR_ARG, fn + "1 <= evals <= 4096");
   if (int rc = acq_opt_check_opts(c, fn, opts)) return rc;
   bool any_bad = false;
-  if (int rc = acq_samples_check(c, fn, models, S, caches, &any_bad)) return rc;
+  if (int rc = acq_samples_check(c, fn, models, S, caches, max_n, &any_bad)) return rc;
   const hbo_model* m0 = &models[0];
   const int dtype = m0->dtype, D = m0->input_dim;
   if (int rc = acq_opt_check_box(c, fn, lo, hi, D, dtype)) return rc;
@@ -127,6 +130,15 @@ extern "C" int hbo_acq_maximize(hbo_ctx* c, const hbo_model* models, int32_t S, 
   HIPCHK(c, hipSetDevice(c->device));
   const size_t es = esize(dtype);
   hipStream_t st = c->stream;
+  const int ldv = acq_blocked_ldv(S, caches);
+  const bool blocked = ldv > HBO_TILE;
+  const size_t plane = (size_t)S * R * ldv;   // k, l, beta of the blocked evaluation: [S][R][ldv] doubles each
+  if (blocked) {
+    size_t total = 0;
+    HIPCHK(c, hipDeviceTotalMem(&total, c->device));
+    if (sizeof(double) * 3 * plane > total / 2)
+      return fail(c, HBO_ERR_UNSUPPORTED, fn + "the evaluation workspace (3 x S x R x npad doubles) exceeds half of the device memory; use fewer starts per call");
+  }
   // one block up: [S records][S x 2 D doubles][lo, hi][R x D pending points][R states]; the log follows the states, and one copy brings
   // [states | log] back.  Scratch of the rounds: [S x R x D gradients][S x R values fp64][S x R values in the model dtype]
   const size_t smp_b = align256(sizeof(AcqSmallSample) * S), vec_b = align256(sizeof(double) * 2 * D * S), box_b = align256(sizeof(double) * 2 * D);
@@ -137,6 +149,8 @@ extern "C" int hbo_acq_maximize(hbo_ctx* c, const hbo_model* models, int32_t S, 
   char* d_in = static_cast<char*>(ws_get(c, WS_AO_IN, up_b + log_b));
   char* d_out = static_cast<char*>(ws_get(c, WS_AO_OUT, grad_b + val_b + acq_b));
   if (!d_in || !d_out) return HBO_ERR_HIP;
+  double* d_work = blocked ? static_cast<double*>(ws_get(c, WS_AB_WORK, sizeof(double) * 3 * plane)) : nullptr;
+  if (blocked && !d_work) return HBO_ERR_HIP;
   char* stage = static_cast<char*>(stage_begin(c, fn.c_str(), up_b + log_b));
   if (!stage) return HBO_ERR_HIP;
   acq_small_pack(reinterpret_cast<AcqSmallSample*>(stage), reinterpret_cast<double*>(stage + smp_b), models, S, caches, params, add_noise);
@@ -179,8 +193,12 @@ extern "C" int hbo_acq_maximize(hbo_ctx* c, const hbo_model* models, int32_t S, 
   k.D = D; k.R = R; k.S = S;
   // hbo_tune poison: the log is written record by record by the control launches; one that was skipped must not pass for an earlier call's
   if (c->opt_poison && log_b) HIPCHK(c, hipMemsetAsync(d_in + up_b, 0xFF, log_b, st));
+  AcqBlockedArgs b = {};
+  b.a = a; b.ldv = ldv; b.q0 = 0; b.mc = R;
+  b.k = d_work; b.l = d_work + plane; b.beta = d_work + 2 * plane;
   for (int e = 0; e < evals; ++e) {
-    launch_acq_small(dtype, a, S, st);
+    if (blocked) launch_acq_blocked(dtype, b, S, st);
+    else launch_acq_small(dtype, a, S, st);
     launch_acq_opt_ctl(dtype, k, e, st);
   }
   HIPCHK(c, hipGetLastError());
@@ -196,6 +214,20 @@ extern "C" int hbo_acq_maximize(hbo_ctx* c, const hbo_model* models, int32_t S, 
     status[r] = (int32_t)v.hdr[HBO_ACQ_OPT_S_STATUS];
   }
   return any_bad ? HBO_NOT_PD : HBO_OK;
+}
+extern "C" int hbo_acq_maximize(hbo_ctx* c, const hbo_model* models, int32_t S, hbo_cache* const* caches, const void* x0, int32_t R,
+                                const double* lo, const double* hi, int acq_id, const double* params, const double* add_noise, double scale,
+                                const hbo_acq_opt_opts* opts, double* state, int32_t evals, double* x_out, double* val_out, int32_t* status,
+                                hbo_acq_opt_eval* log) {
+  return acq_maximize(c, "hbo_acq_maximize", HBO_TILE, models, S, caches, x0, R, lo, hi, acq_id, params, add_noise, scale, opts, state, evals,
+                      x_out, val_out, status, log);
+}
+extern "C" int hbo_acq_maximize_blocked(hbo_ctx* c, const hbo_model* models, int32_t S, hbo_cache* const* caches, const void* x0, int32_t R,
+                                        const double* lo, const double* hi, int acq_id, const double* params, const double* add_noise,
+                                        double scale, const hbo_acq_opt_opts* opts, double* state, int32_t evals, double* x_out,
+                                        double* val_out, int32_t* status, hbo_acq_opt_eval* log) {
+  return acq_maximize(c, "hbo_acq_maximize_blocked", INT_MAX, models, S, caches, x0, R, lo, hi, acq_id, params, add_noise, scale, opts, state,
+                      evals, x_out, val_out, status, log);
 }
 
 // include/hbo_tune.h (TEST HOOK): the control code of acq_opt_ctl.h on the host, one thread, for one evaluation of one start

@@ -91,17 +91,10 @@ __global__ __launch_bounds__(256) void acq_small_kernel(AcqSmallArgs a) {
     s_acc[tid] = b;
   }
   if (tid == 0) {
-    const double mu = ka + mean;
-    const double var = kqq - ll;
-    const double v2 = (var + sm.add_noise) * a.scale;
-    const double sd = sqrt(v2);
-    double val, amu, asd;
-    if (a.acq_id == HBO_ACQ_UCB) { val = mu + sm.param * sd; amu = 1.0; asd = sm.param; }
-    else if (a.acq_id == HBO_ACQ_PI) { val = (mu - sm.param) / sd; amu = 1.0 / sd; asd = -(mu - sm.param) / (sd * sd); }
-    else { const double uu = (mu - sm.param) / sd; val = sd * ei_over_sd(uu); amu = norm_cdf(uu); asd = norm_pdf(uu); }
-    s_amu = amu; s_avar = asd / (2.0 * sd) * a.scale;
-    *acq = (T)val;
-    if (a.val64_out) a.val64_out[(int64_t)s * a.M + q] = val;
+    const AcqScalars sc = acq_scalars(a.acq_id, ka + mean, kqq - ll, sm.add_noise, a.scale, sm.param);
+    s_amu = sc.amu; s_avar = sc.avar;
+    *acq = (T)sc.val;
+    if (a.val64_out) a.val64_out[(int64_t)s * a.M + q] = sc.val;
   }
   __syncthreads();
   const double amu = s_amu, avar = s_avar;

@@ -421,9 +421,9 @@ struct hbo_cache {
 };
 
 // What hbo_acq_grad_samples and hbo_acq_maximize ask of their S (model, cache) pairs, before any device work: one model family
-// (model_family_check) without MLP basis or linear_mlp mean, and finished caches of 1..128 observations that match their models.
-// *any_bad: a cache is not positive definite.
-static int acq_samples_check(hbo_ctx* c, const std::string& fn, const hbo_model* models, int32_t S, hbo_cache* const* caches, bool* any_bad) {
+// (model_family_check) without MLP basis or linear_mlp mean, and finished caches of 1..max_n observations that match their models
+// (HBO_TILE: the one-block entry points; INT_MAX: the _blocked ones).  *any_bad: a cache is not positive definite.
+static int acq_samples_check(hbo_ctx* c, const std::string& fn, const hbo_model* models, int32_t S, hbo_cache* const* caches, int max_n, bool* any_bad) {
   if (int rc = model_family_check(c, fn, models, S, "evaluate the samples with hbo_acq_grad")) return rc;
   for (int s = 0; s < S; ++s) {
     const hbo_model* m = &models[s];
@@ -431,7 +431,7 @@ static int acq_samples_check(hbo_ctx* c, const std::string& fn, const hbo_model*
     if (m->mean_id == HBO_MEAN_LINEAR_MLP) return fail(c, HBO_ERR_UNSUPPORTED, fn + "a linear_mlp mean is not supported; evaluate the samples with hbo_acq_grad");
     const hbo_cache* k = caches[s];
     if (!k || !k->t || k->t->n <= 0) return fail(c, HBO_ERR_UNSUPPORTED, fn + "a sample without observations (the prior branch) is not supported; evaluate it with hbo_acq_grad");
-    if (k->t->n > HBO_TILE) return fail(c, HBO_ERR_UNSUPPORTED, fn + "a cache has n > 128; evaluate the samples with hbo_acq_grad");
+    if (k->t->n > max_n) return fail(c, HBO_ERR_UNSUPPORTED, fn + "a cache has n > " + std::to_string(max_n) + "; evaluate the samples with hbo_acq_grad");
     if (k->dtype != m->dtype || k->D != m->input_dim) return fail(c, HBO_ERR_ARG, fn + "cache/model mismatch");
     if (k->input_warp != m->input_warp) return fail(c, HBO_ERR_ARG, fn + "the cache was factorised with another input warp");
     *any_bad = *any_bad || k->info != INT_MAX;
@@ -439,7 +439,8 @@ static int acq_samples_check(hbo_ctx* c, const std::string& fn, const hbo_model*
   return HBO_OK;
 }
 
-// the records acq_small_kernel reads of those pairs (hbo_internal.h: AcqSmallSample) and their per-feature values, hv [S][2 D]
+// the records acq_small_kernel and the kernels of acq_blocked.hip read of those pairs (hbo_internal.h: AcqSmallSample) and their
+// per-feature values, hv [S][2 D]
 static void acq_small_pack(AcqSmallSample* hs, double* hv, const hbo_model* models, int32_t S, hbo_cache* const* caches, const double* params,
                            const double* add_noise) {
   const int D = models[0].input_dim;
@@ -455,6 +456,13 @@ static void acq_small_pack(AcqSmallSample* hs, double* hv, const hbo_model* mode
     memcpy(hv + (size_t)s * 2 * D, md.inv_ls, sizeof(double) * D);
     memcpy(hv + (size_t)s * 2 * D + D, md.lin_w, sizeof(double) * D);
   }
+}
+
+// ldv of the blocked kernels' workspace (acq_blocked.hip): the largest n of the caches rounded up to the 128-row block
+static int acq_blocked_ldv(int32_t S, hbo_cache* const* caches) {
+  int64_t n = 1;
+  for (int s = 0; s < S; ++s) n = std::max<int64_t>(n, caches[s]->t->n);
+  return round_up(n, HBO_TILE);
 }
 
 // ---- sample paths (paths.hip), shared with the path maximiser (path_opt.hip) ------------------

@@ -446,6 +446,17 @@ struct AcqSmallArgs {
   double* val64_out;                                 // nullable [S][M]: the value before it is rounded to the model dtype (acq_opt.hip)
 };
 void launch_acq_small(int dtype, const AcqSmallArgs& a, int S, hipStream_t st);
+// ---- the same for caches of any n >= 1 (acq_blocked.hip): four stream-ordered launches over queries [q0, q0 + mc) of a.M --
+// k = k(x, X), l = W k, beta = W^T l, then one workgroup per (sample, query) pair for the scalars and the gradient.  The records are
+// AcqSmallSample as they are (a sample's rows are padded to its own npad = n rounded up to 128).  The workspace k, l, beta is
+// [S][mc][ldv] doubles each, ldv = the largest npad of the samples; nothing of it is read before this call has written it.
+struct AcqBlockedArgs {
+  AcqSmallArgs a;
+  double* k; double* l; double* beta;                // [S][mc][ldv]
+  int ldv;
+  int64_t q0, mc;
+};
+void launch_acq_blocked(int dtype, const AcqBlockedArgs& b, int S, hipStream_t st);
 // ---- the simulated BO loop on the device (bo_loop.hip: kernels and hbo_bo_simulated) ----
 // The pivot of the next row of a run: written by bo_select_kernel, read by the bo_row_kernel behind it.  Before the first selection
 // only `param` is read (set by the host: the acquisition parameter over an empty y).

@@ -151,4 +151,18 @@ __device__ __forceinline__ double ei_over_sd(double u) {
   const double e = norm_pdf(u) + u * norm_cdf(u);
   return e < 0.0 ? 0.0 : e;
 }
+// The scalar step of the acquisition gradient, from the posterior mean and variance at one query (acq_small.hip, acq_blocked.hip):
+// the value, a_mu = d value / d mu and a_var = d value / d var (through sd = sqrt((var + add_noise) scale)).
+struct AcqScalars { double val, amu, avar; };
+__device__ __forceinline__ AcqScalars acq_scalars(int acq_id, double mu, double var, double add_noise, double scale, double param) {
+  const double v2 = (var + add_noise) * scale;
+  const double sd = sqrt(v2);
+  double val, amu, asd;
+  if (acq_id == HBO_ACQ_UCB) { val = mu + param * sd; amu = 1.0; asd = param; }
+  else if (acq_id == HBO_ACQ_PI) { val = (mu - param) / sd; amu = 1.0 / sd; asd = -(mu - param) / (sd * sd); }
+  else { const double uu = (mu - param) / sd; val = sd * ei_over_sd(uu); amu = norm_cdf(uu); asd = norm_pdf(uu); }
+  AcqScalars r;
+  r.val = val; r.amu = amu; r.avar = asd / (2.0 * sd) * scale;
+  return r;
+}
 }  // namespace

@@ -60,7 +60,8 @@ enum WsSlot { WS_XQ = 1, WS_MU0, WS_KD, WS_MU, WS_VAR, WS_ACQ, WS_K, WS_COLSQ, W
               WS_NS_MODELS, WS_NS_MODELS_X, WS_NS_DESC, WS_NS_PACK, WS_NS_MLP_W, WS_NS_MLPT, WS_NS_ACTS, WS_NS_MAT, WS_TRAIN, WS_AF_IN, WS_AF_OUT,
               WS_BO_IN, WS_BO_FEAT, WS_BO_V, WS_BO_OUT, WS_AO_IN, WS_AO_OUT,
               WS_PATH_DRAWS, WS_PATH_SUMS, WS_PATH_R, WS_PATH_Z, WS_PATH_V, WS_PATH_OUT,
-              WS_PO_IN, WS_PO_OUT, WS_PROBE /* hbo_mfma_peak_probe's sink */, WS_SLOT_END };
+              WS_PO_IN, WS_PO_OUT, WS_PROBE /* hbo_mfma_peak_probe's sink */,
+              WS_AB_WORK /* acq_blocked.hip: k, l, beta */, WS_SLOT_END };
 // every slot is distinct by construction (auto-numbered; the per-layer range WS_FQ0.. is closed by WS_FQ_LAST before WS_K3), and the
 // posterior's per-lane offset (cache.hip: 4096 * lane) must clear the whole range
 static_assert(WS_FQ0 + HBO_MAX_MLP_LAYERS <= WS_K3 && WS_SLOT_END < 4096, "workspace slots overlap a lane offset");
@@ -73,7 +74,7 @@ static inline bool ws_poisonable(int slot) {
     case WS_MU0: case WS_KD: case WS_MU: case WS_VAR: case WS_ACQ: case WS_K: case WS_COLSQ: case WS_V: case WS_KQQ: case WS_COV:
     case WS_VPART: case WS_MUPART: case WS_K3: case WS_SYRK3_A: case WS_SYRK3_B: case WS_TRTRI3_X: case WS_TRTRI3_Y: case WS_LAUUM3:
     case WS_AG_K: case WS_AG_L: case WS_AG_B: case WS_EXTRA_Z: case WS_AF_OUT: case WS_BO_FEAT: case WS_BO_V: case WS_BO_OUT: case WS_AO_OUT:
-    case WS_PATH_SUMS: case WS_PATH_R: case WS_PATH_Z: case WS_PATH_V: case WS_PATH_OUT: case WS_PO_OUT:
+    case WS_PATH_SUMS: case WS_PATH_R: case WS_PATH_Z: case WS_PATH_V: case WS_PATH_OUT: case WS_PO_OUT: case WS_AB_WORK:
       return true;
     default: return false;
   }

@@ -288,6 +288,20 @@ int hbo_acq_grad(hbo_ctx* ctx, const hbo_model* model, hbo_cache* cache, const v
 int hbo_acq_grad_samples(hbo_ctx* ctx, const hbo_model* models, int32_t S, hbo_cache* const* caches, const void* xq, int64_t M,
                          int acq_id, const double* params, const double* add_noise, double scale, void* acq_out, double* grad_out);
 
+/* ---- hbo_acq_grad_samples for caches of ANY n >= 1: same arguments, same checks (before any device work), same return codes and the
+ *      same NaN rows / HBO_NOT_PD for a sample that is not positive definite -- minus the refusal of n > 128; the prior branch, MLP
+ *      bases, a linear_mlp mean and input-warped models stay refused.  When every cache of the call has n <= 128 this IS
+ *      hbo_acq_grad_samples: the same launch, the same bits.  Otherwise every sample of the call, those of n <= 128 included, takes
+ *      four stream-ordered launches per chunk of queries (csrc/acq_blocked.hip: k = k(x, X); l = W k; beta = W^T l; one workgroup
+ *      per (sample, query) pair for the sums, the scalars and the gradient) over an fp64 workspace of three [S, chunk, npad] arrays,
+ *      the chunk chosen so that they stay under 256 MiB; one upload, one copy back and one synchronisation whatever S and M are.  A
+ *      phase boundary is a launch boundary: no grid-wide barrier, no wait between workgroups, no atomics.  Every sum is fp64 in an
+ *      order fixed by the cache's n and input_dim alone: a row does not depend on which samples or queries share the call, on its
+ *      place among them, on the other caches' sizes or on the chunking (bit for bit), and identical calls are bit-identical. */
+int hbo_acq_grad_samples_blocked(hbo_ctx* ctx, const hbo_model* models, int32_t S, hbo_cache* const* caches, const void* xq, int64_t M,
+                                 int acq_id, const double* params, const double* add_noise, double scale, void* acq_out,
+                                 double* grad_out);
+
 /* ---- bayesopt()'s inner maximisation of the acquisition function on the device (hyperbo/bo_utils/bayesopt.py:116-125), R starts
  *      in ONE call: a box-constrained projected L-BFGS that minimises f(x) = -(mean over the S samples of the acquisition) over
  *      lo <= x <= hi (csrc/acq_opt_ctl.h; the algorithm: DESIGN.md section 6).  One upload, then `evals` rounds of two stream-ordered
@@ -332,6 +346,17 @@ int hbo_acq_maximize(hbo_ctx* ctx, const hbo_model* models, int32_t S, hbo_cache
                      const double* lo, const double* hi, int acq_id, const double* params, const double* add_noise, double scale,
                      const hbo_acq_opt_opts* opts, double* state, int32_t evals, double* x_out, double* val_out, int32_t* status,
                      hbo_acq_opt_eval* log);
+
+/* ---- hbo_acq_maximize for caches of ANY n >= 1: same arguments, checks, state and log format, return codes and determinism (a run
+ *      gives the same bits however it is cut into calls), minus the refusal of n > 128.  The evaluation of a round is that of
+ *      hbo_acq_grad_samples_blocked over the R pending points: hbo_acq_maximize's one launch when every cache has n <= 128 (then the
+ *      two entry points agree to the bit: state, log, x_out, val_out, status), four launches otherwise, so five stream-ordered
+ *      launches per round, still without a host wait.  HBO_ERR_UNSUPPORTED (before any device work) also when the evaluation
+ *      workspace, 3 * S * R * npad doubles, exceeds half of the device memory: use fewer starts per call. */
+int hbo_acq_maximize_blocked(hbo_ctx* ctx, const hbo_model* models, int32_t S, hbo_cache* const* caches, const void* x0, int32_t R,
+                             const double* lo, const double* hi, int acq_id, const double* params, const double* add_noise, double scale,
+                             const hbo_acq_opt_opts* opts, double* state, int32_t evals, double* x_out, double* val_out, int32_t* status,
+                             hbo_acq_opt_eval* log);
 
 /* ---- the maximisation of S posterior sample paths over a box, R starts each, in ONE call: continuous Thompson sampling -- q
  *      suggestions from q paths (no counterpart in the reference).  The optimiser is that of hbo_acq_maximize, run on

@@ -92,6 +92,14 @@ int hbo_probe_lbfgs_ctl(double* state, int32_t P, const hbo_lbfgs_opts* opts, co
 int hbo_probe_acq_grad_samples64(hbo_ctx* ctx, const hbo_model* models, int32_t S, hbo_cache* const* caches, const void* xq, int64_t M,
                                  int acq_id, const double* params, const double* add_noise, double scale, void* acq_out, double* grad_out,
                                  double* val64_out);
+/* TEST HOOK: hbo_acq_grad_samples_blocked (same checks, same launches, same results) that also returns val64_out [S, M], the fp64
+ * values the control kernel of hbo_acq_maximize_blocked reads.  force_blocked != 0 sends a call whose caches all have n <= 128 through
+ * the blocked kernels of csrc/acq_blocked.hip too (without it such a call is hbo_acq_grad_samples' one launch); chunk_queries > 0
+ * overrides the number of queries per pass (0: the entry point's own choice; < 0: HBO_ERR_ARG).  Neither changes a bit of a row that
+ * the blocked kernels computed: every sum runs in an order fixed by the cache's n and input_dim alone, without atomics. */
+int hbo_probe_acq_grad_samples_blocked64(hbo_ctx* ctx, const hbo_model* models, int32_t S, hbo_cache* const* caches, const void* xq,
+                                         int64_t M, int acq_id, const double* params, const double* add_noise, double scale, void* acq_out,
+                                         double* grad_out, int32_t force_blocked, int64_t chunk_queries, double* val64_out);
 /* TEST HOOK: the control code of hbo_acq_maximize (csrc/acq_opt_ctl.h, the text its control kernel compiles) on the host, one thread,
  * for one evaluation of one start; no context, no device.  D: input_dim; dtype: the model dtype the pending point is rounded to.
  * lo, hi [D] (both null: 0 and 1).  vals [S] and grads [S, D]: the per-sample acquisition values (fp64) and gradients at the point the
