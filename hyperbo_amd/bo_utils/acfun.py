@@ -337,14 +337,24 @@ def _acq_opt_unmet(model, sub_dataset_key, acfun_sub, n_samples=1, n_kept=None, 
   return _acq_fused_unmet(model, sub_dataset_key, n_samples, n_kept, enabled=True, max_n=max_n)
 
 
-def _device_maximize(built, handles, noises, x0, lo, hi, acq_id, acfun_param, scale, opts, want_log, blocked=False):
-  """hbo_acq_maximize (blocked: hbo_acq_maximize_blocked, caches of any size) in segments of opts['segment'] evaluations until no start
-  is RUNNING or opts['max_evals'] are spent.
+def _mes_args(mes, s_count):
+  """(ystar pointer, K) of the MES entry points, which take them where their siblings take (acq_id, params): mes [S, K] float64."""
+  if mes.dtype != np.float64 or mes.ndim != 2 or mes.shape[0] != s_count or not mes.flags.c_contiguous:
+    raise ValueError(f'maxima must be a contiguous float64 array [{s_count}, K], got {mes.dtype} {mes.shape}')
+  return mes.ctypes.data_as(nat.C.POINTER(nat.C.c_double)), mes.shape[1]
+
+
+def _device_maximize(built, handles, noises, x0, lo, hi, acq_id, acfun_param, scale, opts, want_log, blocked=False, mes=None):
+  """hbo_acq_maximize (blocked: hbo_acq_maximize_blocked, caches of any size; mes, [S, K] maxima: hbo_mes_maximize) in segments of
+  opts['segment'] evaluations until no start is RUNNING or opts['max_evals'] are spent.
   x0 [R, D] in the model dtype; lo / hi [D] float64 or None.  Returns (x [R, D], values [R], status [R], evaluations [R], log or None)."""
   entry = nat.lib().hbo_acq_maximize_blocked if blocked else nat.lib().hbo_acq_maximize
   s_count, (r_count, d) = len(built), x0.shape
   ctx = handles[0].ctx
   structs, caches, prm, nse = _sample_args(built, handles, noises, acfun_param)
+  what = (int(acq_id), prm)
+  if mes is not None:
+    entry, what = nat.lib().hbo_mes_maximize, _mes_args(mes, s_count)
   o = nat.AcqOptOpts(*[opts[k] for k in ('memory', 'ls_steps', 'max_iters', 'c1', 'tau', 'pgtol', 'ftol')])
   ns = nat.lib().hbo_acq_opt_state_doubles(d, o.memory)
   state = np.zeros((r_count, max(ns, 1)), dtype=np.float64)
@@ -355,8 +365,8 @@ def _device_maximize(built, handles, noises, x0, lo, hi, acq_id, acfun_param, sc
   while spent < opts['max_evals']:
     evals = int(min(opts['segment'], opts['max_evals'] - spent))
     log = np.zeros((evals, r_count), dtype=nat.ACQ_OPT_EVAL_DTYPE) if want_log else None
-    ctx.check(entry(ctx.handle, structs, s_count, caches, nat.ptr(x0), r_count, nat.ptr(lo), nat.ptr(hi), int(acq_id),
-                    prm, nse, float(scale), nat.C.byref(o), nat.ptr(state), evals, nat.ptr(x), nat.ptr(val),
+    ctx.check(entry(ctx.handle, structs, s_count, caches, nat.ptr(x0), r_count, nat.ptr(lo), nat.ptr(hi), *what,
+                    nse, float(scale), nat.C.byref(o), nat.ptr(state), evals, nat.ptr(x), nat.ptr(val),
                     nat.ptr(status), nat.ptr(log)))
     spent += evals
     if want_log:
@@ -367,16 +377,20 @@ def _device_maximize(built, handles, noises, x0, lo, hi, acq_id, acfun_param, sc
   return x, val, status, n_evals, (np.concatenate(logs) if want_log else None)
 
 
-def _fused_value_and_grad(built, handles, noises, xq, acq_id, acfun_param, scale, blocked=False):
+def _fused_value_and_grad(built, handles, noises, xq, acq_id, acfun_param, scale, blocked=False, mes=None):
   """((S, M, 1) values in the model dtype, (S, M, D) gradients in float64) of S models over their finished factors: one
-  hbo_acq_grad_samples call -- one upload, one launch, one copy back (blocked: hbo_acq_grad_samples_blocked, caches of any size)."""
+  hbo_acq_grad_samples call -- one upload, one launch, one copy back (blocked: hbo_acq_grad_samples_blocked, caches of any size;
+  mes, [S, K] maxima: hbo_mes_grad_samples)."""
   entry = nat.lib().hbo_acq_grad_samples_blocked if blocked else nat.lib().hbo_acq_grad_samples
   s_count, (nq, d) = len(built), xq.shape
   ctx = handles[0].ctx
   structs, caches, prm, nse = _sample_args(built, handles, noises, acfun_param)
+  what = (int(acq_id), prm)
+  if mes is not None:
+    entry, what = nat.lib().hbo_mes_grad_samples, _mes_args(mes, s_count)
   out = np.empty((s_count, nq, 1), dtype=xq.dtype)
   g = np.empty((s_count, nq, d), dtype=np.float64)
-  ctx.check(entry(ctx.handle, structs, s_count, caches, nat.ptr(xq), nq, int(acq_id), prm, nse, float(scale),
+  ctx.check(entry(ctx.handle, structs, s_count, caches, nat.ptr(xq), nq, *what, nse, float(scale),
                   nat.ptr(out), g.ctypes.data_as(nat.C.POINTER(nat.C.c_double))))
   return out, g
 
@@ -580,3 +594,133 @@ _BO_DEVICE.update({
     ucb3: (nat.ACQ_UCB, nat.BO_PARAM_CONST, 3.0),
     ucb4: (nat.ACQ_UCB, nat.BO_PARAM_CONST, 4.0),
 })
+
+
+# ---- max-value entropy search (Wang & Jegelka 2017; include/hbo.h has the formulas, csrc/mes.hip the entry points) ------------------
+def _plain_gp_only(model, what):
+  if isinstance(model, gp.HGP):
+    raise ValueError(f'{what} is defined for a GP with one set of hyper-parameters, not for an HGP')
+
+
+def max_value_samples(model, sub_dataset_key, x_candidates, num_maxima=16, key=None, num_features=1024, starts=4, bounds=None, opts=None,
+                      refine=True):
+  """[num_maxima] float64: sampled maxima y*_k of the latent function over the box, one per posterior sample path.  One draw of
+  `num_maxima` paths (GP.draw_paths) is scored at the candidates; with `refine` the `starts` best candidates of every path (stable
+  order) start PathDraws.maximize and the larger of the pool maximum and the refined maximum is kept.  With observations every maximum
+  is then raised to the incumbent max_i y_i: a sampled maximum below it is an artefact of the finite basis and would put gamma < 0 at
+  the incumbent.  key: a numpy Generator or an int seed, None takes model.rng; bounds, opts: as PathDraws.maximize."""
+  _plain_gp_only(model, 'max-value entropy search')
+  xc = np.asarray(x_candidates)
+  if xc.ndim != 2 or xc.shape[0] < 1:
+    raise ValueError(f'x_candidates must be [M, D] with M >= 1, got {xc.shape}')
+  k, r = int(num_maxima), min(int(starts), xc.shape[0])
+  if k < 1 or k > nat.MES_MAX_K:
+    raise ValueError(f'num_maxima must lie in 1..{nat.MES_MAX_K}, got {num_maxima}')
+  if refine and r < 1:
+    raise ValueError('starts must be at least 1')
+  draws = model.draw_paths(sub_dataset_key, num_samples=k, num_features=num_features, key=key)
+  scores = np.asarray(draws.values(xc), dtype=np.float64)                      # [M, K]
+  ystar = np.max(scores, axis=0)
+  if refine:
+    order = np.argsort(-scores, axis=0, kind='stable')[:r]                     # [r, K]
+    _, val, _ = draws.maximize(np.asarray(xc, dtype=np.float64)[order.T], bounds=bounds, opts=opts)
+    val = np.asarray(val, dtype=np.float64)
+    ystar = np.maximum(ystar, np.max(np.where(np.isfinite(val), val, -np.inf), axis=1))
+  if model.has_observations(sub_dataset_key):
+    ystar = np.maximum(ystar, float(np.max(model.dataset[sub_dataset_key].y)))
+  return np.ascontiguousarray(ystar, dtype=np.float64)
+
+
+class MaxValueEntropySearch:
+  """Max-value entropy search: the expected reduction of the entropy of the objective's maximum, value = mean_k h(gamma_k) over K
+  sampled maxima (max_value_samples).  Called, it scores a pool (hbo_acq_mes); value_and_grad and maximize go through
+  hbo_mes_grad_samples and hbo_mes_maximize over the cached factor (any number of observations; without observations -- the prior
+  branch -- they raise HboError(HBO_ERR_UNSUPPORTED) here, before any device call; MLP bases and input-warped kernels are refused
+  by the entry points with the same error; no fall-back); `suggest` is what bayesopt.bayesopt calls.
+  The variance is the latent one -- add_noise = 0 and the unbiased scale, as GP.draw_paths scales its paths -- unless with_noise."""
+  __name__ = 'mes'
+
+  def __init__(self, num_maxima=16, num_features=1024, starts=4, opts=None, with_noise=False):
+    self.num_maxima, self.num_features, self.starts, self.opts, self.with_noise = num_maxima, num_features, starts, opts, bool(with_noise)
+
+  def _setup(self, model, sub_dataset_key, x_queries=None, what=None):
+    """`what`: the method that needs a cached factor -- without observations it raises, as the entry point itself would."""
+    _plain_gp_only(model, 'max-value entropy search')
+    if what is not None and not model.has_observations(sub_dataset_key):
+      raise nat.HboError(nat.HBO_ERR_UNSUPPORTED, f'mes.{what}: the sub-dataset has no observations (the prior branch)')
+    handle, xq, bm, _, _ = _single_model(model, sub_dataset_key, x_queries)
+    add_noise, scale = model.predict_noise_and_scale(self.with_noise, True)
+    return handle, xq, bm, add_noise, scale
+
+  @staticmethod
+  def _given(maxima):
+    ystar = np.ascontiguousarray(np.asarray(maxima, dtype=np.float64).reshape(-1))
+    if ystar.size < 1 or ystar.size > nat.MES_MAX_K or not np.all(np.isfinite(ystar)):
+      raise ValueError(f'maxima must be 1..{nat.MES_MAX_K} finite numbers')
+    return ystar
+
+  def __call__(self, model, sub_dataset_key, x_queries, key=None, maxima=None, **unused_kwargs):
+    """[M, 1] MES values in the model dtype.  maxima: [K] sampled maxima; None draws them over x_queries, unrefined, from `key`."""
+    handle, xq, bm, add_noise, scale = self._setup(model, sub_dataset_key, np.asarray(x_queries))
+    out = np.empty((xq.shape[0], 1), dtype=xq.dtype)
+    if bm is None:
+      return out
+    ystar = self._given(maxima) if maxima is not None else max_value_samples(
+        model, sub_dataset_key, xq, self.num_maxima, key, self.num_features, refine=False)
+    ctx = handle.ctx if handle is not None else nat.default_context()
+    ctx.check(nat.lib().hbo_acq_mes(ctx.handle, bm.ref(), handle.handle if handle is not None else None, nat.ptr(xq), xq.shape[0],
+                                    ystar.ctypes.data_as(nat.C.POINTER(nat.C.c_double)), ystar.size, float(add_noise), float(scale),
+                                    nat.ptr(out)))
+    return out
+
+  def value_and_grad(self, *, model, sub_dataset_key, x_queries, maxima):
+    """(values [M, 1] in the model dtype, d value_q / d x_queries[q] [M, D] float64) under the given maxima (hbo_mes_grad_samples)."""
+    handle, xq, bm, add_noise, scale = self._setup(model, sub_dataset_key, np.asarray(x_queries), what='value_and_grad')
+    if bm is None:
+      return np.empty((xq.shape[0], 1), dtype=xq.dtype), np.zeros((xq.shape[0], model.input_dim))
+    outs, gs = _fused_value_and_grad([bm], [handle], [add_noise], xq, 0, 0.0, scale, mes=self._given(maxima)[None])
+    return outs[0], gs[0]
+
+  def maximize(self, *, model, sub_dataset_key, x_init, maxima, bounds=None, opts=None):
+    """Maximises the MES value over a box on the device (hbo_mes_maximize) from the starts x_init [D] or [R, D], under the given
+    maxima.  bounds, opts and the return value (x_best [D] float64, value_best, info) are those of the `maximize` of the EI / PI / UCB
+    objects: segments of ACQ_OPT_SEGMENT evaluations, the start with the largest finite value wins."""
+    o = dict(ACQ_OPT_DEFAULTS, segment=ACQ_OPT_SEGMENT, max_evals=ACQ_OPT_MAX_EVALS, log=False)
+    o.update(self.opts or {})
+    o.update(opts or {})
+    x_init = np.atleast_2d(np.asarray(x_init, dtype=np.float64))
+    handle, _, bm, add_noise, scale = self._setup(model, sub_dataset_key, what='maximize')
+    dtype = handle.dtype
+    lo = hi = None
+    if bounds is not None:
+      b = np.asarray(bounds, dtype=np.float64).reshape(model.input_dim, 2)
+      lo, hi = np.ascontiguousarray(b[:, 0]), np.ascontiguousarray(b[:, 1])
+    x, val, status, n_evals, log = _device_maximize([bm], [handle], [add_noise], np.ascontiguousarray(x_init, dtype=dtype), lo, hi, 0, 0.0,
+                                                    scale, o, bool(o['log']), mes=self._given(maxima)[None])
+    info = {'x': x, 'value': val, 'status': status, 'evals': n_evals}
+    if o['log']:
+      info['log'] = log
+    finite = np.isfinite(val)
+    if not finite.any():
+      return x_init[0].copy(), float('nan'), info
+    best = int(np.argmax(np.where(finite, val, -np.inf)))
+    return x[best].copy(), float(val[best]), info
+
+  def suggest(self, *, model, sub_dataset_key, x_candidates, key=None, batch_size=1, bounds=None):
+    """[1, D] float64, the next point of bayesopt.bayesopt: refined maxima over the candidates (max_value_samples), the candidates'
+    MES values, then hbo_mes_maximize from the `starts` best of them (stable order).  Without observations the best candidate is
+    returned unrefined (the gradient entry points refuse the prior branch).  batch_size other than 1 raises ValueError."""
+    if int(batch_size) != 1:
+      raise ValueError('max-value entropy search suggests one point at a time (batch MES is not implemented)')
+    _plain_gp_only(model, 'max-value entropy search')
+    xc = np.asarray(x_candidates, dtype=np.float64)
+    ystar = max_value_samples(model, sub_dataset_key, xc, self.num_maxima, key, self.num_features, self.starts, bounds, self.opts)
+    vals = np.asarray(self(model, sub_dataset_key, xc, maxima=ystar), dtype=np.float64).reshape(-1)
+    order = np.argsort(-vals, kind='stable')[:max(1, min(int(self.starts), xc.shape[0]))]
+    if not model.has_observations(sub_dataset_key):
+      return xc[order[:1]].copy()
+    x, val, _ = self.maximize(model=model, sub_dataset_key=sub_dataset_key, x_init=xc[order], maxima=ystar, bounds=bounds)
+    return (x if np.isfinite(val) else xc[order[0]])[None, :].copy()
+
+
+max_value_entropy_search = mes = MaxValueEntropySearch()

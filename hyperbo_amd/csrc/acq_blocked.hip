@@ -146,7 +146,8 @@ __global__ __launch_bounds__(256) void acq_blk_trans_kernel(AcqBlockedArgs b) {
 }
 
 // ---- 4: one workgroup per (sample, query): the sums over the rows, the scalar step, the gradient
-template <typename T>
+//         (MES: the scalar step is mes_scalars_block over the sample's K maxima, as in acq_small_kernel)
+template <typename T, bool MES>
 __global__ __launch_bounds__(256) void acq_blk_finish_kernel(AcqBlockedArgs b) {
   __shared__ double s_xq[HBO_MAX_FEATURE_DIM], s_il[HBO_MAX_FEATURE_DIM];
   __shared__ double s_w[256];
@@ -190,14 +191,26 @@ __global__ __launch_bounds__(256) void acq_blk_finish_kernel(AcqBlockedArgs b) {
   if (is_dot) kqq = block_sum(tid < D ? s_xq[tid] * s_xq[tid] : 0.0, sred) * sm.inv_sigma2 + sm.bias2;
   if (a.mean_id == HBO_MEAN_CONSTANT) mean = sm.constant;
   else if (a.mean_id == HBO_MEAN_LINEAR) mean = sm.linear_bias + block_sum(tid < D ? s_xq[tid] * vec[D + tid] : 0.0, sred);
-  if (tid == 0) {
-    const AcqScalars sc = acq_scalars(a.acq_id, ka + mean, kqq - ll, sm.add_noise, a.scale, sm.param);
-    s_amu = sc.amu; s_avar = sc.avar;
-    *acq = (T)sc.val;
-    if (a.val64_out) a.val64_out[(int64_t)s * a.M + q] = sc.val;
+  double amu, avar;
+  if constexpr (MES) {
+    __shared__ double s_mes[3 * HBO_MES_MAX_K], s_mes_sum[3];
+    const AcqScalars sc = mes_scalars_block(ka + mean, kqq - ll, sm.add_noise, a.scale, a.ystar + (int64_t)s * a.K, a.K, s_mes, s_mes_sum);
+    if (tid == 0) {
+      *acq = (T)sc.val;
+      if (a.val64_out) a.val64_out[(int64_t)s * a.M + q] = sc.val;
+    }
+    __syncthreads();
+    amu = sc.amu; avar = sc.avar;   // (every thread holds them: nothing is handed over through LDS)
+  } else {
+    if (tid == 0) {
+      const AcqScalars sc = acq_scalars(a.acq_id, ka + mean, kqq - ll, sm.add_noise, a.scale, sm.param);
+      s_amu = sc.amu; s_avar = sc.avar;
+      *acq = (T)sc.val;
+      if (a.val64_out) a.val64_out[(int64_t)s * a.M + q] = sc.val;
+    }
+    __syncthreads();
+    amu = s_amu; avar = s_avar;
   }
-  __syncthreads();
-  const double amu = s_amu, avar = s_avar;
   // ---- g_d = sum_i w_i (x_d - X_id | X_id), w_i = coef_i * (dk/du_i * 2 | 1 / sigma^2): FD = pow2 >= D lanes along the features, G groups
   //      over the rows of a chunk; a thread keeps its sum across the chunks and the groups meet once, group by group
   int FD = 1; while (FD < D) FD <<= 1;
@@ -248,7 +261,8 @@ void launch_blocked_t(const AcqBlockedArgs& b, int S, hipStream_t st) {
   hipLaunchKernelGGL((acq_blk_k_kernel<T>), dim3(b.ldv / HBO_TILE, mc, S), dim3(HBO_TILE), 0, st, b);
   hipLaunchKernelGGL((acq_blk_fwd_kernel<T, BLK_MC>), dim3(b.ldv / 16, grp, S), dim3(256), 0, st, b);
   hipLaunchKernelGGL((acq_blk_trans_kernel<T, BLK_MC>), dim3(b.ldv / 64, grp, S), dim3(256), 0, st, b);
-  hipLaunchKernelGGL((acq_blk_finish_kernel<T>), dim3(mc, S), dim3(256), 0, st, b);
+  if (b.a.ystar) hipLaunchKernelGGL((acq_blk_finish_kernel<T, true>), dim3(mc, S), dim3(256), 0, st, b);
+  else hipLaunchKernelGGL((acq_blk_finish_kernel<T, false>), dim3(mc, S), dim3(256), 0, st, b);
 }
 }  // namespace
 

@@ -116,20 +116,17 @@ extern "C" int hbo_acq_grad(hbo_ctx* c, const hbo_model* m, hbo_cache* k, const 
 namespace {
 constexpr size_t ACQ_BLOCKED_WS_BYTES = (size_t)256 << 20;
 constexpr int64_t ACQ_BLOCKED_MAX_CHUNK = 65535;   // grid.y of the first launch
-struct AcqSamplesMode {
-  const char* fn;          // the entry point's name in messages
-  int max_n;               // the largest cache the entry point takes (acq_samples_check)
-  bool force_blocked;      // test hook: caches of n <= 128 through the blocked kernels too
-  int64_t chunk_queries;   // test hook: > 0 overrides the chunk size
-};
 }  // namespace
-static int acq_grad_samples(hbo_ctx* c, const AcqSamplesMode& mode, const hbo_model* models, int32_t S, hbo_cache* const* caches, const void* xq,
-                            int64_t M, int acq_id, const double* params, const double* add_noise, double scale, void* acq_out, double* grad_out,
-                            double* val64_out) {
+// (api_internal.h: AcqSamplesMode.  mes -- hbo_mes_grad_samples, mes.hip: the S x K maxima ride up behind the per-feature values and the
+//  kernels take the MES scalar step; acq_id and params are then not read)
+int acq_grad_samples(hbo_ctx* c, const AcqSamplesMode& mode, const hbo_model* models, int32_t S, hbo_cache* const* caches, const void* xq,
+                     int64_t M, int acq_id, const double* params, const MesReq* mes, const double* add_noise, double scale, void* acq_out,
+                     double* grad_out, double* val64_out) {
   const std::string fn = std::string(mode.fn) + ": ";
-  if (!models || !caches || !xq || !params || !add_noise || !acq_out || !grad_out) return fail(c, HBO_ERR_ARG, fn + "null argument");
+  if (!models || !caches || !xq || (mes ? !mes->ystar : !params) || !add_noise || !acq_out || !grad_out) return fail(c, HBO_ERR_ARG, fn + "null argument");
   if (S <= 0 || S > 4096) return fail(c, HBO_ERR_ARG, fn + "1 <= S <= 4096");
-  if (acq_id < 0 || acq_id > HBO_ACQ_UCB) return fail(c, HBO_ERR_ARG, fn + "bad acq_id");
+  if (mes) { if (int rc = mes_check(c, fn, *mes, S)) return rc; }
+  else if (acq_id < 0 || acq_id > HBO_ACQ_UCB) return fail(c, HBO_ERR_ARG, fn + "bad acq_id");
   if (!c) return fail(c, HBO_ERR_ARG, fn + "ctx is null");
   if (M < 0) return fail(c, HBO_ERR_ARG, fn + "M < 0");
   const hbo_model* m0 = &models[0];
@@ -142,8 +139,9 @@ static int acq_grad_samples(hbo_ctx* c, const AcqSamplesMode& mode, const hbo_mo
   hipStream_t st = c->stream;
   const int ldv = acq_blocked_ldv(S, caches);
   const bool blocked = mode.force_blocked || ldv > HBO_TILE;
-  // one block up: [S records][S x 2 D doubles][M x D queries]; one block down: [S x M x D doubles][S x M values]
-  const size_t smp_b = align256(sizeof(AcqSmallSample) * S), vec_b = align256(sizeof(double) * 2 * D * S), xq_b = (size_t)M * D * es;
+  // one block up: [S records][S x 2 D doubles + (MES) S x K maxima][M x D queries]; one block down: [S x M x D doubles][S x M values]
+  const size_t hv_b = sizeof(double) * 2 * D * S, ys_b = mes ? sizeof(double) * (size_t)S * mes->K : 0;
+  const size_t smp_b = align256(sizeof(AcqSmallSample) * S), vec_b = align256(hv_b + ys_b), xq_b = (size_t)M * D * es;
   const size_t grad_b = align256(sizeof(double) * (size_t)S * M * D), acq_b = (size_t)S * M * es;
   const size_t v64_o = align256(grad_b + acq_b), v64_b = val64_out ? sizeof(double) * (size_t)S * M : 0;
   const size_t in_b = smp_b + vec_b + xq_b, out_b = val64_out ? v64_o + v64_b : grad_b + acq_b;
@@ -165,6 +163,7 @@ static int acq_grad_samples(hbo_ctx* c, const AcqSamplesMode& mode, const hbo_mo
   AcqSmallSample* hs = reinterpret_cast<AcqSmallSample*>(stage);
   double* hv = reinterpret_cast<double*>(stage + smp_b);
   acq_small_pack(hs, hv, models, S, caches, params, add_noise);
+  if (mes) memcpy(stage + smp_b + hv_b, mes->ystar, ys_b);
   memcpy(stage + smp_b + vec_b, xq, xq_b);
   HIPCHK(c, stage_upload(c, d_in, stage, in_b, st));
   AcqSmallArgs a = {};
@@ -172,6 +171,7 @@ static int acq_grad_samples(hbo_ctx* c, const AcqSamplesMode& mode, const hbo_mo
   a.D = D; a.M = M; a.kernel_id = m0->kernel_id; a.mean_id = m0->mean_id; a.acq_id = acq_id; a.scale = scale;
   a.grad_out = reinterpret_cast<double*>(d_out); a.acq_out = d_out + grad_b;
   if (val64_out) a.val64_out = reinterpret_cast<double*>(d_out + v64_o);
+  if (mes) { a.ystar = reinterpret_cast<const double*>(d_in + smp_b + hv_b); a.K = mes->K; }
   if (!blocked) launch_acq_small(dtype, a, S, st);
   else {
     AcqBlockedArgs b = {};
@@ -196,13 +196,13 @@ extern "C" int hbo_acq_grad_samples(hbo_ctx* c, const hbo_model* models, int32_t
                                     int acq_id, const double* params, const double* add_noise, double scale, void* acq_out,
                                     double* grad_out) {
   const AcqSamplesMode mode = {"hbo_acq_grad_samples", HBO_TILE, false, 0};
-  return acq_grad_samples(c, mode, models, S, caches, xq, M, acq_id, params, add_noise, scale, acq_out, grad_out, nullptr);
+  return acq_grad_samples(c, mode, models, S, caches, xq, M, acq_id, params, nullptr, add_noise, scale, acq_out, grad_out, nullptr);
 }
 extern "C" int hbo_acq_grad_samples_blocked(hbo_ctx* c, const hbo_model* models, int32_t S, hbo_cache* const* caches, const void* xq,
                                             int64_t M, int acq_id, const double* params, const double* add_noise, double scale,
                                             void* acq_out, double* grad_out) {
   const AcqSamplesMode mode = {"hbo_acq_grad_samples_blocked", INT_MAX, false, 0};
-  return acq_grad_samples(c, mode, models, S, caches, xq, M, acq_id, params, add_noise, scale, acq_out, grad_out, nullptr);
+  return acq_grad_samples(c, mode, models, S, caches, xq, M, acq_id, params, nullptr, add_noise, scale, acq_out, grad_out, nullptr);
 }
 // include/hbo_tune.h (TEST HOOK): hbo_acq_grad_samples with the fp64 values hbo_acq_maximize's control kernel reads
 extern "C" int hbo_probe_acq_grad_samples64(hbo_ctx* c, const hbo_model* models, int32_t S, hbo_cache* const* caches, const void* xq, int64_t M,
@@ -210,7 +210,7 @@ extern "C" int hbo_probe_acq_grad_samples64(hbo_ctx* c, const hbo_model* models,
                                             double* grad_out, double* val64_out) {
   if (!val64_out) return fail(c, HBO_ERR_ARG, "hbo_probe_acq_grad_samples64: val64_out is null");
   const AcqSamplesMode mode = {"hbo_acq_grad_samples", HBO_TILE, false, 0};
-  return acq_grad_samples(c, mode, models, S, caches, xq, M, acq_id, params, add_noise, scale, acq_out, grad_out, val64_out);
+  return acq_grad_samples(c, mode, models, S, caches, xq, M, acq_id, params, nullptr, add_noise, scale, acq_out, grad_out, val64_out);
 }
 // include/hbo_tune.h (TEST HOOK): hbo_acq_grad_samples_blocked with those values, the blocked kernels on request and a chunk size
 extern "C" int hbo_probe_acq_grad_samples_blocked64(hbo_ctx* c, const hbo_model* models, int32_t S, hbo_cache* const* caches, const void* xq,
@@ -220,5 +220,5 @@ extern "C" int hbo_probe_acq_grad_samples_blocked64(hbo_ctx* c, const hbo_model*
   if (!val64_out) return fail(c, HBO_ERR_ARG, "hbo_probe_acq_grad_samples_blocked64: val64_out is null");
   if (chunk_queries < 0) return fail(c, HBO_ERR_ARG, "hbo_probe_acq_grad_samples_blocked64: chunk_queries < 0");
   const AcqSamplesMode mode = {"hbo_acq_grad_samples_blocked", INT_MAX, force_blocked != 0, chunk_queries};
-  return acq_grad_samples(c, mode, models, S, caches, xq, M, acq_id, params, add_noise, scale, acq_out, grad_out, val64_out);
+  return acq_grad_samples(c, mode, models, S, caches, xq, M, acq_id, params, nullptr, add_noise, scale, acq_out, grad_out, val64_out);
 }

@@ -97,14 +97,17 @@ extern "C" int64_t hbo_acq_opt_state_doubles(int32_t D, int32_t memory) {
 
 // The body of hbo_acq_maximize and hbo_acq_maximize_blocked: they differ in the largest cache they take (max_n) and, with it, in the
 // evaluation step -- one launch of acq_small.hip when every cache has n <= 128, the four launches of acq_blocked.hip otherwise.
-static int acq_maximize(hbo_ctx* c, const char* name, int max_n, const hbo_model* models, int32_t S, hbo_cache* const* caches, const void* x0,
-                        int32_t R, const double* lo, const double* hi, int acq_id, const double* params, const double* add_noise, double scale,
-                        const hbo_acq_opt_opts* opts, double* state, int32_t evals, double* x_out, double* val_out, int32_t* status,
-                        hbo_acq_opt_eval* log) {
+// (mes -- hbo_mes_maximize, mes.hip: the S x K maxima ride up behind the box and the evaluation takes the MES scalar step; acq_id and
+//  params are then not read)
+int acq_maximize(hbo_ctx* c, const char* name, int max_n, const hbo_model* models, int32_t S, hbo_cache* const* caches, const void* x0,
+                 int32_t R, const double* lo, const double* hi, int acq_id, const double* params, const MesReq* mes, const double* add_noise,
+                 double scale, const hbo_acq_opt_opts* opts, double* state, int32_t evals, double* x_out, double* val_out, int32_t* status,
+                 hbo_acq_opt_eval* log) {
   const std::string fn = std::string(name) + ": ";
-  if (!models || !caches || !x0 || !params || !add_noise || !state || !x_out || !val_out || !status) return fail(c, HBO_ERR_ARG, fn + "null argument");
+  if (!models || !caches || !x0 || (mes ? !mes->ystar : !params) || !add_noise || !state || !x_out || !val_out || !status) return fail(c, HBO_ERR_ARG, fn + "null argument");
   if (S <= 0 || S > 4096) return fail(c, HBO_ERR_ARG, fn + "1 <= S <= 4096");
-  if (acq_id < 0 || acq_id > HBO_ACQ_UCB) return fail(c, HBO_ERR_ARG, fn + "bad acq_id");
+  if (mes) { if (int rc = mes_check(c, fn, *mes, S)) return rc; }
+  else if (acq_id < 0 || acq_id > HBO_ACQ_UCB) return fail(c, HBO_ERR_ARG, fn + "bad acq_id");
   if (!c) return fail(c, HBO_ERR_ARG, fn + "ctx is null");
   if (R <= 0 || R > 4096) return fail(c, HBO_ERR_ARG, fn + "1 <= R <= 4096");
   if (evals <= 0 || evals > 4096) return fail(c, HBO_ERR_ARG, fn + "1 <= evals <= 4096");
@@ -141,7 +144,9 @@ static int acq_maximize(hbo_ctx* c, const char* name, int max_n, const hbo_model
   }
   // one block up: [S records][S x 2 D doubles][lo, hi][R x D pending points][R states]; the log follows the states, and one copy brings
   // [states | log] back.  Scratch of the rounds: [S x R x D gradients][S x R values fp64][S x R values in the model dtype]
-  const size_t smp_b = align256(sizeof(AcqSmallSample) * S), vec_b = align256(sizeof(double) * 2 * D * S), box_b = align256(sizeof(double) * 2 * D);
+  // (MES: the S x K maxima sit behind the box, in its part of the block)
+  const size_t ys_b = mes ? sizeof(double) * (size_t)S * mes->K : 0;
+  const size_t smp_b = align256(sizeof(AcqSmallSample) * S), vec_b = align256(sizeof(double) * 2 * D * S), box_b = align256(sizeof(double) * 2 * D + ys_b);
   const size_t pend_b = align256((size_t)R * D * es), state_b = align256(sizeof(double) * (size_t)R * ns);
   const size_t log_b = log ? sizeof(hbo_acq_opt_eval) * (size_t)evals * R : 0;
   const size_t o_state = smp_b + vec_b + box_b + pend_b, up_b = o_state + state_b, down_b = state_b + log_b;
@@ -156,6 +161,7 @@ static int acq_maximize(hbo_ctx* c, const char* name, int max_n, const hbo_model
   acq_small_pack(reinterpret_cast<AcqSmallSample*>(stage), reinterpret_cast<double*>(stage + smp_b), models, S, caches, params, add_noise);
   double* hbox = reinterpret_cast<double*>(stage + smp_b + vec_b);
   for (int i = 0; i < D; ++i) { hbox[i] = lo ? lo[i] : 0.0; hbox[D + i] = hi ? hi[i] : 1.0; }
+  if (mes) memcpy(hbox + 2 * D, mes->ystar, ys_b);
   // the states go up from a copy, and a fresh one is started in that copy: the caller's array is written once, by the copy back, so a
   // call that fails on the way (an argument, an allocation, the device) leaves it as it was
   double* hstate = reinterpret_cast<double*>(stage + o_state);
@@ -183,6 +189,7 @@ static int acq_maximize(hbo_ctx* c, const char* name, int max_n, const hbo_model
   a.xq = d_in + smp_b + vec_b + box_b;
   a.D = D; a.M = R; a.kernel_id = m0->kernel_id; a.mean_id = m0->mean_id; a.acq_id = acq_id; a.scale = scale;
   a.grad_out = reinterpret_cast<double*>(d_out); a.val64_out = reinterpret_cast<double*>(d_out + grad_b); a.acq_out = d_out + grad_b + val_b;
+  if (mes) { a.ystar = reinterpret_cast<const double*>(d_in + smp_b + vec_b) + 2 * D; a.K = mes->K; }
   AcqOptArgs k = {};
   k.o = acq_opt_ctl_opts(opts);
   k.state = reinterpret_cast<double*>(d_in + o_state); k.ns = ns;
@@ -219,14 +226,14 @@ extern "C" int hbo_acq_maximize(hbo_ctx* c, const hbo_model* models, int32_t S, 
                                 const double* lo, const double* hi, int acq_id, const double* params, const double* add_noise, double scale,
                                 const hbo_acq_opt_opts* opts, double* state, int32_t evals, double* x_out, double* val_out, int32_t* status,
                                 hbo_acq_opt_eval* log) {
-  return acq_maximize(c, "hbo_acq_maximize", HBO_TILE, models, S, caches, x0, R, lo, hi, acq_id, params, add_noise, scale, opts, state, evals,
+  return acq_maximize(c, "hbo_acq_maximize", HBO_TILE, models, S, caches, x0, R, lo, hi, acq_id, params, nullptr, add_noise, scale, opts, state, evals,
                       x_out, val_out, status, log);
 }
 extern "C" int hbo_acq_maximize_blocked(hbo_ctx* c, const hbo_model* models, int32_t S, hbo_cache* const* caches, const void* x0, int32_t R,
                                         const double* lo, const double* hi, int acq_id, const double* params, const double* add_noise,
                                         double scale, const hbo_acq_opt_opts* opts, double* state, int32_t evals, double* x_out,
                                         double* val_out, int32_t* status, hbo_acq_opt_eval* log) {
-  return acq_maximize(c, "hbo_acq_maximize_blocked", INT_MAX, models, S, caches, x0, R, lo, hi, acq_id, params, add_noise, scale, opts, state,
+  return acq_maximize(c, "hbo_acq_maximize_blocked", INT_MAX, models, S, caches, x0, R, lo, hi, acq_id, params, nullptr, add_noise, scale, opts, state,
                       evals, x_out, val_out, status, log);
 }
 

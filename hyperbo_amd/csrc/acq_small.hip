@@ -10,7 +10,8 @@
 #include "kernfun.h"
 
 namespace {
-template <typename T>
+// MES: the scalar step is mes_scalars_block over the sample's K maxima (a.ystar; hbo_mes_grad_samples) instead of acq_scalars
+template <typename T, bool MES>
 __global__ __launch_bounds__(256) void acq_small_kernel(AcqSmallArgs a) {
   __shared__ double s_xq[HBO_MAX_FEATURE_DIM], s_il[HBO_MAX_FEATURE_DIM];
   __shared__ double s_k[HBO_TILE], s_l[HBO_TILE], s_w[HBO_TILE];
@@ -90,14 +91,26 @@ __global__ __launch_bounds__(256) void acq_small_kernel(AcqSmallArgs a) {
     }
     s_acc[tid] = b;
   }
-  if (tid == 0) {
-    const AcqScalars sc = acq_scalars(a.acq_id, ka + mean, kqq - ll, sm.add_noise, a.scale, sm.param);
-    s_amu = sc.amu; s_avar = sc.avar;
-    *acq = (T)sc.val;
-    if (a.val64_out) a.val64_out[(int64_t)s * a.M + q] = sc.val;
+  double amu, avar;
+  if constexpr (MES) {
+    __shared__ double s_mes[3 * HBO_MES_MAX_K], s_mes_sum[3];
+    const AcqScalars sc = mes_scalars_block(ka + mean, kqq - ll, sm.add_noise, a.scale, a.ystar + (int64_t)s * a.K, a.K, s_mes, s_mes_sum);
+    if (tid == 0) {
+      *acq = (T)sc.val;
+      if (a.val64_out) a.val64_out[(int64_t)s * a.M + q] = sc.val;
+    }
+    __syncthreads();   // (s_acc is read next, and mes_scalars_block leaves without a barrier when v2 <= 0)
+    amu = sc.amu; avar = sc.avar;
+  } else {
+    if (tid == 0) {
+      const AcqScalars sc = acq_scalars(a.acq_id, ka + mean, kqq - ll, sm.add_noise, a.scale, sm.param);
+      s_amu = sc.amu; s_avar = sc.avar;
+      *acq = (T)sc.val;
+      if (a.val64_out) a.val64_out[(int64_t)s * a.M + q] = sc.val;
+    }
+    __syncthreads();
+    amu = s_amu; avar = s_avar;
   }
-  __syncthreads();
-  const double amu = s_amu, avar = s_avar;
   // ---- w_i = coef_i * (dk/du_i * 2 | 1 / sigma^2)
   if (tid < n) {
     const double beta = s_acc[tid] + s_acc[HBO_TILE + tid];
@@ -130,6 +143,11 @@ __global__ __launch_bounds__(256) void acq_small_kernel(AcqSmallArgs a) {
 void launch_acq_small(int dtype, const AcqSmallArgs& a, int S, hipStream_t st) {
   if (a.M <= 0 || S <= 0) return;
   const dim3 grid((unsigned)a.M, (unsigned)S);
-  if (dtype == HBO_F64) hipLaunchKernelGGL((acq_small_kernel<double>), grid, dim3(256), 0, st, a);
-  else hipLaunchKernelGGL((acq_small_kernel<float>), grid, dim3(256), 0, st, a);
+  if (a.ystar) {
+    if (dtype == HBO_F64) hipLaunchKernelGGL((acq_small_kernel<double, true>), grid, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((acq_small_kernel<float, true>), grid, dim3(256), 0, st, a);
+    return;
+  }
+  if (dtype == HBO_F64) hipLaunchKernelGGL((acq_small_kernel<double, false>), grid, dim3(256), 0, st, a);
+  else hipLaunchKernelGGL((acq_small_kernel<float, false>), grid, dim3(256), 0, st, a);
 }

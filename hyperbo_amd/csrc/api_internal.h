@@ -439,8 +439,36 @@ static int acq_samples_check(hbo_ctx* c, const std::string& fn, const hbo_model*
   return HBO_OK;
 }
 
+// ---- max-value entropy search (mes.hip) --------------------------------------------------------
+// The bodies of the acquisition entry points take it as an optional request: ystar [S][K] (hbo_acq_mes: [K]) on the host in the place
+// of acq_id and the per-sample parameter.
+struct MesReq { const double* ystar; int32_t K; };
+// K in 1..HBO_MES_MAX_K and `count` finite maxima (ystar is not null); touches no device (c may be null)
+static int mes_check(hbo_ctx* c, const std::string& fn, const MesReq& r, int64_t count) {
+  if (r.K < 1 || r.K > HBO_MES_MAX_K) return fail(c, HBO_ERR_ARG, fn + "1 <= K <= " + std::to_string(HBO_MES_MAX_K));
+  for (int64_t i = 0; i < count * r.K; ++i) if (!isfinite(r.ystar[i])) return fail(c, HBO_ERR_ARG, fn + "ystar holds a value that is not finite");
+  return HBO_OK;
+}
+// the bodies of hbo_acq_grad_samples[_blocked] (acq_grad.hip) and hbo_acq_maximize[_blocked] (acq_opt.hip); mes: null for these
+struct AcqSamplesMode {
+  const char* fn;          // the entry point's name in messages
+  int max_n;               // the largest cache the entry point takes (acq_samples_check)
+  bool force_blocked;      // test hook: caches of n <= 128 through the blocked kernels too
+  int64_t chunk_queries;   // test hook: > 0 overrides the chunk size
+};
+int acq_grad_samples(hbo_ctx* c, const AcqSamplesMode& mode, const hbo_model* models, int32_t S, hbo_cache* const* caches, const void* xq,
+                     int64_t M, int acq_id, const double* params, const MesReq* mes, const double* add_noise, double scale, void* acq_out,
+                     double* grad_out, double* val64_out);
+int acq_maximize(hbo_ctx* c, const char* name, int max_n, const hbo_model* models, int32_t S, hbo_cache* const* caches, const void* x0,
+                 int32_t R, const double* lo, const double* hi, int acq_id, const double* params, const MesReq* mes, const double* add_noise,
+                 double scale, const hbo_acq_opt_opts* opts, double* state, int32_t evals, double* x_out, double* val_out, int32_t* status,
+                 hbo_acq_opt_eval* log);
+// hbo_acq's posterior pipeline under the MES epilogue (cache.hip); the arguments are checked by the caller (mes.hip: hbo_acq_mes)
+int posterior_mes(hbo_ctx* c, const hbo_model* m, hbo_cache* k, const void* xq, int64_t M, const MesReq& mes, double add_noise, double scale,
+                  void* out);
+
 // the records acq_small_kernel and the kernels of acq_blocked.hip read of those pairs (hbo_internal.h: AcqSmallSample) and their
-// per-feature values, hv [S][2 D]
+// per-feature values, hv [S][2 D] (params: null under a MesReq)
 static void acq_small_pack(AcqSmallSample* hs, double* hv, const hbo_model* models, int32_t S, hbo_cache* const* caches, const double* params,
                            const double* add_noise) {
   const int D = models[0].input_dim;
@@ -452,7 +480,7 @@ static void acq_small_pack(AcqSmallSample* hs, double* hv, const hbo_model* mode
     memset(&r, 0, sizeof r);
     r.F = k->h_desc.F; r.W = t->W; r.alpha = t->svec; r.ld = t->ld; r.n = (int)t->n; r.bad = k->info != INT_MAX;
     r.sv = md.sv; r.inv_sigma2 = 1.0 / (md.dot_sigma * md.dot_sigma); r.bias2 = md.dot_bias * md.dot_bias;
-    r.constant = md.constant; r.linear_bias = md.linear_bias; r.param = params[s]; r.add_noise = add_noise[s];
+    r.constant = md.constant; r.linear_bias = md.linear_bias; r.param = params ? params[s] : 0.0; r.add_noise = add_noise[s];
     memcpy(hv + (size_t)s * 2 * D, md.inv_ls, sizeof(double) * D);
     memcpy(hv + (size_t)s * 2 * D + D, md.lin_w, sizeof(double) * D);
   }

@@ -314,6 +314,7 @@ struct PostCall {
   hbo_ctx* c; const hbo_model* m; hbo_cache* k;
   const ModelDev* md; void* const* mw; void* const* mb;   // the model and its MLP weights on the device
   int acq_id; double param, add_noise, scale;
+  const double* ystar; int K;   // hbo_acq_mes: the K maxima on the device -- the acquisition is the MES epilogue (mes.hip) over mu, var
 };
 // one chunk's view of the workspaces: its buffer of each per-workspace array, its rows of the M-sized results
 struct PostSlice {
@@ -426,7 +427,8 @@ static int produce_chunk(const PostCall& pc, const PostPlan& p, const PostWs& w,
     } else {
       HIPCHK(c, hipMemcpyAsync(s.var, s.kd, (size_t)ch.mc * es, hipMemcpyDeviceToDevice, sb));
     }
-    if (s.acq) {   // acquisition on the prior
+    if (s.acq && pc.ystar) launch_mes_epilogue(dtype, s.mu, s.var, ch.mc, pc.ystar, pc.K, pc.add_noise, pc.scale, s.acq, sb);
+    else if (s.acq) {   // acquisition on the prior
       PostArgs pa = {}; pa.Kxq = nullptr; pa.n = 0; pa.nblk = 0; pa.ldq = ch.ldq; pa.alpha = nullptr; pa.colsq = nullptr;
       pa.kdiag = s.kd; pa.muq = s.mu0; pa.acq_out = s.acq; pa.M = ch.mc; pa.acq_id = pc.acq_id; pa.param = pc.param; pa.add_noise = pc.add_noise; pa.scale = pc.scale;
       launch_post_epilogue(dtype, pa, sb);
@@ -472,9 +474,10 @@ static void consume_chunk(const PostCall& pc, const PostPlan& p, const PostWs& w
     } }
   { ProfScope ps(c, "post_epilogue", 1, sa);
     PostArgs pa = {}; pa.Kxq = s.K; pa.ldq = ch.ldq; pa.npad = t->npad; pa.n = (int)t->n; pa.nblk = t->nblk; pa.alpha = t->svec; pa.colsq = s.colsq; pa.mupart = s.mupart;
-    pa.kdiag = s.kd; pa.muq = s.mu0; pa.mu_out = s.mu; pa.var_out = s.var; pa.acq_out = s.acq; pa.M = ch.mc;
+    pa.kdiag = s.kd; pa.muq = s.mu0; pa.mu_out = s.mu; pa.var_out = s.var; pa.acq_out = pc.ystar ? nullptr : s.acq; pa.M = ch.mc;
     pa.acq_id = pc.acq_id; pa.param = pc.param; pa.add_noise = pc.add_noise; pa.scale = pc.scale;
-    launch_post_epilogue(dtype, pa, sa); }
+    launch_post_epilogue(dtype, pa, sa);
+    if (pc.ystar) launch_mes_epilogue(dtype, s.mu, s.var, ch.mc, pc.ystar, pc.K, pc.add_noise, pc.scale, s.acq, sa); }
 }
 
 // full covariance with a cache: Kqq - V^T V in the Kqq buffer
@@ -490,7 +493,7 @@ static void full_cov_tail(const PostCall& pc, const PostPlan& p, const PostWs& w
 
 static int posterior(hbo_ctx* c, const hbo_model* m, hbo_cache* k, const void* xq, int64_t M, int full_cov,
                      void* mu_out, void* var_out, void* acq_out, int acq_id, double param, double add_noise,
-                     double scale, const PosteriorOverride* ov = nullptr) {
+                     double scale, const PosteriorOverride* ov = nullptr, const MesReq* mes = nullptr) {
   if (!c || !xq) return fail(c, HBO_ERR_ARG, "posterior: null argument");
   if (M <= 0) return HBO_OK;
   HIPCHK(c, hipSetDevice(c->device));
@@ -501,7 +504,10 @@ static int posterior(hbo_ctx* c, const hbo_model* m, hbo_cache* k, const void* x
   if (k && (k->dtype != dtype || k->D != m->input_dim)) return fail(c, HBO_ERR_ARG, "posterior: cache/model mismatch");
   if (k && k->input_warp != m->input_warp) return fail(c, HBO_ERR_ARG, "posterior: the cache was factorised with another input warp");
   const size_t es = esize(dtype);
-  const PostCall pc = {c, m, k, ov ? ov->md : c->d_model, ov ? ov->mlp_w : c->d_mlp_w, ov ? ov->mlp_b : c->d_mlp_b, acq_id, param, add_noise, scale};
+  double* d_ystar = nullptr;   // hbo_acq_mes: the maxima go up on the consumer stream, ahead of everything that reads them
+  if (mes && !(d_ystar = static_cast<double*>(ws_get(c, WS_MES_YSTAR, sizeof(double) * mes->K)))) return HBO_ERR_HIP;
+  const PostCall pc = {c, m, k, ov ? ov->md : c->d_model, ov ? ov->mlp_w : c->d_mlp_w, ov ? ov->mlp_b : c->d_mlp_b, acq_id, param, add_noise, scale,
+                       d_ystar, mes ? mes->K : 0};
   PostPlan p = post_plan(c, m, M, k ? k->t->nblk : 0, full_cov != 0, ov ? &ov->lane : nullptr);
   c->last_post_resident = 0;
   if (p.refuse) return fail(c, p.refuse, "posterior: full_cov limited to 65536 queries");
@@ -514,6 +520,7 @@ static int posterior(hbo_ctx* c, const hbo_model* m, hbo_cache* k, const void* x
   // inside the chunk loop waits for the products in flight on the other stream -- it serialised the two streams and
   // took cfg 3 from 142 to 197 ms
   if (!ov) HIPCHK(c, hipMemcpyAsync(w.xq, xq, (size_t)M * w.row_b, hipMemcpyHostToDevice, sa));
+  if (mes) HIPCHK(c, hipMemcpyAsync(d_ystar, mes->ystar, sizeof(double) * mes->K, hipMemcpyHostToDevice, sa));
   if (k) ensure_w_split(pc, p);
   const bool bad = k && k->info != INT_MAX;
   hipEvent_t ev_free[2] = {nullptr, nullptr};
@@ -570,6 +577,11 @@ extern "C" int hbo_acq(hbo_ctx* c, const hbo_model* m, hbo_cache* k, const void*
   if (acq_id < 0 || acq_id > HBO_ACQ_UCB) return fail(c, HBO_ERR_ARG, "hbo_acq: bad acq_id");
   if (!out) return fail(c, HBO_ERR_ARG, "hbo_acq: out is null");
   return posterior(c, m, k, xq, M, 0, nullptr, nullptr, out, acq_id, param, add_noise, scale);
+}
+// hbo_acq_mes (mes.hip) behind its argument checks: the same pipeline, the MES epilogue in the place of the EI / PI / UCB one
+int posterior_mes(hbo_ctx* c, const hbo_model* m, hbo_cache* k, const void* xq, int64_t M, const MesReq& mes, double add_noise, double scale,
+                  void* out) {
+  return posterior(c, m, k, xq, M, 0, nullptr, nullptr, out, 0, 0.0, add_noise, scale, nullptr, &mes);
 }
 
 // ---- S hyper-parameter samples of one model family as ONE batch ------------------------------------------------------------

@@ -346,6 +346,10 @@ struct PostArgs {
   int acq_id; double param, add_noise, scale;
 };
 void launch_post_epilogue(int dtype, const PostArgs& a, hipStream_t st);
+// hbo_acq_mes's epilogue (mes.hip): out[q] = (1 / K) sum_k h((ystar[k] - mu[q]) / sd[q]) from the mean and variance the kernel above
+// wrote (model dtype, [M]); ystar [K] doubles on the device
+void launch_mes_epilogue(int dtype, const void* mu, const void* var, int64_t M, const double* ystar, int K, double add_noise, double scale,
+                         void* out, hipStream_t st);
 // colsq[i][col] = sum over the 128 rows of row block i of (sum_ch Vpart[ch][row][col])^2, chunks ch < ceil((i + 1) / kchunk)
 void launch_post_colsq_split(int dtype, const void* vpart, int npad, int64_t ldq, int mpad, int nblk, int kchunk, void* colsq, hipStream_t st);
 
@@ -444,6 +448,9 @@ struct AcqSmallArgs {
   int kernel_id, mean_id, acq_id; double scale;
   void* acq_out; double* grad_out;                   // [S][M] model dtype, [S][M][D]
   double* val64_out;                                 // nullable [S][M]: the value before it is rounded to the model dtype (acq_opt.hip)
+  const double* ystar; int K;                        // max-value entropy search (mes.hip): [S][K] maxima (device); null: acq_id decides.
+                                                     // One launch takes one scalar step: the kernels are instantiated for either;
+                                                     // K <= HBO_MES_MAX_K = 256, one term per thread of the pair's workgroup
 };
 void launch_acq_small(int dtype, const AcqSmallArgs& a, int S, hipStream_t st);
 // ---- the same for caches of any n >= 1 (acq_blocked.hip): four stream-ordered launches over queries [q0, q0 + mc) of a.M --

@@ -165,4 +165,72 @@ __device__ __forceinline__ AcqScalars acq_scalars(int acq_id, double mu, double 
   r.val = val; r.amu = amu; r.avar = asd / (2.0 * sd) * scale;
   return r;
 }
+
+// Max-value entropy search (Wang & Jegelka 2017) for a maximised objective: one term of the mean over the sampled maxima y*_k, at
+// gamma = (y*_k - mu) / sd, with r = pdf(gamma) / cdf(gamma):
+//   h(gamma)  = gamma r / 2 - log cdf(gamma)            (>= 0, decreasing, h(+inf) = 0)
+//   h'(gamma) = -(r / 2) (1 + gamma^2 + gamma r)
+// The one expression behind hbo_acq_mes, hbo_mes_grad_samples and hbo_mes_maximize.  Neither side is evaluated literally:
+//   gamma >= 0: cdf = 1 - q with q = cdf(-gamma) from erfc, log cdf = log1p(-q) (the literal log(cdf) is 0 from gamma = 8.3 on);
+//               every term of h and of h' has one sign.  Where pdf underflows (gamma > 38.6) both are 0.
+//   gamma < 0:  with t = -gamma / sqrt 2 and e = erfcx(t): r = sqrt(2 / pi) / e and log cdf = log(e / 2) - gamma^2 / 2.  r + gamma is
+//               formed first (r ~ -gamma - 1 / gamma: the difference of two neighbours is exact), so h = gamma (r + gamma) / 2 - log(e / 2)
+//               and h' = -(r / 2) (1 + gamma (r + gamma)) lose what the rounding of r costs at the scale gamma^2 r -- about 10 digits of
+//               h' are left at gamma = -30, 14 at -8 -- and nothing more.
+// gamma = -inf: (inf, -0), the limits; a NaN stays a NaN.  The floor at 0 guards the sign of h against the last rounding only.
+struct MesTerms { double h, dh; };
+__device__ __forceinline__ MesTerms mes_terms(double g) {
+  MesTerms m;
+  if (g < 0.0) {
+    const double e = erfcx(-g * 0.7071067811865476);
+    const double r = 0.7978845608028654 / e;
+    const double rg = g * (r + g);
+    m.h = 0.5 * rg - log(0.5 * e);
+    m.dh = -0.5 * r * (1.0 + rg);
+    if (g == -INFINITY) { m.h = INFINITY; m.dh = -0.0; }
+  } else {
+    // pdf(gamma) with gamma^2 = s + e taken exactly (e: the rounding of the square, from the fma): the rounded square alone costs
+    // gamma^2 / 2 ulp of the pdf -- 700 at gamma = 37 -- and h' is that pdf times a positive factor
+    const double s = g * g, e = fma(g, g, -s);
+    const double q = norm_cdf(-g);
+    const double r = exp(-0.5 * s) * (1.0 - 0.5 * e) * 0.3989422804014327 / (1.0 - q);
+    m.h = 0.5 * g * r - log1p(-q);
+    m.dh = -0.5 * r * (1.0 + s + g * r);
+    if (r == 0.0 || g == INFINITY) m.dh = -0.0;   // (gamma = inf: inf * 0, and e = nan)
+    if (g == INFINITY) m.h = 0.0;
+  }
+  if (m.h < 0.0) m.h = 0.0;
+  return m;
+}
+// The scalar step of hbo_mes_grad_samples (acq_small.hip, acq_blocked.hip), by the whole 256-thread workgroup that owns the (sample, query)
+// pair; every thread comes with the same mu and var and leaves with the same result:
+//   value = (1 / K) sum_k h(gamma_k),  a_mu = -(1 / K) sum_k h'(gamma_k) / sd,  a_sd = -(1 / K) sum_k h'(gamma_k) gamma_k / sd,
+// a_var from a_sd as acq_scalars forms it.  Thread k < K takes term k; the three sums then run in index order, one thread each, whatever
+// K is.  v2 = (var + add_noise) scale <= 0: no posterior uncertainty, no information -- value and both slopes are 0 (a NaN would win
+// an argmax); a NaN v2 stays NaN.  s_t: [3][HBO_MES_MAX_K] doubles of LDS, s_sum: [3].  Holds barriers: call it from uniform code.
+__device__ __forceinline__ AcqScalars mes_scalars_block(double mu, double var, double add_noise, double scale, const double* ystar, int K,
+                                                         double* s_t, double* s_sum) {
+  const int tid = threadIdx.x;
+  const double v2 = (var + add_noise) * scale;
+  AcqScalars r;
+  r.val = 0.0; r.amu = 0.0; r.avar = 0.0;
+  if (v2 <= 0.0) return r;   // (uniform: every thread holds the same v2)
+  const double sd = sqrt(v2);
+  if (tid < K) {
+    const double g = (ystar[tid] - mu) / sd;
+    const MesTerms m = mes_terms(g);
+    s_t[tid] = m.h; s_t[HBO_MES_MAX_K + tid] = m.dh; s_t[2 * HBO_MES_MAX_K + tid] = m.dh * g;
+  }
+  __syncthreads();
+  if (tid < 3) {
+    const double* t = s_t + tid * HBO_MES_MAX_K;
+    double s = 0.0;
+    for (int k = 0; k < K; ++k) s += t[k];
+    s_sum[tid] = s;
+  }
+  __syncthreads();
+  const double asd = -(s_sum[2] / K) / sd;
+  r.val = s_sum[0] / K; r.amu = -(s_sum[1] / K) / sd; r.avar = asd / (2.0 * sd) * scale;
+  return r;
+}
 }  // namespace

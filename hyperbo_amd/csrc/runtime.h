@@ -61,7 +61,7 @@ enum WsSlot { WS_XQ = 1, WS_MU0, WS_KD, WS_MU, WS_VAR, WS_ACQ, WS_K, WS_COLSQ, W
               WS_BO_IN, WS_BO_FEAT, WS_BO_V, WS_BO_OUT, WS_AO_IN, WS_AO_OUT,
               WS_PATH_DRAWS, WS_PATH_SUMS, WS_PATH_R, WS_PATH_Z, WS_PATH_V, WS_PATH_OUT,
               WS_PO_IN, WS_PO_OUT, WS_PROBE /* hbo_mfma_peak_probe's sink */,
-              WS_AB_WORK /* acq_blocked.hip: k, l, beta */, WS_SLOT_END };
+              WS_AB_WORK /* acq_blocked.hip: k, l, beta */, WS_MES_YSTAR /* hbo_acq_mes: the K maxima */, WS_SLOT_END };
 // every slot is distinct by construction (auto-numbered; the per-layer range WS_FQ0.. is closed by WS_FQ_LAST before WS_K3), and the
 // posterior's per-lane offset (cache.hip: 4096 * lane) must clear the whole range
 static_assert(WS_FQ0 + HBO_MAX_MLP_LAYERS <= WS_K3 && WS_SLOT_END < 4096, "workspace slots overlap a lane offset");

@@ -358,6 +358,49 @@ int hbo_acq_maximize_blocked(hbo_ctx* ctx, const hbo_model* models, int32_t S, h
                              const hbo_acq_opt_opts* opts, double* state, int32_t evals, double* x_out, double* val_out, int32_t* status,
                              hbo_acq_opt_eval* log);
 
+/* ---- max-value entropy search (MES, Wang & Jegelka 2017; no counterpart in the reference): the information a query carries about the
+ *      maximum of the objective, from K sampled maxima y*_1..y*_K (hbo_sample_paths / hbo_paths_maximize draw them).  For posterior mean
+ *      mu and variance var at a query, with pdf and cdf of the standard normal:
+ *        v2 = (var + add_noise) * scale,  sd = sqrt(v2),  gamma_k = (y*_k - mu) / sd,  r = pdf(gamma) / cdf(gamma)
+ *        h(gamma)  = gamma r / 2 - log cdf(gamma)                    (>= 0, decreasing, h(+inf) = 0)
+ *        h'(gamma) = -(r / 2) (1 + gamma^2 + gamma r)
+ *        value = (1 / K) sum_k h(gamma_k)                            fp64, summed in index order
+ *        a_mu  = -(1 / K) sum_k h'(gamma_k) / sd,   a_sd = -(1 / K) sum_k h'(gamma_k) gamma_k / sd,   a_var = a_sd / (2 sd) * scale
+ *      v2 <= 0: the value, a_mu and a_var are 0 (no posterior uncertainty, no information; a NaN there would win an argmax); a NaN v2
+ *      stays NaN.  For every finite gamma the value is finite and >= 0: it reaches 0 by underflow for large gamma and is never
+ *      negative.  Neither tail is evaluated literally (csrc/kernfun.h: mes_terms): log cdf is log1p(-cdf(-gamma)) from erfc for
+ *      gamma >= 0, and r and log cdf come from the scaled complementary error function erfcx for gamma < 0; what is left of the
+ *      cancellation in h' for gamma << 0 is about 10 digits at gamma = -30 and 14 at -8, relative to the un-cancelled terms.
+ *      MES is not a fourth acq_id: hbo_acq, hbo_acq_grad_samples[_blocked] and hbo_acq_maximize[_blocked] keep refusing acq_id = 3.
+ *      K is 1..HBO_MES_MAX_K.  HBO_ERR_ARG (before any device work, outputs untouched) for every entry point below: K outside that
+ *      range, a null ystar or one that holds a value that is not finite, plus what the sibling entry point checks. */
+#define HBO_MES_MAX_K 256
+/* ---- the values over a pool: hbo_acq's posterior pipeline (any n, every model family hbo_acq serves, cache == NULL -> the prior
+ *      branch, queries in chunks of post_chunk) under an epilogue of its own: a thread per query, mu, var and sd in the model dtype as
+ *      hbo_acq forms them, the K terms in fp64 in index order, rounded once to the model dtype.  ystar [K] doubles; out [M,1] model
+ *      dtype.  A row does not depend on post_chunk nor on what the other rows of the call hold (bit for bit); as in hbo_acq, the form
+ *      of the posterior product follows from the TOTAL number of queries M, so calls of different M may differ in the order of the
+ *      sums behind mu and var.  Not positive definite: NaN and HBO_NOT_PD, as hbo_acq. */
+int hbo_acq_mes(hbo_ctx* ctx, const hbo_model* model, hbo_cache* cache /* nullable */, const void* xq, int64_t M, const double* ystar,
+                int32_t K, double add_noise, double scale, void* out);
+/* ---- value and d value / d x_query for S samples over their finished caches: hbo_acq_grad_samples_blocked with ystar [S,K] (row s:
+ *      the maxima of sample s) in the place of acq_id and params -- its semantics, checks, refusals and return codes, for any n >= 1:
+ *      one launch when every cache has n <= 128 (csrc/acq_small.hip), four per chunk of queries otherwise (csrc/acq_blocked.hip).  Only
+ *      the scalar step differs: the K terms are taken by K threads of the workgroup that owns the (sample, query) pair and the three
+ *      sums then run in index order out of LDS, whatever K is; a_mu and a_var feed the unchanged gradient code.  No atomics, every sum
+ *      in a fixed order: a row does not depend on which samples or queries share the call nor on the chunking (bit for bit), and
+ *      identical calls are bit-identical.  acq_out [S,M] model dtype, grad_out [S,M,input_dim] doubles. */
+int hbo_mes_grad_samples(hbo_ctx* ctx, const hbo_model* models, int32_t S, hbo_cache* const* caches, const void* xq, int64_t M,
+                         const double* ystar, int32_t K, const double* add_noise, double scale, void* acq_out, double* grad_out);
+/* ---- the maximisation of the MES value (mean over the S samples) over a box, R starts in one call: hbo_acq_maximize_blocked with
+ *      ystar [S,K], K in the place of acq_id, params -- the same control kernel, state format, log, checks, return codes and
+ *      determinism (no atomics, sums in a fixed order; a run gives the same bits however it is cut into calls); the evaluation of a
+ *      round is hbo_mes_grad_samples' over the R pending points, and val_out the mean over s of its fp64 values at x_out. */
+int hbo_mes_maximize(hbo_ctx* ctx, const hbo_model* models, int32_t S, hbo_cache* const* caches, const void* x0, int32_t R,
+                     const double* lo, const double* hi, const double* ystar, int32_t K, const double* add_noise, double scale,
+                     const hbo_acq_opt_opts* opts, double* state, int32_t evals, double* x_out, double* val_out, int32_t* status,
+                     hbo_acq_opt_eval* log);
+
 /* ---- the maximisation of S posterior sample paths over a box, R starts each, in ONE call: continuous Thompson sampling -- q
  *      suggestions from q paths (no counterpart in the reference).  The optimiser is that of hbo_acq_maximize, run on
  *      f(x) = -f_s(x) for each of the S * R (path, start) pairs: one upload and one solve for u (hbo_sample_paths_grad), then `evals`

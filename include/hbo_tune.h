@@ -100,6 +100,12 @@ int hbo_probe_acq_grad_samples64(hbo_ctx* ctx, const hbo_model* models, int32_t 
 int hbo_probe_acq_grad_samples_blocked64(hbo_ctx* ctx, const hbo_model* models, int32_t S, hbo_cache* const* caches, const void* xq,
                                          int64_t M, int acq_id, const double* params, const double* add_noise, double scale, void* acq_out,
                                          double* grad_out, int32_t force_blocked, int64_t chunk_queries, double* val64_out);
+/* TEST HOOK: hbo_mes_grad_samples (same checks, same launches, same results) with the three extras of the hook above: val64_out [S, M],
+ * the fp64 values the control kernel of hbo_mes_maximize reads; force_blocked, the blocked kernels for caches of n <= 128 too;
+ * chunk_queries.  Neither changes a bit of a row that the blocked kernels computed: every sum runs in a fixed order, without atomics. */
+int hbo_probe_mes_grad_samples64(hbo_ctx* ctx, const hbo_model* models, int32_t S, hbo_cache* const* caches, const void* xq, int64_t M,
+                                 const double* ystar, int32_t K, const double* add_noise, double scale, void* acq_out, double* grad_out,
+                                 int32_t force_blocked, int64_t chunk_queries, double* val64_out);
 /* TEST HOOK: the control code of hbo_acq_maximize (csrc/acq_opt_ctl.h, the text its control kernel compiles) on the host, one thread,
  * for one evaluation of one start; no context, no device.  D: input_dim; dtype: the model dtype the pending point is rounded to.
  * lo, hi [D] (both null: 0 and 1).  vals [S] and grads [S, D]: the per-sample acquisition values (fp64) and gradients at the point the
