@@ -108,6 +108,15 @@ class AcqOptEval(C.Structure):
   _fields_ = [('kind', C.c_int32), ('iter', C.c_int32), ('alpha', C.c_double), ('value', C.c_double)]
 
 
+class ProbePlan(C.Structure):
+  """hbo_probe_plan (include/hbo_tune.h): what the test hook hbo_probe_factor_inverse planned."""
+  _fields_ = [(k, C.c_int32) for k in ('la', 'q', 'q_inner', 'early_at', 'tgran', 'split_f1', 'yield_', 'sweep', 'qs', 'early',
+                                       'small_shape', 'batch_bg', 'd_own_stream')]
+
+  def as_dict(self):
+    return {k.rstrip('_'): int(getattr(self, k)) for k, _ in self._fields_}
+
+
 # the same record as a NumPy dtype ([evals, R] logs)
 ACQ_OPT_EVAL_DTYPE = np.dtype([('kind', np.int32), ('iter', np.int32), ('alpha', np.float64), ('value', np.float64)])
 
@@ -200,6 +209,8 @@ SIGNATURES = {
     'hbo_probe_post_product': (C.c_int, [_P, C.c_int, _P, C.c_int64, _P, C.c_int64, C.c_double, C.c_int, _P]),   # include/hbo_tune.h (test hook)
     'hbo_probe_gram': (C.c_int, [_P, C.c_int, _P, C.c_int32, _P, C.POINTER(C.c_int64), C.c_int32, _P, C.c_int64, C.c_int, C.c_double, _P,
                                  C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),   # include/hbo_tune.h (test hook)
+    'hbo_probe_factor_inverse': (C.c_int, [_P, C.c_int, C.c_int32, C.POINTER(C.c_int64), _P, _P, C.c_int32, C.c_int, _P, _P, _P, _P, _P,
+                                           C.POINTER(C.c_int32), _P]),   # include/hbo_tune.h (test hook; the last: hbo_probe_plan*)
     'hbo_comm_unique_id': (C.c_int, [_P]),
     'hbo_comm_init': (C.c_int, [_P, C.c_int, C.c_int, _P]),
     'hbo_comm_allreduce_sum': (C.c_int, [_P, C.POINTER(C.c_double), C.c_int32]),

@@ -199,6 +199,13 @@ struct ShardReq { double* count; double* timing; };
 struct ShardOut { double* d_red = nullptr; hipEvent_t ev0 = nullptr, ev1 = nullptr; int red_count = 0; int* d_map = nullptr; int nseg = 0; int out_stride = 0; };
 int objective_local(hbo_ctx* c, const hbo_model* m_in, hbo_dataset* ds, int objective, double* nll_sum, double* nll_per_task,
                     double* grad_sum, const ShardReq* sh, ShardOut* so);
+// Two pieces of an evaluation with gradient that the test hook hbo_probe_factor_inverse (probe.hip) runs as well (objective.hip):
+// the fork to the stream of the small reductions behind run_potrf (side_reduce: the idle panel stream; otherwise the main stream
+// itself), and everything between the factorisation and the contraction -- W = L^-1 and K^-1 by the route of inv.pl, alpha = W^T z
+// for the first max_naug augmented rows behind W on `side`, there also d f / d mu (dmu_obj: the objective; < 0: none).  Returns the
+// event behind the side stream's work, which the main stream has been told to wait for (null: there is no side stream).
+hipStream_t obj_fork_side(hbo_ctx* c, bool side_reduce);
+hipEvent_t obj_inverse_step(hbo_ctx* c, InvRun& inv, int max_naug, hipStream_t side, int dmu_obj);
 // one row gather of hbo_dataset_subsample (dataset.hip): row r of task blockIdx.y of the destination = row idx[idx_off + r] (or r) of
 // the source task; hbo_train_adam points the destinations at a batch that already exists and overwrites its rows in place
 struct GatherTask { const void* sx; const void* sys; const void* syd; void* dx; void* dys; void* dyd; int64_t n_src, n_dst, idx_off; int m, has_idx; };

@@ -74,6 +74,39 @@ int enqueue_backward(hbo_ctx* c, const hbo_model* m, hbo_dataset* ds, int64_t ma
   return HBO_OK;
 }
 
+// ---- what hbo_probe_factor_inverse (probe.hip) runs too: api_internal.h ------------------------------------------------------
+hipStream_t obj_fork_side(hbo_ctx* c, bool side_reduce) {
+  hipStream_t st = c->stream, side = side_reduce ? c->stream2 : st;
+  if (side != st) { hipEvent_t e = pool_event(c, 2); hipEventRecord(e, st); hipStreamWaitEvent(side, e, 0); }
+  return side;
+}
+hipEvent_t obj_inverse_step(hbo_ctx* c, InvRun& inv, int max_naug, hipStream_t side, int dmu_obj) {
+  const int dtype = inv.dtype, T = inv.ntasks, max_nblk = inv.max_nblk, max_npad = max_nblk * HBO_TILE;
+  hipStream_t st = c->stream;
+  hipEvent_t ev_side = nullptr;
+  hipEvent_t w_done = side != st ? pool_event(c, 3) : nullptr;   // W is complete
+  if (inv.pl.sweep) {
+    // what the chain left: the last row group(s).  W is complete behind the last group's rows (event), K^-1 behind its update
+    ProfScope ps(c, "sweep_tail", 1);
+    sweep_advance(inv, max_nblk, st, w_done);
+  } else {
+    { ProfScope ps(c, "trtri", 1); run_trtri(inv); }
+    if (w_done) hipEventRecord(w_done, st);
+  }
+  if (w_done) hipStreamWaitEvent(side, w_done, 0);
+  { ProfScope ps(c, "wt_z", 1, side);
+    for (int b = 0; b < max_naug; ++b) launch_wt_z(dtype, inv.d_tasks, T, max_nblk, b, b, max_npad, side); }
+  if (side != st) {
+    if (dmu_obj >= 0) launch_dmu(dtype, inv.d_tasks, T, dmu_obj, side);
+    ev_side = pool_event(c, 4); hipEventRecord(ev_side, side);
+  }
+  // One sequence for both forms: record; [K^-1 = W^T W of the recursive form]; the main stream's wait.  The sweep has its K^-1
+  // already and queues nothing on the main stream between the record and the wait, so its wait follows the record at once.
+  if (!inv.pl.sweep) { ProfScope ps(c, "lauum", 1); run_lauum(inv); }
+  if (ev_side) hipStreamWaitEvent(st, ev_side, 0);
+  return ev_side;
+}
+
 namespace {
 // what set-up and the steps of one evaluation share: the call, its plan (api_internal.h: obj_plan), and the events in flight
 struct ObjState {
@@ -223,37 +256,12 @@ void step_factor(ObjState& s) {
 // the fork to the side stream (where the plan sends the small reductions there) and the first of them
 void step_reduce(ObjState& s) {
   hbo_ctx* c = s.c; hbo_dataset* ds = s.ds; const ObjPlan& p = s.p;
-  hipStream_t st = c->stream;
-  s.side = p.side_reduce ? c->stream2 : st;
-  if (s.side != st) { hipEvent_t e = pool_event(c, 2); hipEventRecord(e, st); hipStreamWaitEvent(s.side, e, 0); }
+  s.side = obj_fork_side(c, p.side_reduce);
   ProfScope ps(c, "nll_reduce", 1, s.side);
   launch_nll_reduce(p.dtype, ds->d_desc, p.T, ds->d_info, ds->d_nll, s.side);
 }
 // W = L^-1 and K^-1 in either form, alpha = W^T z and (side stream) d nll / d mu beside them
-void step_inverse(ObjState& s) {
-  hbo_ctx* c = s.c; hbo_dataset* ds = s.ds; const ObjPlan& p = s.p;
-  hipStream_t st = c->stream, side = s.side;
-  hipEvent_t w_done = side != st ? pool_event(c, 3) : nullptr;   // W is complete
-  if (p.inv.sweep) {
-    // what the chain left: the last row group(s).  W is complete behind the last group's rows (event), K^-1 behind its update
-    ProfScope ps(c, "sweep_tail", 1);
-    sweep_advance(s.inv, p.max_nblk, st, w_done);
-  } else {
-    { ProfScope ps(c, "trtri", 1); run_trtri(s.inv); }
-    if (w_done) hipEventRecord(w_done, st);
-  }
-  if (w_done) hipStreamWaitEvent(side, w_done, 0);
-  { ProfScope ps(c, "wt_z", 1, side);
-    for (int b = 0; b < s.max_naug; ++b) launch_wt_z(p.dtype, ds->d_desc, p.T, p.max_nblk, b, b, p.max_npad, side); }
-  if (side != st) {
-    launch_dmu(p.dtype, ds->d_desc, p.T, p.obj, side);
-    s.ev_side = pool_event(c, 4); hipEventRecord(s.ev_side, side);
-  }
-  // One sequence for both forms: record; [K^-1 = W^T W of the recursive form]; the main stream's wait.  The sweep has its K^-1
-  // already and queues nothing on the main stream between the record and the wait, so its wait follows the record at once.
-  if (!p.inv.sweep) { ProfScope ps(c, "lauum", 1); run_lauum(s.inv); }
-  if (s.ev_side) hipStreamWaitEvent(st, s.ev_side, 0);
-}
+void step_inverse(ObjState& s) { s.ev_side = obj_inverse_step(s.c, s.inv, s.max_naug, s.side, s.p.obj); }
 // the data rows of tasks with more than 127 aligned columns, as outer-product vectors in svec columns 1..m (objectives.py:29-106
 // has no limit on m).  EUC: the rows themselves.  EKL: tr(K1^-1 C0) = sum_b |W row_b|^2 and alpha_b = W^T W row_b from the explicit
 // inverse (two triangular products over all m rows), the quadratic forms added to the task's value.  Main stream, W complete.

@@ -1,7 +1,8 @@
 // What include/hbo_tune.h declares apart from hbo_tune itself (api.hip): the MFMA rate probe of bench.py and the test hooks that run
-// single launches of the posterior and the Gram on caller-chosen operands.  (hbo_probe_acq_grad_samples64 is a second door to
+// single launches of the posterior and the Gram, and the factor and inverse steps of an evaluation, on caller-chosen operands.  (hbo_probe_acq_grad_samples64 is a second door to
 // acq_grad.hip's acq_grad_samples and stays beside it; the control-text probes stay with their kernels in train.hip and acq_opt.hip.)
 #include "api_internal.h"
+#include "../../include/hbo_tune.h"
 
 // Sustained fp64 MFMA rate of THIS device, measured now (include/hbo_tune.h): every SIMD of every CU runs two waves of
 // back-to-back independent v_mfma_f64_16x16x4_f64 (4 accumulators per wave, no memory traffic) for ~`ms` milliseconds between two
@@ -229,4 +230,139 @@ extern "C" int hbo_probe_gram(hbo_ctx* c, int form, const hbo_model* models, int
   HIPCHK(c, hipStreamSynchronize(st));
   HIPCHK(c, hipGetLastError());
   return HBO_OK;
+}
+
+// Test hook (include/hbo_tune.h): the factor and inverse steps of an NLL evaluation with gradient on caller-chosen SPD matrices.  The
+// batch is form 2's of hbo_probe_gram (dataset, workspaces, descriptors; one input column of zeros stands for x), A is filled as
+// hbo_spd_solve fills it, and the steps are the objective's own: run_potrf with the InvRun of the plan, then obj_inverse_step
+// (objective.hip).  Only the main stream is waited for before the copies back, as in the objective: a join that a schedule forgot shows.
+extern "C" int hbo_probe_factor_inverse(hbo_ctx* c, int dtype, int32_t T, const int64_t* ns, const void* a, const void* b, int32_t m,
+                                        int beside_chain, void* chol_out, void* w_out, void* kinv_out, void* x_out, void* z_out,
+                                        int32_t* info_out, hbo_probe_plan* plan_out) {
+  if (!c || !ns || !a) return fail(c, HBO_ERR_ARG, "hbo_probe_factor_inverse: null argument");
+  if (dtype != HBO_F32 && dtype != HBO_F64) return fail(c, HBO_ERR_ARG, "hbo_probe_factor_inverse: bad dtype");
+  if (T <= 0 || T > 64) return fail(c, HBO_ERR_ARG, "hbo_probe_factor_inverse: 1 <= T <= 64");
+  for (int k = 0; k < T; ++k) if (ns[k] <= 0 || ns[k] > 4096) return fail(c, HBO_ERR_ARG, "hbo_probe_factor_inverse: need 1 <= n <= 4096 for every task");
+  if (b ? (m < 1 || m > 8) : m != 0) return fail(c, HBO_ERR_ARG, "hbo_probe_factor_inverse: 1 <= m <= 8 with b, m = 0 without");
+  if (!b && (x_out || z_out)) return fail(c, HBO_ERR_ARG, "hbo_probe_factor_inverse: x_out and z_out need b");
+  if (beside_chain != 0 && beside_chain != 1) return fail(c, HBO_ERR_ARG, "hbo_probe_factor_inverse: beside_chain is 0 or 1");
+  HIPCHK(c, hipSetDevice(c->device));
+  prof_begin(c);
+  const size_t es = esize(dtype);
+  const int naug = b ? m : 1;   // (without right-hand sides: one augmented row of zeros)
+  hipStream_t st = c->stream;
+  // the dataset of the T tasks: one input column and naug target columns of zeros
+  int64_t max_n = 0;
+  std::vector<size_t> a_off(T), b_off(T);   // element offsets of task k in a / the [n, n] outputs, and in b / the [n, m] outputs
+  size_t a_total = 0, b_total = 0;
+  for (int k = 0; k < T; ++k) { a_off[k] = a_total; b_off[k] = b_total; a_total += (size_t)ns[k] * ns[k]; b_total += (size_t)ns[k] * m; max_n = std::max(max_n, ns[k]); }
+  const std::vector<unsigned char> zeros((size_t)max_n * naug * es, 0);
+  std::vector<hbo_task> tasks(T);
+  int64_t rows = 0;
+  std::vector<unsigned char> x0;
+  for (int k = 0; k < T; ++k) rows += ns[k];
+  x0.assign((size_t)rows * es, 0);
+  rows = 0;
+  for (int k = 0; k < T; ++k) {
+    memset(&tasks[k], 0, sizeof(hbo_task));
+    tasks[k].x = x0.data() + (size_t)rows * es; tasks[k].y = zeros.data(); tasks[k].n = ns[k]; tasks[k].m = naug;
+    rows += ns[k];
+  }
+  hbo_dataset* ds = nullptr;
+  int rc = hbo_dataset_create(c, dtype, 1, tasks.data(), T, &ds);
+  if (rc) return rc;
+  DevBuf buf;
+  // (the dataset leaves when the call does, behind a wait: launches may still read its pooled buffers.  Before buf's memory is freed.)
+  struct DatasetGuard { hbo_ctx* c; hipStream_t st; hbo_dataset* ds; ~DatasetGuard() { hipStreamSynchronize(st); hbo_dataset_free(c, ds); } } guard = {c, st, ds};
+  // the dataset holds its tasks largest first; its inputs lie in the caller's order: order[z] = the caller's index of dataset task z
+  std::vector<TaskHost*> by_x(ds->tasks);
+  std::sort(by_x.begin(), by_x.end(), [](TaskHost* p, TaskHost* q) { return (const char*)p->X < (const char*)q->X; });
+  std::vector<int> order(T);
+  for (int z = 0; z < T; ++z) order[z] = (int)(std::find(by_x.begin(), by_x.end(), ds->tasks[z]) - by_x.begin());
+  hbo_model model; memset(&model, 0, sizeof model);
+  model.dtype = dtype; model.input_dim = 1;
+  ds->h_desc.resize(T);
+  for (int z = 0; z < T; ++z) {
+    TaskHost* t = ds->tasks[z];
+    rc = ensure_task_workspace(c, dtype, t, true, naug);
+    if (rc) return rc;
+    fill_desc(ds->h_desc[z], t, &model, dtype, ROLE_FACTOR);   // (naug = the task's m columns, as hbo_spd_solve sets it)
+  }
+  const int max_nblk = ds->max_nblk, max_npad = max_nblk * HBO_TILE;
+  void *d_a = nullptr, *d_b = nullptr, *d_tmp = nullptr; int* d_info = nullptr;
+  HIPCHK(c, dev_alloc(c, (void**)&ds->d_desc, sizeof(TaskDesc) * T));
+  HIPCHK(c, buf.get(c, &d_info, sizeof(int) * T));
+  HIPCHK(c, buf.get(c, &d_a, a_total * es));
+  if (b) HIPCHK(c, buf.get(c, &d_b, b_total * es));
+  if (chol_out) HIPCHK(c, buf.get(c, &d_tmp, a_total * es));
+  HIPCHK(c, hipMemcpyAsync(ds->d_desc, ds->h_desc.data(), sizeof(TaskDesc) * T, hipMemcpyHostToDevice, st));
+  HIPCHK(c, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_info), INT_MAX, T, st));
+  HIPCHK(c, hipMemcpyAsync(d_a, a, a_total * es, hipMemcpyHostToDevice, st));
+  if (b) HIPCHK(c, hipMemcpyAsync(d_b, b, b_total * es, hipMemcpyHostToDevice, st));
+  if (c->opt_poison) launch_poison(dtype, ds->d_desc, T, max_npad, st);
+  for (int z = 0; z < T; ++z) {
+    TaskHost* t = ds->tasks[z];
+    const int k = order[z];
+    launch_fill_spd(dtype, (const char*)d_a + a_off[k] * es, t->n, t->A, t->ld, t->npad, st);
+    launch_set_aug(dtype, b ? (const char*)d_b + b_off[k] * es : nullptr, t->n, m, t->A, t->ld, t->npad, st);
+  }
+  // option spd_diag_bound: the largest max_i A_ii of the batch, as hbo_spd_solve takes it off its one matrix
+  double diag_bound = 0;
+  if (c->opt_spd_diag_bound) for (int k = 0; k < T; ++k) for (int64_t i = 0; i < ns[k]; ++i) diag_bound = std::max(diag_bound, host_elem(a, dtype, (int64_t)a_off[k] + i * ns[k] + i));
+  CholBoundScope bound_scope(c, diag_bound);
+  // the steps of an evaluation with gradient (objective.hip: step_factor without its Gram, step_reduce's fork, step_inverse)
+  InvRun inv = {c, dtype, ds->d_desc, T, max_nblk, T == 1 ? &ds->h_desc[0] : nullptr, inv_plan(c, dtype, T, max_nblk, INV_W_KINV, T == 1, beside_chain != 0)};
+  const PotrfPlan pp = potrf_plan(c, dtype, T, max_nblk, &inv.pl);
+  if (plan_out) {
+    *plan_out = {pp.la, pp.q, pp.q_inner, pp.early_at, pp.tgran, pp.split_f1, (int32_t)pp.yield,
+                 inv.pl.sweep, inv.pl.qs, inv.pl.early, inv.pl.small_shape, inv.pl.batch_bg, inv.pl.d_own_stream};
+  }
+  { ProfScope ps(c, "potrf", 1); run_potrf(c, dtype, ds->d_desc, T, max_nblk, d_info, &inv); }
+  hipStream_t side = obj_fork_side(c, pp.la);
+  obj_inverse_step(c, inv, naug, side, -1);
+  // the copies back, main stream only
+  std::vector<int> h_info(T, INT_MAX);
+  HIPCHK(c, hipMemcpyAsync(h_info.data(), d_info, sizeof(int) * T, hipMemcpyDeviceToHost, st));
+  std::vector<unsigned char> xr, zr;
+  for (int z = 0; z < T; ++z) {
+    TaskHost* t = ds->tasks[z];
+    const int k = order[z];
+    const size_t n = (size_t)t->n, row_b = n * es, pitch = (size_t)t->ld * es;
+    if (chol_out) {
+      launch_extract_lower(dtype, t->A, t->ld, t->n, (char*)d_tmp + a_off[k] * es, st);
+      HIPCHK(c, hipMemcpyAsync((char*)chol_out + a_off[k] * es, (char*)d_tmp + a_off[k] * es, n * n * es, hipMemcpyDeviceToHost, st));
+    }
+    if (w_out) HIPCHK(c, hipMemcpy2DAsync((char*)w_out + a_off[k] * es, row_b, t->W, pitch, row_b, n, hipMemcpyDeviceToHost, st));
+    if (kinv_out) HIPCHK(c, hipMemcpy2DAsync((char*)kinv_out + a_off[k] * es, row_b, t->S, pitch, row_b, n, hipMemcpyDeviceToHost, st));
+  }
+  HIPCHK(c, hipStreamSynchronize(st));
+  for (int z = 0; z < T && b; ++z) {
+    TaskHost* t = ds->tasks[z];
+    const int k = order[z];
+    if (x_out) {   // alpha: m rows of npad elements
+      xr.resize((size_t)m * t->npad * es);
+      HIPCHK(c, hipMemcpy(xr.data(), t->svec, xr.size(), hipMemcpyDeviceToHost));
+      rows_to_cols((char*)x_out + b_off[k] * es, xr.data(), t->n, m, t->npad, es);
+    }
+    if (z_out) {   // the augmented rows of A: m rows of ld elements, repacked to npad
+      zr.resize((size_t)m * t->npad * es);
+      HIPCHK(c, hipMemcpy2D(zr.data(), (size_t)t->npad * es, (const char*)t->A + (size_t)t->npad * t->ld * es, (size_t)t->ld * es, (size_t)t->npad * es, (size_t)m,
+                            hipMemcpyDeviceToHost));
+      rows_to_cols((char*)z_out + b_off[k] * es, zr.data(), t->n, m, t->npad, es);
+    }
+  }
+  HIPCHK(c, hipGetLastError());
+  prof_collect(c);
+  bool bad = false;
+  for (int z = 0; z < T; ++z) {
+    const int k = order[z];
+    const bool bad_k = h_info[z] != INT_MAX;
+    if (info_out) info_out[k] = bad_k ? h_info[z] : 0;
+    if (!bad_k) continue;
+    bad = true;
+    const size_t nn = (size_t)ns[k] * ns[k], nm = (size_t)ns[k] * m;
+    for (void* o : {chol_out, w_out, kinv_out}) if (o) fill_nan((char*)o + a_off[k] * es, nn, dtype);
+    for (void* o : {x_out, z_out}) if (o) fill_nan((char*)o + b_off[k] * es, nm, dtype);
+  }
+  return bad ? HBO_NOT_PD : HBO_OK;
 }

@@ -53,7 +53,8 @@
  *                          -1 (default): 1 up to 8 tasks, 0 above (8 tasks 2.52 -> 2.44 ms, 64 tasks 14.13 / 14.31)
  *   spd_diag_bound 0/1     TEST HOOK (tests/test_gpu_split_products.py): with 1, hbo_spd_solve takes max_i A_ii from the host matrix it was given
  *                          and holds it as the factorisation's diagonal bound for the call, so that an fp32 solve of a caller-chosen matrix
- *                          takes the f16x2 form exactly as hbo_factor does (chol_f16x2); default 0: hbo_spd_solve stays on bf16x3
+ *                          takes the f16x2 form exactly as hbo_factor does (chol_f16x2); default 0: hbo_spd_solve stays on bf16x3.
+ *                          hbo_probe_factor_inverse (below) reads it the same way, over all matrices of its batch
  *
  * Read-only, through hbo_get_option:
  *   chol_form              form of the trailing updates of the context's last factorisation: 0 fp32 MFMA (and all of fp64), 1 bf16x3,
@@ -132,6 +133,39 @@ int hbo_probe_acq_opt_ctl(double* state, int32_t D, int dtype, const hbo_acq_opt
 int hbo_probe_gram(hbo_ctx* ctx, int form, const hbo_model* models, int32_t n_models, const void* x, const int64_t* ns, int32_t T,
                    const void* x2, int64_t n2, int direct_form, double sentinel, void* out, int64_t out_cap, int64_t* rows_out,
                    int64_t* ld_out);
+/* What hbo_probe_factor_inverse planned (csrc/sched.h: PotrfPlan, InvPlan), so that a test can tell which route it reached.
+ * Factorisation: la look-ahead, q / q_inner panels per trailing update / per inner group (0: one level), early_at / tgran when the
+ * early inverse gets its work (after panel early_at, -1: never; after every tgran-th panel), split_f1, yield (0 none, 1 potf2, 2 the
+ * chain's wide kernels too).  Inverse: sweep and its row group qs (0: no sweep), early (block-recursive inverse started beside the
+ * chain), small_shape (64-tiles throughout), batch_bg (0 plain grids, 1 persistent, 2 and polling the yield table), d_own_stream (the
+ * sweep's K^-1 updates on the third stream). */
+typedef struct hbo_probe_plan {
+  int32_t la, q, q_inner, early_at, tgran, split_f1, yield;
+  int32_t sweep, qs, early, small_shape, batch_bg, d_own_stream;
+} hbo_probe_plan;
+/* TEST HOOK (tests/test_gpu_inverse.py): the factor and inverse steps of an NLL evaluation with gradient on caller-chosen SPD matrices
+ * instead of a Gram.  T tasks (1 <= T <= 64), task k of ns[k] points (1 <= ns[k] <= 4096); a: the tasks' matrices [ns[k], ns[k]]
+ * row-major one after the other (only the lower triangles are read), b (nullable): their right-hand sides [ns[k], m] one after the
+ * other, 1 <= m <= 8 (m = 0 without b).  The batch is built as hbo_probe_gram form 2 builds it (dataset, workspaces, descriptors),
+ * poisoned first where the option says so, then the steps run as the objective runs them: the InvRun of
+ * inv_plan(T, max_nblk, W and K^-1, beside_chain), run_potrf with it, the rest of the sweep or of the recursive inverse, W^T z for
+ * the m columns behind W on the stream the objective uses, K^-1 = W^T W unless the plan sweeps.  The hook decides nothing itself;
+ * beside_chain = 0 is the plan of hbo_spd_solve.  With option spd_diag_bound the largest max_i A_ii of the batch is the
+ * factorisation's diagonal bound (fp32: the f16x2 form), as for hbo_spd_solve.
+ * Outputs, each nullable, dense, task after task in the caller's order:
+ *   chol_out [n, n]  L; zeros above the diagonal (written by the export)
+ *   w_out    [n, n]  W = L^-1 as it stands in the task's W buffer, the part above the diagonal included (zeros: an invariant the
+ *                    products rely on)
+ *   kinv_out [n, n]  K^-1 as it stands in S: valid on and below the 128-tile diagonal (whole diagonal tiles); tiles above it are
+ *                    scratch (the sweep's running matrix lived there)
+ *   z_out    [n, m]  L^-1 b (the augmented rows after the factorisation), x_out [n, m] = A^-1 b = W^T z; both need b
+ *   info_out [T]     0 for a task that factorised, else the 1-based row of its first non-positive pivot
+ *   plan_out         what was planned (filled before the factorisation is queued: also there when a task turns out not PD)
+ * HBO_ERR_ARG on a bad argument, before any device call and with no output touched; HBO_NOT_PD when a task did not factorise: the
+ * outputs of those tasks (and only those) are NaN.  No product path calls this. */
+int hbo_probe_factor_inverse(hbo_ctx* ctx, int dtype, int32_t T, const int64_t* ns, const void* a, const void* b, int32_t m,
+                             int beside_chain, void* chol_out, void* w_out, void* kinv_out, void* x_out, void* z_out, int32_t* info_out,
+                             hbo_probe_plan* plan_out);
 #ifdef __cplusplus
 }
 #endif
