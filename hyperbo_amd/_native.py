@@ -165,11 +165,18 @@ SIGNATURES = {
     'hbo_probe_acq_grad_samples_blocked64': (C.c_int, [_P, _P, C.c_int32, C.POINTER(_P), _P, C.c_int64, C.c_int, C.POINTER(C.c_double),
                                                        C.POINTER(C.c_double), C.c_double, _P, C.POINTER(C.c_double), C.c_int32, C.c_int64,
                                                        C.POINTER(C.c_double)]),   # hbo_tune.h (test hook)
+    'hbo_acq_grad_samples_mlp': (C.c_int, [_P, _P, C.c_int32, C.POINTER(_P), _P, C.c_int64, C.c_int, C.POINTER(C.c_double),
+                                           C.POINTER(C.c_double), C.c_double, _P, C.POINTER(C.c_double)]),
+    'hbo_probe_acq_grad_samples_mlp64': (C.c_int, [_P, _P, C.c_int32, C.POINTER(_P), _P, C.c_int64, C.c_int, C.POINTER(C.c_double),
+                                                   C.POINTER(C.c_double), C.c_double, _P, C.POINTER(C.c_double), C.c_int32, C.c_int64,
+                                                   C.POINTER(C.c_double)]),   # hbo_tune.h (test hook)
     'hbo_acq_opt_state_doubles': (C.c_int64, [C.c_int32, C.c_int32]),
     'hbo_acq_maximize': (C.c_int, [_P, _P, C.c_int32, C.POINTER(_P), _P, C.c_int32, _P, _P, C.c_int, C.POINTER(C.c_double),
                                    C.POINTER(C.c_double), C.c_double, C.POINTER(AcqOptOpts), _P, C.c_int32, _P, _P, _P, _P]),
     'hbo_acq_maximize_blocked': (C.c_int, [_P, _P, C.c_int32, C.POINTER(_P), _P, C.c_int32, _P, _P, C.c_int, C.POINTER(C.c_double),
                                            C.POINTER(C.c_double), C.c_double, C.POINTER(AcqOptOpts), _P, C.c_int32, _P, _P, _P, _P]),
+    'hbo_acq_maximize_mlp': (C.c_int, [_P, _P, C.c_int32, C.POINTER(_P), _P, C.c_int32, _P, _P, C.c_int, C.POINTER(C.c_double),
+                                       C.POINTER(C.c_double), C.c_double, C.POINTER(AcqOptOpts), _P, C.c_int32, _P, _P, _P, _P]),
     'hbo_acq_mes': (C.c_int, [_P, C.POINTER(Model), _P, _P, C.c_int64, C.POINTER(C.c_double), C.c_int32, C.c_double, C.c_double, _P]),
     'hbo_mes_grad_samples': (C.c_int, [_P, _P, C.c_int32, C.POINTER(_P), _P, C.c_int64, C.POINTER(C.c_double), C.c_int32,
                                        C.POINTER(C.c_double), C.c_double, _P, C.POINTER(C.c_double)]),

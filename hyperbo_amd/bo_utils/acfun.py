@@ -301,11 +301,20 @@ def _blocked_max_n(model):
   return None if _acq_blocked(model) else ACQ_FUSED_MAX_N
 
 
-def _acq_fused_unmet(model, sub_dataset_key, n_samples=1, n_kept=None, enabled=None, max_n=ACQ_FUSED_MAX_N):
+def _acq_mlp(model):
+  """True when model.params.config['acq_mlp'] asks for the entry points that serve MLP-basis kernels and the linear_mlp mean
+  (hbo_acq_grad_samples_mlp, hbo_acq_maximize_mlp).  They have no 128-observation limit: the key implies 'acq_blocked'.  A model
+  without params or config has not asked."""
+  cfg = getattr(getattr(model, 'params', None), 'config', None)
+  return bool(cfg.get('acq_mlp')) if isinstance(cfg, dict) else False
+
+
+def _acq_fused_unmet(model, sub_dataset_key, n_samples=1, n_kept=None, enabled=None, max_n=ACQ_FUSED_MAX_N, allow_mlp=False):
   """The first condition that keeps a value_and_grad call from the one-launch path (hbo_acq_grad_samples, context option
   'acq_fused'), as a message, or None.  Host-side checks only.  n_kept: factor handles at hand for the n_samples parameter samples
   (None: not known yet); enabled: the option's value (None: read from the default context); max_n: the largest sub-dataset (None:
-  no limit -- the caller goes to the _blocked entry points)."""
+  no limit -- the caller goes to the _blocked entry points); allow_mlp: the MLP-basis and linear_mlp conditions are skipped (the
+  caller goes to the _mlp entry points)."""
   if not (nat.acq_fused_enabled() if enabled is None else enabled):
     return "the context option 'acq_fused' is off"
   if not model.has_observations(sub_dataset_key):
@@ -313,9 +322,9 @@ def _acq_fused_unmet(model, sub_dataset_key, n_samples=1, n_kept=None, enabled=N
   n = np.shape(model.dataset[sub_dataset_key].x)[0]
   if max_n is not None and n > max_n:
     return f'the sub-dataset has {n} > {max_n} observations'
-  if getattr(model.cov_func, 'uses_mlp', False):
+  if not allow_mlp and getattr(model.cov_func, 'uses_mlp', False):
     return 'the kernel runs on an MLP basis'
-  if getattr(model.mean_func, 'mean_id', None) == nat.MEAN_LINEAR_MLP:
+  if not allow_mlp and getattr(model.mean_func, 'mean_id', None) == nat.MEAN_LINEAR_MLP:
     return 'the mean is linear_mlp'
   if getattr(model.cov_func, 'uses_kumar', False):
     return 'the kernel is input-warped (Kumaraswamy)'
@@ -329,12 +338,12 @@ ACQ_OPT_SEGMENT = 48       # evaluations per hbo_acq_maximize call (profiles/acq
 ACQ_OPT_MAX_EVALS = 4096   # evaluations a maximisation may spend in all
 
 
-def _acq_opt_unmet(model, sub_dataset_key, acfun_sub, n_samples=1, n_kept=None, max_n=ACQ_FUSED_MAX_N):
+def _acq_opt_unmet(model, sub_dataset_key, acfun_sub, n_samples=1, n_kept=None, max_n=ACQ_FUSED_MAX_N, allow_mlp=False):
   """The first condition that keeps a maximisation off the device loop (hbo_acq_maximize), as a message, or None: an acquisition
   function outside the native registry, then `_acq_fused_unmet`'s conditions without the option check.  Host-side checks only."""
   if acfun_sub not in _NATIVE_ID:
     return f'the acquisition function {getattr(acfun_sub, "__name__", acfun_sub)!r} is not one of the native ones (EI, PI, UCB)'
-  return _acq_fused_unmet(model, sub_dataset_key, n_samples, n_kept, enabled=True, max_n=max_n)
+  return _acq_fused_unmet(model, sub_dataset_key, n_samples, n_kept, enabled=True, max_n=max_n, allow_mlp=allow_mlp)
 
 
 def _mes_args(mes, s_count):
@@ -344,11 +353,12 @@ def _mes_args(mes, s_count):
   return mes.ctypes.data_as(nat.C.POINTER(nat.C.c_double)), mes.shape[1]
 
 
-def _device_maximize(built, handles, noises, x0, lo, hi, acq_id, acfun_param, scale, opts, want_log, blocked=False, mes=None):
+def _device_maximize(built, handles, noises, x0, lo, hi, acq_id, acfun_param, scale, opts, want_log, blocked=False, mes=None, entry=None):
   """hbo_acq_maximize (blocked: hbo_acq_maximize_blocked, caches of any size; mes, [S, K] maxima: hbo_mes_maximize) in segments of
-  opts['segment'] evaluations until no start is RUNNING or opts['max_evals'] are spent.
+  opts['segment'] evaluations until no start is RUNNING or opts['max_evals'] are spent.  entry: another sibling by name
+  (hbo_acq_maximize_mlp).
   x0 [R, D] in the model dtype; lo / hi [D] float64 or None.  Returns (x [R, D], values [R], status [R], evaluations [R], log or None)."""
-  entry = nat.lib().hbo_acq_maximize_blocked if blocked else nat.lib().hbo_acq_maximize
+  entry = getattr(nat.lib(), entry) if entry else (nat.lib().hbo_acq_maximize_blocked if blocked else nat.lib().hbo_acq_maximize)
   s_count, (r_count, d) = len(built), x0.shape
   ctx = handles[0].ctx
   structs, caches, prm, nse = _sample_args(built, handles, noises, acfun_param)
@@ -377,11 +387,11 @@ def _device_maximize(built, handles, noises, x0, lo, hi, acq_id, acfun_param, sc
   return x, val, status, n_evals, (np.concatenate(logs) if want_log else None)
 
 
-def _fused_value_and_grad(built, handles, noises, xq, acq_id, acfun_param, scale, blocked=False, mes=None):
+def _fused_value_and_grad(built, handles, noises, xq, acq_id, acfun_param, scale, blocked=False, mes=None, entry=None):
   """((S, M, 1) values in the model dtype, (S, M, D) gradients in float64) of S models over their finished factors: one
   hbo_acq_grad_samples call -- one upload, one launch, one copy back (blocked: hbo_acq_grad_samples_blocked, caches of any size;
-  mes, [S, K] maxima: hbo_mes_grad_samples)."""
-  entry = nat.lib().hbo_acq_grad_samples_blocked if blocked else nat.lib().hbo_acq_grad_samples
+  mes, [S, K] maxima: hbo_mes_grad_samples; entry: another sibling by name -- hbo_acq_grad_samples_mlp)."""
+  entry = getattr(nat.lib(), entry) if entry else (nat.lib().hbo_acq_grad_samples_blocked if blocked else nat.lib().hbo_acq_grad_samples)
   s_count, (nq, d) = len(built), xq.shape
   ctx = handles[0].ctx
   structs, caches, prm, nse = _sample_args(built, handles, noises, acfun_param)
@@ -416,9 +426,11 @@ def _hgp_value_and_grad(model, sub_dataset_key, x_queries, acq_id, acfun_param):
   built, noises = _sample_models(model, samples, dtype)
   handles = _hgp_sample_caches(model, sub_dataset_key, samples, dtype) if has_obs else []
   _, scale = model.predict_noise_and_scale(True, True)
-  if _acq_fused_unmet(model, sub_dataset_key, len(samples), len(handles), max_n=_blocked_max_n(model)) is None:
+  mlp = _acq_mlp(model)   # config['acq_mlp']: the _mlp entry point, MLP models included, no 128-observation limit
+  if _acq_fused_unmet(model, sub_dataset_key, len(samples), len(handles), max_n=None if mlp else _blocked_max_n(model), allow_mlp=mlp) is None:
     # option 'acq_fused': every sample's pass in ONE call over the kept factors; the mean as the loop below takes it
-    outs, gs = _fused_value_and_grad(built, handles, noises, xq, acq_id, acfun_param, scale, blocked=_acq_blocked(model))
+    outs, gs = _fused_value_and_grad(built, handles, noises, xq, acq_id, acfun_param, scale, blocked=_acq_blocked(model),
+                                     entry='hbo_acq_grad_samples_mlp' if mlp else None)
     for out, g in zip(outs, gs):
       val += out
       grad += g
@@ -485,9 +497,10 @@ def acfun_wrapper(acfun_sub, acfun_callback_default):
     grad = np.zeros((xq.shape[0], model.input_dim), dtype=np.float64)
     if bm is None:
       return out, grad
-    if _acq_fused_unmet(model, sub_dataset_key, max_n=_blocked_max_n(model)) is None:   # option 'acq_fused': the one-launch path with S = 1
+    mlp = _acq_mlp(model)   # config['acq_mlp']: the _mlp entry point, MLP models included, no 128-observation limit
+    if _acq_fused_unmet(model, sub_dataset_key, max_n=None if mlp else _blocked_max_n(model), allow_mlp=mlp) is None:   # option 'acq_fused': the one-launch path with S = 1
       outs, gs = _fused_value_and_grad([bm], [handle], [add_noise], xq, _NATIVE_ID[acfun_sub], acfun_param, scale,
-                                       blocked=_acq_blocked(model))
+                                       blocked=_acq_blocked(model), entry='hbo_acq_grad_samples_mlp' if mlp else None)
       return outs[0], gs[0]
     ctx = handle.ctx if handle is not None else nat.default_context()
     ctx.check(nat.lib().hbo_acq_grad(ctx.handle, bm.ref(), handle.handle if handle is not None else None,
@@ -504,15 +517,19 @@ def acfun_wrapper(acfun_sub, acfun_callback_default):
     without any, x_init[0] and NaN.  info: per-start 'x', 'value', 'status', 'evals', and 'log' ([evaluations, R] records) on
     request.  Works on the cached factors value_and_grad uses; a model the device loop does not cover raises
     HboError(HBO_ERR_UNSUPPORTED) -- there is no fall-back.  More than 128 observations are such a model unless
-    model.params.config['acq_blocked'] is set: the calls then go to hbo_acq_maximize_blocked."""
+    model.params.config['acq_blocked'] is set: the calls then go to hbo_acq_maximize_blocked.  An MLP-basis kernel or a linear_mlp
+    mean is such a model unless model.params.config['acq_mlp'] is set: the calls then go to hbo_acq_maximize_mlp (any number of
+    observations)."""
     o = dict(ACQ_OPT_DEFAULTS, segment=ACQ_OPT_SEGMENT, max_evals=ACQ_OPT_MAX_EVALS, log=False)
     o.update(opts or {})
     x_init = np.atleast_2d(np.asarray(x_init, dtype=np.float64))
     hgp = isinstance(model, gp.HGP)
     samples = model.get_model_params_samples() if hgp else None
     n_samples = len(samples) if hgp else 1
-    blocked, max_n = _acq_blocked(model), _blocked_max_n(model)
-    unmet = _acq_opt_unmet(model, sub_dataset_key, acfun_sub, n_samples, max_n=max_n)
+    blocked, max_n, mlp = _acq_blocked(model), _blocked_max_n(model), _acq_mlp(model)
+    if mlp:
+      max_n = None
+    unmet = _acq_opt_unmet(model, sub_dataset_key, acfun_sub, n_samples, max_n=max_n, allow_mlp=mlp)
     if unmet is not None:
       raise nat.HboError(nat.HBO_ERR_UNSUPPORTED, 'ac_func.maximize: ' + unmet)
     acfun_param = acfun_callback(model, sub_dataset_key)
@@ -521,7 +538,7 @@ def acfun_wrapper(acfun_sub, acfun_callback_default):
       dtype = _model.infer_dtype(sd.x, sd.y)
       built, noises = _sample_models(model, samples, dtype)
       handles = _hgp_sample_caches(model, sub_dataset_key, samples, dtype)
-      unmet = _acq_opt_unmet(model, sub_dataset_key, acfun_sub, n_samples, len(handles), max_n=max_n)
+      unmet = _acq_opt_unmet(model, sub_dataset_key, acfun_sub, n_samples, len(handles), max_n=max_n, allow_mlp=mlp)
       if unmet is not None:
         raise nat.HboError(nat.HBO_ERR_UNSUPPORTED, 'ac_func.maximize: ' + unmet)
       _, scale = model.predict_noise_and_scale(True, True)
@@ -535,7 +552,7 @@ def acfun_wrapper(acfun_sub, acfun_callback_default):
       lo, hi = np.ascontiguousarray(b[:, 0]), np.ascontiguousarray(b[:, 1])
     x0 = np.ascontiguousarray(x_init, dtype=dtype)
     x, val, status, n_evals, log = _device_maximize(built, handles, noises, x0, lo, hi, _NATIVE_ID[acfun_sub], acfun_param, scale, o,
-                                                    bool(o['log']), blocked=blocked)
+                                                    bool(o['log']), blocked=blocked, entry='hbo_acq_maximize_mlp' if mlp else None)
     if hgp:
       model.update_model_params(samples[-1])   # as every HGP path here leaves it (gp.py:674-678)
     info = {'x': x, 'value': val, 'status': status, 'evals': n_evals}

@@ -51,7 +51,9 @@ def bayesopt(key, model, sub_dataset_key, query_oracle, ac_func, iters, input_sa
   among equals -- once the sub-dataset has observations; an iteration without any (the prior branch) takes the SciPy path.  There is
   no fall-back: the iteration at which the sub-dataset has grown past 128 observations raises HboError(HBO_ERR_UNSUPPORTED).
   With config['acq_blocked'] set as well, `ac_func.maximize` calls hbo_acq_maximize_blocked and the loop continues on the device
-  past 128 observations (below them the two are the same launches and the same bits).
+  past 128 observations (below them the two are the same launches and the same bits).  A model on the MLP basis (`*_mlp` kernels,
+  the linear_mlp mean) raises as well unless config['acq_mlp'] is set: `ac_func.maximize` then calls hbo_acq_maximize_mlp, at any
+  number of observations.
 
   An `ac_func` with a `suggest` attribute (acfun.thompson_continuous) proposes the point itself: x_opt is
   `ac_func.suggest(model=, sub_dataset_key=, x_candidates=, key=)[0]` over the iteration's candidates and this loop's Generator."""

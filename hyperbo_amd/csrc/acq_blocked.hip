@@ -12,7 +12,12 @@
 // other queries, its place in a group of eight, the other samples, ldv or how the call was cut into query chunks, and identical calls give
 // identical bits.  Entries of W above the diagonal and rows beyond n_s are dropped by a select, never multiplied: the padding of a cache
 // and what an earlier call left in the workspace cannot reach a result.
-#include "kernfun.h"
+// MLP basis (FEAT != 0; acq_mlp.h, hbo_acq_grad_samples_mlp): one launch in front of the four,
+//   0  acq_blk_mlp_kernel    grid (mc, S)                    the forward pass of the pair's query; every layer's activations into the
+//                                                            fp64 plane acts [S][mc][ftot]
+// launch 1 then reads the pair's query in the kernel's space from that plane and launch 4 reads the activations back for the mean and
+// the backward pass: five launches per chunk.
+#include "acq_mlp.h"
 
 namespace {
 enum { BLK_MC = 8 };   // queries per workgroup of the two triangular products
@@ -20,8 +25,27 @@ enum { BLK_MC = 8 };   // queries per workgroup of the two triangular products
 __device__ __forceinline__ int blk_npad(int n) { return (n + HBO_TILE - 1) / HBO_TILE * HBO_TILE; }
 __device__ __forceinline__ int64_t blk_row(const AcqBlockedArgs& b, int s, int64_t ql) { return ((int64_t)s * b.mc + ql) * b.ldv; }
 
-// ---- 1: k[s][q][i] = k(x_q, X_i) for i < n_s, zeros up to ldv
+__device__ __forceinline__ double* blk_acts(const AcqBlockedArgs& b, int s, int64_t ql) { return b.acts + ((int64_t)s * b.mc + ql) * b.ftot; }
+
+// ---- 0 (FEAT): the forward pass of query q under sample s's weights, layer after layer into acts[s][q][ftot]
 template <typename T>
+__global__ __launch_bounds__(256) void acq_blk_mlp_kernel(AcqBlockedArgs b) {
+  __shared__ double s_x0[HBO_MAX_FEATURE_DIM], s_act[HBO_MAX_MLP_LAYERS * HBO_MAX_FEATURE_DIM];
+  const AcqSmallArgs& a = b.a;
+  const int64_t ql = blockIdx.x;
+  const int s = blockIdx.y, tid = threadIdx.x;
+  if (a.smp[s].bad) return;   // (uniform) nothing of the sample's planes is read
+  const T* xq = static_cast<const T*>(a.xq) + (b.q0 + ql) * a.D;
+  for (int d = tid; d < a.D; d += 256) s_x0[d] = (double)xq[d];
+  __syncthreads();
+  acq_mlp_fwd_block<T>(a, s, s_x0, s_act);
+  double* out = blk_acts(b, s, ql);
+  for (int l = 0, off = 0; l < a.L; off += a.fout[l], ++l)
+    if (tid < a.fout[l]) out[off + tid] = s_act[l * HBO_MAX_FEATURE_DIM + tid];
+}
+
+// ---- 1: k[s][q][i] = k(x_q, X_i) for i < n_s, zeros up to ldv
+template <typename T, int FEAT>
 __global__ __launch_bounds__(HBO_TILE) void acq_blk_k_kernel(AcqBlockedArgs b) {
   __shared__ double s_xq[HBO_MAX_FEATURE_DIM], s_il[HBO_MAX_FEATURE_DIM];
   const AcqSmallArgs& a = b.a;
@@ -29,13 +53,18 @@ __global__ __launch_bounds__(HBO_TILE) void acq_blk_k_kernel(AcqBlockedArgs b) {
   const int64_t ql = blockIdx.y;
   const AcqSmallSample& sm = a.smp[s];
   if (sm.bad) return;   // (uniform) the finish kernel writes the NaN rows and reads nothing of the workspace
-  const int D = a.D, n = sm.n;
+  const int D = (FEAT & ACQ_FEAT_KERNEL) ? a.fdim : a.D, n = sm.n;   // width of the kernel's space
   const int i = blockIdx.x * HBO_TILE + tid;
   double* kout = b.k + blk_row(b, s, ql);
   if (blockIdx.x * HBO_TILE >= n) { kout[i] = 0.0; return; }   // (uniform) a block of padding
-  const double* vec = a.vec + (int64_t)s * 2 * D;
-  const T* xq = static_cast<const T*>(a.xq) + (b.q0 + ql) * D;
-  for (int d = tid; d < D; d += HBO_TILE) { s_xq[d] = (double)xq[d]; s_il[d] = vec[d]; }
+  const double* vec = a.vec + (int64_t)s * (FEAT ? a.fdim + a.mdim : 2 * D);
+  if constexpr ((FEAT & ACQ_FEAT_KERNEL) != 0) {
+    const double* fq = blk_acts(b, s, ql) + (b.ftot - D);   // the last layer
+    for (int d = tid; d < D; d += HBO_TILE) { s_xq[d] = fq[d]; s_il[d] = vec[d]; }
+  } else {
+    const T* xq = static_cast<const T*>(a.xq) + (b.q0 + ql) * D;
+    for (int d = tid; d < D; d += HBO_TILE) { s_xq[d] = (double)xq[d]; s_il[d] = vec[d]; }
+  }
   __syncthreads();
   const ExpCoef ec = hbo_exp_coef();
   double u = 0, k = 0;
@@ -147,7 +176,8 @@ __global__ __launch_bounds__(256) void acq_blk_trans_kernel(AcqBlockedArgs b) {
 
 // ---- 4: one workgroup per (sample, query): the sums over the rows, the scalar step, the gradient
 //         (MES: the scalar step is mes_scalars_block over the sample's K maxima, as in acq_small_kernel)
-template <typename T, bool MES>
+//         (FEAT: D below is the width of the kernel's space; the activations come back from the plane and acq_mlp_tail ends the pair)
+template <typename T, bool MES, int FEAT>
 __global__ __launch_bounds__(256) void acq_blk_finish_kernel(AcqBlockedArgs b) {
   __shared__ double s_xq[HBO_MAX_FEATURE_DIM], s_il[HBO_MAX_FEATURE_DIM];
   __shared__ double s_w[256];
@@ -159,16 +189,16 @@ __global__ __launch_bounds__(256) void acq_blk_finish_kernel(AcqBlockedArgs b) {
   const int s = blockIdx.y;
   const int tid = threadIdx.x;
   const AcqSmallSample& sm = a.smp[s];
-  const int D = a.D, n = sm.n;
+  const int D = (FEAT & ACQ_FEAT_KERNEL) ? a.fdim : a.D, n = sm.n;
   T* acq = static_cast<T*>(a.acq_out) + (int64_t)s * a.M + q;
-  double* g = a.grad_out + ((int64_t)s * a.M + q) * D;
+  double* g = a.grad_out + ((int64_t)s * a.M + q) * a.D;
   if (sm.bad) {   // (uniform) the factor is not positive definite: NaN rows, as hbo_acq_grad
     if (tid == 0) { *acq = (T)NAN; if (a.val64_out) a.val64_out[(int64_t)s * a.M + q] = NAN; }
-    for (int d = tid; d < D; d += 256) g[d] = NAN;
+    for (int d = tid; d < a.D; d += 256) g[d] = NAN;
     return;
   }
-  const double* vec = a.vec + (int64_t)s * 2 * D;
-  const T* xq = static_cast<const T*>(a.xq) + q * D;
+  const double* vec = a.vec + (int64_t)s * (FEAT ? a.fdim + a.mdim : 2 * D);
+  const T* xq = static_cast<const T*>(a.xq) + q * a.D;
   const T* F = static_cast<const T*>(sm.F);
   const T* al = static_cast<const T*>(sm.alpha);
   const double* kv = b.k + blk_row(b, s, ql);
@@ -176,7 +206,22 @@ __global__ __launch_bounds__(256) void acq_blk_finish_kernel(AcqBlockedArgs b) {
   const double* bv = b.beta + blk_row(b, s, ql);
   const int kid = a.kernel_id;
   const bool is_dot = (kid == HBO_KERNEL_DOT);
-  for (int d = tid; d < D; d += 256) { s_xq[d] = (double)xq[d]; s_il[d] = vec[d]; }
+  const double* s_raw = s_xq;   // the raw query; s_xq: the query in the kernel's space
+  double* s_act = nullptr;      // FEAT: every layer's activations, as acq_mlp_fwd_block lays them out
+  if constexpr (FEAT != 0) {
+    __shared__ double s_x0[HBO_MAX_FEATURE_DIM], s_acts[HBO_MAX_MLP_LAYERS * HBO_MAX_FEATURE_DIM];
+    const double* in = blk_acts(b, s, ql);
+    for (int l = 0, off = 0; l < a.L; off += a.fout[l], ++l)
+      if (tid < a.fout[l]) s_acts[l * HBO_MAX_FEATURE_DIM + tid] = in[off + tid];
+    for (int d = tid; d < a.D; d += 256) s_x0[d] = (double)xq[d];
+    for (int d = tid; d < D; d += 256) s_il[d] = vec[d];
+    __syncthreads();
+    const double* last = s_acts + (a.L - 1) * HBO_MAX_FEATURE_DIM;
+    for (int d = tid; d < D; d += 256) s_xq[d] = (FEAT & ACQ_FEAT_KERNEL) ? last[d] : s_x0[d];
+    s_raw = s_x0; s_act = s_acts;
+  } else {
+    for (int d = tid; d < D; d += 256) { s_xq[d] = (double)xq[d]; s_il[d] = vec[d]; }
+  }
   __syncthreads();
   // ---- ka = sum k_i alpha_i, ll = sum l_i^2: chunk by chunk of 256 rows, then over the workgroup
   double pka = 0, pll = 0;
@@ -190,7 +235,11 @@ __global__ __launch_bounds__(256) void acq_blk_finish_kernel(AcqBlockedArgs b) {
   double kqq = sm.sv, mean = 0;
   if (is_dot) kqq = block_sum(tid < D ? s_xq[tid] * s_xq[tid] : 0.0, sred) * sm.inv_sigma2 + sm.bias2;
   if (a.mean_id == HBO_MEAN_CONSTANT) mean = sm.constant;
-  else if (a.mean_id == HBO_MEAN_LINEAR) mean = sm.linear_bias + block_sum(tid < D ? s_xq[tid] * vec[D + tid] : 0.0, sred);
+  else if (a.mean_id == HBO_MEAN_LINEAR) mean = sm.linear_bias + block_sum(tid < a.D ? s_raw[tid] * vec[D + tid] : 0.0, sred);
+  if constexpr (FEAT != 0) {
+    if (a.mean_id == HBO_MEAN_LINEAR_MLP)   // on the last layer, whoever else reads it
+      mean = sm.linear_bias + block_sum(tid < a.mdim ? s_act[(a.L - 1) * HBO_MAX_FEATURE_DIM + tid] * vec[D + tid] : 0.0, sred);
+  }
   double amu, avar;
   if constexpr (MES) {
     __shared__ double s_mes[3 * HBO_MES_MAX_K], s_mes_sum[3];
@@ -250,19 +299,41 @@ __global__ __launch_bounds__(256) void acq_blk_finish_kernel(AcqBlockedArgs b) {
     for (int gg = 0; gg < G; ++gg) r += s_acc[gg * FD + dl];
     if (is_dot) r += avar * 2.0 * s_xq[dl] * sm.inv_sigma2;
     else r *= s_il[dl] * s_il[dl];
-    if (a.mean_id == HBO_MEAN_LINEAR) r += amu * vec[D + dl];
-    g[dl] = r;
+    if constexpr (FEAT == 0) {
+      if (a.mean_id == HBO_MEAN_LINEAR) r += amu * vec[D + dl];
+      g[dl] = r;
+    } else {
+      s_acc[dl] = r;   // the gradient in the kernel's space (thread dl of group 0 has read its column of s_acc, and only it did)
+    }
+  }
+  if constexpr (FEAT != 0) {
+    __shared__ double s_gk[HBO_MAX_FEATURE_DIM], s_top[HBO_MAX_FEATURE_DIM], s_tmp[HBO_MAX_FEATURE_DIM];
+    __syncthreads();
+    if (tid < D) s_gk[tid] = s_acc[tid];
+    acq_mlp_tail<T, FEAT>(a, s, s_act, s_gk, vec + D, amu, s_top, s_tmp, g);
   }
 }
 
-template <typename T>
-void launch_blocked_t(const AcqBlockedArgs& b, int S, hipStream_t st) {
+template <typename T, int FEAT>
+void launch_blocked_f(const AcqBlockedArgs& b, int S, hipStream_t st) {
   const unsigned mc = (unsigned)b.mc, grp = (unsigned)((b.mc + BLK_MC - 1) / BLK_MC);
-  hipLaunchKernelGGL((acq_blk_k_kernel<T>), dim3(b.ldv / HBO_TILE, mc, S), dim3(HBO_TILE), 0, st, b);
+  if constexpr (FEAT != 0) hipLaunchKernelGGL((acq_blk_mlp_kernel<T>), dim3(mc, S), dim3(256), 0, st, b);
+  hipLaunchKernelGGL((acq_blk_k_kernel<T, FEAT>), dim3(b.ldv / HBO_TILE, mc, S), dim3(HBO_TILE), 0, st, b);
   hipLaunchKernelGGL((acq_blk_fwd_kernel<T, BLK_MC>), dim3(b.ldv / 16, grp, S), dim3(256), 0, st, b);
   hipLaunchKernelGGL((acq_blk_trans_kernel<T, BLK_MC>), dim3(b.ldv / 64, grp, S), dim3(256), 0, st, b);
-  if (b.a.ystar) hipLaunchKernelGGL((acq_blk_finish_kernel<T, true>), dim3(mc, S), dim3(256), 0, st, b);
-  else hipLaunchKernelGGL((acq_blk_finish_kernel<T, false>), dim3(mc, S), dim3(256), 0, st, b);
+  if constexpr (FEAT == 0) {
+    if (b.a.ystar) { hipLaunchKernelGGL((acq_blk_finish_kernel<T, true, 0>), dim3(mc, S), dim3(256), 0, st, b); return; }
+  }
+  hipLaunchKernelGGL((acq_blk_finish_kernel<T, false, FEAT>), dim3(mc, S), dim3(256), 0, st, b);
+}
+template <typename T>
+void launch_blocked_t(const AcqBlockedArgs& b, int S, hipStream_t st) {
+  switch (b.a.ystar ? 0 : b.a.feat) {   // (the MES entry points refuse MLP models)
+    case 0: launch_blocked_f<T, 0>(b, S, st); break;
+    case ACQ_FEAT_KERNEL: launch_blocked_f<T, ACQ_FEAT_KERNEL>(b, S, st); break;
+    case ACQ_FEAT_MEAN: launch_blocked_f<T, ACQ_FEAT_MEAN>(b, S, st); break;
+    default: launch_blocked_f<T, ACQ_FEAT_KERNEL | ACQ_FEAT_MEAN>(b, S, st); break;
+  }
 }
 }  // namespace
 

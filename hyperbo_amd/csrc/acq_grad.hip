@@ -131,7 +131,7 @@ int acq_grad_samples(hbo_ctx* c, const AcqSamplesMode& mode, const hbo_model* mo
   if (M < 0) return fail(c, HBO_ERR_ARG, fn + "M < 0");
   const hbo_model* m0 = &models[0];
   bool any_bad = false;
-  if (int rc = acq_samples_check(c, fn, models, S, caches, mode.max_n, &any_bad)) return rc;
+  if (int rc = acq_samples_check(c, fn, models, S, caches, mode.max_n, &any_bad, mode.allow_mlp)) return rc;
   if (M == 0) return HBO_OK;
   HIPCHK(c, hipSetDevice(c->device));
   const int dtype = m0->dtype, D = m0->input_dim;
@@ -139,9 +139,13 @@ int acq_grad_samples(hbo_ctx* c, const AcqSamplesMode& mode, const hbo_model* mo
   hipStream_t st = c->stream;
   const int ldv = acq_blocked_ldv(S, caches);
   const bool blocked = mode.force_blocked || ldv > HBO_TILE;
-  // one block up: [S records][S x 2 D doubles + (MES) S x K maxima][M x D queries]; one block down: [S x M x D doubles][S x M values]
-  const size_t hv_b = sizeof(double) * 2 * D * S, ys_b = mes ? sizeof(double) * (size_t)S * mes->K : 0;
-  const size_t smp_b = align256(sizeof(AcqSmallSample) * S), vec_b = align256(hv_b + ys_b), xq_b = (size_t)M * D * es;
+  // one block up: [S records][S x 2 D doubles + (MES) S x K maxima][M x D queries][(MLP basis) the S weight sets and their address
+  // tables]; one block down: [S x M x D doubles][S x M values]
+  const AcqVecWidths vw = acq_vec_widths(m0);   // (without an MLP: D and D)
+  const AcqMlpPack mlp = acq_mlp_layout(m0, S);
+  const size_t hv_b = sizeof(double) * ((size_t)vw.fdim + vw.mdim) * S, ys_b = mes ? sizeof(double) * (size_t)S * mes->K : 0;
+  const size_t smp_b = align256(sizeof(AcqSmallSample) * S), vec_b = align256(hv_b + ys_b);
+  const size_t xq_b = mlp.bytes ? align256((size_t)M * D * es) + mlp.bytes : (size_t)M * D * es, o_mlp = smp_b + vec_b + align256((size_t)M * D * es);
   const size_t grad_b = align256(sizeof(double) * (size_t)S * M * D), acq_b = (size_t)S * M * es;
   const size_t v64_o = align256(grad_b + acq_b), v64_b = val64_out ? sizeof(double) * (size_t)S * M : 0;
   const size_t in_b = smp_b + vec_b + xq_b, out_b = val64_out ? v64_o + v64_b : grad_b + acq_b;
@@ -151,7 +155,7 @@ int acq_grad_samples(hbo_ctx* c, const AcqSamplesMode& mode, const hbo_model* mo
   int64_t chunk = 0;
   double* d_work = nullptr;
   if (blocked) {
-    const size_t per_query = sizeof(double) * 3 * (size_t)S * ldv;
+    const size_t per_query = sizeof(double) * (size_t)S * (3 * (size_t)ldv + mlp.ftot);   // k, l, beta and (MLP basis) the activations
     chunk = mode.chunk_queries > 0 ? mode.chunk_queries : std::max<int64_t>(1, (int64_t)(ACQ_BLOCKED_WS_BYTES / per_query));
     chunk = std::min(std::min(chunk, M), ACQ_BLOCKED_MAX_CHUNK);
     d_work = static_cast<double*>(ws_get(c, WS_AB_WORK, per_query * (size_t)chunk));
@@ -164,9 +168,10 @@ int acq_grad_samples(hbo_ctx* c, const AcqSamplesMode& mode, const hbo_model* mo
   double* hv = reinterpret_cast<double*>(stage + smp_b);
   acq_small_pack(hs, hv, models, S, caches, params, add_noise);
   if (mes) memcpy(stage + smp_b + hv_b, mes->ystar, ys_b);
-  memcpy(stage + smp_b + vec_b, xq, xq_b);
-  HIPCHK(c, stage_upload(c, d_in, stage, in_b, st));
+  memcpy(stage + smp_b + vec_b, xq, (size_t)M * D * es);
   AcqSmallArgs a = {};
+  acq_mlp_fill(mlp, stage + o_mlp, d_in + o_mlp, models, S, a);
+  HIPCHK(c, stage_upload(c, d_in, stage, in_b, st));
   a.smp = reinterpret_cast<const AcqSmallSample*>(d_in); a.vec = reinterpret_cast<const double*>(d_in + smp_b); a.xq = d_in + smp_b + vec_b;
   a.D = D; a.M = M; a.kernel_id = m0->kernel_id; a.mean_id = m0->mean_id; a.acq_id = acq_id; a.scale = scale;
   a.grad_out = reinterpret_cast<double*>(d_out); a.acq_out = d_out + grad_b;
@@ -178,6 +183,7 @@ int acq_grad_samples(hbo_ctx* c, const AcqSamplesMode& mode, const hbo_model* mo
     b.a = a; b.ldv = ldv;
     const size_t plane = (size_t)S * chunk * ldv;
     b.k = d_work; b.l = d_work + plane; b.beta = d_work + 2 * plane;
+    b.acts = d_work + 3 * plane; b.ftot = mlp.ftot;
     for (int64_t q0 = 0; q0 < M; q0 += chunk) {   // (stream order: a chunk's launches run after the ones before it have read the workspace)
       b.q0 = q0; b.mc = std::min(chunk, M - q0);
       launch_acq_blocked(dtype, b, S, st);
@@ -195,13 +201,13 @@ int acq_grad_samples(hbo_ctx* c, const AcqSamplesMode& mode, const hbo_model* mo
 extern "C" int hbo_acq_grad_samples(hbo_ctx* c, const hbo_model* models, int32_t S, hbo_cache* const* caches, const void* xq, int64_t M,
                                     int acq_id, const double* params, const double* add_noise, double scale, void* acq_out,
                                     double* grad_out) {
-  const AcqSamplesMode mode = {"hbo_acq_grad_samples", HBO_TILE, false, 0};
+  const AcqSamplesMode mode = {"hbo_acq_grad_samples", HBO_TILE, false, 0, false};
   return acq_grad_samples(c, mode, models, S, caches, xq, M, acq_id, params, nullptr, add_noise, scale, acq_out, grad_out, nullptr);
 }
 extern "C" int hbo_acq_grad_samples_blocked(hbo_ctx* c, const hbo_model* models, int32_t S, hbo_cache* const* caches, const void* xq,
                                             int64_t M, int acq_id, const double* params, const double* add_noise, double scale,
                                             void* acq_out, double* grad_out) {
-  const AcqSamplesMode mode = {"hbo_acq_grad_samples_blocked", INT_MAX, false, 0};
+  const AcqSamplesMode mode = {"hbo_acq_grad_samples_blocked", INT_MAX, false, 0, false};
   return acq_grad_samples(c, mode, models, S, caches, xq, M, acq_id, params, nullptr, add_noise, scale, acq_out, grad_out, nullptr);
 }
 // include/hbo_tune.h (TEST HOOK): hbo_acq_grad_samples with the fp64 values hbo_acq_maximize's control kernel reads
@@ -209,7 +215,7 @@ extern "C" int hbo_probe_acq_grad_samples64(hbo_ctx* c, const hbo_model* models,
                                             int acq_id, const double* params, const double* add_noise, double scale, void* acq_out,
                                             double* grad_out, double* val64_out) {
   if (!val64_out) return fail(c, HBO_ERR_ARG, "hbo_probe_acq_grad_samples64: val64_out is null");
-  const AcqSamplesMode mode = {"hbo_acq_grad_samples", HBO_TILE, false, 0};
+  const AcqSamplesMode mode = {"hbo_acq_grad_samples", HBO_TILE, false, 0, false};
   return acq_grad_samples(c, mode, models, S, caches, xq, M, acq_id, params, nullptr, add_noise, scale, acq_out, grad_out, val64_out);
 }
 // include/hbo_tune.h (TEST HOOK): hbo_acq_grad_samples_blocked with those values, the blocked kernels on request and a chunk size
@@ -219,6 +225,25 @@ extern "C" int hbo_probe_acq_grad_samples_blocked64(hbo_ctx* c, const hbo_model*
                                                     double* val64_out) {
   if (!val64_out) return fail(c, HBO_ERR_ARG, "hbo_probe_acq_grad_samples_blocked64: val64_out is null");
   if (chunk_queries < 0) return fail(c, HBO_ERR_ARG, "hbo_probe_acq_grad_samples_blocked64: chunk_queries < 0");
-  const AcqSamplesMode mode = {"hbo_acq_grad_samples_blocked", INT_MAX, force_blocked != 0, chunk_queries};
+  const AcqSamplesMode mode = {"hbo_acq_grad_samples_blocked", INT_MAX, force_blocked != 0, chunk_queries, false};
+  return acq_grad_samples(c, mode, models, S, caches, xq, M, acq_id, params, nullptr, add_noise, scale, acq_out, grad_out, val64_out);
+}
+// ---- the same with MLP-basis kernels and linear_mlp means served (acq_mlp.h): the pair's workgroup runs the forward and backward pass
+//      itself (n <= 128: still ONE launch; otherwise a forward launch in front of the four: five per chunk).  The S weight sets ride up
+//      in the call's one staged upload.  A family without any MLP takes hbo_acq_grad_samples_blocked's launches over the same bytes.
+extern "C" int hbo_acq_grad_samples_mlp(hbo_ctx* c, const hbo_model* models, int32_t S, hbo_cache* const* caches, const void* xq, int64_t M,
+                                        int acq_id, const double* params, const double* add_noise, double scale, void* acq_out,
+                                        double* grad_out) {
+  const AcqSamplesMode mode = {"hbo_acq_grad_samples_mlp", INT_MAX, false, 0, true};
+  return acq_grad_samples(c, mode, models, S, caches, xq, M, acq_id, params, nullptr, add_noise, scale, acq_out, grad_out, nullptr);
+}
+// include/hbo_tune.h (TEST HOOK): hbo_acq_grad_samples_mlp with the fp64 values, the blocked kernels on request and a chunk size
+extern "C" int hbo_probe_acq_grad_samples_mlp64(hbo_ctx* c, const hbo_model* models, int32_t S, hbo_cache* const* caches, const void* xq,
+                                                int64_t M, int acq_id, const double* params, const double* add_noise, double scale,
+                                                void* acq_out, double* grad_out, int32_t force_blocked, int64_t chunk_queries,
+                                                double* val64_out) {
+  if (!val64_out) return fail(c, HBO_ERR_ARG, "hbo_probe_acq_grad_samples_mlp64: val64_out is null");
+  if (chunk_queries < 0) return fail(c, HBO_ERR_ARG, "hbo_probe_acq_grad_samples_mlp64: chunk_queries < 0");
+  const AcqSamplesMode mode = {"hbo_acq_grad_samples_mlp", INT_MAX, force_blocked != 0, chunk_queries, true};
   return acq_grad_samples(c, mode, models, S, caches, xq, M, acq_id, params, nullptr, add_noise, scale, acq_out, grad_out, val64_out);
 }

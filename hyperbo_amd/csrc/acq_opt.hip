@@ -99,10 +99,13 @@ extern "C" int64_t hbo_acq_opt_state_doubles(int32_t D, int32_t memory) {
 // evaluation step -- one launch of acq_small.hip when every cache has n <= 128, the four launches of acq_blocked.hip otherwise.
 // (mes -- hbo_mes_maximize, mes.hip: the S x K maxima ride up behind the box and the evaluation takes the MES scalar step; acq_id and
 //  params are then not read)
-int acq_maximize(hbo_ctx* c, const char* name, int max_n, const hbo_model* models, int32_t S, hbo_cache* const* caches, const void* x0,
-                 int32_t R, const double* lo, const double* hi, int acq_id, const double* params, const MesReq* mes, const double* add_noise,
-                 double scale, const hbo_acq_opt_opts* opts, double* state, int32_t evals, double* x_out, double* val_out, int32_t* status,
-                 hbo_acq_opt_eval* log) {
+// (allow_mlp -- hbo_acq_maximize_mlp: MLP-basis kernels and linear_mlp means are served; the S weight sets ride up between the pending
+//  points and the states, the evaluation runs the pair's forward and backward pass (acq_mlp.h) and the control kernel sees raw points
+//  and raw gradients as ever)
+int acq_maximize(hbo_ctx* c, const char* name, int max_n, bool allow_mlp, const hbo_model* models, int32_t S, hbo_cache* const* caches,
+                 const void* x0, int32_t R, const double* lo, const double* hi, int acq_id, const double* params, const MesReq* mes,
+                 const double* add_noise, double scale, const hbo_acq_opt_opts* opts, double* state, int32_t evals, double* x_out, double* val_out,
+                 int32_t* status, hbo_acq_opt_eval* log) {
   const std::string fn = std::string(name) + ": ";
   if (!models || !caches || !x0 || (mes ? !mes->ystar : !params) || !add_noise || !state || !x_out || !val_out || !status) return fail(c, HBO_ERR_ARG, fn + "null argument");
   if (S <= 0 || S > 4096) return fail(c, HBO_ERR_ARG, fn + "1 <= S <= 4096");
@@ -113,7 +116,7 @@ int acq_maximize(hbo_ctx* c, const char* name, int max_n, const hbo_model* model
   if (evals <= 0 || evals > 4096) return fail(c, HBO_ERR_ARG, fn + "1 <= evals <= 4096");
   if (int rc = acq_opt_check_opts(c, fn, opts)) return rc;
   bool any_bad = false;
-  if (int rc = acq_samples_check(c, fn, models, S, caches, max_n, &any_bad)) return rc;
+  if (int rc = acq_samples_check(c, fn, models, S, caches, max_n, &any_bad, allow_mlp)) return rc;
   const hbo_model* m0 = &models[0];
   const int dtype = m0->dtype, D = m0->input_dim;
   if (int rc = acq_opt_check_box(c, fn, lo, hi, D, dtype)) return rc;
@@ -136,25 +139,28 @@ int acq_maximize(hbo_ctx* c, const char* name, int max_n, const hbo_model* model
   const int ldv = acq_blocked_ldv(S, caches);
   const bool blocked = ldv > HBO_TILE;
   const size_t plane = (size_t)S * R * ldv;   // k, l, beta of the blocked evaluation: [S][R][ldv] doubles each
+  const AcqVecWidths vw = acq_vec_widths(m0);   // (without an MLP: D and D)
+  const AcqMlpPack mlp = acq_mlp_layout(m0, S);
+  const size_t work = 3 * plane + (size_t)S * R * mlp.ftot;   // ... and (MLP basis) the activations [S][R][ftot]
   if (blocked) {
     size_t total = 0;
     HIPCHK(c, hipDeviceTotalMem(&total, c->device));
-    if (sizeof(double) * 3 * plane > total / 2)
+    if (sizeof(double) * work > total / 2)
       return fail(c, HBO_ERR_UNSUPPORTED, fn + "the evaluation workspace (3 x S x R x npad doubles) exceeds half of the device memory; use fewer starts per call");
   }
   // one block up: [S records][S x 2 D doubles][lo, hi][R x D pending points][R states]; the log follows the states, and one copy brings
   // [states | log] back.  Scratch of the rounds: [S x R x D gradients][S x R values fp64][S x R values in the model dtype]
   // (MES: the S x K maxima sit behind the box, in its part of the block)
   const size_t ys_b = mes ? sizeof(double) * (size_t)S * mes->K : 0;
-  const size_t smp_b = align256(sizeof(AcqSmallSample) * S), vec_b = align256(sizeof(double) * 2 * D * S), box_b = align256(sizeof(double) * 2 * D + ys_b);
+  const size_t smp_b = align256(sizeof(AcqSmallSample) * S), vec_b = align256(sizeof(double) * ((size_t)vw.fdim + vw.mdim) * S), box_b = align256(sizeof(double) * 2 * D + ys_b);
   const size_t pend_b = align256((size_t)R * D * es), state_b = align256(sizeof(double) * (size_t)R * ns);
   const size_t log_b = log ? sizeof(hbo_acq_opt_eval) * (size_t)evals * R : 0;
-  const size_t o_state = smp_b + vec_b + box_b + pend_b, up_b = o_state + state_b, down_b = state_b + log_b;
+  const size_t o_mlp = smp_b + vec_b + box_b + pend_b, o_state = o_mlp + mlp.bytes, up_b = o_state + state_b, down_b = state_b + log_b;
   const size_t grad_b = align256(sizeof(double) * (size_t)S * R * D), val_b = align256(sizeof(double) * (size_t)S * R), acq_b = (size_t)S * R * es;
   char* d_in = static_cast<char*>(ws_get(c, WS_AO_IN, up_b + log_b));
   char* d_out = static_cast<char*>(ws_get(c, WS_AO_OUT, grad_b + val_b + acq_b));
   if (!d_in || !d_out) return HBO_ERR_HIP;
-  double* d_work = blocked ? static_cast<double*>(ws_get(c, WS_AB_WORK, sizeof(double) * 3 * plane)) : nullptr;
+  double* d_work = blocked ? static_cast<double*>(ws_get(c, WS_AB_WORK, sizeof(double) * work)) : nullptr;
   if (blocked && !d_work) return HBO_ERR_HIP;
   char* stage = static_cast<char*>(stage_begin(c, fn.c_str(), up_b + log_b));
   if (!stage) return HBO_ERR_HIP;
@@ -182,9 +188,10 @@ int acq_maximize(hbo_ctx* c, const char* name, int max_n, const hbo_model* model
       else reinterpret_cast<float*>(hpend)[(size_t)r * D + i] = (float)v.xt[i];
     }
   }
+  AcqSmallArgs a = {};
+  acq_mlp_fill(mlp, stage + o_mlp, d_in + o_mlp, models, S, a);
   HIPCHK(c, stage_upload(c, d_in, stage, up_b, st));
 
-  AcqSmallArgs a = {};
   a.smp = reinterpret_cast<const AcqSmallSample*>(d_in); a.vec = reinterpret_cast<const double*>(d_in + smp_b);
   a.xq = d_in + smp_b + vec_b + box_b;
   a.D = D; a.M = R; a.kernel_id = m0->kernel_id; a.mean_id = m0->mean_id; a.acq_id = acq_id; a.scale = scale;
@@ -203,6 +210,7 @@ int acq_maximize(hbo_ctx* c, const char* name, int max_n, const hbo_model* model
   AcqBlockedArgs b = {};
   b.a = a; b.ldv = ldv; b.q0 = 0; b.mc = R;
   b.k = d_work; b.l = d_work + plane; b.beta = d_work + 2 * plane;
+  b.acts = d_work + 3 * plane; b.ftot = mlp.ftot;
   for (int e = 0; e < evals; ++e) {
     if (blocked) launch_acq_blocked(dtype, b, S, st);
     else launch_acq_small(dtype, a, S, st);
@@ -226,14 +234,21 @@ extern "C" int hbo_acq_maximize(hbo_ctx* c, const hbo_model* models, int32_t S, 
                                 const double* lo, const double* hi, int acq_id, const double* params, const double* add_noise, double scale,
                                 const hbo_acq_opt_opts* opts, double* state, int32_t evals, double* x_out, double* val_out, int32_t* status,
                                 hbo_acq_opt_eval* log) {
-  return acq_maximize(c, "hbo_acq_maximize", HBO_TILE, models, S, caches, x0, R, lo, hi, acq_id, params, nullptr, add_noise, scale, opts, state, evals,
+  return acq_maximize(c, "hbo_acq_maximize", HBO_TILE, false, models, S, caches, x0, R, lo, hi, acq_id, params, nullptr, add_noise, scale, opts, state, evals,
                       x_out, val_out, status, log);
 }
 extern "C" int hbo_acq_maximize_blocked(hbo_ctx* c, const hbo_model* models, int32_t S, hbo_cache* const* caches, const void* x0, int32_t R,
                                         const double* lo, const double* hi, int acq_id, const double* params, const double* add_noise,
                                         double scale, const hbo_acq_opt_opts* opts, double* state, int32_t evals, double* x_out,
                                         double* val_out, int32_t* status, hbo_acq_opt_eval* log) {
-  return acq_maximize(c, "hbo_acq_maximize_blocked", INT_MAX, models, S, caches, x0, R, lo, hi, acq_id, params, nullptr, add_noise, scale, opts, state,
+  return acq_maximize(c, "hbo_acq_maximize_blocked", INT_MAX, false, models, S, caches, x0, R, lo, hi, acq_id, params, nullptr, add_noise, scale, opts, state,
+                      evals, x_out, val_out, status, log);
+}
+extern "C" int hbo_acq_maximize_mlp(hbo_ctx* c, const hbo_model* models, int32_t S, hbo_cache* const* caches, const void* x0, int32_t R,
+                                    const double* lo, const double* hi, int acq_id, const double* params, const double* add_noise,
+                                    double scale, const hbo_acq_opt_opts* opts, double* state, int32_t evals, double* x_out,
+                                    double* val_out, int32_t* status, hbo_acq_opt_eval* log) {
+  return acq_maximize(c, "hbo_acq_maximize_mlp", INT_MAX, true, models, S, caches, x0, R, lo, hi, acq_id, params, nullptr, add_noise, scale, opts, state,
                       evals, x_out, val_out, status, log);
 }
 

@@ -7,11 +7,14 @@
 //   a linear mean adds a_mu lin_w.
 // Every sum is fp64 in a fixed order (no atomics), and a pair reads nothing another pair writes: a row of the result does not depend
 // on which samples or queries share the launch.  The scalar functions are those of kernfun.h.
-#include "kernfun.h"
+#include "acq_mlp.h"
 
 namespace {
 // MES: the scalar step is mes_scalars_block over the sample's K maxima (a.ystar; hbo_mes_grad_samples) instead of acq_scalars
-template <typename T, bool MES>
+// FEAT (acq_mlp.h; hbo_acq_grad_samples_mlp): 0 -- no MLP basis; otherwise ACQ_FEAT_KERNEL | ACQ_FEAT_MEAN, who reads the last layer.
+// The pair's workgroup then runs the forward pass first, works in the kernel's own space of width D = fdim below, takes the mean in
+// the mean's own space and ends with the backward pass (acq_mlp_tail).
+template <typename T, bool MES, int FEAT>
 __global__ __launch_bounds__(256) void acq_small_kernel(AcqSmallArgs a) {
   __shared__ double s_xq[HBO_MAX_FEATURE_DIM], s_il[HBO_MAX_FEATURE_DIM];
   __shared__ double s_k[HBO_TILE], s_l[HBO_TILE], s_w[HBO_TILE];
@@ -22,23 +25,37 @@ __global__ __launch_bounds__(256) void acq_small_kernel(AcqSmallArgs a) {
   const int s = blockIdx.y;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const AcqSmallSample& sm = a.smp[s];
-  const int D = a.D, n = sm.n;
+  const int n = sm.n;
+  const int D = (FEAT & ACQ_FEAT_KERNEL) ? a.fdim : a.D;   // width of the kernel's space
   T* acq = static_cast<T*>(a.acq_out) + (int64_t)s * a.M + q;
-  double* g = a.grad_out + ((int64_t)s * a.M + q) * D;
+  double* g = a.grad_out + ((int64_t)s * a.M + q) * a.D;
   if (sm.bad) {   // (uniform) the factor is not positive definite: NaN rows, as hbo_acq_grad
     if (tid == 0) { *acq = (T)NAN; if (a.val64_out) a.val64_out[(int64_t)s * a.M + q] = NAN; }
-    for (int d = tid; d < D; d += 256) g[d] = NAN;
+    for (int d = tid; d < a.D; d += 256) g[d] = NAN;
     return;
   }
-  const double* vec = a.vec + (int64_t)s * 2 * D;   // 1 / lengthscale [D], linear mean weights [D]
-  const T* xq = static_cast<const T*>(a.xq) + q * D;
+  const double* vec = a.vec + (int64_t)s * (FEAT ? a.fdim + a.mdim : 2 * D);   // 1 / lengthscale [D], linear mean weights [D | mean width]
+  const T* xq = static_cast<const T*>(a.xq) + q * a.D;
   const T* F = static_cast<const T*>(sm.F);
   const T* W = static_cast<const T*>(sm.W);
   const T* al = static_cast<const T*>(sm.alpha);
   const int64_t ld = sm.ld;
   const int kid = a.kernel_id;
   const bool is_dot = (kid == HBO_KERNEL_DOT);
-  for (int d = tid; d < D; d += 256) { s_xq[d] = (double)xq[d]; s_il[d] = vec[d]; }
+  const double* s_raw = s_xq;   // the raw query; s_xq: the query in the kernel's space
+  double* s_act = nullptr;      // FEAT: every layer's activations
+  if constexpr (FEAT != 0) {
+    __shared__ double s_x0[HBO_MAX_FEATURE_DIM], s_acts[HBO_MAX_MLP_LAYERS * HBO_MAX_FEATURE_DIM];
+    for (int d = tid; d < a.D; d += 256) s_x0[d] = (double)xq[d];
+    for (int d = tid; d < D; d += 256) s_il[d] = vec[d];
+    __syncthreads();
+    acq_mlp_fwd_block<T>(a, s, s_x0, s_acts);
+    const double* last = s_acts + (a.L - 1) * HBO_MAX_FEATURE_DIM;
+    for (int d = tid; d < D; d += 256) s_xq[d] = (FEAT & ACQ_FEAT_KERNEL) ? last[d] : s_x0[d];
+    s_raw = s_x0; s_act = s_acts;
+  } else {
+    for (int d = tid; d < D; d += 256) { s_xq[d] = (double)xq[d]; s_il[d] = vec[d]; }
+  }
   __syncthreads();
   const ExpCoef ec = hbo_exp_coef();
   // ---- k_i = k(x, X_i): thread i walks the features of row i in order
@@ -59,7 +76,11 @@ __global__ __launch_bounds__(256) void acq_small_kernel(AcqSmallArgs a) {
   double kqq = sm.sv, mean = 0;
   if (is_dot) kqq = block_sum(tid < D ? s_xq[tid] * s_xq[tid] : 0.0, sred) * sm.inv_sigma2 + sm.bias2;
   if (a.mean_id == HBO_MEAN_CONSTANT) mean = sm.constant;
-  else if (a.mean_id == HBO_MEAN_LINEAR) mean = sm.linear_bias + block_sum(tid < D ? s_xq[tid] * vec[D + tid] : 0.0, sred);
+  else if (a.mean_id == HBO_MEAN_LINEAR) mean = sm.linear_bias + block_sum(tid < a.D ? s_raw[tid] * vec[D + tid] : 0.0, sred);
+  if constexpr (FEAT != 0) {
+    if (a.mean_id == HBO_MEAN_LINEAR_MLP)   // on the last layer, whoever else reads it
+      mean = sm.linear_bias + block_sum(tid < a.mdim ? s_act[(a.L - 1) * HBO_MAX_FEATURE_DIM + tid] * vec[D + tid] : 0.0, sred);
+  }
   __syncthreads();
   // ---- l = W k: a wave per row, lanes along the row (two columns each); four rows of loads in flight.  Every load comes from a valid
   //      address (row clamped) and entries above the diagonal are dropped by a select, never multiplied
@@ -134,8 +155,18 @@ __global__ __launch_bounds__(256) void acq_small_kernel(AcqSmallArgs a) {
     for (int gg = 0; gg < G; ++gg) r += s_acc[gg * FD + dl];
     if (is_dot) r += avar * 2.0 * s_xq[dl] * sm.inv_sigma2;
     else r *= s_il[dl] * s_il[dl];
-    if (a.mean_id == HBO_MEAN_LINEAR) r += amu * vec[D + dl];
-    g[dl] = r;
+    if constexpr (FEAT == 0) {
+      if (a.mean_id == HBO_MEAN_LINEAR) r += amu * vec[D + dl];
+      g[dl] = r;
+    } else {
+      s_acc[dl] = r;   // the gradient in the kernel's space (thread dl of group 0 has read its column of s_acc, and only it did)
+    }
+  }
+  if constexpr (FEAT != 0) {
+    __shared__ double s_gk[HBO_MAX_FEATURE_DIM], s_top[HBO_MAX_FEATURE_DIM], s_tmp[HBO_MAX_FEATURE_DIM];
+    __syncthreads();
+    if (tid < D) s_gk[tid] = s_acc[tid];
+    acq_mlp_tail<T, FEAT>(a, s, s_act, s_gk, vec + D, amu, s_top, s_tmp, g);
   }
 }
 }  // namespace
@@ -143,11 +174,27 @@ __global__ __launch_bounds__(256) void acq_small_kernel(AcqSmallArgs a) {
 void launch_acq_small(int dtype, const AcqSmallArgs& a, int S, hipStream_t st) {
   if (a.M <= 0 || S <= 0) return;
   const dim3 grid((unsigned)a.M, (unsigned)S);
-  if (a.ystar) {
-    if (dtype == HBO_F64) hipLaunchKernelGGL((acq_small_kernel<double, true>), grid, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((acq_small_kernel<float, true>), grid, dim3(256), 0, st, a);
+  if (a.ystar) {   // (the MES entry points refuse MLP models: a.feat is 0)
+    if (dtype == HBO_F64) hipLaunchKernelGGL((acq_small_kernel<double, true, 0>), grid, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((acq_small_kernel<float, true, 0>), grid, dim3(256), 0, st, a);
     return;
   }
-  if (dtype == HBO_F64) hipLaunchKernelGGL((acq_small_kernel<double, false>), grid, dim3(256), 0, st, a);
-  else hipLaunchKernelGGL((acq_small_kernel<float, false>), grid, dim3(256), 0, st, a);
+  switch (a.feat) {
+    case 0:
+      if (dtype == HBO_F64) hipLaunchKernelGGL((acq_small_kernel<double, false, 0>), grid, dim3(256), 0, st, a);
+      else hipLaunchKernelGGL((acq_small_kernel<float, false, 0>), grid, dim3(256), 0, st, a);
+      break;
+    case ACQ_FEAT_KERNEL:
+      if (dtype == HBO_F64) hipLaunchKernelGGL((acq_small_kernel<double, false, ACQ_FEAT_KERNEL>), grid, dim3(256), 0, st, a);
+      else hipLaunchKernelGGL((acq_small_kernel<float, false, ACQ_FEAT_KERNEL>), grid, dim3(256), 0, st, a);
+      break;
+    case ACQ_FEAT_MEAN:
+      if (dtype == HBO_F64) hipLaunchKernelGGL((acq_small_kernel<double, false, ACQ_FEAT_MEAN>), grid, dim3(256), 0, st, a);
+      else hipLaunchKernelGGL((acq_small_kernel<float, false, ACQ_FEAT_MEAN>), grid, dim3(256), 0, st, a);
+      break;
+    default:
+      if (dtype == HBO_F64) hipLaunchKernelGGL((acq_small_kernel<double, false, ACQ_FEAT_KERNEL | ACQ_FEAT_MEAN>), grid, dim3(256), 0, st, a);
+      else hipLaunchKernelGGL((acq_small_kernel<float, false, ACQ_FEAT_KERNEL | ACQ_FEAT_MEAN>), grid, dim3(256), 0, st, a);
+      break;
+  }
 }

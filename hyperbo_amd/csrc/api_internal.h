@@ -430,12 +430,14 @@ struct hbo_cache {
 // What hbo_acq_grad_samples and hbo_acq_maximize ask of their S (model, cache) pairs, before any device work: one model family
 // (model_family_check) without MLP basis or linear_mlp mean, and finished caches of 1..max_n observations that match their models
 // (HBO_TILE: the one-block entry points; INT_MAX: the _blocked ones).  *any_bad: a cache is not positive definite.
-static int acq_samples_check(hbo_ctx* c, const std::string& fn, const hbo_model* models, int32_t S, hbo_cache* const* caches, int max_n, bool* any_bad) {
+// allow_mlp (the _mlp entry points): the two MLP refusals are skipped, everything else stays.
+static int acq_samples_check(hbo_ctx* c, const std::string& fn, const hbo_model* models, int32_t S, hbo_cache* const* caches, int max_n, bool* any_bad,
+                             bool allow_mlp = false) {
   if (int rc = model_family_check(c, fn, models, S, "evaluate the samples with hbo_acq_grad")) return rc;
   for (int s = 0; s < S; ++s) {
     const hbo_model* m = &models[s];
-    if (m->kernel_uses_mlp) return fail(c, HBO_ERR_UNSUPPORTED, fn + "a kernel on an MLP basis is not supported; evaluate the samples with hbo_acq_grad");
-    if (m->mean_id == HBO_MEAN_LINEAR_MLP) return fail(c, HBO_ERR_UNSUPPORTED, fn + "a linear_mlp mean is not supported; evaluate the samples with hbo_acq_grad");
+    if (!allow_mlp && m->kernel_uses_mlp) return fail(c, HBO_ERR_UNSUPPORTED, fn + "a kernel on an MLP basis is not supported; evaluate the samples with hbo_acq_grad");
+    if (!allow_mlp && m->mean_id == HBO_MEAN_LINEAR_MLP) return fail(c, HBO_ERR_UNSUPPORTED, fn + "a linear_mlp mean is not supported; evaluate the samples with hbo_acq_grad");
     const hbo_cache* k = caches[s];
     if (!k || !k->t || k->t->n <= 0) return fail(c, HBO_ERR_UNSUPPORTED, fn + "a sample without observations (the prior branch) is not supported; evaluate it with hbo_acq_grad");
     if (k->t->n > max_n) return fail(c, HBO_ERR_UNSUPPORTED, fn + "a cache has n > " + std::to_string(max_n) + "; evaluate the samples with hbo_acq_grad");
@@ -462,23 +464,30 @@ struct AcqSamplesMode {
   int max_n;               // the largest cache the entry point takes (acq_samples_check)
   bool force_blocked;      // test hook: caches of n <= 128 through the blocked kernels too
   int64_t chunk_queries;   // test hook: > 0 overrides the chunk size
+  bool allow_mlp;          // the _mlp entry points: MLP-basis kernels and linear_mlp means are served (acq_mlp.h)
 };
 int acq_grad_samples(hbo_ctx* c, const AcqSamplesMode& mode, const hbo_model* models, int32_t S, hbo_cache* const* caches, const void* xq,
                      int64_t M, int acq_id, const double* params, const MesReq* mes, const double* add_noise, double scale, void* acq_out,
                      double* grad_out, double* val64_out);
-int acq_maximize(hbo_ctx* c, const char* name, int max_n, const hbo_model* models, int32_t S, hbo_cache* const* caches, const void* x0,
-                 int32_t R, const double* lo, const double* hi, int acq_id, const double* params, const MesReq* mes, const double* add_noise,
-                 double scale, const hbo_acq_opt_opts* opts, double* state, int32_t evals, double* x_out, double* val_out, int32_t* status,
-                 hbo_acq_opt_eval* log);
+int acq_maximize(hbo_ctx* c, const char* name, int max_n, bool allow_mlp, const hbo_model* models, int32_t S, hbo_cache* const* caches,
+                 const void* x0, int32_t R, const double* lo, const double* hi, int acq_id, const double* params, const MesReq* mes,
+                 const double* add_noise, double scale, const hbo_acq_opt_opts* opts, double* state, int32_t evals, double* x_out, double* val_out,
+                 int32_t* status, hbo_acq_opt_eval* log);
 // hbo_acq's posterior pipeline under the MES epilogue (cache.hip); the arguments are checked by the caller (mes.hip: hbo_acq_mes)
 int posterior_mes(hbo_ctx* c, const hbo_model* m, hbo_cache* k, const void* xq, int64_t M, const MesReq& mes, double add_noise, double scale,
                   void* out);
 
 // the records acq_small_kernel and the kernels of acq_blocked.hip read of those pairs (hbo_internal.h: AcqSmallSample) and their
-// per-feature values, hv [S][2 D] (params: null under a MesReq)
+// per-feature values, hv [S][fdim + mdim]: 1 / lengthscale over the kernel's own space, the linear mean's weights over the mean's
+// (acq_vec_widths; without an MLP both are D: [S][2 D]) (params: null under a MesReq)
+struct AcqVecWidths { int fdim, mdim; };
+static AcqVecWidths acq_vec_widths(const hbo_model* m0) {
+  return {feature_dim(m0), needs_mlp(m0) ? mean_feature_dim(m0) : m0->input_dim};
+}
 static void acq_small_pack(AcqSmallSample* hs, double* hv, const hbo_model* models, int32_t S, hbo_cache* const* caches, const double* params,
                            const double* add_noise) {
-  const int D = models[0].input_dim;
+  const AcqVecWidths vw = acq_vec_widths(&models[0]);
+  const size_t stride = (size_t)vw.fdim + vw.mdim;
   ModelDev md;
   for (int s = 0; s < S; ++s) {
     const hbo_cache* k = caches[s]; const TaskHost* t = k->t;
@@ -488,9 +497,38 @@ static void acq_small_pack(AcqSmallSample* hs, double* hv, const hbo_model* mode
     r.F = k->h_desc.F; r.W = t->W; r.alpha = t->svec; r.ld = t->ld; r.n = (int)t->n; r.bad = k->info != INT_MAX;
     r.sv = md.sv; r.inv_sigma2 = 1.0 / (md.dot_sigma * md.dot_sigma); r.bias2 = md.dot_bias * md.dot_bias;
     r.constant = md.constant; r.linear_bias = md.linear_bias; r.param = params ? params[s] : 0.0; r.add_noise = add_noise[s];
-    memcpy(hv + (size_t)s * 2 * D, md.inv_ls, sizeof(double) * D);
-    memcpy(hv + (size_t)s * 2 * D + D, md.lin_w, sizeof(double) * D);
+    memcpy(hv + (size_t)s * stride, md.inv_ls, sizeof(double) * vw.fdim);
+    memcpy(hv + (size_t)s * stride + vw.fdim, md.lin_w, sizeof(double) * vw.mdim);
   }
+}
+// The MLP part of such a call's one staged upload (the _mlp entry points): the S weight sets as models_pack lays them out, then the
+// tables of their device addresses [S][HBO_MAX_MLP_LAYERS], weights and biases.  bytes = 0 without an MLP: the upload is the
+// _blocked entry point's, byte for byte.  acq_mlp_fill writes the host copy `h` for a block that sits at `d_base` (256-byte aligned)
+// and points the kernels' arguments at it.
+struct AcqMlpPack { MlpShape sh; size_t o_w, o_b, bytes; int ftot; };
+static AcqMlpPack acq_mlp_layout(const hbo_model* m0, int S) {
+  AcqMlpPack p = {};
+  p.sh = mlp_shape(m0);
+  if (!p.sh.L) return p;
+  BlockLayout lay;
+  lay.take(models_pack_bytes(p.sh, S));
+  p.o_w = lay.take(sizeof(void*) * (size_t)S * HBO_MAX_MLP_LAYERS);
+  p.o_b = lay.take(sizeof(void*) * (size_t)S * HBO_MAX_MLP_LAYERS);
+  p.bytes = lay.off;
+  for (int l = 0; l < p.sh.L; ++l) p.ftot += p.sh.fout[l];
+  return p;
+}
+static void acq_mlp_fill(const AcqMlpPack& p, char* h, char* d_base, const hbo_model* models, int S, AcqSmallArgs& a) {
+  const hbo_model* m0 = &models[0];
+  const AcqVecWidths vw = acq_vec_widths(m0);
+  a.fdim = vw.fdim; a.mdim = vw.mdim;
+  if (!p.sh.L) return;
+  memset(h, 0, p.bytes);
+  models_pack(h, d_base, models, S, p.sh, reinterpret_cast<void**>(h + p.o_w), reinterpret_cast<void**>(h + p.o_b));
+  a.feat = (m0->kernel_uses_mlp ? 1 : 0) | (m0->mean_id == HBO_MEAN_LINEAR_MLP ? 2 : 0);   // acq_mlp.h: ACQ_FEAT_KERNEL, ACQ_FEAT_MEAN
+  a.L = p.sh.L;
+  for (int l = 0; l < p.sh.L; ++l) a.fout[l] = p.sh.fout[l];
+  a.mlp_w = reinterpret_cast<const void* const*>(d_base + p.o_w); a.mlp_b = reinterpret_cast<const void* const*>(d_base + p.o_b);
 }
 
 // ldv of the blocked kernels' workspace (acq_blocked.hip): the largest n of the caches rounded up to the 128-row block

@@ -451,6 +451,11 @@ struct AcqSmallArgs {
   const double* ystar; int K;                        // max-value entropy search (mes.hip): [S][K] maxima (device); null: acq_id decides.
                                                      // One launch takes one scalar step: the kernels are instantiated for either;
                                                      // K <= HBO_MES_MAX_K = 256, one term per thread of the pair's workgroup
+  // MLP basis (acq_mlp.h; hbo_acq_grad_samples_mlp).  feat = 0: none, nothing below is read and vec is [S][2 D] as above.  Otherwise
+  // bit 0: the kernel, bit 1: the mean reads the last layer, and vec is [S][fdim + mdim]: 1 / lengthscale over the kernel's own
+  // space (fdim = last layer or D), then the linear mean's weights over the mean's (mdim = last layer, D or 0)
+  int feat, fdim, mdim, L; int fout[HBO_MAX_MLP_LAYERS];
+  const void* const* mlp_w; const void* const* mlp_b;   // device tables [S][HBO_MAX_MLP_LAYERS]: weights [in][out], bias (model dtype)
 };
 void launch_acq_small(int dtype, const AcqSmallArgs& a, int S, hipStream_t st);
 // ---- the same for caches of any n >= 1 (acq_blocked.hip): four stream-ordered launches over queries [q0, q0 + mc) of a.M --
@@ -462,6 +467,8 @@ struct AcqBlockedArgs {
   double* k; double* l; double* beta;                // [S][mc][ldv]
   int ldv;
   int64_t q0, mc;
+  double* acts; int ftot;                            // a.feat: every layer's activations of the chunk's queries, [S][mc][ftot = sum of the
+                                                     // layers' widths]; a launch in front of the four writes it (five launches per chunk)
 };
 void launch_acq_blocked(int dtype, const AcqBlockedArgs& b, int S, hipStream_t st);
 // ---- the simulated BO loop on the device (bo_loop.hip: kernels and hbo_bo_simulated) ----

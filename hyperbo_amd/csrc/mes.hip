@@ -53,7 +53,7 @@ extern "C" int hbo_acq_mes(hbo_ctx* c, const hbo_model* m, hbo_cache* k, const v
 
 extern "C" int hbo_mes_grad_samples(hbo_ctx* c, const hbo_model* models, int32_t S, hbo_cache* const* caches, const void* xq, int64_t M,
                                     const double* ystar, int32_t K, const double* add_noise, double scale, void* acq_out, double* grad_out) {
-  const AcqSamplesMode mode = {"hbo_mes_grad_samples", INT_MAX, false, 0};
+  const AcqSamplesMode mode = {"hbo_mes_grad_samples", INT_MAX, false, 0, false};
   const MesReq mes = {ystar, K};
   return acq_grad_samples(c, mode, models, S, caches, xq, M, 0, nullptr, &mes, add_noise, scale, acq_out, grad_out, nullptr);
 }
@@ -64,7 +64,7 @@ extern "C" int hbo_probe_mes_grad_samples64(hbo_ctx* c, const hbo_model* models,
                                             int32_t force_blocked, int64_t chunk_queries, double* val64_out) {
   if (!val64_out) return fail(c, HBO_ERR_ARG, "hbo_probe_mes_grad_samples64: val64_out is null");
   if (chunk_queries < 0) return fail(c, HBO_ERR_ARG, "hbo_probe_mes_grad_samples64: chunk_queries < 0");
-  const AcqSamplesMode mode = {"hbo_mes_grad_samples", INT_MAX, force_blocked != 0, chunk_queries};
+  const AcqSamplesMode mode = {"hbo_mes_grad_samples", INT_MAX, force_blocked != 0, chunk_queries, false};
   const MesReq mes = {ystar, K};
   return acq_grad_samples(c, mode, models, S, caches, xq, M, 0, nullptr, &mes, add_noise, scale, acq_out, grad_out, val64_out);
 }
@@ -74,6 +74,6 @@ extern "C" int hbo_mes_maximize(hbo_ctx* c, const hbo_model* models, int32_t S, 
                                 const hbo_acq_opt_opts* opts, double* state, int32_t evals, double* x_out, double* val_out, int32_t* status,
                                 hbo_acq_opt_eval* log) {
   const MesReq mes = {ystar, K};
-  return acq_maximize(c, "hbo_mes_maximize", INT_MAX, models, S, caches, x0, R, lo, hi, 0, nullptr, &mes, add_noise, scale, opts, state, evals,
+  return acq_maximize(c, "hbo_mes_maximize", INT_MAX, false, models, S, caches, x0, R, lo, hi, 0, nullptr, &mes, add_noise, scale, opts, state, evals,
                       x_out, val_out, status, log);
 }

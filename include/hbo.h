@@ -358,6 +358,39 @@ int hbo_acq_maximize_blocked(hbo_ctx* ctx, const hbo_model* models, int32_t S, h
                              const hbo_acq_opt_opts* opts, double* state, int32_t evals, double* x_out, double* val_out, int32_t* status,
                              hbo_acq_opt_eval* log);
 
+/* ---- hbo_acq_grad_samples_blocked with MLP-basis kernels (kernel_uses_mlp) and the linear_mlp mean served: same arguments, same
+ *      checks (before any device work), same return codes and the same NaN rows / HBO_NOT_PD -- minus the refusals of kernel_uses_mlp
+ *      and of a linear_mlp mean.  All pairings are taken: MLP kernel + linear_mlp, MLP kernel + linear (raw) / constant / zero mean, raw
+ *      kernel + linear_mlp mean.  xq [M, input_dim] is the RAW input and grad_out [S, M, input_dim] is d value / d raw x (fp64): the
+ *      workgroup that owns a (sample, query) pair runs the query's forward pass through sample s's own weights (all layers in fp64
+ *      LDS), works in the kernel's own space, takes the mean in the mean's own space and ends with the backward pass
+ *      (csrc/acq_mlp.h).  Weights and biases are read in the model dtype; every product and sum is fp64.  The S weight sets ride up
+ *      in the call's one staged upload: still one upload, one copy back, one synchronisation.
+ *      Launches: ONE when every cache has n <= 128; otherwise FIVE per chunk of queries -- a forward launch, grid (chunk, S), writes
+ *      every layer's activations into a further fp64 plane [S, chunk, sum of the layer widths] of the blocked workspace, then the four
+ *      of hbo_acq_grad_samples_blocked, whose first reads the query in the kernel's space from that plane and whose last reads the
+ *      activations back; the chunk keeps the whole workspace under 256 MiB.
+ *      Determinism, as the siblings promise it: no atomics, every sum in an order fixed by the cache's n, the layers' shapes and
+ *      input_dim alone; identical calls are bit-identical and a row does not depend on which samples or queries share the call, its
+ *      place among them, the other caches' sizes or the chunking.
+ *      For a model family WITHOUT any MLP the call IS hbo_acq_grad_samples_blocked: same launches, same bytes of every output.
+ *      HBO_ERR_UNSUPPORTED (before any device work, with the advice to evaluate the samples with hbo_acq_grad): a null or empty cache
+ *      (the prior branch) and input-warped (Kumaraswamy) models.  HBO_ERR_ARG also: samples whose MLP architectures differ. */
+int hbo_acq_grad_samples_mlp(hbo_ctx* ctx, const hbo_model* models, int32_t S, hbo_cache* const* caches, const void* xq, int64_t M,
+                             int acq_id, const double* params, const double* add_noise, double scale, void* acq_out, double* grad_out);
+
+/* ---- hbo_acq_maximize_blocked with those models served: same arguments, checks, state and log format (hbo_acq_opt_state_doubles
+ *      is unchanged), return codes and determinism (identical calls, a start alone or among others, a run cut into calls: the same
+ *      bits).  The evaluation of a round is that of hbo_acq_grad_samples_mlp over the R pending points; the control kernel is the same
+ *      and sees raw points and raw gradients.  Launches per round: two for n <= 128 (evaluation, control), six otherwise (forward,
+ *      the four, control), without a host wait.  The evaluation workspace of the blocked route is S * R * (3 npad + sum of the layer
+ *      widths) doubles (HBO_ERR_UNSUPPORTED beyond half of the device memory).  Refusals: those of hbo_acq_grad_samples_mlp.  For a
+ *      family without any MLP the call IS hbo_acq_maximize_blocked: state, log, x_out, val_out and status to the bit. */
+int hbo_acq_maximize_mlp(hbo_ctx* ctx, const hbo_model* models, int32_t S, hbo_cache* const* caches, const void* x0, int32_t R,
+                         const double* lo, const double* hi, int acq_id, const double* params, const double* add_noise, double scale,
+                         const hbo_acq_opt_opts* opts, double* state, int32_t evals, double* x_out, double* val_out, int32_t* status,
+                         hbo_acq_opt_eval* log);
+
 /* ---- max-value entropy search (MES, Wang & Jegelka 2017; no counterpart in the reference): the information a query carries about the
  *      maximum of the objective, from K sampled maxima y*_1..y*_K (hbo_sample_paths / hbo_paths_maximize draw them).  For posterior mean
  *      mu and variance var at a query, with pdf and cdf of the standard normal:

@@ -101,6 +101,13 @@ int hbo_probe_acq_grad_samples64(hbo_ctx* ctx, const hbo_model* models, int32_t 
 int hbo_probe_acq_grad_samples_blocked64(hbo_ctx* ctx, const hbo_model* models, int32_t S, hbo_cache* const* caches, const void* xq,
                                          int64_t M, int acq_id, const double* params, const double* add_noise, double scale, void* acq_out,
                                          double* grad_out, int32_t force_blocked, int64_t chunk_queries, double* val64_out);
+/* TEST HOOK: hbo_acq_grad_samples_mlp (same checks, same launches, same results) with the three extras of the hook above, same meaning:
+ * val64_out [S, M], the fp64 values the control kernel of hbo_acq_maximize_mlp reads; force_blocked != 0, the five launches of the
+ * blocked route (forward pass, then the four) for caches of n <= 128 too; chunk_queries > 0, the queries per pass (< 0: HBO_ERR_ARG).
+ * Neither changes a bit of a row that the blocked kernels computed.  Refusals: those of hbo_acq_grad_samples_mlp. */
+int hbo_probe_acq_grad_samples_mlp64(hbo_ctx* ctx, const hbo_model* models, int32_t S, hbo_cache* const* caches, const void* xq,
+                                     int64_t M, int acq_id, const double* params, const double* add_noise, double scale, void* acq_out,
+                                     double* grad_out, int32_t force_blocked, int64_t chunk_queries, double* val64_out);
 /* TEST HOOK: hbo_mes_grad_samples (same checks, same launches, same results) with the three extras of the hook above: val64_out [S, M],
  * the fp64 values the control kernel of hbo_mes_maximize reads; force_blocked, the blocked kernels for caches of n <= 128 too;
  * chunk_queries.  Neither changes a bit of a row that the blocked kernels computed: every sum runs in a fixed order, without atomics. */
