@@ -185,6 +185,14 @@ SIGNATURES = {
                                                C.POINTER(C.c_double)]),   # hbo_tune.h (test hook)
     'hbo_mes_maximize': (C.c_int, [_P, _P, C.c_int32, C.POINTER(_P), _P, C.c_int32, _P, _P, C.POINTER(C.c_double), C.c_int32,
                                    C.POINTER(C.c_double), C.c_double, C.POINTER(AcqOptOpts), _P, C.c_int32, _P, _P, _P, _P]),
+    'hbo_acq_logei': (C.c_int, [_P, C.POINTER(Model), _P, _P, C.c_int64, C.c_double, C.c_double, C.c_double, _P]),
+    'hbo_logei_grad_samples': (C.c_int, [_P, _P, C.c_int32, C.POINTER(_P), _P, C.c_int64, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                         C.c_double, _P, C.POINTER(C.c_double)]),
+    'hbo_probe_logei_grad_samples64': (C.c_int, [_P, _P, C.c_int32, C.POINTER(_P), _P, C.c_int64, C.POINTER(C.c_double),
+                                                 C.POINTER(C.c_double), C.c_double, _P, C.POINTER(C.c_double), C.c_int32, C.c_int64,
+                                                 C.POINTER(C.c_double)]),   # hbo_tune.h (test hook)
+    'hbo_logei_maximize': (C.c_int, [_P, _P, C.c_int32, C.POINTER(_P), _P, C.c_int32, _P, _P, C.POINTER(C.c_double),
+                                     C.POINTER(C.c_double), C.c_double, C.POINTER(AcqOptOpts), _P, C.c_int32, _P, _P, _P, _P]),
     'hbo_probe_acq_opt_ctl': (C.c_int, [_P, C.c_int32, C.c_int, C.POINTER(AcqOptOpts), _P, _P, _P, _P, _P, C.c_int32, _P, _P,
                                         C.POINTER(AcqOptEval), C.POINTER(C.c_int32)]),   # include/hbo_tune.h (test hook)
     'hbo_bo_simulated': (C.c_int, [_P, _P, C.POINTER(BoRun), C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_double), _P, _P,

@@ -353,10 +353,11 @@ def _mes_args(mes, s_count):
   return mes.ctypes.data_as(nat.C.POINTER(nat.C.c_double)), mes.shape[1]
 
 
-def _device_maximize(built, handles, noises, x0, lo, hi, acq_id, acfun_param, scale, opts, want_log, blocked=False, mes=None, entry=None):
+def _device_maximize(built, handles, noises, x0, lo, hi, acq_id, acfun_param, scale, opts, want_log, blocked=False, mes=None, entry=None,
+                     logei=False):
   """hbo_acq_maximize (blocked: hbo_acq_maximize_blocked, caches of any size; mes, [S, K] maxima: hbo_mes_maximize) in segments of
   opts['segment'] evaluations until no start is RUNNING or opts['max_evals'] are spent.  entry: another sibling by name
-  (hbo_acq_maximize_mlp).
+  (hbo_acq_maximize_mlp).  logei: hbo_logei_maximize, with acfun_param as every sample's target and no acq_id.
   x0 [R, D] in the model dtype; lo / hi [D] float64 or None.  Returns (x [R, D], values [R], status [R], evaluations [R], log or None)."""
   entry = getattr(nat.lib(), entry) if entry else (nat.lib().hbo_acq_maximize_blocked if blocked else nat.lib().hbo_acq_maximize)
   s_count, (r_count, d) = len(built), x0.shape
@@ -365,6 +366,8 @@ def _device_maximize(built, handles, noises, x0, lo, hi, acq_id, acfun_param, sc
   what = (int(acq_id), prm)
   if mes is not None:
     entry, what = nat.lib().hbo_mes_maximize, _mes_args(mes, s_count)
+  if logei:
+    entry, what = nat.lib().hbo_logei_maximize, (prm,)
   o = nat.AcqOptOpts(*[opts[k] for k in ('memory', 'ls_steps', 'max_iters', 'c1', 'tau', 'pgtol', 'ftol')])
   ns = nat.lib().hbo_acq_opt_state_doubles(d, o.memory)
   state = np.zeros((r_count, max(ns, 1)), dtype=np.float64)
@@ -387,10 +390,11 @@ def _device_maximize(built, handles, noises, x0, lo, hi, acq_id, acfun_param, sc
   return x, val, status, n_evals, (np.concatenate(logs) if want_log else None)
 
 
-def _fused_value_and_grad(built, handles, noises, xq, acq_id, acfun_param, scale, blocked=False, mes=None, entry=None):
+def _fused_value_and_grad(built, handles, noises, xq, acq_id, acfun_param, scale, blocked=False, mes=None, entry=None, logei=False):
   """((S, M, 1) values in the model dtype, (S, M, D) gradients in float64) of S models over their finished factors: one
   hbo_acq_grad_samples call -- one upload, one launch, one copy back (blocked: hbo_acq_grad_samples_blocked, caches of any size;
-  mes, [S, K] maxima: hbo_mes_grad_samples; entry: another sibling by name -- hbo_acq_grad_samples_mlp)."""
+  mes, [S, K] maxima: hbo_mes_grad_samples; entry: another sibling by name -- hbo_acq_grad_samples_mlp; logei:
+  hbo_logei_grad_samples, with acfun_param as every sample's target and no acq_id)."""
   entry = getattr(nat.lib(), entry) if entry else (nat.lib().hbo_acq_grad_samples_blocked if blocked else nat.lib().hbo_acq_grad_samples)
   s_count, (nq, d) = len(built), xq.shape
   ctx = handles[0].ctx
@@ -398,6 +402,8 @@ def _fused_value_and_grad(built, handles, noises, xq, acq_id, acfun_param, scale
   what = (int(acq_id), prm)
   if mes is not None:
     entry, what = nat.lib().hbo_mes_grad_samples, _mes_args(mes, s_count)
+  if logei:
+    entry, what = nat.lib().hbo_logei_grad_samples, (prm,)
   out = np.empty((s_count, nq, 1), dtype=xq.dtype)
   g = np.empty((s_count, nq, d), dtype=np.float64)
   ctx.check(entry(ctx.handle, structs, s_count, caches, nat.ptr(xq), nq, *what, nse, float(scale),
@@ -741,3 +747,186 @@ class MaxValueEntropySearch:
 
 
 max_value_entropy_search = mes = MaxValueEntropySearch()
+
+
+# ---- log expected improvement (Ament et al. 2023; include/hbo.h has the formulas, csrc/logei.hip the entry points) ------------------
+LOGEI_SERIES_U = 256.0   # csrc/kernfun.h: beyond it the asymptotic series replaces 1 + u m
+
+
+def logei_terms_host(u):
+  """(log h, cdf / h, pdf / h) at u, h = pdf + u cdf: the float64 restatement of csrc/kernfun.h: logei_terms (literal for u > -1,
+  erfcx down to -LOGEI_SERIES_U, the asymptotic series beyond)."""
+  from scipy.special import erfc, erfcx
+  u = np.asarray(u, dtype=np.float64)
+  logh, cdf_h, pdf_h = (np.full(u.shape, np.nan) for _ in range(3))
+  with np.errstate(all='ignore'):
+    hi, far = u > -1.0, u < -LOGEI_SERIES_U
+    mid = ~hi & ~far & ~np.isnan(u)
+    x = u[hi]
+    p, c = np.exp(-0.5 * x * x) * 0.3989422804014327, 0.5 * erfc(-x * 0.7071067811865476)
+    h = p + x * c
+    logh[hi], cdf_h[hi], pdf_h[hi] = np.log(h), c / h, p / h
+    x = u[mid]
+    m = 1.2533141373155003 * erfcx(-x * 0.7071067811865476)
+    w = 1.0 + x * m
+    logh[mid], cdf_h[mid], pdf_h[mid] = -0.5 * x * x - 0.9189385332046727 + np.log(w), m / w, 1.0 / w
+    x = u[far]
+    i2 = 1.0 / (x * x)
+    ws = 1.0 + i2 * (-3.0 + i2 * (15.0 - 105.0 * i2))
+    ms = 1.0 + i2 * (-1.0 + i2 * (3.0 - 15.0 * i2))
+    logh[far], cdf_h[far], pdf_h[far] = -0.5 * x * x - 0.9189385332046727 + (np.log(ws) - 2.0 * np.log(-x)), -x * (ms / ws), x * x / ws
+  return logh, cdf_h, pdf_h
+
+
+def log_expected_improvement_sub(mu, std, target):
+  """log EI in the stable form, float64, for the host route: log std + log h((mu - target) / std); std <= 0: log(mu - target) above
+  the target and -inf at or below it; a NaN std stays NaN."""
+  mu, std = np.broadcast_arrays(np.asarray(mu, dtype=np.float64), np.asarray(std, dtype=np.float64))
+  d = mu - float(target)
+  with np.errstate(all='ignore'):
+    flat = std <= 0.0
+    safe = np.where(flat, 1.0, std)
+    val = np.log(safe) + logei_terms_host(d / safe)[0]
+    return np.where(flat, np.where(d > 0.0, np.log(np.where(d > 0.0, d, 1.0)), np.where(d <= 0.0, -np.inf, np.nan)), val)
+
+
+def logei_combine(vals, grads=None):
+  """The acquisition over S parameter samples from per-sample LogEI values [S, ...] (and gradients [S, ..., D]): the log of the MEAN
+  of the samples' EI, m + log(sum_s exp(v_s - m) / S) with m = max_s v_s, and the gradient sum_s w_s g_s / sum_s w_s; float64 sums in
+  sample order.  m = -inf: -inf and gradient 0; any NaN row: NaN.  S = 1: the input to the bit.  Returns value or (value, grad)."""
+  v = np.asarray(vals, dtype=np.float64)
+  s_count = v.shape[0]
+  with np.errstate(all='ignore'):
+    nan = np.isnan(v).any(axis=0)
+    m = np.max(np.where(np.isnan(v), -np.inf, v), axis=0)
+    dead = np.isneginf(m)
+    ms = np.where(dead, 0.0, m)
+    sw = np.zeros(v.shape[1:])
+    for s in range(s_count):
+      sw = sw + np.exp(v[s] - ms)
+    val = np.where(nan, np.nan, np.where(dead, -np.inf, m + np.log(sw / s_count)))
+    if grads is None:
+      return val
+    g = np.asarray(grads, dtype=np.float64)
+    sg = np.zeros(g.shape[1:])
+    for s in range(s_count):
+      sg = sg + np.exp(v[s] - ms)[..., None] * g[s]
+    grad = np.where(nan[..., None], np.nan, np.where(dead[..., None], 0.0, sg / np.where(dead, 1.0, sw)[..., None]))
+  return val, grad
+
+
+class LogExpectedImprovement:
+  """Log expected improvement: log EI with EI's maximiser, finite and with a usable gradient where EI underflows.  Called, it
+  scores a pool (hbo_acq_logei; an HGP: one call per sample cache, combined by logei_combine); value_and_grad and maximize go through
+  hbo_logei_grad_samples and hbo_logei_maximize over the cached factors -- any number of observations, MLP bases included, no opt-in
+  key.  Without observations (the prior branch) the pool values still come (GP: the device's prior branch; HGP: the host route,
+  log_expected_improvement_sub), and value_and_grad and maximize raise HboError(HBO_ERR_UNSUPPORTED), as they do for input-warped
+  (Kumaraswamy) kernels; no fall-back.  The target is EI's: acfun_callback, by default the largest observed y."""
+  __name__ = 'log_ei'
+
+  def _hgp_setup(self, model, sub_dataset_key, what, all_kept=True):
+    """(samples, dtype, built, noises, handles, scale) of an HGP with observations; all_kept: its S factors must all fit the device
+    budget (the gradient and the maximiser take them in one call)."""
+    if getattr(model.cov_func, 'uses_kumar', False):
+      raise nat.HboError(nat.HBO_ERR_UNSUPPORTED, f'log_ei.{what}: HGP acquisition over a Kumaraswamy kernel is not supported')
+    if not model.has_observations(sub_dataset_key):
+      raise nat.HboError(nat.HBO_ERR_UNSUPPORTED, f'log_ei.{what}: the sub-dataset has no observations (the prior branch)')
+    samples = model.get_model_params_samples()
+    sd = model.dataset[sub_dataset_key]
+    dtype = _model.infer_dtype(sd.x, sd.y)
+    built, noises = _sample_models(model, samples, dtype)
+    handles = _hgp_sample_caches(model, sub_dataset_key, samples, dtype)
+    if all_kept and len(handles) < len(samples):
+      raise nat.HboError(nat.HBO_ERR_UNSUPPORTED,
+                         f'log_ei.{what}: only {len(handles)} of the {len(samples)} per-sample factors fit the device budget')
+    _, scale = model.predict_noise_and_scale(True, True)
+    return samples, dtype, built, noises, handles, scale
+
+  def __call__(self, *, model, sub_dataset_key, x_queries, acfun_callback=None):
+    """[M, 1] LogEI values in the model dtype."""
+    x_queries = np.asarray(x_queries)
+    target = float((acfun_callback or ei_callback_default)(model, sub_dataset_key))
+    if isinstance(model, gp.HGP):
+      device = model.has_observations(sub_dataset_key) and x_queries.shape[0] > 0 and not getattr(model.cov_func, 'uses_kumar', False)
+      if not device:   # the host route, as for ei: predict per sample, the stable form in NumPy, the combination
+        predicts = model.predict(x_queries, sub_dataset_key=sub_dataset_key, full_cov=False, with_noise=True)
+        vals = [log_expected_improvement_sub(mu, np.sqrt(var), target) for mu, var in predicts]
+        return logei_combine(vals).astype(np.asarray(predicts[0][0]).dtype)
+      from hyperbo_amd.basics import linalg
+      samples, dtype, built, noises, handles, scale = self._hgp_setup(model, sub_dataset_key, '__call__', all_kept=False)
+      xq = np.ascontiguousarray(x_queries, dtype=dtype)
+      outs = np.empty((len(samples), xq.shape[0], 1), dtype=dtype)
+      sd = model.dataset[sub_dataset_key]
+      for i, (bm, noise, out) in enumerate(zip(built, noises, outs)):
+        kept = i < len(handles)    # (samples beyond the cache budget: factorised, used and released on the spot, as for ei's gradient)
+        h = handles[i] if kept else linalg.factor(model.mean_func, model.cov_func, defs.GPParams(config=model.params.config, model=samples[i]),
+                                                  sd.x, sd.y, model.warp_func)
+        try:
+          h.ctx.check(nat.lib().hbo_acq_logei(h.ctx.handle, bm.ref(), h.handle, nat.ptr(xq), xq.shape[0], target, float(noise), float(scale),
+                                              nat.ptr(out)))
+        finally:
+          if not kept:
+            h.close()
+      model.update_model_params(samples[-1])   # as every HGP path here leaves it (gp.py:674-678)
+      return logei_combine(outs).astype(dtype)
+    handle, xq, bm, add_noise, scale = _single_model(model, sub_dataset_key, x_queries)
+    out = np.empty((xq.shape[0], 1), dtype=xq.dtype)
+    if bm is None:
+      return out
+    ctx = handle.ctx if handle is not None else nat.default_context()
+    ctx.check(nat.lib().hbo_acq_logei(ctx.handle, bm.ref(), handle.handle if handle is not None else None, nat.ptr(xq), xq.shape[0],
+                                      target, float(add_noise), float(scale), nat.ptr(out)))
+    return out
+
+  def _setup(self, model, sub_dataset_key, what, x_queries=None):
+    """(dtype, built, noises, handles, scale, x_queries in the model dtype, samples or None) for the gradient entry points."""
+    if isinstance(model, gp.HGP):
+      samples, dtype, built, noises, handles, scale = self._hgp_setup(model, sub_dataset_key, what)
+      xq = None if x_queries is None else np.ascontiguousarray(x_queries, dtype=dtype)
+      return dtype, built, noises, handles, scale, xq, samples
+    if not model.has_observations(sub_dataset_key):
+      raise nat.HboError(nat.HBO_ERR_UNSUPPORTED, f'log_ei.{what}: the sub-dataset has no observations (the prior branch)')
+    handle, xq, bm, add_noise, scale = _single_model(model, sub_dataset_key, x_queries)
+    return handle.dtype, [bm], [add_noise], [handle], scale, xq, None
+
+  def value_and_grad(self, *, model, sub_dataset_key, x_queries, acfun_callback=None):
+    """(values [M, 1] in the model dtype, d value_q / d x_queries[q] [M, D] float64): hbo_logei_grad_samples, an HGP's per-sample rows
+    combined by logei_combine."""
+    target = float((acfun_callback or ei_callback_default)(model, sub_dataset_key))
+    dtype, built, noises, handles, scale, xq, samples = self._setup(model, sub_dataset_key, 'value_and_grad', np.asarray(x_queries))
+    if xq.shape[0] == 0:
+      return np.empty((0, 1), dtype=dtype), np.zeros((0, model.input_dim))
+    outs, gs = _fused_value_and_grad(built, handles, noises, xq, 0, target, scale, logei=True)
+    if samples is None:
+      return outs[0], gs[0]
+    model.update_model_params(samples[-1])
+    val, grad = logei_combine(outs[:, :, 0], gs)
+    return val[:, None].astype(dtype), grad
+
+  def maximize(self, *, model, sub_dataset_key, x_init, bounds=None, acfun_callback=None, opts=None):
+    """Maximises LogEI over a box on the device (hbo_logei_maximize) from the starts x_init [D] or [R, D].  bounds, opts and the return
+    value (x_best [D] float64, value_best, info) are those of the `maximize` of the EI / PI / UCB objects."""
+    o = dict(ACQ_OPT_DEFAULTS, segment=ACQ_OPT_SEGMENT, max_evals=ACQ_OPT_MAX_EVALS, log=False)
+    o.update(opts or {})
+    x_init = np.atleast_2d(np.asarray(x_init, dtype=np.float64))
+    target = float((acfun_callback or ei_callback_default)(model, sub_dataset_key))
+    dtype, built, noises, handles, scale, _, samples = self._setup(model, sub_dataset_key, 'maximize')
+    lo = hi = None
+    if bounds is not None:
+      b = np.asarray(bounds, dtype=np.float64).reshape(model.input_dim, 2)
+      lo, hi = np.ascontiguousarray(b[:, 0]), np.ascontiguousarray(b[:, 1])
+    x, val, status, n_evals, log = _device_maximize(built, handles, noises, np.ascontiguousarray(x_init, dtype=dtype), lo, hi, 0, target,
+                                                    scale, o, bool(o['log']), logei=True)
+    if samples is not None:
+      model.update_model_params(samples[-1])
+    info = {'x': x, 'value': val, 'status': status, 'evals': n_evals}
+    if o['log']:
+      info['log'] = log
+    finite = np.isfinite(val)
+    if not finite.any():
+      return x_init[0].copy(), float('nan'), info
+    best = int(np.argmax(np.where(finite, val, -np.inf)))
+    return x[best].copy(), float(val[best]), info
+
+
+log_expected_improvement = log_ei = LogExpectedImprovement()

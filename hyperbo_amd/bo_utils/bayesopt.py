@@ -108,6 +108,8 @@ def _bo_on_device_unmet(model, sub_dataset_key, queried_sub_dataset, ac_func):
     return "config['retrain'] > 0 re-trains the model between iterations"
   if getattr(ac_func, '__name__', '') in ('rand', 'random_search'):
     return 'random search draws its selections on the host'
+  if ac_func is acfun.log_ei:
+    return "log_ei is outside the device loop's registry (hbo_bo_simulated scores with EI, PI or UCB)"
   if ac_func not in acfun._BO_DEVICE:
     return f'ac_func {ac_func!r} is not one of the native acquisition functions of bo_utils/acfun.py'
   if getattr(model.cov_func, 'uses_kumar', False):

@@ -175,9 +175,9 @@ __global__ __launch_bounds__(256) void acq_blk_trans_kernel(AcqBlockedArgs b) {
 }
 
 // ---- 4: one workgroup per (sample, query): the sums over the rows, the scalar step, the gradient
-//         (MES: the scalar step is mes_scalars_block over the sample's K maxima, as in acq_small_kernel)
+//         (STEP: the scalar step, as in acq_small_kernel -- the registry's, the MES step over the sample's K maxima, or the LogEI step)
 //         (FEAT: D below is the width of the kernel's space; the activations come back from the plane and acq_mlp_tail ends the pair)
-template <typename T, bool MES, int FEAT>
+template <typename T, int STEP, int FEAT>
 __global__ __launch_bounds__(256) void acq_blk_finish_kernel(AcqBlockedArgs b) {
   __shared__ double s_xq[HBO_MAX_FEATURE_DIM], s_il[HBO_MAX_FEATURE_DIM];
   __shared__ double s_w[256];
@@ -241,7 +241,7 @@ __global__ __launch_bounds__(256) void acq_blk_finish_kernel(AcqBlockedArgs b) {
       mean = sm.linear_bias + block_sum(tid < a.mdim ? s_act[(a.L - 1) * HBO_MAX_FEATURE_DIM + tid] * vec[D + tid] : 0.0, sred);
   }
   double amu, avar;
-  if constexpr (MES) {
+  if constexpr (STEP == ACQ_STEP_MES) {
     __shared__ double s_mes[3 * HBO_MES_MAX_K], s_mes_sum[3];
     const AcqScalars sc = mes_scalars_block(ka + mean, kqq - ll, sm.add_noise, a.scale, a.ystar + (int64_t)s * a.K, a.K, s_mes, s_mes_sum);
     if (tid == 0) {
@@ -251,8 +251,9 @@ __global__ __launch_bounds__(256) void acq_blk_finish_kernel(AcqBlockedArgs b) {
     __syncthreads();
     amu = sc.amu; avar = sc.avar;   // (every thread holds them: nothing is handed over through LDS)
   } else {
-    if (tid == 0) {
-      const AcqScalars sc = acq_scalars(a.acq_id, ka + mean, kqq - ll, sm.add_noise, a.scale, sm.param);
+    if (tid == 0) {   // (STEP is a constant: one of the two is compiled)
+      const AcqScalars sc = STEP == ACQ_STEP_LOGEI ? logei_scalars(ka + mean, kqq - ll, sm.add_noise, a.scale, sm.param)
+                                                   : acq_scalars(a.acq_id, ka + mean, kqq - ll, sm.add_noise, a.scale, sm.param);
       s_amu = sc.amu; s_avar = sc.avar;
       *acq = (T)sc.val;
       if (a.val64_out) a.val64_out[(int64_t)s * a.M + q] = sc.val;
@@ -322,9 +323,10 @@ void launch_blocked_f(const AcqBlockedArgs& b, int S, hipStream_t st) {
   hipLaunchKernelGGL((acq_blk_fwd_kernel<T, BLK_MC>), dim3(b.ldv / 16, grp, S), dim3(256), 0, st, b);
   hipLaunchKernelGGL((acq_blk_trans_kernel<T, BLK_MC>), dim3(b.ldv / 64, grp, S), dim3(256), 0, st, b);
   if constexpr (FEAT == 0) {
-    if (b.a.ystar) { hipLaunchKernelGGL((acq_blk_finish_kernel<T, true, 0>), dim3(mc, S), dim3(256), 0, st, b); return; }
+    if (b.a.ystar) { hipLaunchKernelGGL((acq_blk_finish_kernel<T, ACQ_STEP_MES, 0>), dim3(mc, S), dim3(256), 0, st, b); return; }
   }
-  hipLaunchKernelGGL((acq_blk_finish_kernel<T, false, FEAT>), dim3(mc, S), dim3(256), 0, st, b);
+  if (b.a.logei) { hipLaunchKernelGGL((acq_blk_finish_kernel<T, ACQ_STEP_LOGEI, FEAT>), dim3(mc, S), dim3(256), 0, st, b); return; }
+  hipLaunchKernelGGL((acq_blk_finish_kernel<T, ACQ_STEP_REGISTRY, FEAT>), dim3(mc, S), dim3(256), 0, st, b);
 }
 template <typename T>
 void launch_blocked_t(const AcqBlockedArgs& b, int S, hipStream_t st) {

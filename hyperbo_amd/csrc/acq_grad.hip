@@ -118,7 +118,8 @@ constexpr size_t ACQ_BLOCKED_WS_BYTES = (size_t)256 << 20;
 constexpr int64_t ACQ_BLOCKED_MAX_CHUNK = 65535;   // grid.y of the first launch
 }  // namespace
 // (api_internal.h: AcqSamplesMode.  mes -- hbo_mes_grad_samples, mes.hip: the S x K maxima ride up behind the per-feature values and the
-//  kernels take the MES scalar step; acq_id and params are then not read)
+//  kernels take the MES scalar step; acq_id and params are then not read.  mode.logei -- hbo_logei_grad_samples, logei.hip: params holds
+//  the S targets and the kernels take the LogEI scalar step; acq_id is not read)
 int acq_grad_samples(hbo_ctx* c, const AcqSamplesMode& mode, const hbo_model* models, int32_t S, hbo_cache* const* caches, const void* xq,
                      int64_t M, int acq_id, const double* params, const MesReq* mes, const double* add_noise, double scale, void* acq_out,
                      double* grad_out, double* val64_out) {
@@ -126,6 +127,7 @@ int acq_grad_samples(hbo_ctx* c, const AcqSamplesMode& mode, const hbo_model* mo
   if (!models || !caches || !xq || (mes ? !mes->ystar : !params) || !add_noise || !acq_out || !grad_out) return fail(c, HBO_ERR_ARG, fn + "null argument");
   if (S <= 0 || S > 4096) return fail(c, HBO_ERR_ARG, fn + "1 <= S <= 4096");
   if (mes) { if (int rc = mes_check(c, fn, *mes, S)) return rc; }
+  else if (mode.logei) { if (int rc = logei_check(c, fn, params, S)) return rc; }
   else if (acq_id < 0 || acq_id > HBO_ACQ_UCB) return fail(c, HBO_ERR_ARG, fn + "bad acq_id");
   if (!c) return fail(c, HBO_ERR_ARG, fn + "ctx is null");
   if (M < 0) return fail(c, HBO_ERR_ARG, fn + "M < 0");
@@ -177,6 +179,7 @@ int acq_grad_samples(hbo_ctx* c, const AcqSamplesMode& mode, const hbo_model* mo
   a.grad_out = reinterpret_cast<double*>(d_out); a.acq_out = d_out + grad_b;
   if (val64_out) a.val64_out = reinterpret_cast<double*>(d_out + v64_o);
   if (mes) { a.ystar = reinterpret_cast<const double*>(d_in + smp_b + hv_b); a.K = mes->K; }
+  a.logei = mode.logei;
   if (!blocked) launch_acq_small(dtype, a, S, st);
   else {
     AcqBlockedArgs b = {};

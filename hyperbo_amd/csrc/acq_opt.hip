@@ -15,7 +15,8 @@ enum { ACQ_OPT_THREADS = 256 };
 // already holds that rounded value).  The start's state is staged in LDS for the step -- its dot products are chains of dependent
 // reads -- and written back whole.  A start that has stopped logs IDLE and leaves its pending point alone.
 // Dynamic LDS: [ns doubles: the state][HBO_LBFGS_PARTIALS doubles: the scratch of the sums].
-template <typename T>
+// REDUCE (acq_opt_ctl.h): how the S per-sample results become f -- the mean, or (hbo_logei_maximize) the log of the mean of the exponentials.
+template <typename T, int REDUCE>
 __global__ __launch_bounds__(ACQ_OPT_THREADS) void acq_opt_ctl_kernel(AcqOptArgs a, int slot) {
   extern __shared__ double acq_opt_lds[];
   double* state = acq_opt_lds;
@@ -26,7 +27,7 @@ __global__ __launch_bounds__(ACQ_OPT_THREADS) void acq_opt_ctl_kernel(AcqOptArgs
   for (int64_t i = tid; i < a.ns; i += nthr) state[i] = gstate[i];
   __syncthreads();
   hbo_acq_opt_eval_ctl ev;
-  hbo_acq_opt_ctl_step(state, D, a.o, a.lo, a.hi, sizeof(T) == 4, a.vals + r, a.R, a.grads + r * D, (int64_t)a.R * D, a.S, tid, nthr, scratch, &ev);
+  hbo_acq_opt_ctl_step_t<REDUCE>(state, D, a.o, a.lo, a.hi, sizeof(T) == 4, a.vals + r, a.R, a.grads + r * D, (int64_t)a.R * D, a.S, tid, nthr, scratch, &ev);
   if (tid == 0 && a.log) a.log[(int64_t)slot * a.R + r] = ev;
   if (ev.kind == HBO_ACQ_OPT_CTL_IDLE) return;   // (uniform; nothing of the state has changed)
   for (int64_t i = tid; i < a.ns; i += nthr) gstate[i] = state[i];
@@ -86,8 +87,15 @@ bool acq_opt_in_box(const double* x, const double* lo, const double* hi, int D) 
   return true;
 }
 void launch_acq_opt_ctl(int dtype, const AcqOptArgs& a, int slot, hipStream_t st) {
-  if (dtype == HBO_F64) hipLaunchKernelGGL((acq_opt_ctl_kernel<double>), dim3(a.R), dim3(ACQ_OPT_THREADS), acq_opt_lds_bytes(a.ns), st, a, slot);
-  else hipLaunchKernelGGL((acq_opt_ctl_kernel<float>), dim3(a.R), dim3(ACQ_OPT_THREADS), acq_opt_lds_bytes(a.ns), st, a, slot);
+  const dim3 grid(a.R), block(ACQ_OPT_THREADS);
+  const size_t lds = acq_opt_lds_bytes(a.ns);
+  if (a.reduce == HBO_ACQ_OPT_REDUCE_LME) {
+    if (dtype == HBO_F64) hipLaunchKernelGGL((acq_opt_ctl_kernel<double, HBO_ACQ_OPT_REDUCE_LME>), grid, block, lds, st, a, slot);
+    else hipLaunchKernelGGL((acq_opt_ctl_kernel<float, HBO_ACQ_OPT_REDUCE_LME>), grid, block, lds, st, a, slot);
+    return;
+  }
+  if (dtype == HBO_F64) hipLaunchKernelGGL((acq_opt_ctl_kernel<double, HBO_ACQ_OPT_REDUCE_MEAN>), grid, block, lds, st, a, slot);
+  else hipLaunchKernelGGL((acq_opt_ctl_kernel<float, HBO_ACQ_OPT_REDUCE_MEAN>), grid, block, lds, st, a, slot);
 }
 
 extern "C" int64_t hbo_acq_opt_state_doubles(int32_t D, int32_t memory) {
@@ -102,14 +110,17 @@ extern "C" int64_t hbo_acq_opt_state_doubles(int32_t D, int32_t memory) {
 // (allow_mlp -- hbo_acq_maximize_mlp: MLP-basis kernels and linear_mlp means are served; the S weight sets ride up between the pending
 //  points and the states, the evaluation runs the pair's forward and backward pass (acq_mlp.h) and the control kernel sees raw points
 //  and raw gradients as ever)
+// (logei -- hbo_logei_maximize, logei.hip: params holds the S targets, the evaluation takes the LogEI scalar step and the control kernel
+//  combines the samples as the log of the mean of their exponentials (acq_opt_ctl.h: HBO_ACQ_OPT_REDUCE_LME); acq_id is not read)
 int acq_maximize(hbo_ctx* c, const char* name, int max_n, bool allow_mlp, const hbo_model* models, int32_t S, hbo_cache* const* caches,
                  const void* x0, int32_t R, const double* lo, const double* hi, int acq_id, const double* params, const MesReq* mes,
                  const double* add_noise, double scale, const hbo_acq_opt_opts* opts, double* state, int32_t evals, double* x_out, double* val_out,
-                 int32_t* status, hbo_acq_opt_eval* log) {
+                 int32_t* status, hbo_acq_opt_eval* log, bool logei) {
   const std::string fn = std::string(name) + ": ";
   if (!models || !caches || !x0 || (mes ? !mes->ystar : !params) || !add_noise || !state || !x_out || !val_out || !status) return fail(c, HBO_ERR_ARG, fn + "null argument");
   if (S <= 0 || S > 4096) return fail(c, HBO_ERR_ARG, fn + "1 <= S <= 4096");
   if (mes) { if (int rc = mes_check(c, fn, *mes, S)) return rc; }
+  else if (logei) { if (int rc = logei_check(c, fn, params, S)) return rc; }
   else if (acq_id < 0 || acq_id > HBO_ACQ_UCB) return fail(c, HBO_ERR_ARG, fn + "bad acq_id");
   if (!c) return fail(c, HBO_ERR_ARG, fn + "ctx is null");
   if (R <= 0 || R > 4096) return fail(c, HBO_ERR_ARG, fn + "1 <= R <= 4096");
@@ -197,7 +208,9 @@ int acq_maximize(hbo_ctx* c, const char* name, int max_n, bool allow_mlp, const 
   a.D = D; a.M = R; a.kernel_id = m0->kernel_id; a.mean_id = m0->mean_id; a.acq_id = acq_id; a.scale = scale;
   a.grad_out = reinterpret_cast<double*>(d_out); a.val64_out = reinterpret_cast<double*>(d_out + grad_b); a.acq_out = d_out + grad_b + val_b;
   if (mes) { a.ystar = reinterpret_cast<const double*>(d_in + smp_b + vec_b) + 2 * D; a.K = mes->K; }
+  a.logei = logei;
   AcqOptArgs k = {};
+  k.reduce = logei ? HBO_ACQ_OPT_REDUCE_LME : HBO_ACQ_OPT_REDUCE_MEAN;
   k.o = acq_opt_ctl_opts(opts);
   k.state = reinterpret_cast<double*>(d_in + o_state); k.ns = ns;
   k.lo = reinterpret_cast<const double*>(d_in + smp_b + vec_b); k.hi = k.lo + D;

@@ -101,6 +101,36 @@ HBO_LBFGS_FN double hbo_acq_opt_reduce(const hbo_acq_opt_view& v, const double* 
   return -(hbo_acq_opt_sum_in_order(vals, vstride, S) / (double)S);
 }
 
+// The same from per-sample LOG values (hbo_logei_maximize: the acquisition is the log of the mean of the samples' EI, not the mean of
+// their logs): with m = max_s v_s and w_s = exp(v_s - m),  value = m + log(sum_s w_s / S),  grad = sum_s w_s g_s / sum_s w_s,  the sums
+// in sample order, then negated.  m = -inf (EI is 0 under every sample): f = +inf, gradient 0 -- the caller's isfinite tests reject
+// it.  A NaN value gives NaN.  S = 1: w = 1, log 1 = 0, and f and the gradient are the sample's to the bit.  exp and log are the
+// library's: the device and a host thread agree to the library's ulp here, not to the bit as everywhere else in this file.
+HBO_LBFGS_FN double hbo_acq_opt_reduce_lme(const hbo_acq_opt_view& v, const double* vals, int64_t vstride, const double* grads, int64_t gstride,
+                                           int S, int tid, int nthr) {
+  double m = -INFINITY;
+  bool nan = false;
+  for (int s = 0; s < S; ++s) { const double t = vals[s * vstride]; nan = nan || t != t; m = t > m ? t : m; }
+  if (nan) {
+    for (int i = tid; i < v.D; i += nthr) v.gt[i] = NAN;
+    return NAN;
+  }
+  if (m == -INFINITY) {
+    for (int i = tid; i < v.D; i += nthr) v.gt[i] = 0.0;
+    return INFINITY;
+  }
+  double sw = 0.0;
+  for (int s = 0; s < S; ++s) sw += exp(vals[s * vstride] - m);
+  for (int i = tid; i < v.D; i += nthr) {
+    double sg = 0.0;
+    for (int s = 0; s < S; ++s) { const double w = exp(vals[s * vstride] - m); sg += w * grads[s * gstride + i]; }
+    v.gt[i] = -(sg / sw);
+  }
+  const double mean = sw / (double)S;
+  return -(m + log(mean));
+}
+enum { HBO_ACQ_OPT_REDUCE_MEAN = 0, HBO_ACQ_OPT_REDUCE_LME = 1 };
+
 struct hbo_acq_opt_regs { int phase, status, iter, probes, nhist, head, evals; double alpha, cur; };
 
 // the probe x_t = clip(x + alpha d, lo, hi), rounded to the model dtype
@@ -126,7 +156,10 @@ HBO_LBFGS_FN double hbo_acq_opt_project(const hbo_acq_opt_view& v, const double*
 
 // One evaluation in, the next point out.  vals / grads: the per-sample results at the pending point v.xt (hbo_acq_opt_reduce).  On
 // return v.xt is the point to evaluate next (untouched once the status is not RUNNING) and v.x the iterate.
-HBO_LBFGS_FN void hbo_acq_opt_ctl_step(double* state, int D, const hbo_acq_opt_opts_ctl& o, const double* lo, const double* hi, int round_f32,
+// REDUCE, a compile-time choice: HBO_ACQ_OPT_REDUCE_MEAN -- hbo_acq_opt_reduce, every caller but one (hbo_acq_opt_ctl_step below);
+// HBO_ACQ_OPT_REDUCE_LME -- hbo_acq_opt_reduce_lme (hbo_logei_maximize).  Nothing else differs.
+template <int REDUCE>
+HBO_LBFGS_FN void hbo_acq_opt_ctl_step_t(double* state, int D, const hbo_acq_opt_opts_ctl& o, const double* lo, const double* hi, int round_f32,
                                        const double* vals, int64_t vstride, const double* grads, int64_t gstride, int S, int tid, int nthr,
                                        double* scratch, hbo_acq_opt_eval_ctl* ev) {
   const hbo_acq_opt_view v = hbo_acq_opt_view_of(state, D, o.memory);
@@ -137,7 +170,8 @@ HBO_LBFGS_FN void hbo_acq_opt_ctl_step(double* state, int D, const hbo_acq_opt_o
   HBO_LBFGS_BARRIER();   // every thread has read the header before thread 0 stores it again
   ev->iter = r.iter; ev->alpha = 0.0; ev->value = 0.0;
   if (r.status != HBO_ACQ_OPT_CTL_RUNNING) { ev->kind = HBO_ACQ_OPT_CTL_IDLE; return; }
-  const double ft = hbo_acq_opt_reduce(v, vals, vstride, grads, gstride, S, tid, nthr);
+  const double ft = REDUCE == HBO_ACQ_OPT_REDUCE_LME ? hbo_acq_opt_reduce_lme(v, vals, vstride, grads, gstride, S, tid, nthr)
+                                                     : hbo_acq_opt_reduce(v, vals, vstride, grads, gstride, S, tid, nthr);
   ev->value = ft;
   r.evals += 1;
   bool accepted = false;
@@ -239,6 +273,12 @@ HBO_LBFGS_FN void hbo_acq_opt_ctl_step(double* state, int D, const hbo_acq_opt_o
     v.hdr[HBO_ACQ_OPT_S_EVALS] = r.evals; v.hdr[HBO_ACQ_OPT_S_ALPHA] = r.alpha; v.hdr[HBO_ACQ_OPT_S_CUR] = r.cur;
   }
   HBO_LBFGS_BARRIER();
+}
+
+HBO_LBFGS_FN void hbo_acq_opt_ctl_step(double* state, int D, const hbo_acq_opt_opts_ctl& o, const double* lo, const double* hi, int round_f32,
+                                       const double* vals, int64_t vstride, const double* grads, int64_t gstride, int S, int tid, int nthr,
+                                       double* scratch, hbo_acq_opt_eval_ctl* ev) {
+  hbo_acq_opt_ctl_step_t<HBO_ACQ_OPT_REDUCE_MEAN>(state, D, o, lo, hi, round_f32, vals, vstride, grads, gstride, S, tid, nthr, scratch, ev);
 }
 
 // An all-zero state: the run starts at x0 (already a number of the model dtype, inside the box)

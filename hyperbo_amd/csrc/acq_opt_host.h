@@ -22,6 +22,7 @@ struct AcqOptArgs {
   const double* grads;              // [S][R][D]
   hbo_acq_opt_eval_ctl* log;        // nullable [evals][R]
   int D, R, S;
+  int reduce;                       // HBO_ACQ_OPT_REDUCE_* (acq_opt_ctl.h); 0: the mean
 };
 
 enum { ACQ_OPT_LDS_MAX = 65536 };

@@ -10,11 +10,12 @@
 #include "acq_mlp.h"
 
 namespace {
-// MES: the scalar step is mes_scalars_block over the sample's K maxima (a.ystar; hbo_mes_grad_samples) instead of acq_scalars
+// STEP, the scalar step (hbo_internal.h: ACQ_STEP_*): acq_scalars by a.acq_id; mes_scalars_block over the sample's K maxima (a.ystar;
+// hbo_mes_grad_samples); logei_scalars against the sample's target (sm.param; hbo_logei_grad_samples), per thread like the first
 // FEAT (acq_mlp.h; hbo_acq_grad_samples_mlp): 0 -- no MLP basis; otherwise ACQ_FEAT_KERNEL | ACQ_FEAT_MEAN, who reads the last layer.
 // The pair's workgroup then runs the forward pass first, works in the kernel's own space of width D = fdim below, takes the mean in
 // the mean's own space and ends with the backward pass (acq_mlp_tail).
-template <typename T, bool MES, int FEAT>
+template <typename T, int STEP, int FEAT>
 __global__ __launch_bounds__(256) void acq_small_kernel(AcqSmallArgs a) {
   __shared__ double s_xq[HBO_MAX_FEATURE_DIM], s_il[HBO_MAX_FEATURE_DIM];
   __shared__ double s_k[HBO_TILE], s_l[HBO_TILE], s_w[HBO_TILE];
@@ -113,7 +114,7 @@ __global__ __launch_bounds__(256) void acq_small_kernel(AcqSmallArgs a) {
     s_acc[tid] = b;
   }
   double amu, avar;
-  if constexpr (MES) {
+  if constexpr (STEP == ACQ_STEP_MES) {
     __shared__ double s_mes[3 * HBO_MES_MAX_K], s_mes_sum[3];
     const AcqScalars sc = mes_scalars_block(ka + mean, kqq - ll, sm.add_noise, a.scale, a.ystar + (int64_t)s * a.K, a.K, s_mes, s_mes_sum);
     if (tid == 0) {
@@ -123,8 +124,9 @@ __global__ __launch_bounds__(256) void acq_small_kernel(AcqSmallArgs a) {
     __syncthreads();   // (s_acc is read next, and mes_scalars_block leaves without a barrier when v2 <= 0)
     amu = sc.amu; avar = sc.avar;
   } else {
-    if (tid == 0) {
-      const AcqScalars sc = acq_scalars(a.acq_id, ka + mean, kqq - ll, sm.add_noise, a.scale, sm.param);
+    if (tid == 0) {   // (STEP is a constant: one of the two is compiled)
+      const AcqScalars sc = STEP == ACQ_STEP_LOGEI ? logei_scalars(ka + mean, kqq - ll, sm.add_noise, a.scale, sm.param)
+                                                   : acq_scalars(a.acq_id, ka + mean, kqq - ll, sm.add_noise, a.scale, sm.param);
       s_amu = sc.amu; s_avar = sc.avar;
       *acq = (T)sc.val;
       if (a.val64_out) a.val64_out[(int64_t)s * a.M + q] = sc.val;
@@ -169,32 +171,30 @@ __global__ __launch_bounds__(256) void acq_small_kernel(AcqSmallArgs a) {
     acq_mlp_tail<T, FEAT>(a, s, s_act, s_gk, vec + D, amu, s_top, s_tmp, g);
   }
 }
+template <typename T, int STEP>
+void launch_small_f(const AcqSmallArgs& a, const dim3& grid, hipStream_t st) {
+  switch (a.feat) {
+    case 0: hipLaunchKernelGGL((acq_small_kernel<T, STEP, 0>), grid, dim3(256), 0, st, a); break;
+    case ACQ_FEAT_KERNEL: hipLaunchKernelGGL((acq_small_kernel<T, STEP, ACQ_FEAT_KERNEL>), grid, dim3(256), 0, st, a); break;
+    case ACQ_FEAT_MEAN: hipLaunchKernelGGL((acq_small_kernel<T, STEP, ACQ_FEAT_MEAN>), grid, dim3(256), 0, st, a); break;
+    default: hipLaunchKernelGGL((acq_small_kernel<T, STEP, ACQ_FEAT_KERNEL | ACQ_FEAT_MEAN>), grid, dim3(256), 0, st, a); break;
+  }
+}
 }  // namespace
 
 void launch_acq_small(int dtype, const AcqSmallArgs& a, int S, hipStream_t st) {
   if (a.M <= 0 || S <= 0) return;
   const dim3 grid((unsigned)a.M, (unsigned)S);
   if (a.ystar) {   // (the MES entry points refuse MLP models: a.feat is 0)
-    if (dtype == HBO_F64) hipLaunchKernelGGL((acq_small_kernel<double, true, 0>), grid, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((acq_small_kernel<float, true, 0>), grid, dim3(256), 0, st, a);
+    if (dtype == HBO_F64) hipLaunchKernelGGL((acq_small_kernel<double, ACQ_STEP_MES, 0>), grid, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((acq_small_kernel<float, ACQ_STEP_MES, 0>), grid, dim3(256), 0, st, a);
     return;
   }
-  switch (a.feat) {
-    case 0:
-      if (dtype == HBO_F64) hipLaunchKernelGGL((acq_small_kernel<double, false, 0>), grid, dim3(256), 0, st, a);
-      else hipLaunchKernelGGL((acq_small_kernel<float, false, 0>), grid, dim3(256), 0, st, a);
-      break;
-    case ACQ_FEAT_KERNEL:
-      if (dtype == HBO_F64) hipLaunchKernelGGL((acq_small_kernel<double, false, ACQ_FEAT_KERNEL>), grid, dim3(256), 0, st, a);
-      else hipLaunchKernelGGL((acq_small_kernel<float, false, ACQ_FEAT_KERNEL>), grid, dim3(256), 0, st, a);
-      break;
-    case ACQ_FEAT_MEAN:
-      if (dtype == HBO_F64) hipLaunchKernelGGL((acq_small_kernel<double, false, ACQ_FEAT_MEAN>), grid, dim3(256), 0, st, a);
-      else hipLaunchKernelGGL((acq_small_kernel<float, false, ACQ_FEAT_MEAN>), grid, dim3(256), 0, st, a);
-      break;
-    default:
-      if (dtype == HBO_F64) hipLaunchKernelGGL((acq_small_kernel<double, false, ACQ_FEAT_KERNEL | ACQ_FEAT_MEAN>), grid, dim3(256), 0, st, a);
-      else hipLaunchKernelGGL((acq_small_kernel<float, false, ACQ_FEAT_KERNEL | ACQ_FEAT_MEAN>), grid, dim3(256), 0, st, a);
-      break;
+  if (a.logei) {
+    if (dtype == HBO_F64) launch_small_f<double, ACQ_STEP_LOGEI>(a, grid, st);
+    else launch_small_f<float, ACQ_STEP_LOGEI>(a, grid, st);
+    return;
   }
+  if (dtype == HBO_F64) launch_small_f<double, ACQ_STEP_REGISTRY>(a, grid, st);
+  else launch_small_f<float, ACQ_STEP_REGISTRY>(a, grid, st);
 }

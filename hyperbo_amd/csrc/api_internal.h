@@ -458,6 +458,11 @@ static int mes_check(hbo_ctx* c, const std::string& fn, const MesReq& r, int64_t
   for (int64_t i = 0; i < count * r.K; ++i) if (!isfinite(r.ystar[i])) return fail(c, HBO_ERR_ARG, fn + "ystar holds a value that is not finite");
   return HBO_OK;
 }
+// log expected improvement (logei.hip): `count` finite targets (not null); touches no device (c may be null)
+static int logei_check(hbo_ctx* c, const std::string& fn, const double* targets, int64_t count) {
+  for (int64_t i = 0; i < count; ++i) if (!isfinite(targets[i])) return fail(c, HBO_ERR_ARG, fn + "targets holds a value that is not finite");
+  return HBO_OK;
+}
 // the bodies of hbo_acq_grad_samples[_blocked] (acq_grad.hip) and hbo_acq_maximize[_blocked] (acq_opt.hip); mes: null for these
 struct AcqSamplesMode {
   const char* fn;          // the entry point's name in messages
@@ -465,6 +470,8 @@ struct AcqSamplesMode {
   bool force_blocked;      // test hook: caches of n <= 128 through the blocked kernels too
   int64_t chunk_queries;   // test hook: > 0 overrides the chunk size
   bool allow_mlp;          // the _mlp entry points: MLP-basis kernels and linear_mlp means are served (acq_mlp.h)
+  bool logei;              // hbo_logei_grad_samples (logei.hip): params holds the S targets, the kernels take the LogEI scalar step and
+                           // acq_id is not read
 };
 int acq_grad_samples(hbo_ctx* c, const AcqSamplesMode& mode, const hbo_model* models, int32_t S, hbo_cache* const* caches, const void* xq,
                      int64_t M, int acq_id, const double* params, const MesReq* mes, const double* add_noise, double scale, void* acq_out,
@@ -472,10 +479,13 @@ int acq_grad_samples(hbo_ctx* c, const AcqSamplesMode& mode, const hbo_model* mo
 int acq_maximize(hbo_ctx* c, const char* name, int max_n, bool allow_mlp, const hbo_model* models, int32_t S, hbo_cache* const* caches,
                  const void* x0, int32_t R, const double* lo, const double* hi, int acq_id, const double* params, const MesReq* mes,
                  const double* add_noise, double scale, const hbo_acq_opt_opts* opts, double* state, int32_t evals, double* x_out, double* val_out,
-                 int32_t* status, hbo_acq_opt_eval* log);
+                 int32_t* status, hbo_acq_opt_eval* log, bool logei = false);
 // hbo_acq's posterior pipeline under the MES epilogue (cache.hip); the arguments are checked by the caller (mes.hip: hbo_acq_mes)
 int posterior_mes(hbo_ctx* c, const hbo_model* m, hbo_cache* k, const void* xq, int64_t M, const MesReq& mes, double add_noise, double scale,
                   void* out);
+// ... and under the LogEI epilogue (logei.hip: hbo_acq_logei)
+int posterior_logei(hbo_ctx* c, const hbo_model* m, hbo_cache* k, const void* xq, int64_t M, double target, double add_noise, double scale,
+                    void* out);
 
 // the records acq_small_kernel and the kernels of acq_blocked.hip read of those pairs (hbo_internal.h: AcqSmallSample) and their
 // per-feature values, hv [S][fdim + mdim]: 1 / lengthscale over the kernel's own space, the linear mean's weights over the mean's

@@ -315,6 +315,7 @@ struct PostCall {
   const ModelDev* md; void* const* mw; void* const* mb;   // the model and its MLP weights on the device
   int acq_id; double param, add_noise, scale;
   const double* ystar; int K;   // hbo_acq_mes: the K maxima on the device -- the acquisition is the MES epilogue (mes.hip) over mu, var
+  bool logei;                   // hbo_acq_logei: the acquisition is the LogEI epilogue (logei.hip) over mu, var; param is the target
 };
 // one chunk's view of the workspaces: its buffer of each per-workspace array, its rows of the M-sized results
 struct PostSlice {
@@ -428,6 +429,7 @@ static int produce_chunk(const PostCall& pc, const PostPlan& p, const PostWs& w,
       HIPCHK(c, hipMemcpyAsync(s.var, s.kd, (size_t)ch.mc * es, hipMemcpyDeviceToDevice, sb));
     }
     if (s.acq && pc.ystar) launch_mes_epilogue(dtype, s.mu, s.var, ch.mc, pc.ystar, pc.K, pc.add_noise, pc.scale, s.acq, sb);
+    else if (s.acq && pc.logei) launch_logei_epilogue(dtype, s.mu, s.var, ch.mc, pc.param, pc.add_noise, pc.scale, s.acq, sb);
     else if (s.acq) {   // acquisition on the prior
       PostArgs pa = {}; pa.Kxq = nullptr; pa.n = 0; pa.nblk = 0; pa.ldq = ch.ldq; pa.alpha = nullptr; pa.colsq = nullptr;
       pa.kdiag = s.kd; pa.muq = s.mu0; pa.acq_out = s.acq; pa.M = ch.mc; pa.acq_id = pc.acq_id; pa.param = pc.param; pa.add_noise = pc.add_noise; pa.scale = pc.scale;
@@ -474,10 +476,11 @@ static void consume_chunk(const PostCall& pc, const PostPlan& p, const PostWs& w
     } }
   { ProfScope ps(c, "post_epilogue", 1, sa);
     PostArgs pa = {}; pa.Kxq = s.K; pa.ldq = ch.ldq; pa.npad = t->npad; pa.n = (int)t->n; pa.nblk = t->nblk; pa.alpha = t->svec; pa.colsq = s.colsq; pa.mupart = s.mupart;
-    pa.kdiag = s.kd; pa.muq = s.mu0; pa.mu_out = s.mu; pa.var_out = s.var; pa.acq_out = pc.ystar ? nullptr : s.acq; pa.M = ch.mc;
+    pa.kdiag = s.kd; pa.muq = s.mu0; pa.mu_out = s.mu; pa.var_out = s.var; pa.acq_out = (pc.ystar || pc.logei) ? nullptr : s.acq; pa.M = ch.mc;
     pa.acq_id = pc.acq_id; pa.param = pc.param; pa.add_noise = pc.add_noise; pa.scale = pc.scale;
     launch_post_epilogue(dtype, pa, sa);
-    if (pc.ystar) launch_mes_epilogue(dtype, s.mu, s.var, ch.mc, pc.ystar, pc.K, pc.add_noise, pc.scale, s.acq, sa); }
+    if (pc.ystar) launch_mes_epilogue(dtype, s.mu, s.var, ch.mc, pc.ystar, pc.K, pc.add_noise, pc.scale, s.acq, sa);
+    else if (pc.logei) launch_logei_epilogue(dtype, s.mu, s.var, ch.mc, pc.param, pc.add_noise, pc.scale, s.acq, sa); }
 }
 
 // full covariance with a cache: Kqq - V^T V in the Kqq buffer
@@ -493,7 +496,7 @@ static void full_cov_tail(const PostCall& pc, const PostPlan& p, const PostWs& w
 
 static int posterior(hbo_ctx* c, const hbo_model* m, hbo_cache* k, const void* xq, int64_t M, int full_cov,
                      void* mu_out, void* var_out, void* acq_out, int acq_id, double param, double add_noise,
-                     double scale, const PosteriorOverride* ov = nullptr, const MesReq* mes = nullptr) {
+                     double scale, const PosteriorOverride* ov = nullptr, const MesReq* mes = nullptr, bool logei = false) {
   if (!c || !xq) return fail(c, HBO_ERR_ARG, "posterior: null argument");
   if (M <= 0) return HBO_OK;
   HIPCHK(c, hipSetDevice(c->device));
@@ -507,7 +510,7 @@ static int posterior(hbo_ctx* c, const hbo_model* m, hbo_cache* k, const void* x
   double* d_ystar = nullptr;   // hbo_acq_mes: the maxima go up on the consumer stream, ahead of everything that reads them
   if (mes && !(d_ystar = static_cast<double*>(ws_get(c, WS_MES_YSTAR, sizeof(double) * mes->K)))) return HBO_ERR_HIP;
   const PostCall pc = {c, m, k, ov ? ov->md : c->d_model, ov ? ov->mlp_w : c->d_mlp_w, ov ? ov->mlp_b : c->d_mlp_b, acq_id, param, add_noise, scale,
-                       d_ystar, mes ? mes->K : 0};
+                       d_ystar, mes ? mes->K : 0, logei};
   PostPlan p = post_plan(c, m, M, k ? k->t->nblk : 0, full_cov != 0, ov ? &ov->lane : nullptr);
   c->last_post_resident = 0;
   if (p.refuse) return fail(c, p.refuse, "posterior: full_cov limited to 65536 queries");
@@ -582,6 +585,12 @@ extern "C" int hbo_acq(hbo_ctx* c, const hbo_model* m, hbo_cache* k, const void*
 int posterior_mes(hbo_ctx* c, const hbo_model* m, hbo_cache* k, const void* xq, int64_t M, const MesReq& mes, double add_noise, double scale,
                   void* out) {
   return posterior(c, m, k, xq, M, 0, nullptr, nullptr, out, 0, 0.0, add_noise, scale, nullptr, &mes);
+}
+
+// hbo_acq_logei (logei.hip) behind its argument checks: the same pipeline under the LogEI epilogue, the target in the place of param
+int posterior_logei(hbo_ctx* c, const hbo_model* m, hbo_cache* k, const void* xq, int64_t M, double target, double add_noise, double scale,
+                    void* out) {
+  return posterior(c, m, k, xq, M, 0, nullptr, nullptr, out, 0, target, add_noise, scale, nullptr, nullptr, true);
 }
 
 // ---- S hyper-parameter samples of one model family as ONE batch ------------------------------------------------------------

@@ -350,6 +350,9 @@ void launch_post_epilogue(int dtype, const PostArgs& a, hipStream_t st);
 // wrote (model dtype, [M]); ystar [K] doubles on the device
 void launch_mes_epilogue(int dtype, const void* mu, const void* var, int64_t M, const double* ystar, int K, double add_noise, double scale,
                          void* out, hipStream_t st);
+// hbo_acq_logei's epilogue (logei.hip): out[q] = log sd[q] + log h((mu[q] - target) / sd[q]) from the same mean and variance
+void launch_logei_epilogue(int dtype, const void* mu, const void* var, int64_t M, double target, double add_noise, double scale, void* out,
+                           hipStream_t st);
 // colsq[i][col] = sum over the 128 rows of row block i of (sum_ch Vpart[ch][row][col])^2, chunks ch < ceil((i + 1) / kchunk)
 void launch_post_colsq_split(int dtype, const void* vpart, int npad, int64_t ldq, int mpad, int nblk, int kchunk, void* colsq, hipStream_t st);
 
@@ -442,6 +445,7 @@ struct AcqSmallSample {
   int n, bad;                                        // bad: the cache is not positive definite -- the sample's rows are NaN
   double sv, inv_sigma2, bias2, constant, linear_bias, param, add_noise;
 };
+enum { ACQ_STEP_REGISTRY = 0, ACQ_STEP_MES = 1, ACQ_STEP_LOGEI = 2 };   // the scalar step a launch takes (compile-time in the kernels)
 struct AcqSmallArgs {
   const AcqSmallSample* smp; const double* vec;      // [S], [S][2 D]
   const void* xq; int D; int64_t M;                  // queries [M][D] (model dtype)
@@ -455,6 +459,9 @@ struct AcqSmallArgs {
   // bit 0: the kernel, bit 1: the mean reads the last layer, and vec is [S][fdim + mdim]: 1 / lengthscale over the kernel's own
   // space (fdim = last layer or D), then the linear mean's weights over the mean's (mdim = last layer, D or 0)
   int feat, fdim, mdim, L; int fout[HBO_MAX_MLP_LAYERS];
+  int logei;                                         // log expected improvement (logei.hip): the scalar step is logei_scalars against the
+                                                     // sample's target (AcqSmallSample::param); acq_id is then not read, ystar is null.
+                                                     // (Here it takes the padding in front of the pointers: no other field moves)
   const void* const* mlp_w; const void* const* mlp_b;   // device tables [S][HBO_MAX_MLP_LAYERS]: weights [in][out], bias (model dtype)
 };
 void launch_acq_small(int dtype, const AcqSmallArgs& a, int S, hipStream_t st);

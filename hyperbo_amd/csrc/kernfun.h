@@ -233,4 +233,61 @@ __device__ __forceinline__ AcqScalars mes_scalars_block(double mu, double var, d
   r.val = s_sum[0] / K; r.amu = -(s_sum[1] / K) / sd; r.avar = asd / (2.0 * sd) * scale;
   return r;
 }
+
+// Log expected improvement (Ament et al. 2023) at u = (mu - target) / sd, with h(u) = pdf(u) + u cdf(u) = EI / sd: log h and the two
+// ratios cdf / h and pdf / h, from which the value log sd + log h and its slopes a_mu = (cdf / h) / sd, a_sd = (pdf / h) / sd follow.
+// The one expression behind hbo_acq_logei, hbo_logei_grad_samples and hbo_logei_maximize.
+//   u > -1:       literally, pdf and cdf from erfc as ei_over_sd takes them; nothing cancels by more than a factor of about 5.
+//   u <= -1:      with e = erfcx(-u / sqrt 2): Mills ratio m = cdf / pdf = sqrt(pi / 2) e, w = h / pdf = 1 + u m, and
+//                 log h = -u^2 / 2 - log sqrt(2 pi) + log w, cdf / h = m / w, pdf / h = 1 / w.  w falls like 1 / u^2 and the sum 1 + u m
+//                 cancels: a relative error of about eps u^2 in w, the accepted loss.
+//   u < -LOGEI_SERIES_U: the asymptotic series  w u^2 = 1 - 3 / u^2 + 15 / u^4 - 105 / u^6,  m |u| = 1 - 1 / u^2 + 3 / u^4 - 15 / u^6
+//                 (first term left out: 945 / u^8 < 2^-54 from |u| = 235 on), exact to eps where the form above has lost eps u^2 --
+//                 4 digits at the switch, everything from |u| = 6.7e7 on, where w rounds to 0.  Finite for every finite u whose
+//                 square does not overflow.
+// u = +inf: (inf, 0, 0); u = -inf: (-inf, inf, inf), the limits; a NaN stays a NaN.
+#define LOGEI_SERIES_U 256.0
+struct LogEiTerms { double logh, cdf_h, pdf_h; };
+__device__ __forceinline__ LogEiTerms logei_terms(double u) {
+  LogEiTerms r;
+  if (u > -1.0) {
+    const double p = norm_pdf(u), c = norm_cdf(u);
+    const double h = p + u * c;
+    r.logh = log(h); r.cdf_h = c / h; r.pdf_h = p / h;
+  } else if (u >= -LOGEI_SERIES_U) {
+    const double m = 1.2533141373155003 * erfcx(-u * 0.7071067811865476);
+    const double w = 1.0 + u * m;
+    r.logh = -0.5 * u * u - 0.9189385332046727 + log(w);
+    r.cdf_h = m / w; r.pdf_h = 1.0 / w;
+  } else {
+    const double i2 = 1.0 / (u * u);
+    const double ws = 1.0 + i2 * (-3.0 + i2 * (15.0 - 105.0 * i2));   // w u^2
+    const double ms = 1.0 + i2 * (-1.0 + i2 * (3.0 - 15.0 * i2));    // m |u|
+    r.logh = -0.5 * u * u - 0.9189385332046727 + (log(ws) - 2.0 * log(-u));
+    r.cdf_h = -u * (ms / ws); r.pdf_h = u * u / ws;
+  }
+  return r;
+}
+// The scalar step of hbo_logei_grad_samples, per thread like acq_scalars: value = log sd + log h(u), a_mu = (cdf / h) / sd,
+// a_var = (pdf / h) / sd / (2 sd) * scale.  v2 = (var + add_noise) scale <= 0 (no posterior uncertainty): EI = max(mu - target, 0), so
+// value = log(mu - target), a_mu = 1 / (mu - target), a_var = 0 above the target and (-inf, 0, 0) at or below it -- -inf loses every
+// argmax, and the maximiser's line search rejects it.  A NaN v2 fails the compare and stays NaN.  Wherever the value is -inf both slopes
+// are 0: such a row has weight exp(-inf) = 0 in the combination over an HGP's samples, and 0 times an infinite slope would be a NaN.
+__device__ __forceinline__ AcqScalars logei_scalars(double mu, double var, double add_noise, double scale, double target) {
+  const double v2 = (var + add_noise) * scale;
+  AcqScalars r;
+  if (v2 <= 0.0) {
+    const double d = mu - target;
+    r.avar = 0.0;
+    if (d > 0.0) { r.val = log(d); r.amu = 1.0 / d; }
+    else if (d <= 0.0) { r.val = -INFINITY; r.amu = 0.0; }
+    else { r.val = NAN; r.amu = NAN; }
+    return r;
+  }
+  const double sd = sqrt(v2);
+  const LogEiTerms t = logei_terms((mu - target) / sd);
+  r.val = log(sd) + t.logh; r.amu = t.cdf_h / sd; r.avar = t.pdf_h / sd / (2.0 * sd) * scale;
+  if (r.val == -INFINITY) { r.amu = 0.0; r.avar = 0.0; }   // (u^2 overflows: the same rule -- a -inf row carries no slope into a sum)
+  return r;
+}
 }  // namespace

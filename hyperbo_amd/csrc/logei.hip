@@ -1,0 +1,74 @@
+// Log expected improvement (Ament et al. 2023; include/hbo.h has the formulas): the entry points hbo_acq_logei, hbo_logei_grad_samples and
+// hbo_logei_maximize, and the epilogue kernel of the first.  The one expression behind all three is kernfun.h: logei_terms.  The values
+// over a pool run through hbo_acq's posterior pipeline (cache.hip: posterior_logei) with logei_epilogue_kernel behind
+// post_epilogue_kernel's mean and variance; value + gradient and the maximiser are the bodies of hbo_acq_grad_samples_mlp (acq_grad.hip)
+// and hbo_acq_maximize_mlp (acq_opt.hip) with the S targets in the place of acq_id and params: the kernels of acq_small.hip /
+// acq_blocked.hip then take logei_scalars as their scalar step and the control kernel combines the samples as the log of the mean of
+// their exponentials (acq_opt_ctl.h); everything around the two is shared.
+#include "kernfun.h"
+#include "api_internal.h"
+#include "../../include/hbo_tune.h"
+
+namespace {
+// a thread per query: mu and var as post_epilogue_kernel left them, v2 and sd in the model dtype as it forms them, u and the terms in
+// fp64, one rounding.  v2 <= 0: log(mu - target) above the target, -inf at or below it; a NaN v2 fails the compare and stays NaN.
+template <typename T>
+__global__ __launch_bounds__(256) void logei_epilogue_kernel(const T* __restrict__ mu_in, const T* __restrict__ var_in, int64_t M, double target,
+                                                             double add_noise, double scale, T* out) {
+  const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (q >= M) return;
+  const T mu = mu_in[q], var = var_in[q];
+  const T v2 = (var + (T)add_noise) * (T)scale;
+  const T sd = sqrt(v2);
+  const double d = (double)mu - target;
+  double val;
+  if (v2 <= (T)0) val = d > 0.0 ? log(d) : (d <= 0.0 ? -INFINITY : NAN);
+  else val = log((double)sd) + logei_terms(d / (double)sd).logh;
+  out[q] = (T)val;
+}
+}  // namespace
+
+void launch_logei_epilogue(int dtype, const void* mu, const void* var, int64_t M, double target, double add_noise, double scale, void* out,
+                           hipStream_t st) {
+  if (M <= 0) return;
+  const dim3 grid((unsigned)((M + 255) / 256));
+  if (dtype == HBO_F64)
+    hipLaunchKernelGGL((logei_epilogue_kernel<double>), grid, dim3(256), 0, st, static_cast<const double*>(mu), static_cast<const double*>(var), M, target,
+                       add_noise, scale, static_cast<double*>(out));
+  else
+    hipLaunchKernelGGL((logei_epilogue_kernel<float>), grid, dim3(256), 0, st, static_cast<const float*>(mu), static_cast<const float*>(var), M, target,
+                       add_noise, scale, static_cast<float*>(out));
+}
+
+extern "C" int hbo_acq_logei(hbo_ctx* c, const hbo_model* m, hbo_cache* k, const void* xq, int64_t M, double target, double add_noise,
+                             double scale, void* out) {
+  const std::string fn = "hbo_acq_logei: ";
+  if (!m || !xq || !out) return fail(c, HBO_ERR_ARG, fn + "null argument");
+  if (int rc = logei_check(c, fn, &target, 1)) return rc;
+  if (!c) return fail(c, HBO_ERR_ARG, fn + "ctx is null");
+  return posterior_logei(c, m, k, xq, M, target, add_noise, scale, out);
+}
+
+extern "C" int hbo_logei_grad_samples(hbo_ctx* c, const hbo_model* models, int32_t S, hbo_cache* const* caches, const void* xq, int64_t M,
+                                      const double* targets, const double* add_noise, double scale, void* acq_out, double* grad_out) {
+  const AcqSamplesMode mode = {"hbo_logei_grad_samples", INT_MAX, false, 0, true, true};
+  return acq_grad_samples(c, mode, models, S, caches, xq, M, 0, targets, nullptr, add_noise, scale, acq_out, grad_out, nullptr);
+}
+
+// include/hbo_tune.h (TEST HOOK): hbo_logei_grad_samples with the fp64 values, the blocked kernels on request and a chunk size
+extern "C" int hbo_probe_logei_grad_samples64(hbo_ctx* c, const hbo_model* models, int32_t S, hbo_cache* const* caches, const void* xq, int64_t M,
+                                              const double* targets, const double* add_noise, double scale, void* acq_out, double* grad_out,
+                                              int32_t force_blocked, int64_t chunk_queries, double* val64_out) {
+  if (!val64_out) return fail(c, HBO_ERR_ARG, "hbo_probe_logei_grad_samples64: val64_out is null");
+  if (chunk_queries < 0) return fail(c, HBO_ERR_ARG, "hbo_probe_logei_grad_samples64: chunk_queries < 0");
+  const AcqSamplesMode mode = {"hbo_logei_grad_samples", INT_MAX, force_blocked != 0, chunk_queries, true, true};
+  return acq_grad_samples(c, mode, models, S, caches, xq, M, 0, targets, nullptr, add_noise, scale, acq_out, grad_out, val64_out);
+}
+
+extern "C" int hbo_logei_maximize(hbo_ctx* c, const hbo_model* models, int32_t S, hbo_cache* const* caches, const void* x0, int32_t R,
+                                  const double* lo, const double* hi, const double* targets, const double* add_noise, double scale,
+                                  const hbo_acq_opt_opts* opts, double* state, int32_t evals, double* x_out, double* val_out, int32_t* status,
+                                  hbo_acq_opt_eval* log) {
+  return acq_maximize(c, "hbo_logei_maximize", INT_MAX, true, models, S, caches, x0, R, lo, hi, 0, targets, nullptr, add_noise, scale, opts, state,
+                      evals, x_out, val_out, status, log, true);
+}

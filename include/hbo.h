@@ -434,6 +434,54 @@ int hbo_mes_maximize(hbo_ctx* ctx, const hbo_model* models, int32_t S, hbo_cache
                      const hbo_acq_opt_opts* opts, double* state, int32_t evals, double* x_out, double* val_out, int32_t* status,
                      hbo_acq_opt_eval* log);
 
+/* ---- log expected improvement (LogEI, Ament et al. 2023, "Unexpected improvements to expected improvement"; no counterpart in the
+ *      reference): the logarithm of EI, with EI's maximiser, in a form that stays representable where EI and its gradient underflow
+ *      (u < -8 in fp32 pools, -38 in fp64).  For posterior mean mu and variance var at a query and the target t (EI's param):
+ *        v2 = (var + add_noise) * scale,  sd = sqrt(v2),  u = (mu - t) / sd
+ *        h(u)  = pdf(u) + u cdf(u)                                   EI = sd h(u)
+ *        value = log sd + log h(u)
+ *        a_mu  = cdf(u) / (sd h(u)),   a_sd = pdf(u) / (sd h(u)),   a_var = a_sd / (2 sd) * scale
+ *      log h, cdf / h and pdf / h come from one function (csrc/kernfun.h: logei_terms): literally for u > -1; from the scaled
+ *      complementary error function for -256 <= u <= -1 (Mills ratio m = sqrt(pi / 2) erfcx(-u / sqrt 2), w = h / pdf = 1 + u m,
+ *      log h = -u^2 / 2 - log sqrt(2 pi) + log w, cdf / h = m / w, pdf / h = 1 / w; the cancellation in w costs a relative error of
+ *      about eps u^2); from the asymptotic series w u^2 = 1 - 3 / u^2 + 15 / u^4 - 105 / u^6 (and its counterpart for m) beyond,
+ *      exact to eps.  The value is finite for every finite u whose square does not overflow, and its gradient grows like |u| in the
+ *      tail instead of vanishing.  u = +inf and u = -inf give the limits, never NaN.
+ *      v2 <= 0 (no posterior uncertainty): value = log(mu - t), a_mu = 1 / (mu - t), a_var = 0 if mu > t; otherwise value = -inf and
+ *      both slopes are 0.  -inf loses every argmax, is a probe the maximiser's line search rejects, and at a start gives
+ *      HBO_ACQ_OPT_NONFINITE_AT_START.  Wherever the value is -inf both slopes are 0.  A NaN v2 stays NaN.
+ *      Several samples (HGP): the acquisition is the log of the MEAN of the samples' EI, not the mean of their logs.  From per-sample
+ *      values v_s and gradients g_s, with m = max_s v_s and w_s = exp(v_s - m):  value = m + log(sum_s w_s / S),
+ *      grad = sum_s w_s g_s / sum_s w_s, fp64 sums in sample order; m = -inf: value -inf, gradient 0; any NaN row: NaN; S = 1: v_0 and
+ *      g_0 to the bit.  hbo_logei_maximize combines so on the device; the other two entry points return per-sample rows.
+ *      LogEI is not a fourth acq_id: hbo_acq, hbo_acq_samples, hbo_acq_grad*, hbo_acq_maximize* and hbo_bo_simulated keep refusing
+ *      acq_id = 3.  HBO_ERR_ARG (before any device work, outputs untouched) for every entry point below: a target that is not
+ *      finite, null targets, plus what the sibling entry point checks. */
+/* ---- the values over a pool: hbo_acq's posterior pipeline (any n, every model family hbo_acq serves, cache == NULL -> the prior
+ *      branch, queries in chunks of post_chunk) under an epilogue of its own: a thread per query, mu, var, v2 and sd in the model dtype
+ *      as hbo_acq forms them, u and the terms in fp64, rounded once to the model dtype.  out [M,1] model dtype.  A row does not depend
+ *      on post_chunk nor on what the other rows of the call hold (bit for bit); as in hbo_acq, the form of the posterior product
+ *      follows from the TOTAL number of queries M.  Not positive definite: NaN and HBO_NOT_PD, as hbo_acq. */
+int hbo_acq_logei(hbo_ctx* ctx, const hbo_model* model, hbo_cache* cache /* nullable */, const void* xq, int64_t M, double target,
+                  double add_noise, double scale, void* out);
+/* ---- value and d value / d x_query for S samples over their finished caches, PER SAMPLE: hbo_acq_grad_samples_mlp with targets [S] in
+ *      the place of acq_id and params -- its semantics, checks, refusals (the prior branch, Kumaraswamy-warped models) and return
+ *      codes, for any n >= 1, MLP-basis kernels and the linear_mlp mean included: one launch when every cache has n <= 128, four or
+ *      five per chunk of queries otherwise.  Only the scalar step differs, a per-thread function like EI's; a_mu and a_var feed the
+ *      unchanged gradient code, the MLP backward pass included.  No atomics, every sum in a fixed order: a row does not depend on which
+ *      samples or queries share the call nor on the chunking (bit for bit), and identical calls are bit-identical.
+ *      acq_out [S,M] model dtype, grad_out [S,M,input_dim] doubles. */
+int hbo_logei_grad_samples(hbo_ctx* ctx, const hbo_model* models, int32_t S, hbo_cache* const* caches, const void* xq, int64_t M,
+                           const double* targets, const double* add_noise, double scale, void* acq_out, double* grad_out);
+/* ---- the maximisation of LogEI (combined over the S samples by the rule above) over a box, R starts in one call:
+ *      hbo_acq_maximize_mlp with targets [S] in the place of acq_id, params -- the same control kernel, state format, log, checks,
+ *      return codes and determinism (a run gives the same bits however it is cut into calls); the control kernel's reduction over the
+ *      samples is the log-mean-exp rule in the place of the mean (csrc/acq_opt_ctl.h), and val_out the combined value at x_out. */
+int hbo_logei_maximize(hbo_ctx* ctx, const hbo_model* models, int32_t S, hbo_cache* const* caches, const void* x0, int32_t R,
+                       const double* lo, const double* hi, const double* targets, const double* add_noise, double scale,
+                       const hbo_acq_opt_opts* opts, double* state, int32_t evals, double* x_out, double* val_out, int32_t* status,
+                       hbo_acq_opt_eval* log);
+
 /* ---- the maximisation of S posterior sample paths over a box, R starts each, in ONE call: continuous Thompson sampling -- q
  *      suggestions from q paths (no counterpart in the reference).  The optimiser is that of hbo_acq_maximize, run on
  *      f(x) = -f_s(x) for each of the S * R (path, start) pairs: one upload and one solve for u (hbo_sample_paths_grad), then `evals`

@@ -114,6 +114,11 @@ int hbo_probe_acq_grad_samples_mlp64(hbo_ctx* ctx, const hbo_model* models, int3
 int hbo_probe_mes_grad_samples64(hbo_ctx* ctx, const hbo_model* models, int32_t S, hbo_cache* const* caches, const void* xq, int64_t M,
                                  const double* ystar, int32_t K, const double* add_noise, double scale, void* acq_out, double* grad_out,
                                  int32_t force_blocked, int64_t chunk_queries, double* val64_out);
+/* TEST HOOK: hbo_logei_grad_samples (same checks, same launches, same results) with the same three extras: val64_out [S, M], the fp64
+ * values the control kernel of hbo_logei_maximize reads; force_blocked; chunk_queries. */
+int hbo_probe_logei_grad_samples64(hbo_ctx* ctx, const hbo_model* models, int32_t S, hbo_cache* const* caches, const void* xq, int64_t M,
+                                   const double* targets, const double* add_noise, double scale, void* acq_out, double* grad_out,
+                                   int32_t force_blocked, int64_t chunk_queries, double* val64_out);
 /* TEST HOOK: the control code of hbo_acq_maximize (csrc/acq_opt_ctl.h, the text its control kernel compiles) on the host, one thread,
  * for one evaluation of one start; no context, no device.  D: input_dim; dtype: the model dtype the pending point is rounded to.
  * lo, hi [D] (both null: 0 and 1).  vals [S] and grads [S, D]: the per-sample acquisition values (fp64) and gradients at the point the
