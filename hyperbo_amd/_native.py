@@ -226,6 +226,8 @@ SIGNATURES = {
                                  C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),   # include/hbo_tune.h (test hook)
     'hbo_probe_factor_inverse': (C.c_int, [_P, C.c_int, C.c_int32, C.POINTER(C.c_int64), _P, _P, C.c_int32, C.c_int, _P, _P, _P, _P, _P,
                                            C.POINTER(C.c_int32), _P]),   # include/hbo_tune.h (test hook; the last: hbo_probe_plan*)
+    'hbo_probe_kumar_warp': (C.c_int, [_P, C.POINTER(Model), _P, C.c_int64, _P, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                       C.POINTER(C.c_double)]),   # include/hbo_tune.h (test hook)
     'hbo_comm_unique_id': (C.c_int, [_P]),
     'hbo_comm_init': (C.c_int, [_P, C.c_int, C.c_int, _P]),
     'hbo_comm_allreduce_sum': (C.c_int, [_P, C.POINTER(C.c_double), C.c_int32]),

@@ -36,14 +36,18 @@ __device__ __forceinline__ T kumar_w(T x, T a, T b) {
   const T u = kpow(x, a);
   return b == (T)1 ? u : (T)1 - kpow((T)1 - u, b);
 }
-// dw/da = b v^(b-1) u ln x, dw/db = -v^b ln v (u = x^a, v = 1 - u), in fp64; 0 at x = 0 and x = 1 (their limits), and where
-// v rounds to 0 inside (0, 1), so that 0 ln 0 never reaches a sum.  Outside [0, 1] the formula's NaN goes through.
+// v = 1 - x^a for the derivatives, without the cancellation of 1 - u near x = 1: -expm1(a ln x) is good to a few ulp of v itself
+// (1 - u is off by an ulp of 1, which v^(b-1) with b < 1 turns into anything up to inf once v is of that size).  a == 1: 1 - x, exact
+__device__ __forceinline__ double kumar_v(double x, double a, double lx) { return a == 1.0 ? 1.0 - x : 0.0 - expm1(a * lx); }
+__device__ __forceinline__ float kumar_v(float x, float a, float lx) { return a == 1.f ? 1.f - x : 0.f - expm1f(a * lx); }
+// dw/da = b v^(b-1) u ln x, dw/db = -v^b ln v (u = x^a, v = 1 - u), in fp64; 0 at x = 0 and x = 1 (their limits), so that 0 ln 0
+// never reaches a sum.  ln v: log1p(-u) while u < 1/2 (v near 1), ln of kumar_v above.  Outside [0, 1] the formula's NaN goes through.
 __device__ __forceinline__ void kumar_dab(double x, double a, double b, double& ha, double& hb) {
   ha = 0.0; hb = 0.0;
   if (x == 0.0 || x == 1.0) return;
   const double lx = log(x);
   const double u = a == 1.0 ? x : exp(a * lx);
-  const double lv = log1p(-u);
+  const double lv = u < 0.5 ? log1p(-u) : log(kumar_v(x, a, lx));
   if (lv == -INFINITY) return;
   const double vb1 = b == 1.0 ? 1.0 : exp((b - 1.0) * lv);
   ha = b * vb1 * u * lx;
@@ -192,7 +196,7 @@ __global__ void kumar_chain_dx_kernel(const T* __restrict__ xq, int64_t M, int D
   if (idx >= M * D) return;
   const int d = (int)(idx % D);
   const T a = (T)md->kumar_a[d], b = (T)md->kumar_b[d], x = xq[idx];
-  const T v = (T)1 - kpow(x, a);
+  const T v = kumar_v(x, a, log(x));
   const T dwdx = a * b * kpow(x, a - (T)1) * kpow(v, b - (T)1);
   gx[idx] = gf[idx] * (double)dwdx;
 }

@@ -366,3 +366,34 @@ extern "C" int hbo_probe_factor_inverse(hbo_ctx* c, int dtype, int32_t T, const 
   }
   return bad ? HBO_NOT_PD : HBO_OK;
 }
+
+// Test hook (include/hbo_tune.h): the element-wise Kumaraswamy kernels of kumar.hip on caller-chosen rows -- launch_kumar_forward in its
+// gradient form (h != nullptr: w, dw/da, dw/db) and launch_kumar_chain_dx with gf = 1 in every element (dw/dx), nothing else.
+extern "C" int hbo_probe_kumar_warp(hbo_ctx* c, const hbo_model* m, const void* x, int64_t n, void* w_out, double* dwda_out, double* dwdb_out,
+                                    double* dwdx_out) {
+  if (!c || !m || !x || !w_out || !dwda_out || !dwdb_out || !dwdx_out) return fail(c, HBO_ERR_ARG, "hbo_probe_kumar_warp: null argument");
+  if (!is_kumar(m)) return fail(c, HBO_ERR_ARG, "hbo_probe_kumar_warp: the model has no Kumaraswamy input warp");
+  if (n <= 0 || n > (1 << 20)) return fail(c, HBO_ERR_ARG, "hbo_probe_kumar_warp: need 1 <= n <= 2^20");
+  HIPCHK(c, hipSetDevice(c->device));
+  int rc = upload_model(c, m);
+  if (rc) return rc;
+  const int dtype = m->dtype, D = m->input_dim;
+  const size_t es = esize(dtype), cnt = (size_t)n * D;
+  hipStream_t st = c->stream;
+  DevBuf buf;
+  void *d_x = nullptr, *d_w = nullptr; double *d_h = nullptr, *d_gf = nullptr, *d_gx = nullptr;
+  HIPCHK(c, buf.get(c, &d_x, cnt * es)); HIPCHK(c, buf.get(c, &d_w, cnt * es));
+  HIPCHK(c, buf.get(c, &d_h, 2 * cnt * sizeof(double))); HIPCHK(c, buf.get(c, &d_gf, cnt * sizeof(double))); HIPCHK(c, buf.get(c, &d_gx, cnt * sizeof(double)));
+  const std::vector<double> ones(cnt, 1.0);
+  HIPCHK(c, hipMemcpyAsync(d_x, x, cnt * es, hipMemcpyHostToDevice, st));
+  HIPCHK(c, hipMemcpyAsync(d_gf, ones.data(), cnt * sizeof(double), hipMemcpyHostToDevice, st));
+  launch_kumar_forward(dtype, nullptr, 0, 0, d_x, d_w, d_h, n, D, c->d_model, st);
+  launch_kumar_chain_dx(dtype, d_x, n, D, c->d_model, d_gf, d_gx, st);
+  HIPCHK(c, hipMemcpyAsync(w_out, d_w, cnt * es, hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipMemcpyAsync(dwda_out, d_h, cnt * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipMemcpyAsync(dwdb_out, d_h + cnt, cnt * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipMemcpyAsync(dwdx_out, d_gx, cnt * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipStreamSynchronize(st));
+  HIPCHK(c, hipGetLastError());
+  return HBO_OK;
+}

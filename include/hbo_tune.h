@@ -178,6 +178,13 @@ typedef struct hbo_probe_plan {
 int hbo_probe_factor_inverse(hbo_ctx* ctx, int dtype, int32_t T, const int64_t* ns, const void* a, const void* b, int32_t m,
                              int beside_chain, void* chol_out, void* w_out, void* kinv_out, void* x_out, void* z_out, int32_t* info_out,
                              hbo_probe_plan* plan_out);
+/* TEST HOOK (tests/test_gpu_kumar_leaves.py): the element-wise kernels of the Kumaraswamy input warp (csrc/kumar.hip) on caller-chosen
+ * rows.  model: an hbo_model_kumar (input_warp = HBO_WARP_KUMAR); x [n, input_dim] in the model dtype, 1 <= n <= 2^20.  Two launches, the
+ * shipped ones: the forward pass in its gradient form -- w_out [n, input_dim] (model dtype) = w(x), dwda_out / dwdb_out [n, input_dim]
+ * (fp64) = dw/da, dw/db at the warped a, b -- and the query-side chain rule on a cotangent of ones: dwdx_out [n, input_dim] (fp64) = dw/dx.
+ * HBO_ERR_ARG on a null pointer, a model without the warp or n out of range, before any device call; no product path calls this. */
+int hbo_probe_kumar_warp(hbo_ctx* ctx, const hbo_model* model, const void* x, int64_t n, void* w_out, double* dwda_out, double* dwdb_out,
+                         double* dwdx_out);
 #ifdef __cplusplus
 }
 #endif

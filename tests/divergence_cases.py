@@ -10,7 +10,7 @@ tri_matvec passes and add_sumsq_kernel for EKL, the nvec loops of grad.hip and k
   inputs(case)        model and [(x, y)] in the case's dtype, seeded by the case's id (without its kind and dtype: 'ekl' / 'euc' and
                       fp64 / fp32 see the same numbers, the fp32 ones rounded once, here)
   reference(case)     per task: value, terms, term scale S_k, gradient tree -- oracle._divergence_sub_dataset_value_and_grad in fp64
-                      (a Kumaraswamy kernel: on the warped inputs; its a / b leaves by central differences, ab_reference)
+                      (a Kumaraswamy kernel: on the warped inputs; its a / b leaves analytic from the kernel adjoint, ab_analytic)
   restate_task(...)   the value terms by the formulas of utils.py:84-173 in `wide` = float32, float64 or np.longdouble (Cholesky and
                       substitutions by hand: pathwise_cases.chol / solve_lower), and the value MUTANTS; grad_mutant: the gradient ones
                       (wrong adjoints through the oracle's backward pass); mutant_ratio: how many bounds away a mutant lies
@@ -26,6 +26,7 @@ from typing import NamedTuple, Tuple
 import numpy as np
 
 import helpers
+import kumar_cases
 import kumar_oracle
 import pathwise_cases as pc
 from oracle import hyperbo_oracle as o
@@ -47,7 +48,8 @@ FP32_GRAD_TOL = 2.5e-3      # per leaf, helpers.assert_grad_close (tests/test_gp
 REL_FACTOR = 4.0
 FLOOR_C = 8.0
 AB_FD_STEP = 1e-5           # a / b leaves: central differences of the oracle value (tests/test_gpu_kumar.py: _fd_ab) ...
-AB_FD_TOL = 1e-6            # ... held to rtol = atol / max|leaf| = 1e-6 (test_divergence_value_and_grad there)
+AB_FD_TOL = 1e-6            # ... to which the analytic reference is held on the CPU, rtol = atol / max|leaf| = 1e-6 (test_divergence_value_and_grad there)
+AB_TOL = 1e-10              # the device against the analytic reference (ab_analytic), same form: the suite's fp64 level per leaf
 
 
 class Case(NamedTuple):
@@ -272,12 +274,36 @@ def ab_reference(case):
   return ab_central_differences(case)
 
 
-def ab_errors(got, ref):
-  """Per leaf: max |got - ref| over (AB_FD_TOL |ref| + AB_FD_TOL max |ref leaf|), the allclose of test_gpu_kumar.py."""
+def _capturing_adjoint(store):
+  """The oracle's own adjoint (the formulas of _adjoint without a mutant), which also keeps d f / d K1 of the task in store['dk1']."""
+  def adjoint(kind, k1, c0, d, kinv):
+    dk1, dmu = _adjoint(None)(kind, k1, c0, d, kinv)
+    store['dk1'] = dk1
+    return dk1, dmu
+  return adjoint
+
+
+@functools.lru_cache(maxsize=None)
+def ab_analytic(case):
+  """d (sum of the tasks' values) / d (raw a, b), analytic: the kernel adjoint d f / d K1 of the oracle's backward pass (its adjoint=
+  hook hands K1, C0, d and K1^-1 over), through d K / d w of the base kernel and dw/da, dw/db (kumar_cases.ab_from_adjoint).  What the
+  device is held to, at AB_TOL; ab_reference, the central differences, is its yardstick on the CPU."""
+  model64 = cast(inputs(case).model, np.float64)
+  out = {'a': np.zeros(case.d), 'b': np.zeros(case.d)}
+  for x, y in inputs(case).tasks:
+    store = {}
+    oracle_task(case, model64, x, y, _capturing_adjoint(store))
+    ab = kumar_cases.ab_from_adjoint(case.kname, model64, x, store['dk1'])
+    out = {k: out[k] + ab[k] for k in out}
+  return out
+
+
+def ab_errors(got, ref, tol=AB_FD_TOL):
+  """Per leaf: max |got - ref| over (tol |ref| + tol max |ref leaf|), the allclose of test_gpu_kumar.py."""
   out = {}
   for key in ('a', 'b'):
     g, r = np.asarray(got[key], dtype=np.float64).ravel(), np.asarray(ref[key], dtype=np.float64).ravel()
-    e = np.abs(g - r) / (AB_FD_TOL * np.abs(r) + AB_FD_TOL * np.max(np.abs(r)))
+    e = np.abs(g - r) / (tol * np.abs(r) + tol * np.max(np.abs(r)))
     out[key] = float(np.max(e)) if np.isfinite(e).all() else np.inf
   return out
 

@@ -153,10 +153,23 @@ def test_oracle_gradient_agrees_with_central_differences(case):
 
 @pytest.mark.parametrize('case', [c for c in dc.GROUP_C if c.kumar and c.tasks == ((129, 128),)], ids=lambda c: c.id)
 def test_ab_central_differences_are_stable_in_the_step(case):
-  """The a / b leaves have no analytic reference: the central differences the device is held to (AB_FD_TOL) do not move by more than a
-  tenth of that bound when the step is doubled."""
+  """The central differences the analytic a / b reference is held to (AB_FD_TOL) do not move by more than a tenth of that bound when the
+  step is doubled."""
   ratios = dc.ab_errors(dc.ab_central_differences(case, 2 * dc.AB_FD_STEP), dc.ab_reference(case))
   assert max(ratios.values()) <= 0.1, ratios
+
+
+@pytest.mark.parametrize('case', [c for c in dc.GROUP_C if c.kumar and c.tasks == ((129, 128),)], ids=lambda c: c.id)
+def test_analytic_ab_leaves_agree_with_central_differences(case):
+  """What the device's a / b leaves are held to (ab_analytic, at AB_TOL): the oracle's kernel adjoint through dK/dw and dw/da, dw/db,
+  within AB_FD_TOL of the central differences.  The adjoint that captures d f / d K1 is the oracle's own: every other leaf comes out to
+  the bit."""
+  ratios = dc.ab_errors(dc.ab_analytic(case), dc.ab_reference(case))
+  assert max(ratios.values()) <= 1.0, ratios
+  model64 = dc.cast(dc.inputs(case).model, np.float64)
+  x, y = dc.inputs(case).tasks[0]
+  plain, hooked = dc.oracle_task(case, model64, x, y), dc.oracle_task(case, model64, x, y, dc._capturing_adjoint({}))
+  assert plain[0] == hooked[0] and all(np.array_equal(a, b) for (_, a), (_, b) in zip(helpers.tree_leaves(plain[1]), helpers.tree_leaves(hooked[1])))
 
 
 def test_value_bounds_are_per_task_and_relative_to_the_term_scale():
