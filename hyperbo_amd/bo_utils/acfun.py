@@ -6,6 +6,8 @@ their posteriors + epilogues queue up on the device (hbo_acq_samples) -- the cou
 over the draws; the `*_sub` functions are the host restatement of the maths, used for callables outside
 the registry.
 """
+import collections
+import contextlib
 import functools
 from typing import Any, Callable, Union
 
@@ -167,14 +169,23 @@ def _sample_models(model, samples, dtype):
   return cached[1], cached[2]
 
 
-def _sample_args(built, handles, noises, acfun_param):
-  """The per-sample ctypes arrays of the batched calls: (models, caches or None without handles, acquisition parameters, noises)."""
+def _per_sample(value, s):
+  """[s] doubles for ctypes, every sample with the same value."""
+  return (nat.C.c_double * s)(*([float(value)] * s))
+
+
+def _sample_args(built, handles, noises):
+  """The per-sample ctypes arrays of the batched calls: (models, caches or None without handles, noises)."""
   s = len(built)
   structs = (nat.Model * s)(*[b.struct for b in built])
   caches = None if handles is None else (nat.C.c_void_p * s)(*[h.handle for h in handles])
-  prm = (nat.C.c_double * s)(*([float(acfun_param)] * s))
   nse = (nat.C.c_double * s)(*[float(v) for v in noises])
-  return structs, caches, prm, nse
+  return structs, caches, nse
+
+
+def _ctx_and_cache(handle):
+  """(context, cache pointer) of a call over one factor handle; without one (the prior branch): the default context and None."""
+  return (handle.ctx, handle.handle) if handle is not None else (nat.default_context(), None)
 
 
 def _single_model(model, sub_dataset_key, x_queries=None):
@@ -229,10 +240,10 @@ def hgp_sample_values(model, sub_dataset_key, x_queries, acq_id, acfun_param):
   s0 = 0
   while s0 < s_count:
     sc = min(chunk, s_count - s0)
-    structs, _, prm, nse = _sample_args(built[s0:s0 + sc], None, noises[s0:s0 + sc], acfun_param)
+    structs, _, nse = _sample_args(built[s0:s0 + sc], None, noises[s0:s0 + sc])
     part = out[s0:s0 + sc]
     rc = nat.lib().hbo_acq_samples(ctx.handle, structs, sc, nat.ptr(x), x.shape[0], nat.ptr(y), y.shape[1], nat.ptr(xq), xq.shape[0],
-                                   int(acq_id), prm, nse, float(scale), part.ctypes.data_as(nat.C.c_void_p))
+                                   int(acq_id), _per_sample(acfun_param, sc), nse, float(scale), part.ctypes.data_as(nat.C.c_void_p))
     if rc == nat.HBO_ERR_HIP and sc > 1:      # out of device memory after all: smaller chunks, same result
       chunk = max(1, sc // 2)
       continue
@@ -259,13 +270,18 @@ def drop_sample_caches(model):
     model._hbo_sample_caches = None
 
 
+def _factor_sample(model, sub, smp):
+  """The factorisation of the sub-dataset `sub` under the parameter sample `smp`: a handle the caller keeps or closes."""
+  from hyperbo_amd.basics import linalg
+  return linalg.factor(model.mean_func, model.cov_func, defs.GPParams(config=model.params.config, model=smp), sub.x, sub.y, model.warp_func)
+
+
 def _hgp_sample_caches(model, sub_dataset_key, samples, dtype):
   """Factorisations of one sub-dataset under the parameter samples, kept on the model until the samples or the observations
   change (CONTENT fingerprint of x / y: an in-place edit of the observations must not be served a stale factor): bayesopt()'s inner
   L-BFGS-B (bayesopt.py:116-125) differentiates the acquisition dozens of times with the model fixed, and the reference would
   re-factorise all S samples every time (gp.py:676-678 drops the cache per sample).  Only as many samples as fit HALF of the
   device memory are kept (`_samples_per_call`, the budget of hgp_sample_values); the caller factorises the rest per call."""
-  from hyperbo_amd.basics import linalg
   sd = model.dataset[sub_dataset_key]
   finger = (_samples_fingerprint(model, samples, dtype), sub_dataset_key, _array_digest(sd.x, sd.y))
   cached = getattr(model, '_hbo_sample_caches', None)
@@ -276,14 +292,28 @@ def _hgp_sample_caches(model, sub_dataset_key, samples, dtype):
   handles = []
   try:
     for smp in samples[:keep]:
-      ps = defs.GPParams(config=model.params.config, model=smp)
-      handles.append(linalg.factor(model.mean_func, model.cov_func, ps, sd.x, sd.y, model.warp_func))
+      handles.append(_factor_sample(model, sd, smp))
   except nat.HboError:
     # out of device memory after all: keep the factors that were built, the rest go one at a time
     if not handles:
       raise
   model._hbo_sample_caches = (finger, handles)
   return handles
+
+
+def _each_sample(model, sub_dataset_key, samples, built, noises, handles):
+  """(i, BuiltModel, noise, factor handle) per parameter sample of an HGP, for the calls that take one sample at a time: the kept factors
+  first (`_hgp_sample_caches`); a sample beyond the budget is factorised, yielded and closed on the spot; the prior branch: None.
+  Close the generator (contextlib.closing): a caller's exception then closes the factor in flight at once."""
+  sub = model.dataset[sub_dataset_key] if model.has_observations(sub_dataset_key) else None
+  for i, (bm, noise) in enumerate(zip(built, noises)):
+    transient = sub is not None and i >= len(handles)
+    h = _factor_sample(model, sub, samples[i]) if transient else (handles[i] if sub is not None else None)
+    try:
+      yield i, bm, noise, h
+    finally:
+      if transient:
+        h.close()
 
 
 ACQ_FUSED_MAX_N = 128   # hbo_acq_grad_samples: one 128-block per cache
@@ -346,28 +376,60 @@ def _acq_opt_unmet(model, sub_dataset_key, acfun_sub, n_samples=1, n_kept=None, 
   return _acq_fused_unmet(model, sub_dataset_key, n_samples, n_kept, enabled=True, max_n=max_n, allow_mlp=allow_mlp)
 
 
-def _mes_args(mes, s_count):
-  """(ystar pointer, K) of the MES entry points, which take them where their siblings take (acq_id, params): mes [S, K] float64."""
-  if mes.dtype != np.float64 or mes.ndim != 2 or mes.shape[0] != s_count or not mes.flags.c_contiguous:
-    raise ValueError(f'maxima must be a contiguous float64 array [{s_count}, K], got {mes.dtype} {mes.shape}')
-  return mes.ctypes.data_as(nat.C.POINTER(nat.C.c_double)), mes.shape[1]
+# The routes of the registry's entry points over finished factors: the names of the gradient and the maximiser, and what
+# `_acq_fused_unmet` / `_acq_opt_unmet` are asked on that route (max_n: the largest sub-dataset, None: no limit; allow_mlp)
+_Route = collections.namedtuple('_Route', 'grad maximize max_n allow_mlp')
+_ROUTES = {
+    'small': _Route('hbo_acq_grad_samples', 'hbo_acq_maximize', ACQ_FUSED_MAX_N, False),
+    'blocked': _Route('hbo_acq_grad_samples_blocked', 'hbo_acq_maximize_blocked', None, False),
+    'mlp': _Route('hbo_acq_grad_samples_mlp', 'hbo_acq_maximize_mlp', None, True),
+}
 
 
-def _device_maximize(built, handles, noises, x0, lo, hi, acq_id, acfun_param, scale, opts, want_log, blocked=False, mes=None, entry=None,
-                     logei=False):
-  """hbo_acq_maximize (blocked: hbo_acq_maximize_blocked, caches of any size; mes, [S, K] maxima: hbo_mes_maximize) in segments of
-  opts['segment'] evaluations until no start is RUNNING or opts['max_evals'] are spent.  entry: another sibling by name
-  (hbo_acq_maximize_mlp).  logei: hbo_logei_maximize, with acfun_param as every sample's target and no acq_id.
-  x0 [R, D] in the model dtype; lo / hi [D] float64 or None.  Returns (x [R, D], values [R], status [R], evaluations [R], log or None)."""
-  entry = getattr(nat.lib(), entry) if entry else (nat.lib().hbo_acq_maximize_blocked if blocked else nat.lib().hbo_acq_maximize)
+def _route_of(model):
+  """The route model.params.config asks for: 'acq_mlp' wins (it implies no size limit), then 'acq_blocked', else the one-block one."""
+  return _ROUTES['mlp' if _acq_mlp(model) else ('blocked' if _acq_blocked(model) else 'small')]
+
+
+# What a call over finished factors evaluates: the names of its gradient entry point and its maximiser, and args(s_count), the ctypes
+# arguments they take where the registry's take (acq_id, params[S])
+_Request = collections.namedtuple('_Request', 'grad maximize args')
+
+
+def _registry_request(route, acq_id, param):
+  """EI / PI / UCB by acq_id on a route of _ROUTES, every sample with the parameter `param`."""
+  return _Request(route.grad, route.maximize, lambda s: (int(acq_id), _per_sample(param, s)))
+
+
+def _mes_request(maxima):
+  """Max-value entropy search under the maxima [S, K] float64: (ystar, K)."""
+  def args(s_count):
+    if maxima.dtype != np.float64 or maxima.ndim != 2 or maxima.shape[0] != s_count or not maxima.flags.c_contiguous:
+      raise ValueError(f'maxima must be a contiguous float64 array [{s_count}, K], got {maxima.dtype} {maxima.shape}')
+    return maxima.ctypes.data_as(nat.C.POINTER(nat.C.c_double)), maxima.shape[1]
+  return _Request('hbo_mes_grad_samples', 'hbo_mes_maximize', args)
+
+
+def _logei_request(target):
+  """Log expected improvement, every sample against `target`: (targets[S])."""
+  return _Request('hbo_logei_grad_samples', 'hbo_logei_maximize', lambda s: (_per_sample(target, s),))
+
+
+def _as_request(via, acq_id, acfun_param):
+  """The selector of `_fused_value_and_grad` / `_device_maximize`: a _Request, or a route (None: 'small') for the registry's pair."""
+  return via if isinstance(via, _Request) else _registry_request(via or _ROUTES['small'], acq_id, acfun_param)
+
+
+def _device_maximize(built, handles, noises, x0, lo, hi, acq_id, acfun_param, scale, opts, want_log, via=None):
+  """The maximiser of the request `via` (`_as_request`; a _Request reads neither acq_id nor acfun_param) in segments of opts['segment']
+  evaluations until no start is RUNNING or opts['max_evals'] are spent.  x0 [R, D] in the model dtype; lo / hi [D] float64 or None.
+  Returns (x [R, D], values [R], status [R], evaluations [R], log or None)."""
+  req = _as_request(via, acq_id, acfun_param)
+  entry = getattr(nat.lib(), req.maximize)
   s_count, (r_count, d) = len(built), x0.shape
   ctx = handles[0].ctx
-  structs, caches, prm, nse = _sample_args(built, handles, noises, acfun_param)
-  what = (int(acq_id), prm)
-  if mes is not None:
-    entry, what = nat.lib().hbo_mes_maximize, _mes_args(mes, s_count)
-  if logei:
-    entry, what = nat.lib().hbo_logei_maximize, (prm,)
+  structs, caches, nse = _sample_args(built, handles, noises)
+  what = req.args(s_count)
   o = nat.AcqOptOpts(*[opts[k] for k in ('memory', 'ls_steps', 'max_iters', 'c1', 'tau', 'pgtol', 'ftol')])
   ns = nat.lib().hbo_acq_opt_state_doubles(d, o.memory)
   state = np.zeros((r_count, max(ns, 1)), dtype=np.float64)
@@ -390,24 +452,46 @@ def _device_maximize(built, handles, noises, x0, lo, hi, acq_id, acfun_param, sc
   return x, val, status, n_evals, (np.concatenate(logs) if want_log else None)
 
 
-def _fused_value_and_grad(built, handles, noises, xq, acq_id, acfun_param, scale, blocked=False, mes=None, entry=None, logei=False):
-  """((S, M, 1) values in the model dtype, (S, M, D) gradients in float64) of S models over their finished factors: one
-  hbo_acq_grad_samples call -- one upload, one launch, one copy back (blocked: hbo_acq_grad_samples_blocked, caches of any size;
-  mes, [S, K] maxima: hbo_mes_grad_samples; entry: another sibling by name -- hbo_acq_grad_samples_mlp; logei:
-  hbo_logei_grad_samples, with acfun_param as every sample's target and no acq_id)."""
-  entry = getattr(nat.lib(), entry) if entry else (nat.lib().hbo_acq_grad_samples_blocked if blocked else nat.lib().hbo_acq_grad_samples)
+def _box_of(bounds, d):
+  """(lo, hi) [d] float64 of a box given as d (lo, hi) pairs; (None, None) for None, the unit box of the entry points."""
+  if bounds is None:
+    return None, None
+  b = np.asarray(bounds, dtype=np.float64).reshape(d, 2)
+  return np.ascontiguousarray(b[:, 0]), np.ascontiguousarray(b[:, 1])
+
+
+def _maximize_over_box(built, handles, noises, dtype, input_dim, x_init, bounds, scale, via, *opts):
+  """What the `maximize` methods share around `_device_maximize` under the request `via`: the options (ACQ_OPT_DEFAULTS, 'segment',
+  'max_evals', 'log', then the dicts `opts` in order, None skipped), the starts x_init [D] or [R, D], the box, the per-start `info` and
+  the winner (x_best [D] float64, value_best, info): the largest finite value, the lowest index among equals; without any, x_init[0], NaN."""
+  o = dict(ACQ_OPT_DEFAULTS, segment=ACQ_OPT_SEGMENT, max_evals=ACQ_OPT_MAX_EVALS, log=False)
+  for layer in opts:
+    o.update(layer or {})
+  x_init = np.atleast_2d(np.asarray(x_init, dtype=np.float64))
+  lo, hi = _box_of(bounds, input_dim)
+  x, val, status, n_evals, log = _device_maximize(built, handles, noises, np.ascontiguousarray(x_init, dtype=dtype), lo, hi, None, None,
+                                                  scale, o, bool(o['log']), via)
+  info = {'x': x, 'value': val, 'status': status, 'evals': n_evals}
+  if o['log']:
+    info['log'] = log
+  finite = np.isfinite(val)
+  if not finite.any():
+    return x_init[0].copy(), float('nan'), info
+  best = int(np.argmax(np.where(finite, val, -np.inf)))
+  return x[best].copy(), float(val[best]), info
+
+
+def _fused_value_and_grad(built, handles, noises, xq, acq_id, acfun_param, scale, via=None):
+  """((S, M, 1) values in the model dtype, (S, M, D) gradients in float64) of S models over their finished factors: one call of the gradient
+  entry point of the request `via` (`_as_request`; by default hbo_acq_grad_samples) -- one upload, the launches, one copy back."""
+  req = _as_request(via, acq_id, acfun_param)
   s_count, (nq, d) = len(built), xq.shape
   ctx = handles[0].ctx
-  structs, caches, prm, nse = _sample_args(built, handles, noises, acfun_param)
-  what = (int(acq_id), prm)
-  if mes is not None:
-    entry, what = nat.lib().hbo_mes_grad_samples, _mes_args(mes, s_count)
-  if logei:
-    entry, what = nat.lib().hbo_logei_grad_samples, (prm,)
+  structs, caches, nse = _sample_args(built, handles, noises)
   out = np.empty((s_count, nq, 1), dtype=xq.dtype)
   g = np.empty((s_count, nq, d), dtype=np.float64)
-  ctx.check(entry(ctx.handle, structs, s_count, caches, nat.ptr(xq), nq, *what, nse, float(scale),
-                  nat.ptr(out), g.ctypes.data_as(nat.C.POINTER(nat.C.c_double))))
+  ctx.check(getattr(nat.lib(), req.grad)(ctx.handle, structs, s_count, caches, nat.ptr(xq), nq, *req.args(s_count), nse, float(scale),
+                                         nat.ptr(out), g.ctypes.data_as(nat.C.POINTER(nat.C.c_double))))
   return out, g
 
 
@@ -416,7 +500,6 @@ def _hgp_value_and_grad(model, sub_dataset_key, x_queries, acq_id, acfun_param):
   HGP (acfun.py:72-82 under bayesopt.py:116-125).  One hbo_acq_grad per sample against that sample's cached factor (samples
   beyond the cache budget: factorised, used and released on the spot) -- or, with the context option 'acq_fused' on and a model
   `_acq_fused_unmet` has nothing against, one hbo_acq_grad_samples call over all of them."""
-  from hyperbo_amd.basics import linalg
   if getattr(model.cov_func, 'uses_kumar', False):   # (as hbo_acq_samples: HGP over Kumaraswamy kernels is out of scope)
     raise nat.HboError(nat.HBO_ERR_UNSUPPORTED, 'HGP acquisition over a Kumaraswamy kernel is not supported')
   samples = model.get_model_params_samples()
@@ -432,11 +515,10 @@ def _hgp_value_and_grad(model, sub_dataset_key, x_queries, acq_id, acfun_param):
   built, noises = _sample_models(model, samples, dtype)
   handles = _hgp_sample_caches(model, sub_dataset_key, samples, dtype) if has_obs else []
   _, scale = model.predict_noise_and_scale(True, True)
-  mlp = _acq_mlp(model)   # config['acq_mlp']: the _mlp entry point, MLP models included, no 128-observation limit
-  if _acq_fused_unmet(model, sub_dataset_key, len(samples), len(handles), max_n=None if mlp else _blocked_max_n(model), allow_mlp=mlp) is None:
+  route = _route_of(model)
+  if _acq_fused_unmet(model, sub_dataset_key, len(samples), len(handles), max_n=route.max_n, allow_mlp=route.allow_mlp) is None:
     # option 'acq_fused': every sample's pass in ONE call over the kept factors; the mean as the loop below takes it
-    outs, gs = _fused_value_and_grad(built, handles, noises, xq, acq_id, acfun_param, scale, blocked=_acq_blocked(model),
-                                     entry='hbo_acq_grad_samples_mlp' if mlp else None)
+    outs, gs = _fused_value_and_grad(built, handles, noises, xq, acq_id, acfun_param, scale, route)
     for out, g in zip(outs, gs):
       val += out
       grad += g
@@ -444,23 +526,13 @@ def _hgp_value_and_grad(model, sub_dataset_key, x_queries, acq_id, acfun_param):
     return (val / len(samples)).astype(dtype), grad / len(samples)
   out = np.empty((nq, 1), dtype=dtype)
   g = np.zeros((nq, model.input_dim), dtype=np.float64)
-  ctx = nat.default_context()
-  for i, (bm, noise) in enumerate(zip(built, noises)):
-    h, transient = (handles[i] if i < len(handles) else None), False
-    if h is None and has_obs:
-      sd = model.dataset[sub_dataset_key]
-      ps = defs.GPParams(config=model.params.config, model=samples[i])
-      h, transient = linalg.factor(model.mean_func, model.cov_func, ps, sd.x, sd.y, model.warp_func), True
-    try:
-      c = h.ctx if h is not None else ctx
-      c.check(nat.lib().hbo_acq_grad(c.handle, bm.ref(), h.handle if h is not None else None, nat.ptr(xq), nq, int(acq_id),
-                                     float(acfun_param), float(noise), float(scale), nat.ptr(out),
-                                     g.ctypes.data_as(nat.C.POINTER(nat.C.c_double))))
-    finally:
-      if transient:
-        h.close()
-    val += out
-    grad += g
+  with contextlib.closing(_each_sample(model, sub_dataset_key, samples, built, noises, handles)) as each:
+    for _, bm, noise, h in each:
+      c, cache = _ctx_and_cache(h)
+      c.check(nat.lib().hbo_acq_grad(c.handle, bm.ref(), cache, nat.ptr(xq), nq, int(acq_id), float(acfun_param), float(noise), float(scale),
+                                     nat.ptr(out), g.ctypes.data_as(nat.C.POINTER(nat.C.c_double))))
+      val += out
+      grad += g
   model.update_model_params(samples[-1])     # the side effect of the reference's loop over samples (gp.py:674-678)
   return (val / len(samples)).astype(dtype), grad / len(samples)
 
@@ -485,9 +557,8 @@ def acfun_wrapper(acfun_sub, acfun_callback_default):
     out = np.empty((xq.shape[0], 1), dtype=xq.dtype)
     if bm is None:
       return out
-    ctx = handle.ctx if handle is not None else nat.default_context()
-    ctx.check(nat.lib().hbo_acq(ctx.handle, bm.ref(), handle.handle if handle is not None else None,
-                                nat.ptr(xq), xq.shape[0], _NATIVE_ID[acfun_sub], float(acfun_param),
+    ctx, cache = _ctx_and_cache(handle)
+    ctx.check(nat.lib().hbo_acq(ctx.handle, bm.ref(), cache, nat.ptr(xq), xq.shape[0], _NATIVE_ID[acfun_sub], float(acfun_param),
                                 float(add_noise), float(scale), nat.ptr(out)))
     return out
 
@@ -503,16 +574,13 @@ def acfun_wrapper(acfun_sub, acfun_callback_default):
     grad = np.zeros((xq.shape[0], model.input_dim), dtype=np.float64)
     if bm is None:
       return out, grad
-    mlp = _acq_mlp(model)   # config['acq_mlp']: the _mlp entry point, MLP models included, no 128-observation limit
-    if _acq_fused_unmet(model, sub_dataset_key, max_n=None if mlp else _blocked_max_n(model), allow_mlp=mlp) is None:   # option 'acq_fused': the one-launch path with S = 1
-      outs, gs = _fused_value_and_grad([bm], [handle], [add_noise], xq, _NATIVE_ID[acfun_sub], acfun_param, scale,
-                                       blocked=_acq_blocked(model), entry='hbo_acq_grad_samples_mlp' if mlp else None)
+    route = _route_of(model)
+    if _acq_fused_unmet(model, sub_dataset_key, max_n=route.max_n, allow_mlp=route.allow_mlp) is None:   # option 'acq_fused': the one-launch path with S = 1
+      outs, gs = _fused_value_and_grad([bm], [handle], [add_noise], xq, _NATIVE_ID[acfun_sub], acfun_param, scale, route)
       return outs[0], gs[0]
-    ctx = handle.ctx if handle is not None else nat.default_context()
-    ctx.check(nat.lib().hbo_acq_grad(ctx.handle, bm.ref(), handle.handle if handle is not None else None,
-                                     nat.ptr(xq), xq.shape[0], _NATIVE_ID[acfun_sub], float(acfun_param),
-                                     float(add_noise), float(scale), nat.ptr(out),
-                                     grad.ctypes.data_as(nat.C.POINTER(nat.C.c_double))))
+    ctx, cache = _ctx_and_cache(handle)
+    ctx.check(nat.lib().hbo_acq_grad(ctx.handle, bm.ref(), cache, nat.ptr(xq), xq.shape[0], _NATIVE_ID[acfun_sub], float(acfun_param),
+                                     float(add_noise), float(scale), nat.ptr(out), grad.ctypes.data_as(nat.C.POINTER(nat.C.c_double))))
     return out, grad
 
   def maximize(*, model, sub_dataset_key, x_init, bounds=None, acfun_callback=acfun_callback_default, opts=None):
@@ -526,16 +594,11 @@ def acfun_wrapper(acfun_sub, acfun_callback_default):
     model.params.config['acq_blocked'] is set: the calls then go to hbo_acq_maximize_blocked.  An MLP-basis kernel or a linear_mlp
     mean is such a model unless model.params.config['acq_mlp'] is set: the calls then go to hbo_acq_maximize_mlp (any number of
     observations)."""
-    o = dict(ACQ_OPT_DEFAULTS, segment=ACQ_OPT_SEGMENT, max_evals=ACQ_OPT_MAX_EVALS, log=False)
-    o.update(opts or {})
-    x_init = np.atleast_2d(np.asarray(x_init, dtype=np.float64))
     hgp = isinstance(model, gp.HGP)
     samples = model.get_model_params_samples() if hgp else None
     n_samples = len(samples) if hgp else 1
-    blocked, max_n, mlp = _acq_blocked(model), _blocked_max_n(model), _acq_mlp(model)
-    if mlp:
-      max_n = None
-    unmet = _acq_opt_unmet(model, sub_dataset_key, acfun_sub, n_samples, max_n=max_n, allow_mlp=mlp)
+    route = _route_of(model)
+    unmet = _acq_opt_unmet(model, sub_dataset_key, acfun_sub, n_samples, max_n=route.max_n, allow_mlp=route.allow_mlp)
     if unmet is not None:
       raise nat.HboError(nat.HBO_ERR_UNSUPPORTED, 'ac_func.maximize: ' + unmet)
     acfun_param = acfun_callback(model, sub_dataset_key)
@@ -544,7 +607,7 @@ def acfun_wrapper(acfun_sub, acfun_callback_default):
       dtype = _model.infer_dtype(sd.x, sd.y)
       built, noises = _sample_models(model, samples, dtype)
       handles = _hgp_sample_caches(model, sub_dataset_key, samples, dtype)
-      unmet = _acq_opt_unmet(model, sub_dataset_key, acfun_sub, n_samples, len(handles), max_n=max_n, allow_mlp=mlp)
+      unmet = _acq_opt_unmet(model, sub_dataset_key, acfun_sub, n_samples, len(handles), max_n=route.max_n, allow_mlp=route.allow_mlp)
       if unmet is not None:
         raise nat.HboError(nat.HBO_ERR_UNSUPPORTED, 'ac_func.maximize: ' + unmet)
       _, scale = model.predict_noise_and_scale(True, True)
@@ -552,23 +615,11 @@ def acfun_wrapper(acfun_sub, acfun_callback_default):
       handle, _, bm, add_noise, scale = _single_model(model, sub_dataset_key)   # (_acq_opt_unmet: it has observations)
       dtype = handle.dtype
       built, handles, noises = [bm], [handle], [add_noise]
-    lo = hi = None
-    if bounds is not None:
-      b = np.asarray(bounds, dtype=np.float64).reshape(model.input_dim, 2)
-      lo, hi = np.ascontiguousarray(b[:, 0]), np.ascontiguousarray(b[:, 1])
-    x0 = np.ascontiguousarray(x_init, dtype=dtype)
-    x, val, status, n_evals, log = _device_maximize(built, handles, noises, x0, lo, hi, _NATIVE_ID[acfun_sub], acfun_param, scale, o,
-                                                    bool(o['log']), blocked=blocked, entry='hbo_acq_maximize_mlp' if mlp else None)
+    best = _maximize_over_box(built, handles, noises, dtype, model.input_dim, x_init, bounds, scale,
+                              _registry_request(route, _NATIVE_ID[acfun_sub], acfun_param), opts)
     if hgp:
       model.update_model_params(samples[-1])   # as every HGP path here leaves it (gp.py:674-678)
-    info = {'x': x, 'value': val, 'status': status, 'evals': n_evals}
-    if o['log']:
-      info['log'] = log
-    finite = np.isfinite(val)
-    if not finite.any():
-      return x_init[0].copy(), float('nan'), info
-    best = int(np.argmax(np.where(finite, val, -np.inf)))
-    return x[best].copy(), float(val[best]), info
+    return best
 
   acquisition_function.value_and_grad = value_and_grad
   acquisition_function.maximize = maximize
@@ -690,8 +741,8 @@ class MaxValueEntropySearch:
       return out
     ystar = self._given(maxima) if maxima is not None else max_value_samples(
         model, sub_dataset_key, xq, self.num_maxima, key, self.num_features, refine=False)
-    ctx = handle.ctx if handle is not None else nat.default_context()
-    ctx.check(nat.lib().hbo_acq_mes(ctx.handle, bm.ref(), handle.handle if handle is not None else None, nat.ptr(xq), xq.shape[0],
+    ctx, cache = _ctx_and_cache(handle)
+    ctx.check(nat.lib().hbo_acq_mes(ctx.handle, bm.ref(), cache, nat.ptr(xq), xq.shape[0],
                                     ystar.ctypes.data_as(nat.C.POINTER(nat.C.c_double)), ystar.size, float(add_noise), float(scale),
                                     nat.ptr(out)))
     return out
@@ -701,33 +752,16 @@ class MaxValueEntropySearch:
     handle, xq, bm, add_noise, scale = self._setup(model, sub_dataset_key, np.asarray(x_queries), what='value_and_grad')
     if bm is None:
       return np.empty((xq.shape[0], 1), dtype=xq.dtype), np.zeros((xq.shape[0], model.input_dim))
-    outs, gs = _fused_value_and_grad([bm], [handle], [add_noise], xq, 0, 0.0, scale, mes=self._given(maxima)[None])
+    outs, gs = _fused_value_and_grad([bm], [handle], [add_noise], xq, None, None, scale, _mes_request(self._given(maxima)[None]))
     return outs[0], gs[0]
 
   def maximize(self, *, model, sub_dataset_key, x_init, maxima, bounds=None, opts=None):
     """Maximises the MES value over a box on the device (hbo_mes_maximize) from the starts x_init [D] or [R, D], under the given
     maxima.  bounds, opts and the return value (x_best [D] float64, value_best, info) are those of the `maximize` of the EI / PI / UCB
     objects: segments of ACQ_OPT_SEGMENT evaluations, the start with the largest finite value wins."""
-    o = dict(ACQ_OPT_DEFAULTS, segment=ACQ_OPT_SEGMENT, max_evals=ACQ_OPT_MAX_EVALS, log=False)
-    o.update(self.opts or {})
-    o.update(opts or {})
-    x_init = np.atleast_2d(np.asarray(x_init, dtype=np.float64))
     handle, _, bm, add_noise, scale = self._setup(model, sub_dataset_key, what='maximize')
-    dtype = handle.dtype
-    lo = hi = None
-    if bounds is not None:
-      b = np.asarray(bounds, dtype=np.float64).reshape(model.input_dim, 2)
-      lo, hi = np.ascontiguousarray(b[:, 0]), np.ascontiguousarray(b[:, 1])
-    x, val, status, n_evals, log = _device_maximize([bm], [handle], [add_noise], np.ascontiguousarray(x_init, dtype=dtype), lo, hi, 0, 0.0,
-                                                    scale, o, bool(o['log']), mes=self._given(maxima)[None])
-    info = {'x': x, 'value': val, 'status': status, 'evals': n_evals}
-    if o['log']:
-      info['log'] = log
-    finite = np.isfinite(val)
-    if not finite.any():
-      return x_init[0].copy(), float('nan'), info
-    best = int(np.argmax(np.where(finite, val, -np.inf)))
-    return x[best].copy(), float(val[best]), info
+    return _maximize_over_box([bm], [handle], [add_noise], handle.dtype, model.input_dim, x_init, bounds, scale,
+                              _mes_request(self._given(maxima)[None]), self.opts, opts)
 
   def suggest(self, *, model, sub_dataset_key, x_candidates, key=None, batch_size=1, bounds=None):
     """[1, D] float64, the next point of bayesopt.bayesopt: refined maxima over the candidates (max_value_samples), the candidates'
@@ -852,30 +886,22 @@ class LogExpectedImprovement:
         predicts = model.predict(x_queries, sub_dataset_key=sub_dataset_key, full_cov=False, with_noise=True)
         vals = [log_expected_improvement_sub(mu, np.sqrt(var), target) for mu, var in predicts]
         return logei_combine(vals).astype(np.asarray(predicts[0][0]).dtype)
-      from hyperbo_amd.basics import linalg
       samples, dtype, built, noises, handles, scale = self._hgp_setup(model, sub_dataset_key, '__call__', all_kept=False)
       xq = np.ascontiguousarray(x_queries, dtype=dtype)
       outs = np.empty((len(samples), xq.shape[0], 1), dtype=dtype)
-      sd = model.dataset[sub_dataset_key]
-      for i, (bm, noise, out) in enumerate(zip(built, noises, outs)):
-        kept = i < len(handles)    # (samples beyond the cache budget: factorised, used and released on the spot, as for ei's gradient)
-        h = handles[i] if kept else linalg.factor(model.mean_func, model.cov_func, defs.GPParams(config=model.params.config, model=samples[i]),
-                                                  sd.x, sd.y, model.warp_func)
-        try:
+      # (samples beyond the cache budget: factorised, used and released on the spot, as for ei's gradient)
+      with contextlib.closing(_each_sample(model, sub_dataset_key, samples, built, noises, handles)) as each:
+        for i, bm, noise, h in each:
           h.ctx.check(nat.lib().hbo_acq_logei(h.ctx.handle, bm.ref(), h.handle, nat.ptr(xq), xq.shape[0], target, float(noise), float(scale),
-                                              nat.ptr(out)))
-        finally:
-          if not kept:
-            h.close()
+                                              nat.ptr(outs[i])))
       model.update_model_params(samples[-1])   # as every HGP path here leaves it (gp.py:674-678)
       return logei_combine(outs).astype(dtype)
     handle, xq, bm, add_noise, scale = _single_model(model, sub_dataset_key, x_queries)
     out = np.empty((xq.shape[0], 1), dtype=xq.dtype)
     if bm is None:
       return out
-    ctx = handle.ctx if handle is not None else nat.default_context()
-    ctx.check(nat.lib().hbo_acq_logei(ctx.handle, bm.ref(), handle.handle if handle is not None else None, nat.ptr(xq), xq.shape[0],
-                                      target, float(add_noise), float(scale), nat.ptr(out)))
+    ctx, cache = _ctx_and_cache(handle)
+    ctx.check(nat.lib().hbo_acq_logei(ctx.handle, bm.ref(), cache, nat.ptr(xq), xq.shape[0], target, float(add_noise), float(scale), nat.ptr(out)))
     return out
 
   def _setup(self, model, sub_dataset_key, what, x_queries=None):
@@ -896,7 +922,7 @@ class LogExpectedImprovement:
     dtype, built, noises, handles, scale, xq, samples = self._setup(model, sub_dataset_key, 'value_and_grad', np.asarray(x_queries))
     if xq.shape[0] == 0:
       return np.empty((0, 1), dtype=dtype), np.zeros((0, model.input_dim))
-    outs, gs = _fused_value_and_grad(built, handles, noises, xq, 0, target, scale, logei=True)
+    outs, gs = _fused_value_and_grad(built, handles, noises, xq, None, None, scale, _logei_request(target))
     if samples is None:
       return outs[0], gs[0]
     model.update_model_params(samples[-1])
@@ -906,27 +932,12 @@ class LogExpectedImprovement:
   def maximize(self, *, model, sub_dataset_key, x_init, bounds=None, acfun_callback=None, opts=None):
     """Maximises LogEI over a box on the device (hbo_logei_maximize) from the starts x_init [D] or [R, D].  bounds, opts and the return
     value (x_best [D] float64, value_best, info) are those of the `maximize` of the EI / PI / UCB objects."""
-    o = dict(ACQ_OPT_DEFAULTS, segment=ACQ_OPT_SEGMENT, max_evals=ACQ_OPT_MAX_EVALS, log=False)
-    o.update(opts or {})
-    x_init = np.atleast_2d(np.asarray(x_init, dtype=np.float64))
     target = float((acfun_callback or ei_callback_default)(model, sub_dataset_key))
     dtype, built, noises, handles, scale, _, samples = self._setup(model, sub_dataset_key, 'maximize')
-    lo = hi = None
-    if bounds is not None:
-      b = np.asarray(bounds, dtype=np.float64).reshape(model.input_dim, 2)
-      lo, hi = np.ascontiguousarray(b[:, 0]), np.ascontiguousarray(b[:, 1])
-    x, val, status, n_evals, log = _device_maximize(built, handles, noises, np.ascontiguousarray(x_init, dtype=dtype), lo, hi, 0, target,
-                                                    scale, o, bool(o['log']), logei=True)
+    best = _maximize_over_box(built, handles, noises, dtype, model.input_dim, x_init, bounds, scale, _logei_request(target), opts)
     if samples is not None:
       model.update_model_params(samples[-1])
-    info = {'x': x, 'value': val, 'status': status, 'evals': n_evals}
-    if o['log']:
-      info['log'] = log
-    finite = np.isfinite(val)
-    if not finite.any():
-      return x_init[0].copy(), float('nan'), info
-    best = int(np.argmax(np.where(finite, val, -np.inf)))
-    return x[best].copy(), float(val[best]), info
+    return best
 
 
 log_expected_improvement = log_ei = LogExpectedImprovement()

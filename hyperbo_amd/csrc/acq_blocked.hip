@@ -19,6 +19,8 @@
 // the backward pass: five launches per chunk.
 #include "acq_mlp.h"
 
+#include <assert.h>
+
 namespace {
 enum { BLK_MC = 8 };   // queries per workgroup of the two triangular products
 
@@ -175,7 +177,7 @@ __global__ __launch_bounds__(256) void acq_blk_trans_kernel(AcqBlockedArgs b) {
 }
 
 // ---- 4: one workgroup per (sample, query): the sums over the rows, the scalar step, the gradient
-//         (STEP: the scalar step, as in acq_small_kernel -- the registry's, the MES step over the sample's K maxima, or the LogEI step)
+//         (STEP: the scalar step, as in acq_small_kernel (kernfun.h: acq_scalar_step))
 //         (FEAT: D below is the width of the kernel's space; the activations come back from the plane and acq_mlp_tail ends the pair)
 template <typename T, int STEP, int FEAT>
 __global__ __launch_bounds__(256) void acq_blk_finish_kernel(AcqBlockedArgs b) {
@@ -183,7 +185,6 @@ __global__ __launch_bounds__(256) void acq_blk_finish_kernel(AcqBlockedArgs b) {
   __shared__ double s_w[256];
   __shared__ double s_acc[256];
   __shared__ double sred[4];
-  __shared__ double s_amu, s_avar;
   const AcqSmallArgs& a = b.a;
   const int64_t ql = blockIdx.x, q = b.q0 + ql;
   const int s = blockIdx.y;
@@ -241,26 +242,8 @@ __global__ __launch_bounds__(256) void acq_blk_finish_kernel(AcqBlockedArgs b) {
       mean = sm.linear_bias + block_sum(tid < a.mdim ? s_act[(a.L - 1) * HBO_MAX_FEATURE_DIM + tid] * vec[D + tid] : 0.0, sred);
   }
   double amu, avar;
-  if constexpr (STEP == ACQ_STEP_MES) {
-    __shared__ double s_mes[3 * HBO_MES_MAX_K], s_mes_sum[3];
-    const AcqScalars sc = mes_scalars_block(ka + mean, kqq - ll, sm.add_noise, a.scale, a.ystar + (int64_t)s * a.K, a.K, s_mes, s_mes_sum);
-    if (tid == 0) {
-      *acq = (T)sc.val;
-      if (a.val64_out) a.val64_out[(int64_t)s * a.M + q] = sc.val;
-    }
-    __syncthreads();
-    amu = sc.amu; avar = sc.avar;   // (every thread holds them: nothing is handed over through LDS)
-  } else {
-    if (tid == 0) {   // (STEP is a constant: one of the two is compiled)
-      const AcqScalars sc = STEP == ACQ_STEP_LOGEI ? logei_scalars(ka + mean, kqq - ll, sm.add_noise, a.scale, sm.param)
-                                                   : acq_scalars(a.acq_id, ka + mean, kqq - ll, sm.add_noise, a.scale, sm.param);
-      s_amu = sc.amu; s_avar = sc.avar;
-      *acq = (T)sc.val;
-      if (a.val64_out) a.val64_out[(int64_t)s * a.M + q] = sc.val;
-    }
-    __syncthreads();
-    amu = s_amu; avar = s_avar;
-  }
+  acq_scalar_step<T, STEP>(a, sm, s, q, ka + mean, kqq - ll, acq, amu, avar);
+  if constexpr (STEP == ACQ_STEP_MES) __syncthreads();
   // ---- g_d = sum_i w_i (x_d - X_id | X_id), w_i = coef_i * (dk/du_i * 2 | 1 / sigma^2): FD = pow2 >= D lanes along the features, G groups
   //      over the rows of a chunk; a thread keeps its sum across the chunks and the groups meet once, group by group
   int FD = 1; while (FD < D) FD <<= 1;
@@ -323,14 +306,14 @@ void launch_blocked_f(const AcqBlockedArgs& b, int S, hipStream_t st) {
   hipLaunchKernelGGL((acq_blk_fwd_kernel<T, BLK_MC>), dim3(b.ldv / 16, grp, S), dim3(256), 0, st, b);
   hipLaunchKernelGGL((acq_blk_trans_kernel<T, BLK_MC>), dim3(b.ldv / 64, grp, S), dim3(256), 0, st, b);
   if constexpr (FEAT == 0) {
-    if (b.a.ystar) { hipLaunchKernelGGL((acq_blk_finish_kernel<T, ACQ_STEP_MES, 0>), dim3(mc, S), dim3(256), 0, st, b); return; }
+    if (b.a.step == ACQ_STEP_MES) { hipLaunchKernelGGL((acq_blk_finish_kernel<T, ACQ_STEP_MES, 0>), dim3(mc, S), dim3(256), 0, st, b); return; }
   }
-  if (b.a.logei) { hipLaunchKernelGGL((acq_blk_finish_kernel<T, ACQ_STEP_LOGEI, FEAT>), dim3(mc, S), dim3(256), 0, st, b); return; }
+  if (b.a.step == ACQ_STEP_LOGEI) { hipLaunchKernelGGL((acq_blk_finish_kernel<T, ACQ_STEP_LOGEI, FEAT>), dim3(mc, S), dim3(256), 0, st, b); return; }
   hipLaunchKernelGGL((acq_blk_finish_kernel<T, ACQ_STEP_REGISTRY, FEAT>), dim3(mc, S), dim3(256), 0, st, b);
 }
 template <typename T>
 void launch_blocked_t(const AcqBlockedArgs& b, int S, hipStream_t st) {
-  switch (b.a.ystar ? 0 : b.a.feat) {   // (the MES entry points refuse MLP models)
+  switch (b.a.feat) {
     case 0: launch_blocked_f<T, 0>(b, S, st); break;
     case ACQ_FEAT_KERNEL: launch_blocked_f<T, ACQ_FEAT_KERNEL>(b, S, st); break;
     case ACQ_FEAT_MEAN: launch_blocked_f<T, ACQ_FEAT_MEAN>(b, S, st); break;
@@ -340,8 +323,10 @@ void launch_blocked_t(const AcqBlockedArgs& b, int S, hipStream_t st) {
 }  // namespace
 
 // b.mc <= 65535 (grid.y of the first launch) and S <= 4096: the callers' chunking and checks see to it
+// b.a.step == ACQ_STEP_MES needs b.a.feat == 0 (hbo_internal.h: AcqSmallArgs::step); no MES kernel exists for an MLP basis
 void launch_acq_blocked(int dtype, const AcqBlockedArgs& b, int S, hipStream_t st) {
   if (b.mc <= 0 || S <= 0 || b.ldv <= 0) return;
+  assert(!(b.a.step == ACQ_STEP_MES && b.a.feat != 0) && "the MES step has no instantiation for an MLP basis");
   if (dtype == HBO_F64) launch_blocked_t<double>(b, S, st);
   else launch_blocked_t<float>(b, S, st);
 }

@@ -117,35 +117,32 @@ namespace {
 constexpr size_t ACQ_BLOCKED_WS_BYTES = (size_t)256 << 20;
 constexpr int64_t ACQ_BLOCKED_MAX_CHUNK = 65535;   // grid.y of the first launch
 }  // namespace
-// (api_internal.h: AcqSamplesMode.  mes -- hbo_mes_grad_samples, mes.hip: the S x K maxima ride up behind the per-feature values and the
-//  kernels take the MES scalar step; acq_id and params are then not read.  mode.logei -- hbo_logei_grad_samples, logei.hip: params holds
-//  the S targets and the kernels take the LogEI scalar step; acq_id is not read)
-int acq_grad_samples(hbo_ctx* c, const AcqSamplesMode& mode, const hbo_model* models, int32_t S, hbo_cache* const* caches, const void* xq,
-                     int64_t M, int acq_id, const double* params, const MesReq* mes, const double* add_noise, double scale, void* acq_out,
-                     double* grad_out, double* val64_out) {
-  const std::string fn = std::string(mode.fn) + ": ";
-  if (!models || !caches || !xq || (mes ? !mes->ystar : !params) || !add_noise || !acq_out || !grad_out) return fail(c, HBO_ERR_ARG, fn + "null argument");
+// (api_internal.h: AcqRoute, AcqWhat.  The MES step -- hbo_mes_grad_samples, mes.hip: the S x K maxima ride up behind the per-feature
+//  values.  The LogEI step -- hbo_logei_grad_samples, logei.hip: the S targets ride in the records where the registry's parameters do)
+int acq_grad_samples(hbo_ctx* c, const AcqRoute& route, const AcqWhat& what, const hbo_model* models, int32_t S, hbo_cache* const* caches,
+                     const void* xq, int64_t M, const double* add_noise, double scale, void* acq_out, double* grad_out, double* val64_out) {
+  const std::string fn = std::string(route.fn) + ": ";
+  if (!models || !caches || !xq || !what.given() || !add_noise || !acq_out || !grad_out) return fail(c, HBO_ERR_ARG, fn + "null argument");
   if (S <= 0 || S > 4096) return fail(c, HBO_ERR_ARG, fn + "1 <= S <= 4096");
-  if (mes) { if (int rc = mes_check(c, fn, *mes, S)) return rc; }
-  else if (mode.logei) { if (int rc = logei_check(c, fn, params, S)) return rc; }
-  else if (acq_id < 0 || acq_id > HBO_ACQ_UCB) return fail(c, HBO_ERR_ARG, fn + "bad acq_id");
+  if (int rc = acq_what_check(c, fn, what, S)) return rc;
   if (!c) return fail(c, HBO_ERR_ARG, fn + "ctx is null");
   if (M < 0) return fail(c, HBO_ERR_ARG, fn + "M < 0");
   const hbo_model* m0 = &models[0];
+  const bool mes = what.step == ACQ_STEP_MES;
   bool any_bad = false;
-  if (int rc = acq_samples_check(c, fn, models, S, caches, mode.max_n, &any_bad, mode.allow_mlp)) return rc;
+  if (int rc = acq_samples_check(c, fn, models, S, caches, route.max_n, &any_bad, route.allow_mlp)) return rc;
   if (M == 0) return HBO_OK;
   HIPCHK(c, hipSetDevice(c->device));
   const int dtype = m0->dtype, D = m0->input_dim;
   const size_t es = esize(dtype);
   hipStream_t st = c->stream;
   const int ldv = acq_blocked_ldv(S, caches);
-  const bool blocked = mode.force_blocked || ldv > HBO_TILE;
+  const bool blocked = route.force_blocked || ldv > HBO_TILE;
   // one block up: [S records][S x 2 D doubles + (MES) S x K maxima][M x D queries][(MLP basis) the S weight sets and their address
   // tables]; one block down: [S x M x D doubles][S x M values]
   const AcqVecWidths vw = acq_vec_widths(m0);   // (without an MLP: D and D)
   const AcqMlpPack mlp = acq_mlp_layout(m0, S);
-  const size_t hv_b = sizeof(double) * ((size_t)vw.fdim + vw.mdim) * S, ys_b = mes ? sizeof(double) * (size_t)S * mes->K : 0;
+  const size_t hv_b = sizeof(double) * ((size_t)vw.fdim + vw.mdim) * S, ys_b = mes ? sizeof(double) * (size_t)S * what.K : 0;
   const size_t smp_b = align256(sizeof(AcqSmallSample) * S), vec_b = align256(hv_b + ys_b);
   const size_t xq_b = mlp.bytes ? align256((size_t)M * D * es) + mlp.bytes : (size_t)M * D * es, o_mlp = smp_b + vec_b + align256((size_t)M * D * es);
   const size_t grad_b = align256(sizeof(double) * (size_t)S * M * D), acq_b = (size_t)S * M * es;
@@ -158,7 +155,7 @@ int acq_grad_samples(hbo_ctx* c, const AcqSamplesMode& mode, const hbo_model* mo
   double* d_work = nullptr;
   if (blocked) {
     const size_t per_query = sizeof(double) * (size_t)S * (3 * (size_t)ldv + mlp.ftot);   // k, l, beta and (MLP basis) the activations
-    chunk = mode.chunk_queries > 0 ? mode.chunk_queries : std::max<int64_t>(1, (int64_t)(ACQ_BLOCKED_WS_BYTES / per_query));
+    chunk = route.chunk_queries > 0 ? route.chunk_queries : std::max<int64_t>(1, (int64_t)(ACQ_BLOCKED_WS_BYTES / per_query));
     chunk = std::min(std::min(chunk, M), ACQ_BLOCKED_MAX_CHUNK);
     d_work = static_cast<double*>(ws_get(c, WS_AB_WORK, per_query * (size_t)chunk));
     if (!d_work) return HBO_ERR_HIP;
@@ -168,18 +165,17 @@ int acq_grad_samples(hbo_ctx* c, const AcqSamplesMode& mode, const hbo_model* mo
   char* stage_out = stage + align256(in_b);
   AcqSmallSample* hs = reinterpret_cast<AcqSmallSample*>(stage);
   double* hv = reinterpret_cast<double*>(stage + smp_b);
-  acq_small_pack(hs, hv, models, S, caches, params, add_noise);
-  if (mes) memcpy(stage + smp_b + hv_b, mes->ystar, ys_b);
+  acq_small_pack(hs, hv, models, S, caches, what.params, add_noise);
+  if (mes) memcpy(stage + smp_b + hv_b, what.ystar, ys_b);
   memcpy(stage + smp_b + vec_b, xq, (size_t)M * D * es);
   AcqSmallArgs a = {};
   acq_mlp_fill(mlp, stage + o_mlp, d_in + o_mlp, models, S, a);
   HIPCHK(c, stage_upload(c, d_in, stage, in_b, st));
   a.smp = reinterpret_cast<const AcqSmallSample*>(d_in); a.vec = reinterpret_cast<const double*>(d_in + smp_b); a.xq = d_in + smp_b + vec_b;
-  a.D = D; a.M = M; a.kernel_id = m0->kernel_id; a.mean_id = m0->mean_id; a.acq_id = acq_id; a.scale = scale;
+  a.D = D; a.M = M; a.kernel_id = m0->kernel_id; a.mean_id = m0->mean_id; a.step = what.step; a.acq_id = what.acq_id; a.scale = scale;
   a.grad_out = reinterpret_cast<double*>(d_out); a.acq_out = d_out + grad_b;
   if (val64_out) a.val64_out = reinterpret_cast<double*>(d_out + v64_o);
-  if (mes) { a.ystar = reinterpret_cast<const double*>(d_in + smp_b + hv_b); a.K = mes->K; }
-  a.logei = mode.logei;
+  if (mes) { a.ystar = reinterpret_cast<const double*>(d_in + smp_b + hv_b); a.K = what.K; }
   if (!blocked) launch_acq_small(dtype, a, S, st);
   else {
     AcqBlockedArgs b = {};
@@ -204,32 +200,31 @@ int acq_grad_samples(hbo_ctx* c, const AcqSamplesMode& mode, const hbo_model* mo
 extern "C" int hbo_acq_grad_samples(hbo_ctx* c, const hbo_model* models, int32_t S, hbo_cache* const* caches, const void* xq, int64_t M,
                                     int acq_id, const double* params, const double* add_noise, double scale, void* acq_out,
                                     double* grad_out) {
-  const AcqSamplesMode mode = {"hbo_acq_grad_samples", HBO_TILE, false, 0, false};
-  return acq_grad_samples(c, mode, models, S, caches, xq, M, acq_id, params, nullptr, add_noise, scale, acq_out, grad_out, nullptr);
+  return acq_grad_samples(c, ACQ_ROUTE_SMALL.named("hbo_acq_grad_samples"), acq_what_registry(acq_id, params), models, S, caches, xq, M, add_noise,
+                          scale, acq_out, grad_out, nullptr);
 }
 extern "C" int hbo_acq_grad_samples_blocked(hbo_ctx* c, const hbo_model* models, int32_t S, hbo_cache* const* caches, const void* xq,
                                             int64_t M, int acq_id, const double* params, const double* add_noise, double scale,
                                             void* acq_out, double* grad_out) {
-  const AcqSamplesMode mode = {"hbo_acq_grad_samples_blocked", INT_MAX, false, 0, false};
-  return acq_grad_samples(c, mode, models, S, caches, xq, M, acq_id, params, nullptr, add_noise, scale, acq_out, grad_out, nullptr);
+  return acq_grad_samples(c, ACQ_ROUTE_BLOCKED.named("hbo_acq_grad_samples_blocked"), acq_what_registry(acq_id, params), models, S, caches, xq, M,
+                          add_noise, scale, acq_out, grad_out, nullptr);
 }
 // include/hbo_tune.h (TEST HOOK): hbo_acq_grad_samples with the fp64 values hbo_acq_maximize's control kernel reads
 extern "C" int hbo_probe_acq_grad_samples64(hbo_ctx* c, const hbo_model* models, int32_t S, hbo_cache* const* caches, const void* xq, int64_t M,
                                             int acq_id, const double* params, const double* add_noise, double scale, void* acq_out,
                                             double* grad_out, double* val64_out) {
-  if (!val64_out) return fail(c, HBO_ERR_ARG, "hbo_probe_acq_grad_samples64: val64_out is null");
-  const AcqSamplesMode mode = {"hbo_acq_grad_samples", HBO_TILE, false, 0, false};
-  return acq_grad_samples(c, mode, models, S, caches, xq, M, acq_id, params, nullptr, add_noise, scale, acq_out, grad_out, val64_out);
+  if (int rc = acq_probe_check(c, "hbo_probe_acq_grad_samples64", val64_out, 0)) return rc;
+  return acq_grad_samples(c, ACQ_ROUTE_SMALL.named("hbo_acq_grad_samples"), acq_what_registry(acq_id, params), models, S, caches, xq, M, add_noise,
+                          scale, acq_out, grad_out, val64_out);
 }
 // include/hbo_tune.h (TEST HOOK): hbo_acq_grad_samples_blocked with those values, the blocked kernels on request and a chunk size
 extern "C" int hbo_probe_acq_grad_samples_blocked64(hbo_ctx* c, const hbo_model* models, int32_t S, hbo_cache* const* caches, const void* xq,
                                                     int64_t M, int acq_id, const double* params, const double* add_noise, double scale,
                                                     void* acq_out, double* grad_out, int32_t force_blocked, int64_t chunk_queries,
                                                     double* val64_out) {
-  if (!val64_out) return fail(c, HBO_ERR_ARG, "hbo_probe_acq_grad_samples_blocked64: val64_out is null");
-  if (chunk_queries < 0) return fail(c, HBO_ERR_ARG, "hbo_probe_acq_grad_samples_blocked64: chunk_queries < 0");
-  const AcqSamplesMode mode = {"hbo_acq_grad_samples_blocked", INT_MAX, force_blocked != 0, chunk_queries, false};
-  return acq_grad_samples(c, mode, models, S, caches, xq, M, acq_id, params, nullptr, add_noise, scale, acq_out, grad_out, val64_out);
+  if (int rc = acq_probe_check(c, "hbo_probe_acq_grad_samples_blocked64", val64_out, chunk_queries)) return rc;
+  return acq_grad_samples(c, ACQ_ROUTE_BLOCKED.probed("hbo_acq_grad_samples_blocked", force_blocked, chunk_queries), acq_what_registry(acq_id, params),
+                          models, S, caches, xq, M, add_noise, scale, acq_out, grad_out, val64_out);
 }
 // ---- the same with MLP-basis kernels and linear_mlp means served (acq_mlp.h): the pair's workgroup runs the forward and backward pass
 //      itself (n <= 128: still ONE launch; otherwise a forward launch in front of the four: five per chunk).  The S weight sets ride up
@@ -237,16 +232,15 @@ extern "C" int hbo_probe_acq_grad_samples_blocked64(hbo_ctx* c, const hbo_model*
 extern "C" int hbo_acq_grad_samples_mlp(hbo_ctx* c, const hbo_model* models, int32_t S, hbo_cache* const* caches, const void* xq, int64_t M,
                                         int acq_id, const double* params, const double* add_noise, double scale, void* acq_out,
                                         double* grad_out) {
-  const AcqSamplesMode mode = {"hbo_acq_grad_samples_mlp", INT_MAX, false, 0, true};
-  return acq_grad_samples(c, mode, models, S, caches, xq, M, acq_id, params, nullptr, add_noise, scale, acq_out, grad_out, nullptr);
+  return acq_grad_samples(c, ACQ_ROUTE_MLP.named("hbo_acq_grad_samples_mlp"), acq_what_registry(acq_id, params), models, S, caches, xq, M, add_noise,
+                          scale, acq_out, grad_out, nullptr);
 }
 // include/hbo_tune.h (TEST HOOK): hbo_acq_grad_samples_mlp with the fp64 values, the blocked kernels on request and a chunk size
 extern "C" int hbo_probe_acq_grad_samples_mlp64(hbo_ctx* c, const hbo_model* models, int32_t S, hbo_cache* const* caches, const void* xq,
                                                 int64_t M, int acq_id, const double* params, const double* add_noise, double scale,
                                                 void* acq_out, double* grad_out, int32_t force_blocked, int64_t chunk_queries,
                                                 double* val64_out) {
-  if (!val64_out) return fail(c, HBO_ERR_ARG, "hbo_probe_acq_grad_samples_mlp64: val64_out is null");
-  if (chunk_queries < 0) return fail(c, HBO_ERR_ARG, "hbo_probe_acq_grad_samples_mlp64: chunk_queries < 0");
-  const AcqSamplesMode mode = {"hbo_acq_grad_samples_mlp", INT_MAX, force_blocked != 0, chunk_queries, true};
-  return acq_grad_samples(c, mode, models, S, caches, xq, M, acq_id, params, nullptr, add_noise, scale, acq_out, grad_out, val64_out);
+  if (int rc = acq_probe_check(c, "hbo_probe_acq_grad_samples_mlp64", val64_out, chunk_queries)) return rc;
+  return acq_grad_samples(c, ACQ_ROUTE_MLP.probed("hbo_acq_grad_samples_mlp", force_blocked, chunk_queries), acq_what_registry(acq_id, params), models,
+                          S, caches, xq, M, add_noise, scale, acq_out, grad_out, val64_out);
 }

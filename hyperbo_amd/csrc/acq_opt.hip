@@ -103,31 +103,30 @@ extern "C" int64_t hbo_acq_opt_state_doubles(int32_t D, int32_t memory) {
   return hbo_acq_opt_state_size(D, memory);
 }
 
-// The body of hbo_acq_maximize and hbo_acq_maximize_blocked: they differ in the largest cache they take (max_n) and, with it, in the
-// evaluation step -- one launch of acq_small.hip when every cache has n <= 128, the four launches of acq_blocked.hip otherwise.
-// (mes -- hbo_mes_maximize, mes.hip: the S x K maxima ride up behind the box and the evaluation takes the MES scalar step; acq_id and
-//  params are then not read)
-// (allow_mlp -- hbo_acq_maximize_mlp: MLP-basis kernels and linear_mlp means are served; the S weight sets ride up between the pending
-//  points and the states, the evaluation runs the pair's forward and backward pass (acq_mlp.h) and the control kernel sees raw points
-//  and raw gradients as ever)
-// (logei -- hbo_logei_maximize, logei.hip: params holds the S targets, the evaluation takes the LogEI scalar step and the control kernel
-//  combines the samples as the log of the mean of their exponentials (acq_opt_ctl.h: HBO_ACQ_OPT_REDUCE_LME); acq_id is not read)
-int acq_maximize(hbo_ctx* c, const char* name, int max_n, bool allow_mlp, const hbo_model* models, int32_t S, hbo_cache* const* caches,
-                 const void* x0, int32_t R, const double* lo, const double* hi, int acq_id, const double* params, const MesReq* mes,
-                 const double* add_noise, double scale, const hbo_acq_opt_opts* opts, double* state, int32_t evals, double* x_out, double* val_out,
-                 int32_t* status, hbo_acq_opt_eval* log, bool logei) {
-  const std::string fn = std::string(name) + ": ";
-  if (!models || !caches || !x0 || (mes ? !mes->ystar : !params) || !add_noise || !state || !x_out || !val_out || !status) return fail(c, HBO_ERR_ARG, fn + "null argument");
+// The body of the maximisers (api_internal.h: AcqRoute, AcqWhat).  The routes differ in the largest cache they take (route.max_n) and,
+// with it, in the evaluation step -- one launch of acq_small.hip when every cache has n <= 128, the four launches of acq_blocked.hip
+// otherwise.
+// (route.allow_mlp -- hbo_acq_maximize_mlp: MLP-basis kernels and linear_mlp means are served; the S weight sets ride up between the
+//  pending points and the states, the evaluation runs the pair's forward and backward pass (acq_mlp.h) and the control kernel sees raw
+//  points and raw gradients as ever)
+// (the MES step -- hbo_mes_maximize, mes.hip: the S x K maxima ride up behind the box)
+// (the LogEI step -- hbo_logei_maximize, logei.hip: the S targets ride in the records where the registry's parameters do, and the control
+//  kernel combines the samples as the log of the mean of their exponentials (acq_opt_ctl.h: HBO_ACQ_OPT_REDUCE_LME))
+int acq_maximize(hbo_ctx* c, const AcqRoute& route, const AcqWhat& what, const hbo_model* models, int32_t S, hbo_cache* const* caches,
+                 const void* x0, int32_t R, const double* lo, const double* hi, const double* add_noise, double scale,
+                 const hbo_acq_opt_opts* opts, double* state, int32_t evals, double* x_out, double* val_out, int32_t* status,
+                 hbo_acq_opt_eval* log) {
+  const std::string fn = std::string(route.fn) + ": ";
+  const bool mes = what.step == ACQ_STEP_MES, logei = what.step == ACQ_STEP_LOGEI;
+  if (!models || !caches || !x0 || !what.given() || !add_noise || !state || !x_out || !val_out || !status) return fail(c, HBO_ERR_ARG, fn + "null argument");
   if (S <= 0 || S > 4096) return fail(c, HBO_ERR_ARG, fn + "1 <= S <= 4096");
-  if (mes) { if (int rc = mes_check(c, fn, *mes, S)) return rc; }
-  else if (logei) { if (int rc = logei_check(c, fn, params, S)) return rc; }
-  else if (acq_id < 0 || acq_id > HBO_ACQ_UCB) return fail(c, HBO_ERR_ARG, fn + "bad acq_id");
+  if (int rc = acq_what_check(c, fn, what, S)) return rc;
   if (!c) return fail(c, HBO_ERR_ARG, fn + "ctx is null");
   if (R <= 0 || R > 4096) return fail(c, HBO_ERR_ARG, fn + "1 <= R <= 4096");
   if (evals <= 0 || evals > 4096) return fail(c, HBO_ERR_ARG, fn + "1 <= evals <= 4096");
   if (int rc = acq_opt_check_opts(c, fn, opts)) return rc;
   bool any_bad = false;
-  if (int rc = acq_samples_check(c, fn, models, S, caches, max_n, &any_bad, allow_mlp)) return rc;
+  if (int rc = acq_samples_check(c, fn, models, S, caches, route.max_n, &any_bad, route.allow_mlp)) return rc;
   const hbo_model* m0 = &models[0];
   const int dtype = m0->dtype, D = m0->input_dim;
   if (int rc = acq_opt_check_box(c, fn, lo, hi, D, dtype)) return rc;
@@ -162,7 +161,7 @@ int acq_maximize(hbo_ctx* c, const char* name, int max_n, bool allow_mlp, const 
   // one block up: [S records][S x 2 D doubles][lo, hi][R x D pending points][R states]; the log follows the states, and one copy brings
   // [states | log] back.  Scratch of the rounds: [S x R x D gradients][S x R values fp64][S x R values in the model dtype]
   // (MES: the S x K maxima sit behind the box, in its part of the block)
-  const size_t ys_b = mes ? sizeof(double) * (size_t)S * mes->K : 0;
+  const size_t ys_b = mes ? sizeof(double) * (size_t)S * what.K : 0;
   const size_t smp_b = align256(sizeof(AcqSmallSample) * S), vec_b = align256(sizeof(double) * ((size_t)vw.fdim + vw.mdim) * S), box_b = align256(sizeof(double) * 2 * D + ys_b);
   const size_t pend_b = align256((size_t)R * D * es), state_b = align256(sizeof(double) * (size_t)R * ns);
   const size_t log_b = log ? sizeof(hbo_acq_opt_eval) * (size_t)evals * R : 0;
@@ -175,10 +174,10 @@ int acq_maximize(hbo_ctx* c, const char* name, int max_n, bool allow_mlp, const 
   if (blocked && !d_work) return HBO_ERR_HIP;
   char* stage = static_cast<char*>(stage_begin(c, fn.c_str(), up_b + log_b));
   if (!stage) return HBO_ERR_HIP;
-  acq_small_pack(reinterpret_cast<AcqSmallSample*>(stage), reinterpret_cast<double*>(stage + smp_b), models, S, caches, params, add_noise);
+  acq_small_pack(reinterpret_cast<AcqSmallSample*>(stage), reinterpret_cast<double*>(stage + smp_b), models, S, caches, what.params, add_noise);
   double* hbox = reinterpret_cast<double*>(stage + smp_b + vec_b);
   for (int i = 0; i < D; ++i) { hbox[i] = lo ? lo[i] : 0.0; hbox[D + i] = hi ? hi[i] : 1.0; }
-  if (mes) memcpy(hbox + 2 * D, mes->ystar, ys_b);
+  if (mes) memcpy(hbox + 2 * D, what.ystar, ys_b);
   // the states go up from a copy, and a fresh one is started in that copy: the caller's array is written once, by the copy back, so a
   // call that fails on the way (an argument, an allocation, the device) leaves it as it was
   double* hstate = reinterpret_cast<double*>(stage + o_state);
@@ -205,10 +204,9 @@ int acq_maximize(hbo_ctx* c, const char* name, int max_n, bool allow_mlp, const 
 
   a.smp = reinterpret_cast<const AcqSmallSample*>(d_in); a.vec = reinterpret_cast<const double*>(d_in + smp_b);
   a.xq = d_in + smp_b + vec_b + box_b;
-  a.D = D; a.M = R; a.kernel_id = m0->kernel_id; a.mean_id = m0->mean_id; a.acq_id = acq_id; a.scale = scale;
+  a.D = D; a.M = R; a.kernel_id = m0->kernel_id; a.mean_id = m0->mean_id; a.step = what.step; a.acq_id = what.acq_id; a.scale = scale;
   a.grad_out = reinterpret_cast<double*>(d_out); a.val64_out = reinterpret_cast<double*>(d_out + grad_b); a.acq_out = d_out + grad_b + val_b;
-  if (mes) { a.ystar = reinterpret_cast<const double*>(d_in + smp_b + vec_b) + 2 * D; a.K = mes->K; }
-  a.logei = logei;
+  if (mes) { a.ystar = reinterpret_cast<const double*>(d_in + smp_b + vec_b) + 2 * D; a.K = what.K; }
   AcqOptArgs k = {};
   k.reduce = logei ? HBO_ACQ_OPT_REDUCE_LME : HBO_ACQ_OPT_REDUCE_MEAN;
   k.o = acq_opt_ctl_opts(opts);
@@ -247,22 +245,22 @@ extern "C" int hbo_acq_maximize(hbo_ctx* c, const hbo_model* models, int32_t S, 
                                 const double* lo, const double* hi, int acq_id, const double* params, const double* add_noise, double scale,
                                 const hbo_acq_opt_opts* opts, double* state, int32_t evals, double* x_out, double* val_out, int32_t* status,
                                 hbo_acq_opt_eval* log) {
-  return acq_maximize(c, "hbo_acq_maximize", HBO_TILE, false, models, S, caches, x0, R, lo, hi, acq_id, params, nullptr, add_noise, scale, opts, state, evals,
-                      x_out, val_out, status, log);
+  return acq_maximize(c, ACQ_ROUTE_SMALL.named("hbo_acq_maximize"), acq_what_registry(acq_id, params), models, S, caches, x0, R, lo, hi, add_noise,
+                      scale, opts, state, evals, x_out, val_out, status, log);
 }
 extern "C" int hbo_acq_maximize_blocked(hbo_ctx* c, const hbo_model* models, int32_t S, hbo_cache* const* caches, const void* x0, int32_t R,
                                         const double* lo, const double* hi, int acq_id, const double* params, const double* add_noise,
                                         double scale, const hbo_acq_opt_opts* opts, double* state, int32_t evals, double* x_out,
                                         double* val_out, int32_t* status, hbo_acq_opt_eval* log) {
-  return acq_maximize(c, "hbo_acq_maximize_blocked", INT_MAX, false, models, S, caches, x0, R, lo, hi, acq_id, params, nullptr, add_noise, scale, opts, state,
-                      evals, x_out, val_out, status, log);
+  return acq_maximize(c, ACQ_ROUTE_BLOCKED.named("hbo_acq_maximize_blocked"), acq_what_registry(acq_id, params), models, S, caches, x0, R, lo, hi,
+                      add_noise, scale, opts, state, evals, x_out, val_out, status, log);
 }
 extern "C" int hbo_acq_maximize_mlp(hbo_ctx* c, const hbo_model* models, int32_t S, hbo_cache* const* caches, const void* x0, int32_t R,
                                     const double* lo, const double* hi, int acq_id, const double* params, const double* add_noise,
                                     double scale, const hbo_acq_opt_opts* opts, double* state, int32_t evals, double* x_out,
                                     double* val_out, int32_t* status, hbo_acq_opt_eval* log) {
-  return acq_maximize(c, "hbo_acq_maximize_mlp", INT_MAX, true, models, S, caches, x0, R, lo, hi, acq_id, params, nullptr, add_noise, scale, opts, state,
-                      evals, x_out, val_out, status, log);
+  return acq_maximize(c, ACQ_ROUTE_MLP.named("hbo_acq_maximize_mlp"), acq_what_registry(acq_id, params), models, S, caches, x0, R, lo, hi, add_noise,
+                      scale, opts, state, evals, x_out, val_out, status, log);
 }
 
 // include/hbo_tune.h (TEST HOOK): the control code of acq_opt_ctl.h on the host, one thread, for one evaluation of one start

@@ -9,9 +9,11 @@
 // on which samples or queries share the launch.  The scalar functions are those of kernfun.h.
 #include "acq_mlp.h"
 
+#include <assert.h>
+
 namespace {
-// STEP, the scalar step (hbo_internal.h: ACQ_STEP_*): acq_scalars by a.acq_id; mes_scalars_block over the sample's K maxima (a.ystar;
-// hbo_mes_grad_samples); logei_scalars against the sample's target (sm.param; hbo_logei_grad_samples), per thread like the first
+// STEP, the scalar step (hbo_internal.h: ACQ_STEP_*; kernfun.h: acq_scalar_step): acq_scalars by a.acq_id; mes_scalars_block over the
+// sample's K maxima (a.ystar; hbo_mes_grad_samples); logei_scalars against the sample's target (sm.param; hbo_logei_grad_samples)
 // FEAT (acq_mlp.h; hbo_acq_grad_samples_mlp): 0 -- no MLP basis; otherwise ACQ_FEAT_KERNEL | ACQ_FEAT_MEAN, who reads the last layer.
 // The pair's workgroup then runs the forward pass first, works in the kernel's own space of width D = fdim below, takes the mean in
 // the mean's own space and ends with the backward pass (acq_mlp_tail).
@@ -21,7 +23,6 @@ __global__ __launch_bounds__(256) void acq_small_kernel(AcqSmallArgs a) {
   __shared__ double s_k[HBO_TILE], s_l[HBO_TILE], s_w[HBO_TILE];
   __shared__ double s_acc[256];   // beta's two row-parity partials, then the gradient's partials per row group
   __shared__ double sred[4];
-  __shared__ double s_amu, s_avar;
   const int64_t q = blockIdx.x;
   const int s = blockIdx.y;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -114,26 +115,8 @@ __global__ __launch_bounds__(256) void acq_small_kernel(AcqSmallArgs a) {
     s_acc[tid] = b;
   }
   double amu, avar;
-  if constexpr (STEP == ACQ_STEP_MES) {
-    __shared__ double s_mes[3 * HBO_MES_MAX_K], s_mes_sum[3];
-    const AcqScalars sc = mes_scalars_block(ka + mean, kqq - ll, sm.add_noise, a.scale, a.ystar + (int64_t)s * a.K, a.K, s_mes, s_mes_sum);
-    if (tid == 0) {
-      *acq = (T)sc.val;
-      if (a.val64_out) a.val64_out[(int64_t)s * a.M + q] = sc.val;
-    }
-    __syncthreads();   // (s_acc is read next, and mes_scalars_block leaves without a barrier when v2 <= 0)
-    amu = sc.amu; avar = sc.avar;
-  } else {
-    if (tid == 0) {   // (STEP is a constant: one of the two is compiled)
-      const AcqScalars sc = STEP == ACQ_STEP_LOGEI ? logei_scalars(ka + mean, kqq - ll, sm.add_noise, a.scale, sm.param)
-                                                   : acq_scalars(a.acq_id, ka + mean, kqq - ll, sm.add_noise, a.scale, sm.param);
-      s_amu = sc.amu; s_avar = sc.avar;
-      *acq = (T)sc.val;
-      if (a.val64_out) a.val64_out[(int64_t)s * a.M + q] = sc.val;
-    }
-    __syncthreads();
-    amu = s_amu; avar = s_avar;
-  }
+  acq_scalar_step<T, STEP>(a, sm, s, q, ka + mean, kqq - ll, acq, amu, avar);
+  if constexpr (STEP == ACQ_STEP_MES) __syncthreads();   // (s_acc is read next, and mes_scalars_block leaves without a barrier when v2 <= 0)
   // ---- w_i = coef_i * (dk/du_i * 2 | 1 / sigma^2)
   if (tid < n) {
     const double beta = s_acc[tid] + s_acc[HBO_TILE + tid];
@@ -180,21 +163,21 @@ void launch_small_f(const AcqSmallArgs& a, const dim3& grid, hipStream_t st) {
     default: hipLaunchKernelGGL((acq_small_kernel<T, STEP, ACQ_FEAT_KERNEL | ACQ_FEAT_MEAN>), grid, dim3(256), 0, st, a); break;
   }
 }
+template <typename T>
+void launch_small_t(const AcqSmallArgs& a, const dim3& grid, hipStream_t st) {
+  switch (a.step) {
+    case ACQ_STEP_MES: hipLaunchKernelGGL((acq_small_kernel<T, ACQ_STEP_MES, 0>), grid, dim3(256), 0, st, a); break;
+    case ACQ_STEP_LOGEI: launch_small_f<T, ACQ_STEP_LOGEI>(a, grid, st); break;
+    default: launch_small_f<T, ACQ_STEP_REGISTRY>(a, grid, st); break;
+  }
+}
 }  // namespace
 
+// a.step == ACQ_STEP_MES needs a.feat == 0 (hbo_internal.h: AcqSmallArgs::step); no MES kernel exists for an MLP basis
 void launch_acq_small(int dtype, const AcqSmallArgs& a, int S, hipStream_t st) {
   if (a.M <= 0 || S <= 0) return;
+  assert(!(a.step == ACQ_STEP_MES && a.feat != 0) && "the MES step has no instantiation for an MLP basis");
   const dim3 grid((unsigned)a.M, (unsigned)S);
-  if (a.ystar) {   // (the MES entry points refuse MLP models: a.feat is 0)
-    if (dtype == HBO_F64) hipLaunchKernelGGL((acq_small_kernel<double, ACQ_STEP_MES, 0>), grid, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((acq_small_kernel<float, ACQ_STEP_MES, 0>), grid, dim3(256), 0, st, a);
-    return;
-  }
-  if (a.logei) {
-    if (dtype == HBO_F64) launch_small_f<double, ACQ_STEP_LOGEI>(a, grid, st);
-    else launch_small_f<float, ACQ_STEP_LOGEI>(a, grid, st);
-    return;
-  }
-  if (dtype == HBO_F64) launch_small_f<double, ACQ_STEP_REGISTRY>(a, grid, st);
-  else launch_small_f<float, ACQ_STEP_REGISTRY>(a, grid, st);
+  if (dtype == HBO_F64) launch_small_t<double>(a, grid, st);
+  else launch_small_t<float>(a, grid, st);
 }

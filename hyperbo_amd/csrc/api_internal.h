@@ -432,7 +432,7 @@ struct hbo_cache {
 // (HBO_TILE: the one-block entry points; INT_MAX: the _blocked ones).  *any_bad: a cache is not positive definite.
 // allow_mlp (the _mlp entry points): the two MLP refusals are skipped, everything else stays.
 static int acq_samples_check(hbo_ctx* c, const std::string& fn, const hbo_model* models, int32_t S, hbo_cache* const* caches, int max_n, bool* any_bad,
-                             bool allow_mlp = false) {
+                             bool allow_mlp) {
   if (int rc = model_family_check(c, fn, models, S, "evaluate the samples with hbo_acq_grad")) return rc;
   for (int s = 0; s < S; ++s) {
     const hbo_model* m = &models[s];
@@ -448,48 +448,69 @@ static int acq_samples_check(hbo_ctx* c, const std::string& fn, const hbo_model*
   return HBO_OK;
 }
 
-// ---- max-value entropy search (mes.hip) --------------------------------------------------------
-// The bodies of the acquisition entry points take it as an optional request: ystar [S][K] (hbo_acq_mes: [K]) on the host in the place
-// of acq_id and the per-sample parameter.
-struct MesReq { const double* ystar; int32_t K; };
-// K in 1..HBO_MES_MAX_K and `count` finite maxima (ystar is not null); touches no device (c may be null)
-static int mes_check(hbo_ctx* c, const std::string& fn, const MesReq& r, int64_t count) {
-  if (r.K < 1 || r.K > HBO_MES_MAX_K) return fail(c, HBO_ERR_ARG, fn + "1 <= K <= " + std::to_string(HBO_MES_MAX_K));
-  for (int64_t i = 0; i < count * r.K; ++i) if (!isfinite(r.ystar[i])) return fail(c, HBO_ERR_ARG, fn + "ystar holds a value that is not finite");
-  return HBO_OK;
+// ---- which acquisition a call asks for, and by which route --------------------------------------
+// AcqWhat: what the entry points over finished caches and posterior() (cache.hip) evaluate.  `step` is the scalar step of the kernels of
+// acq_small.hip / acq_blocked.hip and the epilogue of posterior() (hbo_internal.h: ACQ_STEP_*); the other fields are the host arrays the
+// step reads, per sample: REGISTRY -- acq_id and params [S]; MES -- ystar [S][K], the sampled maxima; LOGEI -- params [S], the targets.
+struct AcqWhat {
+  int step, acq_id;
+  const double* params;
+  const double* ystar; int32_t K;
+  const double* given() const { return step == ACQ_STEP_MES ? ystar : params; }   // the array the caller must have passed
+};
+static AcqWhat acq_what_registry(int acq_id, const double* params) { return {ACQ_STEP_REGISTRY, acq_id, params, nullptr, 0}; }
+static AcqWhat acq_what_mes(const double* ystar, int32_t K) { return {ACQ_STEP_MES, 0, nullptr, ystar, K}; }
+static AcqWhat acq_what_logei(const double* targets) { return {ACQ_STEP_LOGEI, 0, targets, nullptr, 0}; }
+// The request over `count` samples (given() is not null): acq_id in the registry; K in 1..HBO_MES_MAX_K and finite maxima; finite
+// targets.  Touches no device (c may be null).
+static int acq_what_check(hbo_ctx* c, const std::string& fn, const AcqWhat& w, int64_t count) {
+  switch (w.step) {
+    case ACQ_STEP_MES:
+      if (w.K < 1 || w.K > HBO_MES_MAX_K) return fail(c, HBO_ERR_ARG, fn + "1 <= K <= " + std::to_string(HBO_MES_MAX_K));
+      for (int64_t i = 0; i < count * w.K; ++i) if (!isfinite(w.ystar[i])) return fail(c, HBO_ERR_ARG, fn + "ystar holds a value that is not finite");
+      return HBO_OK;
+    case ACQ_STEP_LOGEI:
+      for (int64_t i = 0; i < count; ++i) if (!isfinite(w.params[i])) return fail(c, HBO_ERR_ARG, fn + "targets holds a value that is not finite");
+      return HBO_OK;
+    default:
+      return (w.acq_id < 0 || w.acq_id > HBO_ACQ_UCB) ? fail(c, HBO_ERR_ARG, fn + "bad acq_id") : HBO_OK;
+  }
 }
-// log expected improvement (logei.hip): `count` finite targets (not null); touches no device (c may be null)
-static int logei_check(hbo_ctx* c, const std::string& fn, const double* targets, int64_t count) {
-  for (int64_t i = 0; i < count; ++i) if (!isfinite(targets[i])) return fail(c, HBO_ERR_ARG, fn + "targets holds a value that is not finite");
-  return HBO_OK;
-}
-// the bodies of hbo_acq_grad_samples[_blocked] (acq_grad.hip) and hbo_acq_maximize[_blocked] (acq_opt.hip); mes: null for these
-struct AcqSamplesMode {
+// AcqRoute: how an entry point runs the bodies acq_grad_samples (acq_grad.hip) and acq_maximize (acq_opt.hip).  An entry point copies
+// one of the three constants and sets fn; the test hooks of include/hbo_tune.h also set force_blocked and chunk_queries.
+struct AcqRoute {
   const char* fn;          // the entry point's name in messages
   int max_n;               // the largest cache the entry point takes (acq_samples_check)
+  bool allow_mlp;          // MLP-basis kernels and linear_mlp means are served (acq_mlp.h)
   bool force_blocked;      // test hook: caches of n <= 128 through the blocked kernels too
   int64_t chunk_queries;   // test hook: > 0 overrides the chunk size
-  bool allow_mlp;          // the _mlp entry points: MLP-basis kernels and linear_mlp means are served (acq_mlp.h)
-  bool logei;              // hbo_logei_grad_samples (logei.hip): params holds the S targets, the kernels take the LogEI scalar step and
-                           // acq_id is not read
+  AcqRoute named(const char* name) const { AcqRoute r = *this; r.fn = name; return r; }
+  AcqRoute probed(const char* name, int32_t force, int64_t chunk) const { AcqRoute r = named(name); r.force_blocked = force != 0; r.chunk_queries = chunk; return r; }
 };
-int acq_grad_samples(hbo_ctx* c, const AcqSamplesMode& mode, const hbo_model* models, int32_t S, hbo_cache* const* caches, const void* xq,
-                     int64_t M, int acq_id, const double* params, const MesReq* mes, const double* add_noise, double scale, void* acq_out,
-                     double* grad_out, double* val64_out);
-int acq_maximize(hbo_ctx* c, const char* name, int max_n, bool allow_mlp, const hbo_model* models, int32_t S, hbo_cache* const* caches,
-                 const void* x0, int32_t R, const double* lo, const double* hi, int acq_id, const double* params, const MesReq* mes,
-                 const double* add_noise, double scale, const hbo_acq_opt_opts* opts, double* state, int32_t evals, double* x_out, double* val_out,
-                 int32_t* status, hbo_acq_opt_eval* log, bool logei = false);
-// hbo_acq's posterior pipeline under the MES epilogue (cache.hip); the arguments are checked by the caller (mes.hip: hbo_acq_mes)
-int posterior_mes(hbo_ctx* c, const hbo_model* m, hbo_cache* k, const void* xq, int64_t M, const MesReq& mes, double add_noise, double scale,
-                  void* out);
-// ... and under the LogEI epilogue (logei.hip: hbo_acq_logei)
-int posterior_logei(hbo_ctx* c, const hbo_model* m, hbo_cache* k, const void* xq, int64_t M, double target, double add_noise, double scale,
-                    void* out);
+constexpr AcqRoute ACQ_ROUTE_SMALL = {nullptr, HBO_TILE, false, false, 0};     // one 128-block per cache: one launch
+constexpr AcqRoute ACQ_ROUTE_BLOCKED = {nullptr, INT_MAX, false, false, 0};    // caches of any size
+constexpr AcqRoute ACQ_ROUTE_MLP = {nullptr, INT_MAX, true, false, 0};         // ... and MLP models
+// what the hooks hbo_probe_*_grad_samples*64 ask of their own two arguments; `hook` names the hook in the message
+static int acq_probe_check(hbo_ctx* c, const char* hook, const double* val64_out, int64_t chunk_queries) {
+  if (!val64_out) return fail(c, HBO_ERR_ARG, std::string(hook) + ": val64_out is null");
+  if (chunk_queries < 0) return fail(c, HBO_ERR_ARG, std::string(hook) + ": chunk_queries < 0");
+  return HBO_OK;
+}
+int acq_grad_samples(hbo_ctx* c, const AcqRoute& route, const AcqWhat& what, const hbo_model* models, int32_t S, hbo_cache* const* caches,
+                     const void* xq, int64_t M, const double* add_noise, double scale, void* acq_out, double* grad_out, double* val64_out);
+int acq_maximize(hbo_ctx* c, const AcqRoute& route, const AcqWhat& what, const hbo_model* models, int32_t S, hbo_cache* const* caches,
+                 const void* x0, int32_t R, const double* lo, const double* hi, const double* add_noise, double scale,
+                 const hbo_acq_opt_opts* opts, double* state, int32_t evals, double* x_out, double* val_out, int32_t* status,
+                 hbo_acq_opt_eval* log);
+// hbo_predict / hbo_acq / hbo_acq_mes / hbo_acq_logei / one sample of hbo_acq_samples (cache.hip).  what: one sample's request (its
+// params[0], its K maxima), read when acq_out or an override asks for the acquisition; the entry points check it (acq_what_check).
+struct PosteriorOverride;
+int posterior(hbo_ctx* c, const hbo_model* m, hbo_cache* k, const void* xq, int64_t M, int full_cov, void* mu_out, void* var_out,
+              void* acq_out, const AcqWhat& what, double add_noise, double scale, const PosteriorOverride* ov = nullptr);
 
 // the records acq_small_kernel and the kernels of acq_blocked.hip read of those pairs (hbo_internal.h: AcqSmallSample) and their
 // per-feature values, hv [S][fdim + mdim]: 1 / lengthscale over the kernel's own space, the linear mean's weights over the mean's
-// (acq_vec_widths; without an MLP both are D: [S][2 D]) (params: null under a MesReq)
+// (acq_vec_widths; without an MLP both are D: [S][2 D]) (params: null for the MES step, which reads none)
 struct AcqVecWidths { int fdim, mdim; };
 static AcqVecWidths acq_vec_widths(const hbo_model* m0) {
   return {feature_dim(m0), needs_mlp(m0) ? mean_feature_dim(m0) : m0->input_dim};

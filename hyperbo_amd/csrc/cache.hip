@@ -313,9 +313,9 @@ struct PosteriorOverride { const ModelDev* md; void* const* mlp_w; void* const* 
 struct PostCall {
   hbo_ctx* c; const hbo_model* m; hbo_cache* k;
   const ModelDev* md; void* const* mw; void* const* mb;   // the model and its MLP weights on the device
-  int acq_id; double param, add_noise, scale;
-  const double* ystar; int K;   // hbo_acq_mes: the K maxima on the device -- the acquisition is the MES epilogue (mes.hip) over mu, var
-  bool logei;                   // hbo_acq_logei: the acquisition is the LogEI epilogue (logei.hip) over mu, var; param is the target
+  AcqWhat what;                 // the caller's request with `ystar` on the DEVICE (hbo_acq_mes: the K maxima); params is not read here:
+  double param;                 // its first entry -- the registry's parameter, hbo_acq_logei's target
+  double add_noise, scale;
 };
 // one chunk's view of the workspaces: its buffer of each per-workspace array, its rows of the M-sized results
 struct PostSlice {
@@ -413,6 +413,16 @@ static void ensure_w_split(const PostCall& pc, const PostPlan& p) {
   k->w3_valid = true; k->w3_planes = p.planes;
 }
 
+// The acquisition of a chunk from the mean and variance post_epilogue_kernel (or the prior branch) left, for the steps that kernel does
+// not take itself: the MES epilogue (mes.hip), the LogEI epilogue (logei.hip).  false: the registry's step, nothing was launched.
+static bool step_epilogue(const PostCall& pc, int dtype, const PostChunk& ch, const PostSlice& s, hipStream_t st) {
+  switch (pc.what.step) {
+    case ACQ_STEP_MES: launch_mes_epilogue(dtype, s.mu, s.var, ch.mc, pc.what.ystar, pc.what.K, pc.add_noise, pc.scale, s.acq, st); return true;
+    case ACQ_STEP_LOGEI: launch_logei_epilogue(dtype, s.mu, s.var, ch.mc, pc.param, pc.add_noise, pc.scale, s.acq, st); return true;
+    default: return false;
+  }
+}
+
 // ---- producer side (sb): features, prior mean / variance, then the prior branch's results or the cross Gram into the chunk's workspace ----
 static int produce_chunk(const PostCall& pc, const PostPlan& p, const PostWs& w, const PostChunk& ch, const PostSlice& s, const void** Fq_out) {
   hbo_ctx* c = pc.c; const hbo_model* m = pc.m; hbo_cache* k = pc.k;
@@ -428,11 +438,9 @@ static int produce_chunk(const PostCall& pc, const PostPlan& p, const PostWs& w,
     } else {
       HIPCHK(c, hipMemcpyAsync(s.var, s.kd, (size_t)ch.mc * es, hipMemcpyDeviceToDevice, sb));
     }
-    if (s.acq && pc.ystar) launch_mes_epilogue(dtype, s.mu, s.var, ch.mc, pc.ystar, pc.K, pc.add_noise, pc.scale, s.acq, sb);
-    else if (s.acq && pc.logei) launch_logei_epilogue(dtype, s.mu, s.var, ch.mc, pc.param, pc.add_noise, pc.scale, s.acq, sb);
-    else if (s.acq) {   // acquisition on the prior
+    if (s.acq && !step_epilogue(pc, dtype, ch, s, sb)) {   // acquisition on the prior
       PostArgs pa = {}; pa.Kxq = nullptr; pa.n = 0; pa.nblk = 0; pa.ldq = ch.ldq; pa.alpha = nullptr; pa.colsq = nullptr;
-      pa.kdiag = s.kd; pa.muq = s.mu0; pa.acq_out = s.acq; pa.M = ch.mc; pa.acq_id = pc.acq_id; pa.param = pc.param; pa.add_noise = pc.add_noise; pa.scale = pc.scale;
+      pa.kdiag = s.kd; pa.muq = s.mu0; pa.acq_out = s.acq; pa.M = ch.mc; pa.acq_id = pc.what.acq_id; pa.param = pc.param; pa.add_noise = pc.add_noise; pa.scale = pc.scale;
       launch_post_epilogue(dtype, pa, sb);
     }
     return HBO_OK;
@@ -476,11 +484,10 @@ static void consume_chunk(const PostCall& pc, const PostPlan& p, const PostWs& w
     } }
   { ProfScope ps(c, "post_epilogue", 1, sa);
     PostArgs pa = {}; pa.Kxq = s.K; pa.ldq = ch.ldq; pa.npad = t->npad; pa.n = (int)t->n; pa.nblk = t->nblk; pa.alpha = t->svec; pa.colsq = s.colsq; pa.mupart = s.mupart;
-    pa.kdiag = s.kd; pa.muq = s.mu0; pa.mu_out = s.mu; pa.var_out = s.var; pa.acq_out = (pc.ystar || pc.logei) ? nullptr : s.acq; pa.M = ch.mc;
-    pa.acq_id = pc.acq_id; pa.param = pc.param; pa.add_noise = pc.add_noise; pa.scale = pc.scale;
+    pa.kdiag = s.kd; pa.muq = s.mu0; pa.mu_out = s.mu; pa.var_out = s.var; pa.acq_out = pc.what.step == ACQ_STEP_REGISTRY ? s.acq : nullptr; pa.M = ch.mc;
+    pa.acq_id = pc.what.acq_id; pa.param = pc.param; pa.add_noise = pc.add_noise; pa.scale = pc.scale;
     launch_post_epilogue(dtype, pa, sa);
-    if (pc.ystar) launch_mes_epilogue(dtype, s.mu, s.var, ch.mc, pc.ystar, pc.K, pc.add_noise, pc.scale, s.acq, sa);
-    else if (pc.logei) launch_logei_epilogue(dtype, s.mu, s.var, ch.mc, pc.param, pc.add_noise, pc.scale, s.acq, sa); }
+    step_epilogue(pc, dtype, ch, s, sa); }
 }
 
 // full covariance with a cache: Kqq - V^T V in the Kqq buffer
@@ -494,9 +501,8 @@ static void full_cov_tail(const PostCall& pc, const PostPlan& p, const PostWs& w
   launch_gemm(p.dtype, a, dim3(ch.mpad / HBO_TILE, ch.mpad / HBO_TILE, 1), p.sa);
 }
 
-static int posterior(hbo_ctx* c, const hbo_model* m, hbo_cache* k, const void* xq, int64_t M, int full_cov,
-                     void* mu_out, void* var_out, void* acq_out, int acq_id, double param, double add_noise,
-                     double scale, const PosteriorOverride* ov = nullptr, const MesReq* mes = nullptr, bool logei = false) {
+int posterior(hbo_ctx* c, const hbo_model* m, hbo_cache* k, const void* xq, int64_t M, int full_cov, void* mu_out, void* var_out,
+              void* acq_out, const AcqWhat& what, double add_noise, double scale, const PosteriorOverride* ov) {
   if (!c || !xq) return fail(c, HBO_ERR_ARG, "posterior: null argument");
   if (M <= 0) return HBO_OK;
   HIPCHK(c, hipSetDevice(c->device));
@@ -508,9 +514,12 @@ static int posterior(hbo_ctx* c, const hbo_model* m, hbo_cache* k, const void* x
   if (k && k->input_warp != m->input_warp) return fail(c, HBO_ERR_ARG, "posterior: the cache was factorised with another input warp");
   const size_t es = esize(dtype);
   double* d_ystar = nullptr;   // hbo_acq_mes: the maxima go up on the consumer stream, ahead of everything that reads them
-  if (mes && !(d_ystar = static_cast<double*>(ws_get(c, WS_MES_YSTAR, sizeof(double) * mes->K)))) return HBO_ERR_HIP;
-  const PostCall pc = {c, m, k, ov ? ov->md : c->d_model, ov ? ov->mlp_w : c->d_mlp_w, ov ? ov->mlp_b : c->d_mlp_b, acq_id, param, add_noise, scale,
-                       d_ystar, mes ? mes->K : 0, logei};
+  const bool mes = what.step == ACQ_STEP_MES;
+  if (mes && !(d_ystar = static_cast<double*>(ws_get(c, WS_MES_YSTAR, sizeof(double) * what.K)))) return HBO_ERR_HIP;
+  AcqWhat on_dev = what;
+  on_dev.ystar = d_ystar;
+  const PostCall pc = {c, m, k, ov ? ov->md : c->d_model, ov ? ov->mlp_w : c->d_mlp_w, ov ? ov->mlp_b : c->d_mlp_b, on_dev,
+                       what.params ? what.params[0] : 0.0, add_noise, scale};
   PostPlan p = post_plan(c, m, M, k ? k->t->nblk : 0, full_cov != 0, ov ? &ov->lane : nullptr);
   c->last_post_resident = 0;
   if (p.refuse) return fail(c, p.refuse, "posterior: full_cov limited to 65536 queries");
@@ -523,7 +532,7 @@ static int posterior(hbo_ctx* c, const hbo_model* m, hbo_cache* k, const void* x
   // inside the chunk loop waits for the products in flight on the other stream -- it serialised the two streams and
   // took cfg 3 from 142 to 197 ms
   if (!ov) HIPCHK(c, hipMemcpyAsync(w.xq, xq, (size_t)M * w.row_b, hipMemcpyHostToDevice, sa));
-  if (mes) HIPCHK(c, hipMemcpyAsync(d_ystar, mes->ystar, sizeof(double) * mes->K, hipMemcpyHostToDevice, sa));
+  if (mes) HIPCHK(c, hipMemcpyAsync(d_ystar, what.ystar, sizeof(double) * what.K, hipMemcpyHostToDevice, sa));
   if (k) ensure_w_split(pc, p);
   const bool bad = k && k->info != INT_MAX;
   hipEvent_t ev_free[2] = {nullptr, nullptr};
@@ -573,24 +582,13 @@ static int posterior(hbo_ctx* c, const hbo_model* m, hbo_cache* k, const void* x
 
 extern "C" int hbo_predict(hbo_ctx* c, const hbo_model* m, hbo_cache* k, const void* xq, int64_t M, int full_cov,
                            void* mu_out, void* var_out) {
-  return posterior(c, m, k, xq, M, full_cov, mu_out, var_out, nullptr, 0, 0, 0, 1);
+  return posterior(c, m, k, xq, M, full_cov, mu_out, var_out, nullptr, acq_what_registry(0, nullptr), 0, 1);
 }
 extern "C" int hbo_acq(hbo_ctx* c, const hbo_model* m, hbo_cache* k, const void* xq, int64_t M, int acq_id,
                        double param, double add_noise, double scale, void* out) {
   if (acq_id < 0 || acq_id > HBO_ACQ_UCB) return fail(c, HBO_ERR_ARG, "hbo_acq: bad acq_id");
   if (!out) return fail(c, HBO_ERR_ARG, "hbo_acq: out is null");
-  return posterior(c, m, k, xq, M, 0, nullptr, nullptr, out, acq_id, param, add_noise, scale);
-}
-// hbo_acq_mes (mes.hip) behind its argument checks: the same pipeline, the MES epilogue in the place of the EI / PI / UCB one
-int posterior_mes(hbo_ctx* c, const hbo_model* m, hbo_cache* k, const void* xq, int64_t M, const MesReq& mes, double add_noise, double scale,
-                  void* out) {
-  return posterior(c, m, k, xq, M, 0, nullptr, nullptr, out, 0, 0.0, add_noise, scale, nullptr, &mes);
-}
-
-// hbo_acq_logei (logei.hip) behind its argument checks: the same pipeline under the LogEI epilogue, the target in the place of param
-int posterior_logei(hbo_ctx* c, const hbo_model* m, hbo_cache* k, const void* xq, int64_t M, double target, double add_noise, double scale,
-                    void* out) {
-  return posterior(c, m, k, xq, M, 0, nullptr, nullptr, out, 0, target, add_noise, scale, nullptr, nullptr, true);
+  return posterior(c, m, k, xq, M, 0, nullptr, nullptr, out, acq_what_registry(acq_id, &param), add_noise, scale);
 }
 
 // ---- S hyper-parameter samples of one model family as ONE batch ------------------------------------------------------------
@@ -671,7 +669,7 @@ extern "C" int hbo_acq_samples(hbo_ctx* c, const hbo_model* models, int32_t S, c
     ks[s]->info = h_infos[s];
     PosteriorOverride ov = {d_models + s, mlp ? &w_dev[(size_t)s * HBO_MAX_MLP_LAYERS] : nullptr, mlp ? &b_dev[(size_t)s * HBO_MAX_MLP_LAYERS] : nullptr, d_xq,
                             d_acq + (size_t)s * M * es, lanes > 1 ? s % lanes : 0};
-    int rc = posterior(c, &models[s], ks[s], xq, M, 0, nullptr, nullptr, out, acq_id, params[s], add_noise[s], scale, &ov);
+    int rc = posterior(c, &models[s], ks[s], xq, M, 0, nullptr, nullptr, out, acq_what_registry(acq_id, &params[s]), add_noise[s], scale, &ov);
     if (rc == HBO_NOT_PD) any_bad = true;
     else if (rc) { for (hipStream_t q : lane_stream) hipStreamSynchronize(q); cleanup(); return rc; }
   }

@@ -1,6 +1,7 @@
 // Internal declarations shared by the HIP translation units of libhbo (gfx950 only).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 #include <type_traits>
 #include "../../include/hbo.h"
@@ -452,18 +453,21 @@ struct AcqSmallArgs {
   int kernel_id, mean_id, acq_id; double scale;
   void* acq_out; double* grad_out;                   // [S][M] model dtype, [S][M][D]
   double* val64_out;                                 // nullable [S][M]: the value before it is rounded to the model dtype (acq_opt.hip)
-  const double* ystar; int K;                        // max-value entropy search (mes.hip): [S][K] maxima (device); null: acq_id decides.
-                                                     // One launch takes one scalar step: the kernels are instantiated for either;
-                                                     // K <= HBO_MES_MAX_K = 256, one term per thread of the pair's workgroup
+  const double* ystar; int K;                        // ACQ_STEP_MES (mes.hip): [S][K] maxima (device), K <= HBO_MES_MAX_K = 256, one
+                                                     // term per thread of the pair's workgroup; not read by the other steps
   // MLP basis (acq_mlp.h; hbo_acq_grad_samples_mlp).  feat = 0: none, nothing below is read and vec is [S][2 D] as above.  Otherwise
   // bit 0: the kernel, bit 1: the mean reads the last layer, and vec is [S][fdim + mdim]: 1 / lengthscale over the kernel's own
   // space (fdim = last layer or D), then the linear mean's weights over the mean's (mdim = last layer, D or 0)
   int feat, fdim, mdim, L; int fout[HBO_MAX_MLP_LAYERS];
-  int logei;                                         // log expected improvement (logei.hip): the scalar step is logei_scalars against the
-                                                     // sample's target (AcqSmallSample::param); acq_id is then not read, ystar is null.
-                                                     // (Here it takes the padding in front of the pointers: no other field moves)
+  int step;                                          // ACQ_STEP_*: the scalar step of this launch, which picks the kernels' instantiation
+                                                     // on the host.  REGISTRY: acq_scalars by acq_id against AcqSmallSample::param;
+                                                     // MES: mes_scalars_block over ystar (precondition: feat == 0, the MES entry points
+                                                     // refuse MLP models); LOGEI: logei_scalars against the target in AcqSmallSample::param
   const void* const* mlp_w; const void* const* mlp_b;   // device tables [S][HBO_MAX_MLP_LAYERS]: weights [in][out], bias (model dtype)
 };
+// a kernel argument: the layout is pinned (the values of the struct as it stood with `int logei` in the place of `step`)
+static_assert(sizeof(AcqSmallArgs) == 168 && offsetof(AcqSmallArgs, step) == 148 && offsetof(AcqSmallArgs, mlp_w) == 152,
+              "AcqSmallArgs: the kernel argument's layout has moved");
 void launch_acq_small(int dtype, const AcqSmallArgs& a, int S, hipStream_t st);
 // ---- the same for caches of any n >= 1 (acq_blocked.hip): four stream-ordered launches over queries [q0, q0 + mc) of a.M --
 // k = k(x, X), l = W k, beta = W^T l, then one workgroup per (sample, query) pair for the scalars and the gradient.  The records are

@@ -290,4 +290,35 @@ __device__ __forceinline__ AcqScalars logei_scalars(double mu, double var, doubl
   if (r.val == -INFINITY) { r.amu = 0.0; r.avar = 0.0; }   // (u^2 overflows: the same rule -- a -inf row carries no slope into a sum)
   return r;
 }
+// The scalar step of a (sample, query) pair's 256-thread workgroup in acq_small_kernel and acq_blk_finish_kernel, by STEP
+// (hbo_internal.h: ACQ_STEP_*): acq_scalars by a.acq_id or logei_scalars on thread 0, against sm.param, handed over through LDS behind a
+// barrier; mes_scalars_block over the sample's K maxima by the whole workgroup.  Thread 0 writes the value to *acq (model dtype) and to
+// a.val64_out where that is set; every thread leaves with the same amu, avar.  Call it from uniform code.  The MES step returns WITHOUT
+// a barrier behind its LDS when v2 <= 0: the caller places one before it reuses LDS of its own.
+// (`a` by value: a reference to acq_small_kernel's own argument costs its plain instantiations 4 VGPRs and a wave of occupancy)
+template <typename T, int STEP>
+__device__ __forceinline__ void acq_scalar_step(const AcqSmallArgs a, const AcqSmallSample& sm, int s, int64_t q, double mu, double var, T* acq,
+                                                double& amu, double& avar) {
+  const int tid = threadIdx.x;
+  if constexpr (STEP == ACQ_STEP_MES) {
+    __shared__ double s_mes[3 * HBO_MES_MAX_K], s_mes_sum[3];
+    const AcqScalars sc = mes_scalars_block(mu, var, sm.add_noise, a.scale, a.ystar + (int64_t)s * a.K, a.K, s_mes, s_mes_sum);
+    if (tid == 0) {
+      *acq = (T)sc.val;
+      if (a.val64_out) a.val64_out[(int64_t)s * a.M + q] = sc.val;
+    }
+    amu = sc.amu; avar = sc.avar;   // (every thread holds them: nothing is handed over through LDS)
+  } else {
+    __shared__ double s_amu, s_avar;
+    if (tid == 0) {   // (STEP is a constant: one of the two is compiled)
+      const AcqScalars sc = STEP == ACQ_STEP_LOGEI ? logei_scalars(mu, var, sm.add_noise, a.scale, sm.param)
+                                                   : acq_scalars(a.acq_id, mu, var, sm.add_noise, a.scale, sm.param);
+      s_amu = sc.amu; s_avar = sc.avar;
+      *acq = (T)sc.val;
+      if (a.val64_out) a.val64_out[(int64_t)s * a.M + q] = sc.val;
+    }
+    __syncthreads();
+    amu = s_amu; avar = s_avar;
+  }
+}
 }  // namespace

@@ -1,10 +1,10 @@
 // Log expected improvement (Ament et al. 2023; include/hbo.h has the formulas): the entry points hbo_acq_logei, hbo_logei_grad_samples and
-// hbo_logei_maximize, and the epilogue kernel of the first.  The one expression behind all three is kernfun.h: logei_terms.  The values
-// over a pool run through hbo_acq's posterior pipeline (cache.hip: posterior_logei) with logei_epilogue_kernel behind
-// post_epilogue_kernel's mean and variance; value + gradient and the maximiser are the bodies of hbo_acq_grad_samples_mlp (acq_grad.hip)
-// and hbo_acq_maximize_mlp (acq_opt.hip) with the S targets in the place of acq_id and params: the kernels of acq_small.hip /
-// acq_blocked.hip then take logei_scalars as their scalar step and the control kernel combines the samples as the log of the mean of
-// their exponentials (acq_opt_ctl.h); everything around the two is shared.
+// hbo_logei_maximize, and the epilogue kernel of the first.  The one expression behind all three is kernfun.h: logei_terms.  Each entry
+// point is its sibling's body under the request acq_what_logei (api_internal.h: AcqWhat), the S targets where the registry has its
+// parameters: the values over a pool run through posterior() (cache.hip) with logei_epilogue_kernel behind post_epilogue_kernel's mean
+// and variance; value + gradient and the maximiser are acq_grad_samples (acq_grad.hip) and acq_maximize (acq_opt.hip) on the MLP route,
+// where the kernels of acq_small.hip / acq_blocked.hip take logei_scalars as their scalar step (kernfun.h: acq_scalar_step) and the
+// control kernel combines the samples as the log of the mean of their exponentials (acq_opt_ctl.h); everything around the two is shared.
 #include "kernfun.h"
 #include "api_internal.h"
 #include "../../include/hbo_tune.h"
@@ -44,31 +44,31 @@ extern "C" int hbo_acq_logei(hbo_ctx* c, const hbo_model* m, hbo_cache* k, const
                              double scale, void* out) {
   const std::string fn = "hbo_acq_logei: ";
   if (!m || !xq || !out) return fail(c, HBO_ERR_ARG, fn + "null argument");
-  if (int rc = logei_check(c, fn, &target, 1)) return rc;
+  const AcqWhat what = acq_what_logei(&target);
+  if (int rc = acq_what_check(c, fn, what, 1)) return rc;
   if (!c) return fail(c, HBO_ERR_ARG, fn + "ctx is null");
-  return posterior_logei(c, m, k, xq, M, target, add_noise, scale, out);
+  return posterior(c, m, k, xq, M, 0, nullptr, nullptr, out, what, add_noise, scale);
 }
 
 extern "C" int hbo_logei_grad_samples(hbo_ctx* c, const hbo_model* models, int32_t S, hbo_cache* const* caches, const void* xq, int64_t M,
                                       const double* targets, const double* add_noise, double scale, void* acq_out, double* grad_out) {
-  const AcqSamplesMode mode = {"hbo_logei_grad_samples", INT_MAX, false, 0, true, true};
-  return acq_grad_samples(c, mode, models, S, caches, xq, M, 0, targets, nullptr, add_noise, scale, acq_out, grad_out, nullptr);
+  return acq_grad_samples(c, ACQ_ROUTE_MLP.named("hbo_logei_grad_samples"), acq_what_logei(targets), models, S, caches, xq, M, add_noise, scale,
+                          acq_out, grad_out, nullptr);
 }
 
 // include/hbo_tune.h (TEST HOOK): hbo_logei_grad_samples with the fp64 values, the blocked kernels on request and a chunk size
 extern "C" int hbo_probe_logei_grad_samples64(hbo_ctx* c, const hbo_model* models, int32_t S, hbo_cache* const* caches, const void* xq, int64_t M,
                                               const double* targets, const double* add_noise, double scale, void* acq_out, double* grad_out,
                                               int32_t force_blocked, int64_t chunk_queries, double* val64_out) {
-  if (!val64_out) return fail(c, HBO_ERR_ARG, "hbo_probe_logei_grad_samples64: val64_out is null");
-  if (chunk_queries < 0) return fail(c, HBO_ERR_ARG, "hbo_probe_logei_grad_samples64: chunk_queries < 0");
-  const AcqSamplesMode mode = {"hbo_logei_grad_samples", INT_MAX, force_blocked != 0, chunk_queries, true, true};
-  return acq_grad_samples(c, mode, models, S, caches, xq, M, 0, targets, nullptr, add_noise, scale, acq_out, grad_out, val64_out);
+  if (int rc = acq_probe_check(c, "hbo_probe_logei_grad_samples64", val64_out, chunk_queries)) return rc;
+  return acq_grad_samples(c, ACQ_ROUTE_MLP.probed("hbo_logei_grad_samples", force_blocked, chunk_queries), acq_what_logei(targets), models, S, caches,
+                          xq, M, add_noise, scale, acq_out, grad_out, val64_out);
 }
 
 extern "C" int hbo_logei_maximize(hbo_ctx* c, const hbo_model* models, int32_t S, hbo_cache* const* caches, const void* x0, int32_t R,
                                   const double* lo, const double* hi, const double* targets, const double* add_noise, double scale,
                                   const hbo_acq_opt_opts* opts, double* state, int32_t evals, double* x_out, double* val_out, int32_t* status,
                                   hbo_acq_opt_eval* log) {
-  return acq_maximize(c, "hbo_logei_maximize", INT_MAX, true, models, S, caches, x0, R, lo, hi, 0, targets, nullptr, add_noise, scale, opts, state,
-                      evals, x_out, val_out, status, log, true);
+  return acq_maximize(c, ACQ_ROUTE_MLP.named("hbo_logei_maximize"), acq_what_logei(targets), models, S, caches, x0, R, lo, hi, add_noise, scale, opts,
+                      state, evals, x_out, val_out, status, log);
 }

@@ -200,10 +200,7 @@ class PathDraws:
     if s * r > MAX_PAIRS:
       raise ValueError(f'{s} paths x {r} starts exceed {MAX_PAIRS} pairs')
     x0 = np.ascontiguousarray(x0, dtype=self.dtype)
-    lo = hi = None
-    if bounds is not None:
-      b = np.asarray(bounds, dtype=np.float64).reshape(d, 2)
-      lo, hi = np.ascontiguousarray(b[:, 0]), np.ascontiguousarray(b[:, 1])
+    lo, hi = acfun._box_of(bounds, d)
     co = nat.AcqOptOpts(*[o[k] for k in ('memory', 'ls_steps', 'max_iters', 'c1', 'tau', 'pgtol', 'ftol')])
     ns = nat.lib().hbo_acq_opt_state_doubles(d, co.memory)
     state = np.zeros((s * r, max(ns, 1)), dtype=np.float64)

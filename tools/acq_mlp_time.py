@@ -80,7 +80,7 @@ def measure(S, n, M, D, feats, seconds, repeats):
       built, noises = acfun._sample_models(new, samples, np.float64)
       handles = acfun._hgp_sample_caches(new, 0, samples, np.float64)
       _, scale = new.predict_noise_and_scale(True, True)
-    raw = lambda: acfun._fused_value_and_grad(built, handles, noises, xq, nat.ACQ_EI, 0.5, scale, entry='hbo_acq_grad_samples_mlp')
+    raw = lambda: acfun._fused_value_and_grad(built, handles, noises, xq, nat.ACQ_EI, 0.5, scale, acfun._ROUTES['mlp'])
     raw(); raw()
     tr, sr = _stat([window(raw, seconds) for _ in range(repeats)])
     # the maximiser: R = 16 starts, rounds (evaluations of every start) per second over whole maximisations
