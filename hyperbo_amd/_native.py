@@ -20,6 +20,7 @@ F32, F64 = 0, 1
 WARP_NONE, WARP_KUMAR = 0, 1
 ACQ_EI, ACQ_PI, ACQ_UCB = 0, 1, 2
 MES_MAX_K = 256   # HBO_MES_MAX_K
+QEI_MAX_Q, QEI_MAX_BASE = 16, 1024   # HBO_QEI_MAX_Q, HBO_QEI_MAX_BASE
 BO_PARAM_CONST, BO_PARAM_MAX_PLUS, BO_PARAM_MAX_PLUS_STD = 0, 1, 2
 MAX_MLP_LAYERS = 8
 MAX_FEATURE_DIM = 256
@@ -193,6 +194,12 @@ SIGNATURES = {
                                                  C.POINTER(C.c_double)]),   # hbo_tune.h (test hook)
     'hbo_logei_maximize': (C.c_int, [_P, _P, C.c_int32, C.POINTER(_P), _P, C.c_int32, _P, _P, C.POINTER(C.c_double),
                                      C.POINTER(C.c_double), C.c_double, C.POINTER(AcqOptOpts), _P, C.c_int32, _P, _P, _P, _P]),
+    'hbo_qei_grad_samples': (C.c_int, [_P, _P, C.c_int32, C.POINTER(_P), _P, C.c_int64, C.c_int32, C.POINTER(C.c_double), C.c_int32,
+                                       C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_double, C.POINTER(C.c_double),
+                                       C.POINTER(C.c_double)]),
+    'hbo_qei_maximize': (C.c_int, [_P, _P, C.c_int32, C.POINTER(_P), _P, C.c_int32, C.c_int32, _P, _P, C.POINTER(C.c_double), C.c_int32,
+                                   C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_double, C.POINTER(AcqOptOpts), _P, C.c_int32, _P, _P,
+                                   _P, _P]),
     'hbo_probe_acq_opt_ctl': (C.c_int, [_P, C.c_int32, C.c_int, C.POINTER(AcqOptOpts), _P, _P, _P, _P, _P, C.c_int32, _P, _P,
                                         C.POINTER(AcqOptEval), C.POINTER(C.c_int32)]),   # include/hbo_tune.h (test hook)
     'hbo_bo_simulated': (C.c_int, [_P, _P, C.POINTER(BoRun), C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_double), _P, _P,

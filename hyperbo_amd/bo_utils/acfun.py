@@ -941,3 +941,178 @@ class LogExpectedImprovement:
 
 
 log_expected_improvement = log_ei = LogExpectedImprovement()
+
+
+# ---- batch (q-point) expected improvement (Ginsbourger et al. 2010; Wilson et al. 2018; include/hbo.h has the formulas, csrc/qei.hip
+#      the kernel and the entry points) -----------------------------------------------------------------------------------------------
+def _generator(model, key):
+  """A numpy Generator from `key`: a Generator itself, an int seed, or None -- model.rng, or seed 0 without one."""
+  if isinstance(key, np.random.Generator):
+    return key
+  if key is None:
+    return model.rng if getattr(model, 'rng', None) is not None else np.random.default_rng(0)
+  return np.random.default_rng(key)
+
+
+def _qei_checked(ctx, rc):
+  """ctx.check, with a refusal of the entry point (HBO_ERR_UNSUPPORTED, HBO_ERR_ARG) as ValueError under the entry point's message."""
+  try:
+    return ctx.check(rc)
+  except nat.HboError as e:
+    if e.code in (nat.HBO_ERR_UNSUPPORTED, nat.HBO_ERR_ARG):
+      raise ValueError(str(e)) from e
+    raise
+
+
+class BatchExpectedImprovement:
+  """Joint expected improvement of q points evaluated together, qEI(x_1..x_q) = E[max(0, max_j f(x_j) - t)], as the average over
+  `num_base` fixed base samples of the reparameterised posterior draw (include/hbo.h).  Called, it scores batches [M, q, D]
+  (hbo_qei_grad_samples; an HGP: the mean over its parameter samples); value_and_grad adds the exact gradient of that average with
+  respect to every coordinate of every point; maximize refines starting batches over a box on the device (hbo_qei_maximize); `suggest`
+  proposes `batch_size` points from a pool of candidates and is what bayesopt.bayesopt_batch calls.  The device route serves caches of
+  up to 128 observations without MLP bases or Kumaraswamy warps; a model it refuses raises ValueError with the entry point's message --
+  there is no fall-back.  The target is EI's: acfun_callback, by default the largest observed y."""
+  __name__ = 'q_expected_improvement'
+
+  def __init__(self, num_base=256, starts=8, opts=None):
+    if not 1 <= int(num_base) <= nat.QEI_MAX_BASE:
+      raise ValueError(f'num_base must lie in 1..{nat.QEI_MAX_BASE}, got {num_base}')
+    self.num_base, self.starts, self.opts = int(num_base), int(starts), opts
+
+  def base_samples(self, q, key=None):
+    """[num_base, q] float64 standard normals from a numpy Generator (`key`: a Generator or an int seed; None: seed 0)."""
+    rng = key if isinstance(key, np.random.Generator) else np.random.default_rng(0 if key is None else key)
+    return np.ascontiguousarray(rng.standard_normal((self.num_base, int(q))), dtype=np.float64)
+
+  @staticmethod
+  def _base(base_samples, q):
+    z = np.ascontiguousarray(base_samples, dtype=np.float64)
+    if z.ndim != 2 or z.shape[1] != q or not 1 <= z.shape[0] <= nat.QEI_MAX_BASE:
+      raise ValueError(f'base_samples must be [B, {q}] with 1 <= B <= {nat.QEI_MAX_BASE}, got {z.shape}')
+    return z
+
+  def _setup(self, model, sub_dataset_key, what):
+    """(dtype, built, noises, handles, scale, samples or None): the per-sample models and finished factors of the call."""
+    if not model.has_observations(sub_dataset_key):
+      raise ValueError(f'q_expected_improvement.{what}: the sub-dataset has no observations (the prior branch)')
+    if isinstance(model, gp.HGP):
+      samples = model.get_model_params_samples()
+      sd = model.dataset[sub_dataset_key]
+      dtype = _model.infer_dtype(sd.x, sd.y)
+      built, noises = _sample_models(model, samples, dtype)
+      handles = _hgp_sample_caches(model, sub_dataset_key, samples, dtype)
+      if len(handles) < len(samples):
+        raise ValueError(f'q_expected_improvement.{what}: only {len(handles)} of the {len(samples)} per-sample factors fit the device budget')
+      _, scale = model.predict_noise_and_scale(True, True)
+      return dtype, built, noises, handles, scale, samples
+    handle, _, bm, add_noise, scale = _single_model(model, sub_dataset_key)
+    return handle.dtype, [bm], [add_noise], [handle], scale, None
+
+  def _batches(self, x_batches, dtype, input_dim):
+    xb = np.asarray(x_batches)
+    if xb.ndim != 3 or xb.shape[2] != input_dim or not 1 <= xb.shape[1] <= nat.QEI_MAX_Q:
+      raise ValueError(f'batches must be [M, q, {input_dim}] with 1 <= q <= {nat.QEI_MAX_Q}, got {xb.shape}')
+    return np.ascontiguousarray(xb, dtype=dtype)
+
+  def value_and_grad(self, *, model, sub_dataset_key, x_batches, base_samples, acfun_callback=None):
+    """(values [M, 1] float64, d value_m / d x_batches[m] [M, q, D] float64): the mean over the parameter samples of
+    hbo_qei_grad_samples' rows."""
+    target = float((acfun_callback or ei_callback_default)(model, sub_dataset_key))
+    dtype, built, noises, handles, scale, samples = self._setup(model, sub_dataset_key, 'value_and_grad')
+    xb = self._batches(x_batches, dtype, model.input_dim)
+    m_count, q, d = xb.shape
+    z = self._base(base_samples, q)
+    s_count = len(built)
+    ctx = handles[0].ctx
+    structs, caches, nse = _sample_args(built, handles, noises)
+    vals = np.empty((s_count, m_count), dtype=np.float64)
+    grads = np.empty((s_count, m_count, q, d), dtype=np.float64)
+    dp = nat.C.POINTER(nat.C.c_double)
+    _qei_checked(ctx, nat.lib().hbo_qei_grad_samples(ctx.handle, structs, s_count, caches, nat.ptr(xb), m_count, q, z.ctypes.data_as(dp),
+                                                     z.shape[0], _per_sample(target, s_count), nse, float(scale), vals.ctypes.data_as(dp),
+                                                     grads.ctypes.data_as(dp)))
+    if samples is not None:
+      model.update_model_params(samples[-1])   # as every HGP path here leaves it (gp.py:674-678)
+    val, grad = np.zeros(m_count), np.zeros((m_count, q, d))
+    for s in range(s_count):   # sample order, as the control kernel sums
+      val = val + vals[s]
+      grad = grad + grads[s]
+    return (val / s_count)[:, None], grad / s_count
+
+  def __call__(self, *, model, sub_dataset_key, x_batches, base_samples, acfun_callback=None):
+    """[M, 1] float64: qEI of every batch, the mean over an HGP's parameter samples."""
+    return self.value_and_grad(model=model, sub_dataset_key=sub_dataset_key, x_batches=x_batches, base_samples=base_samples,
+                               acfun_callback=acfun_callback)[0]
+
+  def maximize(self, *, model, sub_dataset_key, x_init, base_samples, bounds=None, opts=None, acfun_callback=None):
+    """Maximises qEI over the box on the device (hbo_qei_maximize) from the starting batches x_init [q, D] or [R, q, D], all in one
+    call per segment of opts['segment'] evaluations until no start is RUNNING or opts['max_evals'] are spent.  bounds: None ([0, 1]^D)
+    or D (lo, hi) pairs; opts: as the `maximize` of the EI / PI / UCB objects.  Returns (x_best [q, D] float64, value_best, info): the
+    start with the largest finite value, the lowest index among equals; without any, x_init[0] and NaN."""
+    target = float((acfun_callback or ei_callback_default)(model, sub_dataset_key))
+    dtype, built, noises, handles, scale, samples = self._setup(model, sub_dataset_key, 'maximize')
+    o = dict(ACQ_OPT_DEFAULTS, segment=ACQ_OPT_SEGMENT, max_evals=ACQ_OPT_MAX_EVALS, log=False)
+    for layer in (self.opts, opts):
+      o.update(layer or {})
+    x_init = np.asarray(x_init, dtype=np.float64)
+    x0 = self._batches(x_init[None] if x_init.ndim == 2 else x_init, dtype, model.input_dim)
+    r_count, q, d = x0.shape
+    z = self._base(base_samples, q)
+    lo, hi = _box_of(bounds, d)
+    s_count = len(built)
+    ctx = handles[0].ctx
+    structs, caches, nse = _sample_args(built, handles, noises)
+    oo = nat.AcqOptOpts(*[o[k] for k in ('memory', 'ls_steps', 'max_iters', 'c1', 'tau', 'pgtol', 'ftol')])
+    ns = nat.lib().hbo_acq_opt_state_doubles(q * d, oo.memory)
+    state = np.zeros((r_count, max(ns, 1)), dtype=np.float64)
+    x = np.zeros((r_count, q, d), dtype=np.float64)
+    val = np.full(r_count, np.nan)
+    status = np.zeros(r_count, dtype=np.int32)
+    dp = nat.C.POINTER(nat.C.c_double)
+    targets = _per_sample(target, s_count)
+    logs, spent = [], 0
+    while spent < o['max_evals']:
+      evals = int(min(o['segment'], o['max_evals'] - spent))
+      log = np.zeros((evals, r_count), dtype=nat.ACQ_OPT_EVAL_DTYPE) if o['log'] else None
+      _qei_checked(ctx, nat.lib().hbo_qei_maximize(ctx.handle, structs, s_count, caches, nat.ptr(x0), r_count, q, nat.ptr(lo), nat.ptr(hi),
+                                                   z.ctypes.data_as(dp), z.shape[0], targets, nse, float(scale), nat.C.byref(oo),
+                                                   nat.ptr(state), evals, nat.ptr(x), nat.ptr(val), nat.ptr(status), nat.ptr(log)))
+      spent += evals
+      if o['log']:
+        logs.append(log)
+      if not np.any(status == nat.ACQ_OPT_RUNNING):
+        break
+    if samples is not None:
+      model.update_model_params(samples[-1])
+    info = {'x': x, 'value': val, 'status': status, 'evals': state[:, nat.ACQ_OPT_S_EVALS].astype(np.int64)}
+    if o['log']:
+      info['log'] = np.concatenate(logs)
+    finite = np.isfinite(val)
+    if not finite.any():
+      return np.asarray(x0[0], dtype=np.float64).copy(), float('nan'), info
+    best = int(np.argmax(np.where(finite, val, -np.inf)))
+    return x[best].copy(), float(val[best]), info
+
+  def suggest(self, *, model, sub_dataset_key, x_candidates, key=None, batch_size=1, bounds=None):
+    """[batch_size, D] float64: the candidates are scored with EI over the pool; start 0 is the `batch_size` best of them (stable
+    order), every further start `batch_size` distinct candidates drawn by the Generator from the best 4 * batch_size * starts; all
+    starts are refined in one hbo_qei_maximize call under base samples drawn from the same Generator, and the best final batch is
+    returned.  Without observations (the prior branch): `batch_size` distinct candidates drawn by the Generator.  Deterministic given
+    `key` (a numpy Generator or an int seed; None takes model.rng, or seed 0 without one)."""
+    xc = np.asarray(x_candidates, dtype=np.float64)
+    q = int(batch_size)
+    if xc.ndim != 2 or not 1 <= q <= min(nat.QEI_MAX_Q, xc.shape[0]):
+      raise ValueError(f'x_candidates must be [M, D] and 1 <= batch_size <= min({nat.QEI_MAX_Q}, M), got {xc.shape} and {batch_size}')
+    rng = _generator(model, key)
+    if not model.has_observations(sub_dataset_key):
+      return xc[rng.choice(xc.shape[0], size=q, replace=False)].copy()
+    scores = np.asarray(expected_improvement(model=model, sub_dataset_key=sub_dataset_key, x_queries=xc), dtype=np.float64).reshape(-1)
+    order = np.argsort(-np.where(np.isnan(scores), -np.inf, scores), kind='stable')
+    pool = order[:min(xc.shape[0], 4 * q * max(1, self.starts))]
+    starts = [xc[order[:q]]] + [xc[rng.choice(pool, size=q, replace=False)] for _ in range(max(1, self.starts) - 1)]
+    z = self.base_samples(q, rng)
+    x, val, _ = self.maximize(model=model, sub_dataset_key=sub_dataset_key, x_init=np.stack(starts), base_samples=z, bounds=bounds)
+    return (x if np.isfinite(val) else starts[0]).copy()
+
+
+q_expected_improvement = BatchExpectedImprovement()

@@ -97,6 +97,33 @@ def bayesopt(key, model, sub_dataset_key, query_oracle, ac_func, iters, input_sa
   return model.dataset.get(sub_dataset_key, SubDataset(np.empty(0), np.empty(0)))
 
 
+def bayesopt_batch(model, sub_dataset_key, queried_sub_dataset, ac_func, iters, batch_size, input_sampler, key=None):
+  """Continuous BO on [0,1]^D with `batch_size` points per iteration, for evaluation on parallel workers: every iteration takes
+  `ac_func.suggest(model=, sub_dataset_key=, x_candidates=, key=, batch_size=)` [batch_size, D] over `input_sampler`'s candidates and
+  this loop's Generator, queries the oracle `queried_sub_dataset` (a callable on [batch_size, D]) once for the whole batch and appends
+  the batch_size observations.  `ac_func` needs a `suggest` that takes batch_size: acfun.q_expected_improvement (the joint criterion,
+  refined on the device) or acfun.thompson_continuous (independent posterior paths).  Returns the sub-dataset after iters * batch_size
+  appended observations."""
+  suggest = getattr(ac_func, 'suggest', None)
+  if suggest is None:
+    raise ValueError('bayesopt_batch needs an ac_func with a `suggest` method (acfun.q_expected_improvement, acfun.thompson_continuous)')
+  q = int(batch_size)
+  if q < 1:
+    raise ValueError('batch_size must be at least 1')
+  rng = _rng(key)
+  input_dim = model.input_dim
+  for i in range(iters):
+    start_time = time.time()
+    retrain_model(model, sub_dataset_key=sub_dataset_key, random_key=rng)
+    x_samples = np.asarray(input_sampler(rng, input_dim))
+    x_batch = np.asarray(suggest(model=model, sub_dataset_key=sub_dataset_key, x_candidates=x_samples, key=rng, batch_size=q),
+                         dtype=np.float64).reshape(q, input_dim)
+    y_batch = np.asarray(queried_sub_dataset(x_batch)).reshape(q, -1)
+    logging.info('%d-th iter, batch=%s, values=%s, elapsed_time=%s', i, x_batch, y_batch, time.time() - start_time)
+    model.update_sub_dataset((x_batch, y_batch), sub_dataset_key=sub_dataset_key, is_append=True)
+  return model.dataset.get(sub_dataset_key, SubDataset(np.empty(0), np.empty(0)))
+
+
 def _bo_on_device_unmet(model, sub_dataset_key, queried_sub_dataset, ac_func):
   """The first condition that keeps a simulated BO loop off the device loop (hbo_bo_simulated, config['bo_on_device']), as a
   message, or None.  Host-side checks only."""

@@ -431,16 +431,19 @@ struct hbo_cache {
 // (model_family_check) without MLP basis or linear_mlp mean, and finished caches of 1..max_n observations that match their models
 // (HBO_TILE: the one-block entry points; INT_MAX: the _blocked ones).  *any_bad: a cache is not positive definite.
 // allow_mlp (the _mlp entry points): the two MLP refusals are skipped, everything else stays.
+// advice, advice_one: what the message of a refusal tells the caller to do instead, about the samples and about one sample (the qEI
+// entry points, which have no other route, say so).
 static int acq_samples_check(hbo_ctx* c, const std::string& fn, const hbo_model* models, int32_t S, hbo_cache* const* caches, int max_n, bool* any_bad,
-                             bool allow_mlp) {
-  if (int rc = model_family_check(c, fn, models, S, "evaluate the samples with hbo_acq_grad")) return rc;
+                             bool allow_mlp, const char* advice = "evaluate the samples with hbo_acq_grad",
+                             const char* advice_one = "evaluate it with hbo_acq_grad") {
+  if (int rc = model_family_check(c, fn, models, S, advice)) return rc;
   for (int s = 0; s < S; ++s) {
     const hbo_model* m = &models[s];
-    if (!allow_mlp && m->kernel_uses_mlp) return fail(c, HBO_ERR_UNSUPPORTED, fn + "a kernel on an MLP basis is not supported; evaluate the samples with hbo_acq_grad");
-    if (!allow_mlp && m->mean_id == HBO_MEAN_LINEAR_MLP) return fail(c, HBO_ERR_UNSUPPORTED, fn + "a linear_mlp mean is not supported; evaluate the samples with hbo_acq_grad");
+    if (!allow_mlp && m->kernel_uses_mlp) return fail(c, HBO_ERR_UNSUPPORTED, fn + "a kernel on an MLP basis is not supported; " + advice);
+    if (!allow_mlp && m->mean_id == HBO_MEAN_LINEAR_MLP) return fail(c, HBO_ERR_UNSUPPORTED, fn + "a linear_mlp mean is not supported; " + advice);
     const hbo_cache* k = caches[s];
-    if (!k || !k->t || k->t->n <= 0) return fail(c, HBO_ERR_UNSUPPORTED, fn + "a sample without observations (the prior branch) is not supported; evaluate it with hbo_acq_grad");
-    if (k->t->n > max_n) return fail(c, HBO_ERR_UNSUPPORTED, fn + "a cache has n > " + std::to_string(max_n) + "; evaluate the samples with hbo_acq_grad");
+    if (!k || !k->t || k->t->n <= 0) return fail(c, HBO_ERR_UNSUPPORTED, fn + "a sample without observations (the prior branch) is not supported; " + advice_one);
+    if (k->t->n > max_n) return fail(c, HBO_ERR_UNSUPPORTED, fn + "a cache has n > " + std::to_string(max_n) + "; " + advice);
     if (k->dtype != m->dtype || k->D != m->input_dim) return fail(c, HBO_ERR_ARG, fn + "cache/model mismatch");
     if (k->input_warp != m->input_warp) return fail(c, HBO_ERR_ARG, fn + "the cache was factorised with another input warp");
     *any_bad = *any_bad || k->info != INT_MAX;

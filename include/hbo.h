@@ -482,6 +482,59 @@ int hbo_logei_maximize(hbo_ctx* ctx, const hbo_model* models, int32_t S, hbo_cac
                        const hbo_acq_opt_opts* opts, double* state, int32_t evals, double* x_out, double* val_out, int32_t* status,
                        hbo_acq_opt_eval* log);
 
+/* ---- batch (q-point) expected improvement (qEI, Ginsbourger et al. 2010, in the reparameterised Monte-Carlo form of Wilson et al.
+ *      2018; no counterpart in the reference): the expected improvement of the BEST of q points evaluated together, under their JOINT
+ *      posterior.  For a batch x_1..x_q over a finished cache (X, W = L^-1 lower, alpha), a target t and B base samples z [B, q]
+ *      (standard normals the caller draws once; every sample, batch and start reads the same z):
+ *        k_j = k(x_j, X),  l_j = W k_j,  beta_j = W^T l_j,  mu_j = k_j . alpha + m(x_j)
+ *        Sigma_jl = k(x_j, x_l) - l_j . l_l,  Sigma' = (Sigma + add_noise I) scale,  C = chol(Sigma') lower    (noise first, then the
+ *                                                                                     scale: GP.predict(full_cov, with_noise, unbiased))
+ *        f_bj = mu_j + sum_{l<=j} C_jl z_bl,  j*_b = the LOWEST index of the largest f_bj,  imp_b = f_{b j*_b} - t
+ *        value = (1 / B) sum_b max(0, imp_b)                       (imp_b == 0 contributes nothing)
+ *      grad_out is the exact gradient of that sample average (z is fixed: the function is deterministic and piecewise smooth):
+ *        w_bj = [j == j*_b and imp_b > 0] / B,  mubar_j = sum_b w_bj,  Cbar_jl = sum_b w_bj z_bl (l <= j)
+ *        P = tril(C^T Cbar) with its diagonal halved,  Sbar = C^-T P C^-1,  G = scale (Sbar + Sbar^T) / 2       (= d value / d Sigma)
+ *        coef_j = mubar_j alpha - 2 sum_l G_jl beta_l
+ *        d value / d x_j = sum_i coef_ji dk(x_j, X_i)/dx_j + 2 sum_{l != j} G_jl dk(x_j, x_l)/dx_j + G_jj dk(x_j, x_j)/dx_j + mubar_j dm/dx_j
+ *      (the G_jj term is 0 for SE and Matern and 2 x_j / sigma^2 G_jj for the dot product; a Matern pair at zero distance -- a query on
+ *      an observation, two equal batch points -- contributes 0, as in hbo_acq_grad).  With q = 1 this is hbo_acq_grad's formula with
+ *      a_mu = mubar and a_var = G_11.
+ *      One 256-thread workgroup owns one (batch, sample) pair and reads the sample's W once for all q points (csrc/qei.hip).  Every
+ *      product and sum is fp64 whatever the model dtype (X, W, alpha and the points are read in the model dtype), in an order fixed by
+ *      (n, input_dim, q, B) alone; no atomics: a pair does not depend on what shares the call (bit for bit) and identical calls are
+ *      bit-identical.
+ *      A pivot of the q x q factorisation that is not > 0 (duplicate points with add_noise == 0, a non-finite input): the value and
+ *      every gradient component of that (sample, batch) pair are NaN, the other pairs are unaffected and the call still returns
+ *      HBO_OK.  A cache that is not positive definite: NaN rows for that sample and HBO_NOT_PD, as the siblings.
+ *      HBO_ERR_ARG (before any device work, outputs and state untouched): null arguments, S outside 1..4096, q outside
+ *      1..HBO_QEI_MAX_Q, B outside 1..HBO_QEI_MAX_BASE, a z, target, add_noise or scale that is not finite, add_noise < 0,
+ *      scale <= 0, samples that do not share dtype, covariance, mean or input_dim, a cache that does not match its model.
+ *      HBO_ERR_UNSUPPORTED (before any device work, the message names the reason): a cache of n > 128, a null or empty cache (the
+ *      prior branch), kernel_uses_mlp or a linear_mlp mean, a Kumaraswamy-warped model.  These three are OUT OF SCOPE of this entry
+ *      point: caches beyond 128 observations (a blocked route in the manner of csrc/acq_blocked.hip), MLP bases, Kumaraswamy warps. */
+#define HBO_QEI_MAX_Q 16
+#define HBO_QEI_MAX_BASE 1024
+/* ---- value and gradient, PER SAMPLE: xq [M, q, input_dim] model dtype, z [B, q], targets [S], add_noise [S];
+ *      val_out [S, M] fp64 (not rounded to the model dtype), grad_out [S, M, q, input_dim].  The acquisition of an HGP is the mean
+ *      over s of the rows.  M == 0 returns HBO_OK. */
+int hbo_qei_grad_samples(hbo_ctx* ctx, const hbo_model* models, int32_t S, hbo_cache* const* caches, const void* xq, int64_t M, int32_t q,
+                         const double* z, int32_t B, const double* targets, const double* add_noise, double scale, double* val_out,
+                         double* grad_out);
+/* ---- the maximisation of qEI (mean over the S samples) over the box, R starting batches in one call: hbo_acq_maximize over a
+ *      variable of dimension q * input_dim -- the same control kernel, state format (hbo_acq_opt_state_doubles(q * input_dim,
+ *      memory)), log, status codes and opts, the box lo, hi [input_dim] tiled q times.  One upload, then `evals` rounds of two
+ *      stream-ordered launches (the qEI kernel on grid (R, S) over the pending batches, then the control kernel), one synchronisation
+ *      and one copy back.  A run gives the same bits however it is cut into calls, a start does not depend on what shares the call,
+ *      bounds are hit exactly and points are rounded to the model dtype.  x0, x_out [R, q, input_dim]; val_out [R]: the mean over s of
+ *      hbo_qei_grad_samples' values at x_out.  The line search rejects a non-finite probe; a non-finite start ends with
+ *      HBO_ACQ_OPT_NONFINITE_AT_START.  Checks: those above and the R, evals, opts, box, start and state checks of hbo_acq_maximize;
+ *      HBO_ERR_UNSUPPORTED also for a state (q * input_dim, opts.memory) beyond the control kernel's 64 KB of LDS (memory 10 fits
+ *      q * input_dim <= 256). */
+int hbo_qei_maximize(hbo_ctx* ctx, const hbo_model* models, int32_t S, hbo_cache* const* caches, const void* x0, int32_t R, int32_t q,
+                     const double* lo, const double* hi, const double* z, int32_t B, const double* targets, const double* add_noise,
+                     double scale, const hbo_acq_opt_opts* opts, double* state, int32_t evals, double* x_out, double* val_out,
+                     int32_t* status, hbo_acq_opt_eval* log);
+
 /* ---- the maximisation of S posterior sample paths over a box, R starts each, in ONE call: continuous Thompson sampling -- q
  *      suggestions from q paths (no counterpart in the reference).  The optimiser is that of hbo_acq_maximize, run on
  *      f(x) = -f_s(x) for each of the S * R (path, start) pairs: one upload and one solve for u (hbo_sample_paths_grad), then `evals`
