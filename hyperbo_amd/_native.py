@@ -235,6 +235,10 @@ SIGNATURES = {
                                            C.POINTER(C.c_int32), _P]),   # include/hbo_tune.h (test hook; the last: hbo_probe_plan*)
     'hbo_probe_kumar_warp': (C.c_int, [_P, C.POINTER(Model), _P, C.c_int64, _P, C.POINTER(C.c_double), C.POINTER(C.c_double),
                                        C.POINTER(C.c_double)]),   # include/hbo_tune.h (test hook)
+    'hbo_probe_grad_contract': (C.c_int, [_P, C.POINTER(Model), C.c_int, C.c_int32, C.POINTER(C.c_int64), _P, _P, _P, C.c_int32,
+                                          C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_double,
+                                          C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                          C.POINTER(C.c_int32)]),   # include/hbo_tune.h (test hook)
     'hbo_comm_unique_id': (C.c_int, [_P]),
     'hbo_comm_init': (C.c_int, [_P, C.c_int, C.c_int, _P]),
     'hbo_comm_allreduce_sum': (C.c_int, [_P, C.POINTER(C.c_double), C.c_int32]),

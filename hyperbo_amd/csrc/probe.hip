@@ -1,5 +1,5 @@
 // What include/hbo_tune.h declares apart from hbo_tune itself (api.hip): the MFMA rate probe of bench.py and the test hooks that run
-// single launches of the posterior and the Gram, and the factor and inverse steps of an evaluation, on caller-chosen operands.  (hbo_probe_acq_grad_samples64 is a second door to
+// single launches of the posterior and the Gram, and the factor, inverse and gradient-contraction steps of an evaluation, on caller-chosen operands.  (hbo_probe_acq_grad_samples64 is a second door to
 // acq_grad.hip's acq_grad_samples and stays beside it; the control-text probes stay with their kernels in train.hip and acq_opt.hip.)
 #include "api_internal.h"
 #include "../../include/hbo_tune.h"
@@ -395,5 +395,173 @@ extern "C" int hbo_probe_kumar_warp(hbo_ctx* c, const hbo_model* m, const void* 
   HIPCHK(c, hipMemcpyAsync(dwdx_out, d_gx, cnt * sizeof(double), hipMemcpyDeviceToHost, st));
   HIPCHK(c, hipStreamSynchronize(st));
   HIPCHK(c, hipGetLastError());
+  return HBO_OK;
+}
+
+// Test hook (include/hbo_tune.h): the gradient contraction of an evaluation on a caller-chosen G.  The batch is form 2's of hbo_probe_gram
+// (dataset, workspaces, descriptors from the set-up of an evaluation with gradient of `obj`, the MLP activations and dF as obj_setup
+// allocates them; sizes from obj_plan), poisoned first where the option says so.  Then the operands go where step_inverse and
+// step_extra_rows would have left them -- S (K^-1), the outer-product vectors where outer_vecs finds them (svec rows; EUC: the augmented
+// tile row of A), d f / d mu -- and the shipped launches run in objective.hip's order with its arguments: launch_grad_contract,
+// launch_grad_finalize with `pre` behind the partials, and for an MLP kernel launch_grad_feat (+ launch_scale_dF for EUC) on a zeroed dF.
+// Padding: everything beyond a task's n rows / columns and every 128-tile of S strictly above the tile diagonal holds the sentinel; the
+// kernels mask by row < n && col < n and rely on no zero the pipeline writes there.  One exception, said here: an EKL task carries
+// naug = m + 1 >= 2 vectors, so nvec = 1 is given as m = 1 with a second vector of zeros in its n data elements (0 * 0 added to the outer
+// product; its padding holds the sentinel as well).  Partials, the gradient block and `pre` are preset to NaN: a slot no launch wrote shows.
+extern "C" int hbo_probe_grad_contract(hbo_ctx* c, const hbo_model* m, int obj, int32_t T, const int64_t* ns, const void* x, const void* s,
+                                       const void* vecs, int32_t nvec, const double* coef_lh, const double* coef_c, const double* dmu,
+                                       double sentinel, double* grad_out, double* partials_out, double* fro_out, double* dF_out,
+                                       int32_t* prereduced_out) {
+  if (!c || !m || !ns || !x || !vecs || !coef_lh || !coef_c) return fail(c, HBO_ERR_ARG, "hbo_probe_grad_contract: null argument");
+  if (obj != OBJ_NLL && obj != OBJ_EKL && obj != OBJ_EUC) return fail(c, HBO_ERR_ARG, "hbo_probe_grad_contract: obj is 0 (NLL), 1 (EKL) or 2 (EUC)");
+  if (T <= 0 || T > 64) return fail(c, HBO_ERR_ARG, "hbo_probe_grad_contract: 1 <= T <= 64");
+  for (int k = 0; k < T; ++k) if (ns[k] <= 0 || ns[k] > 4096) return fail(c, HBO_ERR_ARG, "hbo_probe_grad_contract: need 1 <= n <= 4096 for every task");
+  if (obj == OBJ_NLL ? nvec != 1 : (nvec < 1 || nvec > 9)) return fail(c, HBO_ERR_ARG, "hbo_probe_grad_contract: nvec is 1 for NLL, 1..9 otherwise");
+  if (obj != OBJ_EUC && !s) return fail(c, HBO_ERR_ARG, "hbo_probe_grad_contract: NLL and EKL need s");
+  if (m->input_warp != HBO_WARP_NONE) return fail(c, HBO_ERR_ARG, "hbo_probe_grad_contract: models with an input warp are not taken");
+  if (validate_model(c, m)) return HBO_ERR_ARG;
+  if (needs_mlp(m) && !m->kernel_uses_mlp) return fail(c, HBO_ERR_ARG, "hbo_probe_grad_contract: a linear_mlp mean is taken with an MLP kernel only");
+  if (m->kernel_uses_mlp && m->mean_id == HBO_MEAN_LINEAR) return fail(c, HBO_ERR_ARG, "hbo_probe_grad_contract: an MLP kernel is taken with a zero, constant or linear_mlp mean");
+  if (fro_out && obj != OBJ_EUC) return fail(c, HBO_ERR_ARG, "hbo_probe_grad_contract: fro_out needs EUC");
+  if (dF_out && !m->kernel_uses_mlp) return fail(c, HBO_ERR_ARG, "hbo_probe_grad_contract: dF_out needs an MLP kernel");
+  HIPCHK(c, hipSetDevice(c->device));
+  const int dtype = m->dtype, D = m->input_dim, fdim = feature_dim(m);
+  const bool euc = obj == OBJ_EUC, mlp = m->kernel_uses_mlp != 0;
+  const size_t es = esize(dtype);
+  const int mcols = obj == OBJ_NLL ? 1 : (euc ? nvec : std::max(nvec - 1, 1));   // target columns: NLL 1 vector, EUC naug - 1 = m, EKL naug = m + 1
+  hipStream_t st = c->stream;
+  auto fill = [&](std::vector<unsigned char>& h, size_t count) {
+    h.resize(count * es);
+    if (dtype == HBO_F64) for (size_t i = 0; i < count; ++i) ((double*)h.data())[i] = sentinel;
+    else for (size_t i = 0; i < count; ++i) ((float*)h.data())[i] = (float)sentinel;
+  };
+  // the dataset of the T tasks: targets of zeros; an MLP kernel reads x as its features F, its raw inputs are zeros
+  int64_t max_n = 0, rows = 0;
+  std::vector<size_t> r_off(T), a_off(T);   // first row of task k in x / dmu / dF; first element in s
+  size_t a_total = 0;
+  for (int k = 0; k < T; ++k) { r_off[k] = (size_t)rows; a_off[k] = a_total; rows += ns[k]; a_total += (size_t)ns[k] * ns[k]; max_n = std::max(max_n, ns[k]); }
+  const std::vector<unsigned char> y0((size_t)max_n * mcols * es, 0), x0(mlp ? (size_t)max_n * D * es : 0, 0);
+  std::vector<hbo_task> tasks(T);
+  for (int k = 0; k < T; ++k) {
+    memset(&tasks[k], 0, sizeof(hbo_task));
+    tasks[k].x = mlp ? (const void*)x0.data() : (const void*)((const char*)x + r_off[k] * D * es);
+    tasks[k].y = y0.data(); tasks[k].n = ns[k]; tasks[k].m = mcols;
+  }
+  hbo_dataset* ds = nullptr;
+  int rc = hbo_dataset_create(c, dtype, D, tasks.data(), T, &ds);
+  if (rc) return rc;
+  DevBuf buf;
+  // (the dataset leaves when the call does, behind a wait: launches may still read its pooled buffers.  Before buf's memory is freed.)
+  struct DatasetGuard { hbo_ctx* c; hipStream_t st; hbo_dataset* ds; ~DatasetGuard() { hipStreamSynchronize(st); hbo_dataset_free(c, ds); } } guard = {c, st, ds};
+  // the dataset holds its tasks largest first; its inputs lie in the caller's order: order[z] = the caller's index of dataset task z
+  std::vector<TaskHost*> by_x(ds->tasks);
+  std::sort(by_x.begin(), by_x.end(), [](TaskHost* p, TaskHost* q) { return (const char*)p->X < (const char*)q->X; });
+  std::vector<int> order(T);
+  for (int z = 0; z < T; ++z) order[z] = (int)(std::find(by_x.begin(), by_x.end(), ds->tasks[z]) - by_x.begin());
+  rc = upload_model(c, m);
+  if (rc) return rc;
+  hbo_grad_layout lay; memset(&lay, 0, sizeof lay);
+  const ObjPlan p = obj_plan(c, m, ds, lay, obj, true, false);
+  const int max_nblk = ds->max_nblk, max_npad = max_nblk * HBO_TILE, nacc = p.nacc, out_stride = p.out_stride;
+  ds->h_desc.resize(T);
+  for (int z = 0; z < T; ++z) {
+    TaskHost* t = ds->tasks[z];
+    rc = ensure_task_workspace(c, dtype, t, p.need_S, obj == OBJ_NLL ? 1 : t->m + 1);
+    if (rc) return rc;
+    if (mlp) {
+      rc = t->feat.ensure(c, m, t->n);
+      if (rc) return rc;
+      int maxf = m->input_dim;
+      for (int l = 0; l < m->n_layers; ++l) maxf = std::max(maxf, (int)m->features[l]);
+      const size_t need = (size_t)t->n * maxf;
+      HIPCHK(c, dev_alloc(c, (void**)&t->dF, need * sizeof(double)));
+      HIPCHK(c, dev_alloc(c, (void**)&t->dtmp, need * sizeof(double)));
+      t->dF_elems = need;
+    }
+    fill_desc(ds->h_desc[z], t, m, dtype, obj);
+    ds->h_desc[z].coef_lh = coef_lh[order[z]]; ds->h_desc[z].coef_c = coef_c[order[z]];   // the caller's, where fill_desc put the objective's
+  }
+  // partials + their pre-reduction, placed as obj_plan sizes them (also for a one-block NLL batch, which the product sends to small.hip)
+  const size_t part_elems = (size_t)p.stride_task * T, pre_elems = (size_t)HBO_GRAD_PRE_ROWS * nacc * T;
+  double *d_part = nullptr, *d_out = nullptr, *d_val = nullptr;
+  HIPCHK(c, dev_alloc(c, (void**)&ds->d_desc, sizeof(TaskDesc) * T));
+  HIPCHK(c, buf.get(c, &d_part, (part_elems + pre_elems) * sizeof(double)));
+  HIPCHK(c, buf.get(c, &d_out, (size_t)T * out_stride * sizeof(double)));
+  HIPCHK(c, buf.get(c, &d_val, (size_t)T * sizeof(double)));
+  HIPCHK(c, hipMemcpyAsync(ds->d_desc, ds->h_desc.data(), sizeof(TaskDesc) * T, hipMemcpyHostToDevice, st));
+  HIPCHK(c, hipMemsetAsync(d_part, 0xFF, (part_elems + pre_elems) * sizeof(double), st));
+  HIPCHK(c, hipMemsetAsync(d_out, 0xFF, (size_t)T * out_stride * sizeof(double), st));
+  HIPCHK(c, hipMemsetAsync(d_val, 0xFF, (size_t)T * sizeof(double), st));
+  if (c->opt_poison) launch_poison(dtype, ds->d_desc, T, max_npad, st);
+  // the operands, padded with the sentinel (the staging buffers live until the wait below)
+  std::vector<std::vector<unsigned char>> hS(T), hV(T);
+  std::vector<std::vector<double>> hM(T);
+  size_t v_off = 0;
+  std::vector<size_t> v_offs(T);
+  for (int k = 0; k < T; ++k) { v_offs[k] = v_off; v_off += (size_t)nvec * ns[k]; }
+  for (int z = 0; z < T; ++z) {
+    TaskHost* t = ds->tasks[z];
+    const int k = order[z];
+    const size_t n = (size_t)t->n, npad = (size_t)t->npad, ld = (size_t)t->ld;
+    if (!euc) {
+      fill(hS[z], npad * ld);
+      const char* sk = (const char*)s + a_off[k] * es;
+      for (size_t i = 0; i < n; ++i) {
+        const size_t cols = std::min(n, (i / HBO_TILE + 1) * HBO_TILE);   // up to the end of the row's diagonal tile
+        memcpy(hS[z].data() + i * ld * es, sk + i * n * es, cols * es);
+      }
+      HIPCHK(c, hipMemcpyAsync(t->S, hS[z].data(), npad * ld * es, hipMemcpyHostToDevice, st));
+    }
+    const char* vk = (const char*)vecs + v_offs[k] * es;
+    if (euc) {   // rows npad ... of A, ld apart
+      fill(hV[z], (size_t)HBO_TILE * ld);
+      for (int b = 0; b < nvec; ++b) memcpy(hV[z].data() + (size_t)b * ld * es, vk + (size_t)b * n * es, n * es);
+      HIPCHK(c, hipMemcpyAsync((char*)t->A + npad * ld * es, hV[z].data(), (size_t)HBO_TILE * ld * es, hipMemcpyHostToDevice, st));
+    } else {     // svec: naug rows of npad
+      const int ncol = ds->h_desc[z].naug;
+      fill(hV[z], (size_t)ncol * npad);
+      for (int b = 0; b < ncol; ++b) {
+        if (b < nvec) memcpy(hV[z].data() + (size_t)b * npad * es, vk + (size_t)b * n * es, n * es);
+        else memset(hV[z].data() + (size_t)b * npad * es, 0, n * es);
+      }
+      HIPCHK(c, hipMemcpyAsync(t->svec, hV[z].data(), (size_t)ncol * npad * es, hipMemcpyHostToDevice, st));
+    }
+    hM[z].assign(npad, sentinel);
+    for (size_t i = 0; i < n; ++i) hM[z][i] = dmu ? dmu[r_off[k] + i] : 0.0;
+    HIPCHK(c, hipMemcpyAsync(t->dmu, hM[z].data(), npad * sizeof(double), hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemsetAsync(t->fnorm, 0, 2 * sizeof(double), st));
+    if (mlp) {
+      HIPCHK(c, hipMemcpyAsync(t->feat.acts[m->n_layers - 1], (const char*)x + r_off[k] * fdim * es, n * fdim * es, hipMemcpyHostToDevice, st));
+      HIPCHK(c, hipMemsetAsync(t->dF, 0, n * fdim * sizeof(double), st));
+    }
+  }
+  // the launches of step_contract and enqueue_backward (objective.hip)
+  launch_grad_contract(dtype, ds->d_desc, T, max_nblk, c->d_model, m->kernel_id, p.fdim, obj, d_part, p.stride_task, st);
+  launch_grad_finalize(dtype, ds->d_desc, T, c->d_model, m->kernel_id, p.fdim, obj, d_part, p.stride_task, d_out, out_stride, euc ? d_val : nullptr, st,
+                       d_part + p.stride_task * T, max_nblk);
+  if (mlp) {
+    launch_grad_feat(dtype, ds->d_desc, T, max_nblk, c->d_model, m->kernel_id, fdim, obj, st);
+    if (euc) launch_scale_dF(ds->d_desc, T, (int64_t)max_npad, fdim, st);
+  }
+  // the copies back, in the caller's order
+  std::vector<double> h_out((size_t)T * out_stride), h_fro(T, 0.0);
+  double pre0 = 0;
+  HIPCHK(c, hipMemcpyAsync(h_out.data(), d_out, h_out.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipMemcpyAsync(&pre0, d_part + part_elems, sizeof(double), hipMemcpyDeviceToHost, st));
+  std::vector<size_t> p_off(T);
+  size_t p_total = 0;
+  for (int k = 0; k < T; ++k) { p_off[k] = p_total; p_total += (size_t)by_x[k]->nblk * (by_x[k]->nblk + 1) * nacc; }
+  for (int z = 0; z < T; ++z) {
+    TaskHost* t = ds->tasks[z];
+    const int k = order[z];
+    if (partials_out) HIPCHK(c, hipMemcpyAsync(partials_out + p_off[k], d_part + (size_t)z * p.stride_task, (size_t)t->nblk * (t->nblk + 1) * nacc * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (fro_out) HIPCHK(c, hipMemcpyAsync(&h_fro[k], t->fnorm, sizeof(double), hipMemcpyDeviceToHost, st));
+    if (dF_out) HIPCHK(c, hipMemcpyAsync(dF_out + r_off[k] * fdim, t->dF, (size_t)t->n * fdim * sizeof(double), hipMemcpyDeviceToHost, st));
+  }
+  HIPCHK(c, hipStreamSynchronize(st));
+  HIPCHK(c, hipGetLastError());
+  for (int z = 0; z < T && grad_out; ++z) memcpy(grad_out + (size_t)order[z] * out_stride, h_out.data() + (size_t)z * out_stride, out_stride * sizeof(double));
+  if (fro_out) memcpy(fro_out, h_fro.data(), T * sizeof(double));
+  if (prereduced_out) *prereduced_out = pre0 == pre0 ? 1 : 0;   // `pre` was preset to NaN: its first slot holds a number once grad_prereduce_kernel ran
   return HBO_OK;
 }

@@ -185,6 +185,38 @@ int hbo_probe_factor_inverse(hbo_ctx* ctx, int dtype, int32_t T, const int64_t* 
  * HBO_ERR_ARG on a null pointer, a model without the warp or n out of range, before any device call; no product path calls this. */
 int hbo_probe_kumar_warp(hbo_ctx* ctx, const hbo_model* model, const void* x, int64_t n, void* w_out, double* dwda_out, double* dwdb_out,
                          double* dwdx_out);
+/* TEST HOOK (tests/test_gpu_grad_contract.py): the blocked gradient contraction sum_ij G_ij dK_ij / dtheta (csrc/grad.hip) on a
+ * caller-chosen G.  T tasks (1 <= T <= 64), task k of ns[k] points (1 <= ns[k] <= 4096), one model (no input warp; a linear_mlp mean only
+ * with an MLP kernel, an MLP kernel not with a linear mean); obj: 0 NLL, 1 EKL, 2 EUC.  All arrays hold the tasks one after the other in
+ * the caller's order, in the model dtype unless said:
+ *   x       [n, fdim]  the kernel's features: the inputs, or for an MLP kernel the MLP OUTPUT F itself (fdim = the last layer's width;
+ *                      the weights of the model are validated but never read: no MLP pass runs)
+ *   s       [n, n]     dense symmetric, where K^-1 stands (G = lh s - c sum_b v_b v_b^T); ignored for EUC (G = K1 - sum_b v_b v_b^T), may be
+ *                      NULL then
+ *   vecs    [nvec, n]  the outer-product vectors; nvec = 1 for NLL, 1..9 otherwise
+ *   coef_lh, coef_c [T] doubles, the task's lh and c (what fill_desc derives from the objective otherwise)
+ *   dmu     [n] doubles, nullable (zeros): d f / d mu_i, what the mean leaves are summed from
+ * The batch is built as hbo_probe_gram form 2 builds it, with the workspaces, descriptors and buffer sizes of an evaluation with gradient
+ * (obj_setup, obj_plan), poisoned first where the option says so.  The operands are then written where the inverse and the extra-rows
+ * step leave them: s into S on and below the 128-tile diagonal (whole diagonal tiles), the vectors where outer_vecs finds them, dmu.
+ * Rows and columns beyond n, and the tiles of S above the tile diagonal, hold `sentinel` (rounded to the model dtype; the tests pass NaN).
+ * (EKL with nvec = 1: a task of one target column, whose second vector is zeros over its n elements.)  Then the shipped launches, and only
+ * those, in objective.hip's order: launch_grad_contract; launch_grad_finalize with `pre` behind the partials as obj_plan places it (the
+ * two-step column sum switches on by the shipped rule); for an MLP kernel launch_grad_feat, and launch_scale_dF for EUC, on a zeroed dF.
+ * The hook decides nothing itself.  Outputs, each nullable, doubles, task after task in the caller's order:
+ *   grad_out       [T, out_stride]  the finalised block, out_stride = (dot product: 0, else n_lengthscale) + 6 + the mean's feature count:
+ *                                   [lengthscale] [signal_variance] [noise_variance] [constant] [dot_prod_sigma] [dot_prod_bias]
+ *                                   [linear_kernel] [linear_bias]
+ *   partials_out   per task [nblk (nblk + 1), nacc], nblk = ceil(n / 128): the raw slots of the 64 x 128 half tiles, slot
+ *                  (ti (ti + 1) / 2 + tj) 2 + h for rows 128 ti + 64 h ..., columns 128 tj ...; nacc = 4 (dot product) or fdim + 3:
+ *                  [sum G k] [tr G] [dot: sum G | else fdim of sum G dk/du (ds_d)^2] [sum G0 G, the Frobenius slot (EKL, EUC)]
+ *   fro_out        [T]  EUC: |C0 - K1|_F as grad_finalize_kernel leaves it in fnorm[0]
+ *   dF_out         [n, fdim]  MLP kernel: d f / d F (EUC: rescaled by 1 / |C0 - K1|_F)
+ *   prereduced_out 1 when grad_prereduce_kernel ran (read off `pre`, which is preset to NaN as the partials and the gradient block are)
+ * HBO_ERR_ARG on a bad argument, before any device call and with no output touched; no product path calls this. */
+int hbo_probe_grad_contract(hbo_ctx* ctx, const hbo_model* model, int obj, int32_t T, const int64_t* ns, const void* x, const void* s,
+                            const void* vecs, int32_t nvec, const double* coef_lh, const double* coef_c, const double* dmu, double sentinel,
+                            double* grad_out, double* partials_out, double* fro_out, double* dF_out, int32_t* prereduced_out);
 #ifdef __cplusplus
 }
 #endif

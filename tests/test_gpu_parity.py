@@ -21,6 +21,8 @@ GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden')
 WFO = o.DEFAULT_WARP_FUNC
 FP64_GRAD_TOL = 1e-10   # per leaf (helpers.assert_grad_close); worst measured over the suite: 4.4e-12 of its bound (round 6, gpurun_out/grad_log.txt)
 FP32_GRAD_TOL = 2.5e-3   # worst measured: 2.3e-4
+# (the conditioning of K^-1 sets that bound.  The contraction stage alone, on a caller-chosen G, is held to at most 1.5e-6 of each leaf's term
+#  scale in fp32, about 1700 times tighter: tests/test_gpu_grad_contract.py, profiles/grad_contract_errors.md)
 FP32_REGISTRY_LEAF_TOL = 2e-3   # worst leaf of the fp32 registry sweep, relative to max(leaf norm, 1e-2 max|g|)
 
 
