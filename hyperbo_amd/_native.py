@@ -118,6 +118,14 @@ class ProbePlan(C.Structure):
     return {k.rstrip('_'): int(getattr(self, k)) for k, _ in self._fields_}
 
 
+class ProbePostPlan(C.Structure):
+  """hbo_probe_post_plan (include/hbo_tune.h): what the test hook hbo_probe_posterior ran."""
+  _fields_ = [(k, C.c_int32) for k in ('form', 'kchunk', 'nch', 'nchunks', 'nbuf', 'resident_chunks', 'direct_form')]
+
+  def as_dict(self):
+    return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
 # the same record as a NumPy dtype ([evals, R] logs)
 ACQ_OPT_EVAL_DTYPE = np.dtype([('kind', np.int32), ('iter', np.int32), ('alpha', np.float64), ('value', np.float64)])
 
@@ -239,6 +247,8 @@ SIGNATURES = {
                                           C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_double,
                                           C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
                                           C.POINTER(C.c_int32)]),   # include/hbo_tune.h (test hook)
+    'hbo_probe_posterior': (C.c_int, [_P, C.c_int, _P, C.c_int64, _P, _P, _P, _P, C.c_int64, C.c_double, _P, _P, _P, _P,
+                                      _P]),   # include/hbo_tune.h (test hook; the last: hbo_probe_post_plan*)
     'hbo_comm_unique_id': (C.c_int, [_P]),
     'hbo_comm_init': (C.c_int, [_P, C.c_int, C.c_int, _P]),
     'hbo_comm_allreduce_sum': (C.c_int, [_P, C.POINTER(C.c_double), C.c_int32]),

@@ -508,8 +508,10 @@ int acq_maximize(hbo_ctx* c, const AcqRoute& route, const AcqWhat& what, const h
 // hbo_predict / hbo_acq / hbo_acq_mes / hbo_acq_logei / one sample of hbo_acq_samples (cache.hip).  what: one sample's request (its
 // params[0], its K maxima), read when acq_out or an override asks for the acquisition; the entry points check it (acq_what_check).
 struct PosteriorOverride;
+struct PostProbe;   // test hook hbo_probe_posterior (probe.hip): caller-chosen operands in place of the producer's launches; below, after PostPlan
 int posterior(hbo_ctx* c, const hbo_model* m, hbo_cache* k, const void* xq, int64_t M, int full_cov, void* mu_out, void* var_out,
-              void* acq_out, const AcqWhat& what, double add_noise, double scale, const PosteriorOverride* ov = nullptr);
+              void* acq_out, const AcqWhat& what, double add_noise, double scale, const PosteriorOverride* ov = nullptr,
+              PostProbe* probe = nullptr);
 
 // the records acq_small_kernel and the kernels of acq_blocked.hip read of those pairs (hbo_internal.h: AcqSmallSample) and their
 // per-feature values, hv [S][fdim + mdim]: 1 / lengthscale over the kernel's own space, the linear mean's weights over the mean's
@@ -681,6 +683,14 @@ static PostPlan post_plan(const hbo_ctx* c, const hbo_model* m, int64_t M, int n
   p.own_counters = c->opt_lauum_persist && !ov_lane;
   return p;
 }
+// hbo_probe_posterior (probe.hip): the one step of posterior() a test swaps.  With a PostProbe, produce_chunk copies columns
+// [q0, q0 + mc) of these device operands into the chunk's slices (on the producer stream, the padding zeroed as the padded Gram leaves
+// it) instead of running query_features and the cross Gram; everything else of the call is untouched.  Kxq [n, M] dense, kdiag, mu0 [M].
+// Out: the plan as it ran (after post_acquire) and the chunks whose product ran as a resident grid.
+struct PostProbe {
+  const void *Kxq, *kdiag, *mu0;
+  PostPlan plan; int resident_chunks;
+};
 
 // ---- objective plan ------------------------------------------------------------------------
 // Every decision of one hbo_objective evaluation (objective.hip: objective_local) that follows from the options, the model, the

@@ -316,6 +316,7 @@ struct PostCall {
   AcqWhat what;                 // the caller's request with `ystar` on the DEVICE (hbo_acq_mes: the K maxima); params is not read here:
   double param;                 // its first entry -- the registry's parameter, hbo_acq_logei's target
   double add_noise, scale;
+  PostProbe* probe;             // test hook (hbo_probe_posterior): the chunk's cross Gram, prior variance and prior mean come from here
 };
 // one chunk's view of the workspaces: its buffer of each per-workspace array, its rows of the M-sized results
 struct PostSlice {
@@ -429,6 +430,18 @@ static int produce_chunk(const PostCall& pc, const PostPlan& p, const PostWs& w,
   const int dtype = p.dtype, fdim = feature_dim(m);
   const size_t es = w.es;
   hipStream_t sb = p.sb;
+  if (pc.probe) {   // the caller's columns [q0, q0 + mc) in place of the features and the cross Gram; what follows them stays
+    TaskHost* t = k->t;
+    const PostProbe& pr = *pc.probe;
+    *Fq_out = nullptr;
+    HIPCHK(c, hipMemsetAsync(s.K, 0, (size_t)t->npad * ch.ldq * es, sb));
+    HIPCHK(c, hipMemcpy2DAsync(s.K, (size_t)ch.ldq * es, (const char*)pr.Kxq + (size_t)ch.q0 * es, (size_t)p.M * es, (size_t)ch.mc * es, (size_t)t->n,
+                               hipMemcpyDeviceToDevice, sb));
+    HIPCHK(c, hipMemcpyAsync(s.kd, (const char*)pr.kdiag + (size_t)ch.q0 * es, (size_t)ch.mc * es, hipMemcpyDeviceToDevice, sb));
+    HIPCHK(c, hipMemcpyAsync(s.mu0, (const char*)pr.mu0 + (size_t)ch.q0 * es, (size_t)ch.mc * es, hipMemcpyDeviceToDevice, sb));
+    if (p.form != FORM_MFMA) post3_split_kxq(reinterpret_cast<const float*>(s.K), ch.ldq, ch.mpad, t->npad, p.form == FORM_F16X2, p.kscale, s.K3, sb);
+    return HBO_OK;
+  }
   const void* Fq = *Fq_out = query_features(c, m, pc.md, pc.mw, pc.mb, s.xq, ch.mc, s.acts, s.kwq, s.mu0, s.kd, sb, true).Fq;
   if (!k) {  // prior branch (gp.py:275-282)
     HIPCHK(c, hipMemcpyAsync(s.mu, s.mu0, (size_t)ch.mc * es, hipMemcpyDeviceToDevice, sb));
@@ -482,6 +495,7 @@ static void consume_chunk(const PostCall& pc, const PostPlan& p, const PostWs& w
       launch_gemm(dtype, a, dim3(ch.mpad / HBO_TILE, t->nblk, 1), sa);
       c->last_post_resident = a.work_counter && a.persistent > 0;   // (gemm.hip: gemm_plan keeps a one-task GEMM_POST with both resident)
     } }
+  if (pc.probe) pc.probe->resident_chunks += c->last_post_resident;
   { ProfScope ps(c, "post_epilogue", 1, sa);
     PostArgs pa = {}; pa.Kxq = s.K; pa.ldq = ch.ldq; pa.npad = t->npad; pa.n = (int)t->n; pa.nblk = t->nblk; pa.alpha = t->svec; pa.colsq = s.colsq; pa.mupart = s.mupart;
     pa.kdiag = s.kd; pa.muq = s.mu0; pa.mu_out = s.mu; pa.var_out = s.var; pa.acq_out = pc.what.step == ACQ_STEP_REGISTRY ? s.acq : nullptr; pa.M = ch.mc;
@@ -502,7 +516,7 @@ static void full_cov_tail(const PostCall& pc, const PostPlan& p, const PostWs& w
 }
 
 int posterior(hbo_ctx* c, const hbo_model* m, hbo_cache* k, const void* xq, int64_t M, int full_cov, void* mu_out, void* var_out,
-              void* acq_out, const AcqWhat& what, double add_noise, double scale, const PosteriorOverride* ov) {
+              void* acq_out, const AcqWhat& what, double add_noise, double scale, const PosteriorOverride* ov, PostProbe* probe) {
   if (!c || !xq) return fail(c, HBO_ERR_ARG, "posterior: null argument");
   if (M <= 0) return HBO_OK;
   HIPCHK(c, hipSetDevice(c->device));
@@ -519,13 +533,14 @@ int posterior(hbo_ctx* c, const hbo_model* m, hbo_cache* k, const void* xq, int6
   AcqWhat on_dev = what;
   on_dev.ystar = d_ystar;
   const PostCall pc = {c, m, k, ov ? ov->md : c->d_model, ov ? ov->mlp_w : c->d_mlp_w, ov ? ov->mlp_b : c->d_mlp_b, on_dev,
-                       what.params ? what.params[0] : 0.0, add_noise, scale};
+                       what.params ? what.params[0] : 0.0, add_noise, scale, probe};
   PostPlan p = post_plan(c, m, M, k ? k->t->nblk : 0, full_cov != 0, ov ? &ov->lane : nullptr);
   c->last_post_resident = 0;
   if (p.refuse) return fail(c, p.refuse, "posterior: full_cov limited to 65536 queries");
   PostWs w;
   rc = post_acquire(pc, M, ov, acq_out != nullptr, p, w);
   if (rc) return rc;
+  if (probe) { probe->plan = p; probe->resident_chunks = 0; }
   hipStream_t sa = p.sa, sb = p.sb;
   const int nbuf = p.nbuf;
   // the queries go up in ONE copy (M x D elements: small beside the N x CH workspace): a pageable host-to-device copy

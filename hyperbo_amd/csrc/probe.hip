@@ -100,6 +100,69 @@ extern "C" int hbo_probe_post_product(hbo_ctx* c, int form, const float* W, int6
   return HBO_OK;
 }
 
+// Test hook (include/hbo_tune.h): the streamed posterior on caller-chosen operands.  A cache-shaped object is built with the shipped
+// helpers (task_shape, ensure_task_workspace, fill_desc; W in t->W, alpha in t->svec, info = INT_MAX) and posterior() (cache.hip) runs
+// over it with a PostProbe: its produce_chunk then copies the caller's columns of Kxq, kdiag and mu0 into each chunk's slices instead of
+// launching the features and the cross Gram.  Plan, workspaces, split of W, the products, the epilogue, the chunk loop and its events
+// are posterior()'s own; the model handed to it only carries what post_plan reads (dtype; stationary with signal variance k_bound, or the
+// dot product) and a zero mean that is never evaluated.
+extern "C" int hbo_probe_posterior(hbo_ctx* c, int dtype, const void* W, int64_t n, const void* alpha, const void* Kxq, const void* kdiag,
+                                   const void* mu0, int64_t M, double k_bound, void* mu_out, void* var_out, void* colsq_out,
+                                   void* mupart_out, hbo_probe_post_plan* plan_out) {
+  if (!c || !W || !alpha || !Kxq || !kdiag || !mu0 || !mu_out || !var_out) return fail(c, HBO_ERR_ARG, "hbo_probe_posterior: null argument");
+  if (dtype != HBO_F32 && dtype != HBO_F64) return fail(c, HBO_ERR_ARG, "hbo_probe_posterior: bad dtype");
+  if (n <= 0 || n > 4096 || M <= 0 || M > (1 << 17)) return fail(c, HBO_ERR_ARG, "hbo_probe_posterior: need 1 <= n <= 4096 and 1 <= M <= 2^17");
+  if (!(k_bound >= 0) || !(k_bound < 1e30)) return fail(c, HBO_ERR_ARG, "hbo_probe_posterior: k_bound is 0 (unbounded kernel) or positive and finite");
+  for (int64_t i = 0; i < n; ++i) for (int64_t j = i + 1; j < n; ++j)
+    if (host_elem(W, dtype, i * n + j) != 0) return fail(c, HBO_ERR_ARG, "hbo_probe_posterior: W must hold zeros above the diagonal");
+  const size_t es = esize(dtype);
+  const double one64 = 1.0; const float one32 = 1.f;
+  hbo_model model; memset(&model, 0, sizeof model);
+  model.dtype = dtype; model.input_dim = 1; model.mean_id = HBO_MEAN_ZERO;
+  model.kernel_id = k_bound > 0 ? HBO_KERNEL_SE : HBO_KERNEL_DOT;
+  model.signal_variance = k_bound > 0 ? k_bound : 1.0; model.dot_prod_sigma = 1.0;
+  model.n_lengthscale = 1; model.lengthscale = dtype == HBO_F64 ? (const void*)&one64 : (const void*)&one32;
+  const int nblk = (int)(round_up(n, HBO_TILE) / HBO_TILE);
+  const PostPlan pre = post_plan(c, &model, M, nblk, false, nullptr);
+  if ((colsq_out || mupart_out) && pre.nchunks != 1) return fail(c, HBO_ERR_ARG, "hbo_probe_posterior: colsq_out and mupart_out need a single-chunk call (option post_chunk)");
+  HIPCHK(c, hipSetDevice(c->device));
+  hipStream_t st = c->stream;
+  hbo_cache* k = new hbo_cache();
+  // (the cache leaves when the call does, behind a wait: its buffers go back to the pool.  Before buf's memory is freed.)
+  DevBuf buf;
+  struct CacheGuard { hbo_ctx* c; hbo_cache* k; ~CacheGuard() { hipDeviceSynchronize(); hbo_cache_free(c, k); } } guard = {c, k};
+  k->dtype = dtype; k->D = 1; k->m = 1; k->input_warp = HBO_WARP_NONE; k->info = INT_MAX;
+  TaskHost* t = k->t = new TaskHost();
+  task_shape(t, n, 1, dtype);
+  int rc = ensure_task_workspace(c, dtype, t, false, 1);
+  if (rc) return rc;
+  fill_desc(k->h_desc, t, &model, dtype, ROLE_FACTOR);
+  HIPCHK(c, hbo_malloc(c, (void**)&k->d_desc, sizeof(TaskDesc)));
+  void *d_kxq = nullptr, *d_kd = nullptr, *d_mu0 = nullptr;
+  HIPCHK(c, buf.get(c, &d_kxq, (size_t)n * M * es)); HIPCHK(c, buf.get(c, &d_kd, (size_t)M * es)); HIPCHK(c, buf.get(c, &d_mu0, (size_t)M * es));
+  const size_t w_b = (size_t)t->npad * t->ld * es;
+  HIPCHK(c, hipMemcpyAsync(k->d_desc, &k->h_desc, sizeof(TaskDesc), hipMemcpyHostToDevice, st));
+  HIPCHK(c, hipMemsetAsync(t->W, 0, w_b, st));   // (a pooled W keeps what its last owner left below the diagonal)
+  HIPCHK(c, hipMemcpy2DAsync(t->W, (size_t)t->ld * es, W, (size_t)n * es, (size_t)n * es, (size_t)n, hipMemcpyHostToDevice, st));
+  HIPCHK(c, hipMemsetAsync(t->svec, 0, (size_t)t->npad * es, st));
+  HIPCHK(c, hipMemcpyAsync(t->svec, alpha, (size_t)n * es, hipMemcpyHostToDevice, st));
+  HIPCHK(c, hipMemcpyAsync(d_kxq, Kxq, (size_t)n * M * es, hipMemcpyHostToDevice, st));
+  HIPCHK(c, hipMemcpyAsync(d_kd, kdiag, (size_t)M * es, hipMemcpyHostToDevice, st));
+  HIPCHK(c, hipMemcpyAsync(d_mu0, mu0, (size_t)M * es, hipMemcpyHostToDevice, st));
+  HIPCHK(c, hipStreamSynchronize(st));
+  const std::vector<unsigned char> xq0((size_t)M * es, 0);   // the queries posterior() uploads; nothing reads them here
+  PostProbe probe = {}; probe.Kxq = d_kxq; probe.kdiag = d_kd; probe.mu0 = d_mu0;
+  rc = posterior(c, &model, k, xq0.data(), M, 0, mu_out, var_out, nullptr, acq_what_registry(0, nullptr), 0, 1, nullptr, &probe);
+  if (rc) return rc;
+  const PostPlan& p = probe.plan;
+  if (plan_out) *plan_out = {(int32_t)p.form, p.kchunk, p.nch, (int32_t)p.nchunks, p.nbuf, probe.resident_chunks, p.direct_form ? 1 : 0};
+  // single-chunk calls: the partials the epilogue summed stand in workspace 0 of their slots, rows ldq apart
+  const size_t pitch = (size_t)p.chunk(0).ldq * es;
+  if (colsq_out) HIPCHK(c, hipMemcpy2D(colsq_out, (size_t)M * es, c->ws[WS_COLSQ].first, pitch, (size_t)M * es, (size_t)nblk, hipMemcpyDeviceToHost));
+  if (mupart_out) HIPCHK(c, hipMemcpy2D(mupart_out, (size_t)M * es, c->ws[WS_MUPART].first, pitch, (size_t)M * es, (size_t)nblk, hipMemcpyDeviceToHost));
+  return HBO_OK;
+}
+
 // Test hook (include/hbo_tune.h): launch_gram in the two forms hbo_gram never takes, on caller-chosen inputs, with every element of the
 // output buffer preset to a sentinel so that what the kernel leaves alone shows.  Form 1 is the launch of cache.hip's produce_chunk (sizes from
 // post_plan), form 2 the launch of objective_local / enqueue_factor over a dataset built by hbo_dataset_create, its workspaces by

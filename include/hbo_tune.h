@@ -217,6 +217,33 @@ int hbo_probe_kumar_warp(hbo_ctx* ctx, const hbo_model* model, const void* x, in
 int hbo_probe_grad_contract(hbo_ctx* ctx, const hbo_model* model, int obj, int32_t T, const int64_t* ns, const void* x, const void* s,
                             const void* vecs, int32_t nvec, const double* coef_lh, const double* coef_c, const double* dmu, double sentinel,
                             double* grad_out, double* partials_out, double* fro_out, double* dF_out, int32_t* prereduced_out);
+/* What hbo_probe_posterior ran (csrc/api_internal.h: PostPlan, after the workspaces were acquired), so that a test can tell which route
+ * it reached.  form: the product's form, 0 fp32 MFMA (and all of fp64: GEMM_POST), 1 bf16x3, 2 f16x2; kchunk / nch: the split-K
+ * product's 128-blocks per K chunk (0: not split) and the chunks of the longest row tile; nchunks / nbuf: query chunks and alternating
+ * workspaces; resident_chunks: chunks whose product ran as a resident grid drawing its tiles from a counter; direct_form: what the
+ * streamed producer's cross Gram would be told (1 exactly when nbuf = 2). */
+typedef struct hbo_probe_post_plan {
+  int32_t form, kchunk, nch, nchunks, nbuf, resident_chunks, direct_form;
+} hbo_probe_post_plan;
+/* TEST HOOK (tests/test_gpu_posterior.py): the streamed posterior of hbo_predict / hbo_acq (no full_cov) on caller-chosen operands.  All
+ * arrays are host arrays in `dtype` (HBO_F32 / HBO_F64), row-major: W [n, n] lower triangular with zeros above the diagonal (checked),
+ * where a cache holds L^-1; alpha [n], where it holds K^-1 (y - mu); Kxq [n, M], the cross Gram; kdiag [M], k(x_q, x_q); mu0 [M], the prior
+ * mean.  1 <= n <= 4096, 1 <= M <= 2^17.  k_bound > 0: a stationary covariance with that signal variance, |Kxq| <= k_bound (fp32: the
+ * f16x2 product is allowed and scales Kxq by it); k_bound = 0: an unbounded covariance, treated as the dot product (fp32: bf16x3 at most).
+ * The hook builds a cache-shaped object with the helpers hbo_factor uses (shape, workspaces, descriptor; W and alpha uploaded padded
+ * with zeros) and runs the posterior's own code over it: the plan from the context's options (post_chunk, post_bf16x3, post_f16x2,
+ * lauum_persist) and the CU count, the workspaces, the split of W, per chunk the product (GEMM_POST plain, resident or split along K with
+ * post_colsq_split_kernel; post3_kernel / post2h_kernel), post_mupart_kernel and post_epilogue_kernel, the two alternating workspaces and
+ * the events between the two streams.  ONE step is swapped: where the producer would compute the features, the prior mean and variance
+ * and the padded cross Gram of queries [q0, q0 + mc), it copies those columns of Kxq, kdiag and mu0 into the chunk's slices, on the
+ * producer stream, the padding zero as the padded Gram leaves it; the transposed split of Kxq for the 16-bit forms stays.  The hook
+ * decides nothing itself.
+ * Outputs: mu_out, var_out [M]; colsq_out, mupart_out [ceil(n / 128), M] (nullable): per 128-row block i the column sums of V^2 and of
+ * Kxq[i-block] * alpha as the epilogue read them -- single-chunk calls only (M <= post_chunk), HBO_ERR_ARG otherwise; plan_out
+ * (nullable): what ran.  HBO_ERR_ARG on a bad argument, before any device call and with no output touched; no product path calls this. */
+int hbo_probe_posterior(hbo_ctx* ctx, int dtype, const void* W, int64_t n, const void* alpha, const void* Kxq, const void* kdiag,
+                        const void* mu0, int64_t M, double k_bound, void* mu_out, void* var_out, void* colsq_out, void* mupart_out,
+                        hbo_probe_post_plan* plan_out);
 #ifdef __cplusplus
 }
 #endif
